@@ -14,6 +14,12 @@ Prints ONE JSON line.  roofline: the step is a dense contraction -> MFMA bound; 
 step (2 x forward census, SURVEY.md 8d: 13.66 TFLOP for this config) / measured step time (HIP events on the stream
 the graph is replayed on); peak = 2.5 PFLOP/s dense bf16 (MI355X_MICROARCH.md).  cpu_baseline: the fp32 oracle
 (oracle/, a port of the reference path) timed on this host's cores on a bounded sample.
+
+A plain run (no --full) sets up, warms up, times the K steps and prints the line with the headline figure and the roofline
+fraction of those steps.  Every other measurement - cpu_baseline, library_gpu_baseline, train_loop, two_jobs_per_gpu,
+sustained, telemetry, the per-family times of roofline.families_this_run and the committed profiles quoted in roofline - runs
+only with --full (each still honours its own --no-* switch).  --dump-outputs DIR writes what the last timed step computed
+(the loss and the trained tensors, see dump_outputs) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -201,6 +207,38 @@ class GpuTelemetry:
             v = [s[k] for s in self.samples if isinstance(s[k], (int, float))]
             out[name] = {"mean": round(sum(v) / len(v), 1), "min": round(min(v), 1), "max": round(max(v), 1)} if v else None
         return out
+
+
+DUMP_BUDGET_BYTES = 60 << 20
+
+
+def dump_outputs(out_dir, jobs):
+    """What a caller of the timed path holds after its last step, one .npy per array: `loss` (float64 [2]: the logged total loss and
+    the image loss), `params` (float32: the flat fp32 master of every trained tensor - LoRA A / B, DoRA magnitudes, or every UNet weight
+    of --full-ft) and `ti_params` (float32: the trained token rows, with textual inversion).  J > 1 jobs: one set per job, suffix `_job<j>`.
+    A `params` larger than its share of DUMP_BUDGET_BYTES is written as a fixed sample: the elements at sorted indices drawn from a CPU
+    generator seeded with 0, so the same build arguments always pick the same elements."""
+    import numpy as np
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for j, (tsj, arena, _, _) in enumerate(jobs):
+        sfx = "" if len(jobs) == 1 else f"_job{j}"
+        arrays["loss" + sfx] = np.array([tsj.total_loss(), float(tsj.loss)], dtype=np.float64)
+        if getattr(tsj, "ti", None) is not None:
+            arrays["ti_params" + sfx] = tsj.ti.params.detach().float().cpu().numpy()
+    left = DUMP_BUDGET_BYTES - sum(a.nbytes for a in arrays.values())
+    cap = max(1, left // (4 * len(jobs)))
+    for j, (_, arena, _, _) in enumerate(jobs):
+        sfx = "" if len(jobs) == 1 else f"_job{j}"
+        p = arena.params.detach()
+        if p.numel() > cap:
+            idx = torch.randint(0, p.numel(), (cap,), generator=torch.Generator().manual_seed(0)).sort().values
+            p = p[idx.to(p.device)]
+        arrays["params" + sfx] = p.float().cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"[bench] outputs of the last timed step written to {out_dir}: " + ", ".join(f"{n} {list(a.shape)}" for n, a in arrays.items()), file=sys.stderr, flush=True)
 
 
 def run_guarded(argv, timeout_s):
@@ -478,6 +516,11 @@ def main():
     ap.add_argument("--no-sustained", action="store_true", help="skip the extra sustained-rate measurement behind the timed region")
     ap.add_argument("--sustained-steps", type=int, default=100)
     ap.add_argument("--launch-test", action="store_true", help=argparse.SUPPRESS)            # tests/test_parallel_cpu.py: launcher + timing protocol on CPU
+    ap.add_argument("--full", action="store_true", help="run the extra measurements behind the timed region as well (cpu_baseline, library_gpu_baseline, "
+                    "roofline.families_this_run, train_loop, two_jobs_per_gpu, sustained, telemetry, the committed profiles quoted in roofline); "
+                    "a plain run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last one computed (loss, trained tensors) "
+                    "as DIR/<name>.npy (bench.dump_outputs)")
     args = ap.parse_args()
     world_env = int(os.environ.get("WORLD_SIZE", "0") or 0)
     if args.gpus > 1 and world_env == 0:
@@ -620,7 +663,7 @@ def main():
         cur.wait_stream(st)
 
     barrier = parallel.barrier_sync
-    tele = GpuTelemetry(index=local_rank if world > 1 else 0) if rank == 0 else None
+    tele = GpuTelemetry(index=local_rank if world > 1 else 0) if (rank == 0 and args.full) else None
     barrier()
     if tele:
         tele.start()
@@ -641,6 +684,8 @@ def main():
     losses = [tsj.total_loss() for tsj, _, _, _ in jobs]
     loss = losses[0]
     assert all(math.isfinite(x) for x in losses), "non-finite loss in the timed region"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, jobs)
 
     if args.families_only:
         # per-family kernel time of the replayed step IN THIS PROCESS (the families of the bench line used to come from a committed profile of another box):
@@ -690,8 +735,9 @@ def main():
         # back through --profile-json; the default workload falls back to the committed profile of this round and says which commit it is from
         traffic = traffic_commit = hbm_kernels = families = traffic_sources_match = None
         pdir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles")
-        default_workload = (version == "sdxl" and res == 1024 and B == 1 and args.rank == 16 and text is not None and not args.ti_frozen and not full_ft
-                            and not args.dora and J == 1)
+        # (the committed profiles are quoted by --full runs only; an explicit --profile-json always is)
+        default_workload = (args.full and version == "sdxl" and res == 1024 and B == 1 and args.rank == 16 and text is not None and not args.ti_frozen
+                            and not full_ft and not args.dora and J == 1)
         import glob
         committed = sorted(glob.glob(os.path.join(pdir, "r[0-9][0-9]_sdxl1024_ti_step_profile.json")))     # the newest round's committed profile
         ppath = args.profile_json or (committed[-1] if (default_workload and committed) else None)
@@ -741,7 +787,7 @@ def main():
                 with open(tpath) as fh:
                     traffic, traffic_commit = json.load(fh).get("traffic_bytes_per_step"), "round 2 final"
         fpath = os.path.join(pdir, "r01_fullft_hbm_traffic_pmc.json")
-        if full_ft and version == "sdxl" and res == 512 and B == 4 and os.path.exists(fpath):
+        if args.full and full_ft and version == "sdxl" and res == 512 and B == 4 and os.path.exists(fpath):
             with open(fpath) as fh:
                 traffic, traffic_commit = json.load(fh).get("traffic_bytes_per_step"), "round 1"
         out = {
@@ -776,9 +822,10 @@ def main():
                                  "hbm_kernels: the HBM-bound kernel families - algorithmic bytes (topology.hbm_bytes) / their time in the profiled step, against 8 TB/s; "
                                  "families: the MFMA-bound kernel families of the same profiled step - algorithmic TFLOP (2 x fwd census) / their kernel time, against 2.5 PFLOP/s"},
         }
-        out["telemetry"] = dict(telemetry or {}, note="shader clock (mean over the XCDs) / socket power / hotspot temperature of this GPU sampled every 20 ms from a host thread "
-                                "over the timed region - the chip clocks to its power budget, so the same kernels time differently on a cold and a warm box (DESIGN 6)")
-        if world == 1 and not args.no_sustained and not args.no_graph:
+        if args.full:
+            out["telemetry"] = dict(telemetry or {}, note="shader clock (mean over the XCDs) / socket power / hotspot temperature of this GPU sampled every 20 ms from a host thread "
+                                    "over the timed region - the chip clocks to its power budget, so the same kernels time differently on a cold and a warm box (DESIGN 6)")
+        if args.full and world == 1 and not args.no_sustained and not args.no_graph:
             # Extra object (never `value`): the same replay loop for `--sustained-steps` more steps right behind the timed region - the figure a job sees once the
             # chip has settled into its power budget, with its own clock / power samples; the K-step figure above is what the contract asks for
             tele2 = GpuTelemetry(index=0).start()
@@ -815,8 +862,8 @@ def main():
                                           "(x2 for all-reduce) / 153 GB/s per xGMI link, over one link (a single ring) and over all N-1 links of the fully connected node - bounds "
                                           "that the overlap with the weight-gradient GEMMs hides or not"}
             out["config"]["parallelism"] = (f"dry run of dp-N on one GPU: {len(log)} collectives per step on a 1-rank RCCL communicator (" + "; ".join(out["collectives"]["sequence"]) + ")")
-        print(f"[bench] timed region done: {t_step * 1e3:.2f} ms/step; extras follow", file=sys.stderr, flush=True)
-        if world == 1 and not args.no_cpu_baseline and not full_ft:
+        print(f"[bench] timed region done: {t_step * 1e3:.2f} ms/step" + ("; extras follow" if args.full else ""), file=sys.stderr, flush=True)
+        if args.full and world == 1 and not args.no_cpu_baseline and not full_ft:
             # measured in a CHILD process with a wall-clock limit: nothing on the host side may keep the JSON line from being printed
             child = run_guarded(["--cpu-baseline-only", "--config", version, "--res", str(res), "--rank", str(args.rank)] + (["--no-ti"] if args.no_ti else []), 420)
             if child:
@@ -833,7 +880,7 @@ def main():
             if not child:
                 out["cpu_baseline"] = {"value": None, "unit": "images/s", "cores": usable_cores(), "kind": "port", "step_seconds": [],
                                        "sample": "the CPU oracle did not complete a step within the 420 s guard of the default run"}
-        if world == 1 and J == 1 and not full_ft and not args.no_cpu_baseline and not args.no_library_gpu and text is not None and not args.no_ti and not args.dora and version in ("sdxl", "sd15") and not args.batch:
+        if args.full and world == 1 and J == 1 and not full_ft and not args.no_cpu_baseline and not args.no_library_gpu and text is not None and not args.no_ti and not args.dora and version in ("sdxl", "sd15") and not args.batch:
             # Extra object beside cpu_baseline (never `value`): the same torch restatement of the step on THIS GPU through PyTorch-ROCm's library kernels
             # (library_gpu_baseline), in a child process with a wall-clock limit; the parent's model stays resident, the child needs ~25 GB more
             if B == 1:
@@ -842,7 +889,7 @@ def main():
                     out["library_gpu_baseline"] = child[-1]
                     out["library_gpu_baseline"]["speedup_of_value"] = out["value"] / child[-1]["value"]
                 print("[bench] library GPU baseline done", file=sys.stderr, flush=True)
-        if world == 1 and J == 1 and not args.no_graph and not args.no_families and not args.no_cpu_baseline:
+        if args.full and world == 1 and J == 1 and not args.no_graph and not args.no_families and not args.no_cpu_baseline:
             # Extra measurement (never `value`), child process with a wall-clock limit: the per-family kernel times of THIS box and THIS code (torch.profiler over three replayed steps of
             # the same workload) next to the families of the committed rocprofv3 profile above; fractions against the same algorithmic FLOPs
             argv = ["--families-only", "--config", version, "--res", str(res), "--rank", str(args.rank), "--steps", "5", "--warmup", "3", "--no-cpu-baseline", "--no-sustained"] \
@@ -859,14 +906,14 @@ def main():
                 fr["note"] = "torch.profiler (roctracer kernel records) over three replayed steps in a child process of this run: kernel time per family and step on THIS box with THIS code"
                 out["roofline"]["families_this_run"] = fr
             print("[bench] in-run family times done", file=sys.stderr, flush=True)
-        if world == 1 and J == 1 and not full_ft and not args.no_graph and not args.no_train_loop and text is not None:
+        if args.full and world == 1 and J == 1 and not full_ft and not args.no_graph and not args.no_train_loop and text is not None:
             # Extra measurement (never `value`), in a child process with a wall-clock limit (see train_loop_measure)
             child = run_guarded(["--train-loop-only", "--config", version, "--res", str(res), "--rank", str(args.rank), "--steps", str(args.steps)]
                                 + (["--batch", str(args.batch)] if args.batch else []), 420)
             if child:
                 out["train_loop"] = child[-1]
             print("[bench] train loop done", file=sys.stderr, flush=True)
-        if world == 1 and J == 1 and not full_ft and not args.no_graph and not args.no_concurrent:
+        if args.full and world == 1 and J == 1 and not full_ft and not args.no_graph and not args.no_concurrent:
             # Extra measurement (never `value`): the same workload with TWO independent jobs stepped concurrently on this GPU,
             # each on its own stream with its own hipGraph (train.train_concurrent).
             from sd_lora_trainer_amd import ops as _ops

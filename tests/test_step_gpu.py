@@ -242,7 +242,7 @@ def test_train_concurrent_on_gpu(tmp_path, monkeypatch):
 
 
 def test_bench_json_contract():
-    """bench.py prints ONE JSON line with the driver's fields plus `roofline`, `cpu_baseline` and the extra `two_jobs_per_gpu`
+    """bench.py --full prints ONE JSON line with the driver's fields plus `roofline`, `cpu_baseline` and the extra `two_jobs_per_gpu`
     object (toy topology so that the whole script takes seconds)."""
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
@@ -251,7 +251,7 @@ def test_bench_json_contract():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "tinyxl", "--res", "256", "--steps", "3", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "tinyxl", "--res", "256", "--steps", "3", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -269,6 +269,40 @@ def test_bench_json_contract():
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and "sample" in c and len(c["step_seconds"]) >= 1
     assert d["train_loop"]["value"] > 0 and d["train_loop"]["unit"] == "images/s"          # the train() generator's own loop, extra object
     assert d["two_jobs_per_gpu"]["value"] > 0 and d["two_jobs_per_gpu"]["unit"] == "images/s"
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain bench run prints the headline line without the extras of --full, and --dump-outputs writes what its last timed
+    step computed: the loss (== the line's final_loss), the trained tensors and the token rows, float32 / float64, within 64 MB."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "tinyxl", "--res", "256", "--steps", "4", "--warmup", "1",
+                          "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "images/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert abs(d["value"] - d["config"]["global_batch"] * 4 / (d["ms_per_step"] * 4e-3)) <= 1e-6 * d["value"]
+    for k in ("cpu_baseline", "library_gpu_baseline", "train_loop", "two_jobs_per_gpu", "sustained", "telemetry"):
+        assert k not in d, k
+    assert "families_this_run" not in d["roofline"]
+    files = sorted(os.listdir(dump))
+    assert files == ["loss.npy", "params.npy", "ti_params.npy"], files
+    arrays = {f[:-4]: np.load(dump / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays["loss"][0] == d["config"]["final_loss"]
+    assert arrays["params"].size == d["config"]["trained_params"] and np.isfinite(arrays["params"]).all() and np.isfinite(arrays["ti_params"]).all()
 
 
 def test_cfg1_style_sd15_job_on_the_real_topology(tmp_path, monkeypatch):

@@ -40,7 +40,7 @@ done
 # the per-launch floor model of the step (roofline.shape_floor_ms of the bench line)
 timeout 1200 python tools/step_floor.py --out $O/r06_step_floor.json --commit $C 2>&1 | grep -v "Warning\|amdgpu.ids" > $O/r06_step_floor.txt
 cp $O/r06_step_floor.json $R/profiles/r06_step_floor.json
-timeout 900 python bench.py --profile-json $O/r06_sdxl1024_ti_step_profile.json > $O/r06_bench_line.json 2> $O/bench_default.err
+timeout 900 python bench.py --full --profile-json $O/r06_sdxl1024_ti_step_profile.json > $O/r06_bench_line.json 2> $O/bench_default.err
 # RCCL sanity on the one GPU of the box: the driver's launch line with one rank (process group "nccl" = RCCL, barrier + MAX reduction of the timing)
 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 5 --warmup 2 $B > $O/r06_bench_line_torchrun_1rank.json 2> $O/torchrun.err
 timeout 900 python bench.py --full-ft --dry-collectives --no-cpu-baseline --steps 5 --warmup 2 2>/dev/null | grep "^{" | tail -1 > $O/r06_fullft_dry_collectives.json

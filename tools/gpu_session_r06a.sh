@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
 O=gpurun_out/r06a
 mkdir -p $O
-B="--no-cpu-baseline --no-concurrent --no-train-loop"
+B="--full --no-cpu-baseline --no-concurrent --no-train-loop"
 timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 $B 2>$O/bench_cold.err | tail -1 > $O/bench_cold.json
 timeout 300 python tools/telemetry_probe.py > $O/telemetry_probe.txt 2>&1
 timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 $B 2>/dev/null | tail -1 > $O/bench_warm1.json
