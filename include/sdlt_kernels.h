@@ -33,6 +33,8 @@ int sdlt_struct_size(int which); /* 0 gemm, 1 lora_grad_desc, 2 attn, 3 groupnor
  *         upsampled input; flip=1 mirrors the taps (dX of a stride-1 conv); tr=1 is the transposed
  *         stride-2 form (dX of a stride-2 conv).  `zero` = >=128 B of zeros (out-of-image taps).
  * K, K2 multiples of 64; lora_R (padded rank) in {0,16,32,64}; Adown [lora_R,K], Bup [N,lora_R].
+ * The second segment X2 [M,K2] . W2^T [N,K2] is row-major in either mode (mode 1: a convolution followed by a plain
+ * product - the wide adapters' T . Bup^T behind ResnetBlock conv2); it excludes the fused adapter (lora_R = 0).
  * T_out (optional) receives s*X.Adown^T as bf16 [M,lora_R] (needed by the LoRA weight gradients).
  * tile: 0 = auto, 1 = 128x128 (8 waves), 2 = 64x128 (8 waves), 3 = 64x64 (4 waves), 4 = 256x128 (8 waves),
  *       5 = 128x128 (4 waves), 6 = 256x256 (8 waves)   (rows x cols of C per workgroup).
@@ -131,6 +133,10 @@ typedef struct sdlt_gemm_params {
      kernel variant for it exists (the shapes of the 1280-wide blocks); otherwise ignored and the statistics are computed from the K walk. */
   int32_t ln_nparts;
   const void* ln_parts;
+  /* x2_group_n > 0: grouped second segment (the wide-rank adapters of stacked projections, T . Bup^T per projection): N is a
+     concatenation of projections of x2_group_n columns each; output column n reads X2 columns [g*K2, (g+1)*K2), g = n / x2_group_n,
+     and W2 row n as usual (W2 [N, K2], X2 [M, G*K2]).  Mode 0, no adapter, no batch; a multiple of the N tile (64 suffices). */
+  int32_t x2_group_n;
 } sdlt_gemm_params;
 int sdlt_gemm_bf16(const sdlt_gemm_params* p, void* stream);
 
@@ -168,6 +174,11 @@ typedef struct sdlt_lora_grad_desc {
 int sdlt_lora_grad_grouped(const sdlt_lora_grad_desc* descs_dev, const int32_t* block_desc_dev,
                            int32_t n_blocks, int32_t Rp, int32_t mfma, void* stream);
 int32_t sdlt_lora_grad_block_cols(void);
+/* sdlt_lora_grad_wide : sdlt_lora_grad_grouped for wide adapters, padded rank Rp in {128, 192, 256} (desc.Rp = Rp, desc.R <= Rp
+ * the real rank; the descriptor table and block_desc are built exactly as for sdlt_lora_grad_grouped).  The grid is
+ * n_blocks x Rp/64: workgroup (b, j) reduces ranks [64j, 64j + 64) of its problem's 64 columns; ranks >= R are never written. */
+int sdlt_lora_grad_wide(const sdlt_lora_grad_desc* descs_dev, const int32_t* block_desc_dev,
+                        int32_t n_blocks, int32_t Rp, int32_t mfma, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * sdlt_attn_fwd / sdlt_attn_bwd : multi-head softmax attention, flash style (no score matrix in HBM).

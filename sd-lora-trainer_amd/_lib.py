@@ -40,6 +40,7 @@ class GemmParams(C.Structure):
         ("epi_op", i32), ("epi_act", i32), ("epi_out", vp), ("ld_epi_out", i64), ("epi_in", vp), ("ld_epi_in", i64),
         ("col_scale", vp),
         ("ln_c1", vp), ("ln_stats", vp), ("ln_adapter", vp), ("ln_eps", f32), ("ln_nparts", i32), ("ln_parts", vp),
+        ("x2_group_n", i32),
     ]
 
 
@@ -160,6 +161,7 @@ SYMBOLS = {
     "sdlt_gemm_bf16": (i32, [C.POINTER(GemmParams), vp]),
     "sdlt_lora_grad_grouped": (i32, [vp, vp, i32, i32, i32, vp]),
     "sdlt_lora_grad_block_cols": (i32, []),
+    "sdlt_lora_grad_wide": (i32, [vp, vp, i32, i32, i32, vp]),
     "sdlt_attn_fwd": (i32, [C.POINTER(AttnParams), vp]),
     "sdlt_attn_bwd": (i32, [C.POINTER(AttnParams), vp]),
     "sdlt_attn_splitsum_batch": (i32, [vp, vp, vp, i32, vp]),

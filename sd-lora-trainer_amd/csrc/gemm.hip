@@ -9,7 +9,7 @@
 // * X rows can be gathered on the fly: MODE 1 turns the kernel into an implicit-GEMM 3x3 convolution
 //   over an NHWC activation (K = 9*Cin, k = tap*Cin + ci), incl. stride 2, nearest-2x upsampled input,
 //   tap flip (dX of a stride-1 conv) and the transposed stride-2 form (dX of a downsampling conv).
-//   Out-of-image taps read a zero page.
+//   Out-of-image taps read a zero page.  MODE 2 is MODE 1 followed by a plain row-major second K segment (X2 . W2^T).
 // * rank-r LoRA is fused: the LoRA-down product T = X.Adown^T is accumulated by the same K loop on
 //   16 extra MFMA columns, scaled, rounded to bf16, and applied with one 16x16x16 MFMA per tile pair
 //   (the 16x16 accumulator layout IS the 16x16x16 B-operand layout, so no cross-lane movement).
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_kernel(const sdlt_gemm_para
 #ifndef SDLT_CONV_GROUP_FACTOR
 #define SDLT_CONV_GROUP_FACTOR 9
 #endif
-    int GROUP_M = (int)(sqrtf((float)live * BN / BM * (MODE == 1 ? SDLT_CONV_GROUP_FACTOR : 1)) + 0.5f);
+    int GROUP_M = (int)(sqrtf((float)live * BN / BM * (MODE != 0 ? SDLT_CONV_GROUP_FACTOR : 1)) + 0.5f);
     GROUP_M = GROUP_M < 1 ? 1 : (GROUP_M > nbm ? nbm : GROUP_M);
     const int per_group = GROUP_M * nbn;
     const int grp = div_small_u(tile_id, per_group), first_m = grp * GROUP_M;
@@ -176,6 +176,11 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_kernel(const sdlt_gemm_para
       int mc = m < p.M ? m : p.M - 1;
       x2ptr[i] = (const bf16_t*)p.X2 + (size_t)mc * p.ldx2 + schunk * 8;
     }
+    if (p.x2_group_n > 0) {      // grouped second segment: this tile's column group reads its own K2 columns of X2 (host: tile inside one group)
+      const size_t goff = (size_t)div_small_u(n0, p.x2_group_n) * p.K2;
+#pragma unroll
+      for (int i = 0; i < XI; ++i) x2ptr[i] += goff;
+    }
 #pragma unroll
     for (int i = 0; i < WI; ++i) {
       int n = n0 + (wave + NW * i) * 8 + srow;
@@ -218,7 +223,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_kernel(const sdlt_gemm_para
 
   // implicit-GEMM conv: tap / channel offset of the NEXT stage to be issued (stages are issued strictly in K order from kbeg)
   int cv_tap = 0, cv_ci0 = 0;
-  if (MODE == 1) {
+  if (MODE != 0) {
     cv_tap = kbeg == 0 ? 0 : div_small_u(kbeg * BK, p.Cin);
     cv_ci0 = kbeg * BK - cv_tap * p.Cin;
   }
@@ -228,10 +233,12 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_kernel(const sdlt_gemm_para
   // scratch_load + s_waitcnt vmcnt(0) in front of the W pieces of EVERY stage, i.e. the whole DMA ring drained once per
   // K-step in every kernel without LoRA.
   auto for_each_piece = [&](int kt, auto&& f) {
-    constexpr bool TWOSEG = MODE == 0 && R16 == 0;     // only plain GEMMs may carry a second K segment (host-checked)
+    // only plain GEMMs (mode 0) and convolutions followed by a plain row-major [M, K2] segment (MODE 2: the wide adapters' T . Bup^T, a
+    // variant of its own so that the mode-1 kernels keep their pointer arrays out of scratch) carry a second K segment (host-checked)
+    constexpr bool TWOSEG = (MODE == 0 || MODE == 2) && R16 == 0;
     const bool seg1 = !TWOSEG || kt < nk1;
     const int k0 = (seg1 ? kt : kt - nk1) * BK;
-    if (MODE == 1) {
+    if (MODE != 0) {
         // stages are issued in K order, so the (tap, channel offset) of the step is tracked incrementally (no division)
         const int tap = cv_tap, ci0 = cv_ci0;
         cv_ci0 += BK;
@@ -241,7 +248,12 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_kernel(const sdlt_gemm_para
 #pragma unroll
         for (int i = 0; i < XI; ++i) {
           const bf16_t* src = (const bf16_t*)p.zero + schunk * 8;
-          if (xb[i] >= 0) {
+          if (MODE == 2 && !seg1) {
+            // the second segment behind a convolution: a plain row of X2 (row address recomputed per stage - a pointer array selected
+            // against the gathered conv rows went to scratch); the tap tracking above runs on, unused
+            const int m = m0 + (wave + NW * i) * 8 + srow;
+            src = (const bf16_t*)p.X2 + (size_t)(m < p.M ? m : p.M - 1) * p.ldx2 + schunk * 8 + k0;
+          } else if (xb[i] >= 0) {
             int hi, wi;
             bool ok;
             if (p.tr) {
@@ -265,6 +277,18 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_kernel(const sdlt_gemm_para
         f(i, src + k0, (wave + NW * i) * 1024);
       }
     }
+    if constexpr (MODE == 2) {
+      // (MODE 2: segment base and row stride selected as scalars, the row recomputed - no pointer arrays to select between)
+      const bf16_t* wb = seg1 ? (const bf16_t*)pW : (const bf16_t*)p.W2;
+      const int64_t wld = seg1 ? p.ldw : p.ldw2;
+#pragma unroll
+      for (int i = 0; i < WI; ++i) {
+        if (i < WF || w_extra) {
+          const int n = n0 + (wave + NW * i) * 8 + srow;
+          f(XI + i, wb + (size_t)(n < p.N ? n : p.N - 1) * wld + schunk * 8 + k0, XT + (wave + NW * i) * 1024);
+        }
+      }
+    } else {
 #pragma unroll
     for (int i = 0; i < WF; ++i) {
       const bf16_t* src = (!TWOSEG || seg1) ? wptr[i] : w2ptr[i];
@@ -275,6 +299,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_kernel(const sdlt_gemm_para
         const bf16_t* src = (!TWOSEG || seg1) ? wptr[WF] : w2ptr[WF];
         f(XI + WF, src + k0, XT + (wave + NW * WF) * 1024);
       }
+    }
     }
     if (R16) {
       // (LoRA excludes a second segment.)  Every wave moves the SAME number of pieces per stage (the counted vmcnt of the
@@ -1029,7 +1054,7 @@ int dispatch_tile(const sdlt_gemm_params& pin, hipStream_t s) {
         else if (t8 >= 224) p.tile = 8;
       } else if (MODE == 0 && R16 == 1 && !p.lora_group_n && ktot <= 640 && t8 >= 224 && t8 <= 320) {
         p.tile = 8;
-      } else if (MODE == 1 && (t8 == 256 || t8 == 128 || t8 == 64)) {
+      } else if (MODE != 0 && (t8 == 256 || t8 == 128 || t8 == 64)) {
         const int sk = (int)(256 / t8);
         if (sk == 1 || (ws && !p.splitk && nk / sk >= 16)) { p.tile = 8; if (sk > 1) p.splitk = sk; }
       }
@@ -1049,7 +1074,7 @@ int dispatch_tile(const sdlt_gemm_params& pin, hipStream_t s) {
         p.splitk = sk;
       }
     }
-    else if (p.throughput_hint && !p.batch && !p.lora_group_k && (t128 >= 320 || (MODE == 1 && t128 >= 160))) {
+    else if (p.throughput_hint && !p.batch && !p.lora_group_k && (t128 >= 320 || (MODE != 0 && t128 >= 160))) {
       // several jobs share the device (whole-step A/B with two concurrent SDXL jobs: 85.0 -> 82.8 ms per pair): the other job
       // fills the CUs a launch leaves idle, so the 256x128 tile (0.75 operand-path cycles per MFMA cycle instead of 1.0) wins
       // although it halves the workgroup count.  With ONE job the same rule loses 0.3 ms.
@@ -1087,6 +1112,12 @@ int dispatch_tile(const sdlt_gemm_params& pin, hipStream_t s) {
   }
   int bm, bn;
   tile_dims(p.tile, bm, bn);
+  if (!R16 && p.x2_group_n > 0 && (p.x2_group_n % bn) && pin.tile == 0 && p.x2_group_n % 64 == 0) {
+    p.tile = 3;   // grouped second segment: the 64x64 tile never straddles two groups
+    tile_dims(p.tile, bm, bn);
+  }
+  if (!R16 && p.x2_group_n > 0 && (p.x2_group_n % bn))
+    SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_gemm_bf16: x2_group_n=%d is not a multiple of the %d-column tile", p.x2_group_n, bn);
   if (R16 && p.lora_group_n > 0 && (p.lora_group_n % bn) && pin.tile == 0 && p.lora_group_n % 64 == 0) {
     p.tile = 3;   // narrow groups (head width 64): the 64x64 tile never straddles two adapters
     tile_dims(p.tile, bm, bn);
@@ -1248,11 +1279,13 @@ extern "C" int sdlt_gemm_bf16(const sdlt_gemm_params* pp, void* stream) {
     SDLT_FAIL(SDLT_ERR_ALIGN, "sdlt_gemm_bf16: operand rows must be 16-byte aligned (ld %% 8)");
   if (((uintptr_t)p.X | (uintptr_t)p.W | (uintptr_t)p.X2 | (uintptr_t)p.W2 | (uintptr_t)p.Adown) & 15)
     SDLT_FAIL(SDLT_ERR_ALIGN, "sdlt_gemm_bf16: operand base pointers must be 16-byte aligned");
+  if (p.x2_group_n && (p.x2_group_n < 0 || !p.K2 || p.mode != 0 || p.lora_R || p.batch || (p.N % p.x2_group_n)))
+    SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: x2_group_n=%d needs a second segment, mode 0, no adapter / batch, N %% x2_group_n == 0", p.x2_group_n);
   if (p.ln_c1 && (p.N & 3)) SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_gemm_bf16: N=%d with a folded LayerNorm must be a multiple of 4", p.N);
   if (p.mode == 1) {
     if (!p.zero) SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_gemm_bf16: conv mode needs a zero page");
     if (p.Cin % BK || p.K != 9 * p.Cin) SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_gemm_bf16: conv needs Cin%%64==0 and K==9*Cin (Cin=%d K=%d)", p.Cin, p.K);
-    if (p.K2) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: conv + second segment");
+    if (p.K2 && (p.lora_R || p.x2_group_n)) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: conv + second segment takes no adapter and no x2_group_n");
     if (p.M % (p.Hout * p.Wout)) SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_gemm_bf16: conv M %% (Hout*Wout)");
   } else if (p.mode != 0) {
     SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: mode %d", p.mode);
@@ -1301,7 +1334,7 @@ extern "C" int sdlt_gemm_bf16(const sdlt_gemm_params* pp, void* stream) {
     case 2: rc = dispatch_tile<MODE_, 2>(p, s); break;                  \
     default: rc = dispatch_tile<MODE_, 4>(p, s); break;                 \
   }
-  if (p.mode == 0) { DISPATCH(0) } else { DISPATCH(1) }
+  if (p.mode == 0) { DISPATCH(0) } else if (p.K2) { rc = dispatch_tile<2, 0>(p, s); } else { DISPATCH(1) }
 #undef DISPATCH
   if (rc != SDLT_OK) return rc;
   SDLT_CHECK_LAUNCH();

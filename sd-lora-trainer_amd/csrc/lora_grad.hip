@@ -12,6 +12,9 @@
 // straddle a conv tap, i.e. Cin % 64 != 0, or operands that are not 16-byte aligned) fall to the VALU kernel below.
 // Keeping every dY / s*T / s*U alive until the end of the backward pass (a few GB of the 288 GB) is what lets the
 // 1154 SDXL problems share one launch.
+// Wide adapters (padded rank 128 / 192 / 256, sdlt_lora_grad_wide): the same kernels instantiated at RP = 64 with WIDE set walk the
+// rank in 64-column chunks, one chunk per blockIdx.y - the 4-wave LDS reduction stays at 64 KB (a whole rank of 256 would need 256 KB)
+// and chunks at or beyond the real rank exit before any load.
 #include "common.h"
 #include "../../include/sdlt_kernels.h"
 
@@ -30,7 +33,7 @@ __device__ __forceinline__ bf16x4_t lds_read_tr(uint32_t addr) {
   return v;
 }
 
-template <int RP>
+template <int RP, bool WIDE = false>
 __global__ __launch_bounds__(256) void lora_grad_mfma_kernel(const sdlt_lora_grad_desc* descs, const int32_t* block_desc) {
   constexpr int NR = RP / 16;                       // rank fragments
   constexpr int PT = BT * BC * 2;                   // 4 KB: P chunk, row-major [32][64]
@@ -44,12 +47,16 @@ __global__ __launch_bounds__(256) void lora_grad_mfma_kernel(const sdlt_lora_gra
   __shared__ __attribute__((aligned(16))) char smem[SMEM];
 
   const sdlt_lora_grad_desc d = descs[block_desc[blockIdx.x]];
+  // WIDE: this workgroup's rank chunk [r0, r0 + RP) of the padded rank; Rn of its ranks are real (workgroup-uniform exit before any barrier)
+  const int r0 = WIDE ? (int)blockIdx.y * RP : 0;
+  if (WIDE && r0 >= d.R) return;
+  const int Rn = WIDE ? (d.R - r0 < RP ? d.R - r0 : RP) : d.R;
   const int cb = blockIdx.x - d.first_block;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int c0 = cb * BC;
   const bf16_t* P = (const bf16_t*)d.P;
-  const bf16_t* Q = (const bf16_t*)d.Q;
+  const bf16_t* Q = (const bf16_t*)d.Q + r0;
   const bf16_t* Z = (const bf16_t*)d.zero;
 
   // conv: this block's 64 columns lie inside one tap (Cin % 64 == 0)
@@ -160,13 +167,13 @@ __global__ __launch_bounds__(256) void lora_grad_mfma_kernel(const sdlt_lora_gra
       }
   __syncthreads();
   const int R = d.R;
-  for (int e = threadIdx.x; e < BC * R; e += 256) {
+  for (int e = threadIdx.x; e < BC * Rn; e += 256) {
     int cc, r;
-    if (d.rank_major) { r = e / BC; cc = e - r * BC; } else { cc = e / R; r = e - cc * R; }
+    if (d.rank_major) { r = e / BC; cc = e - r * BC; } else { cc = e / Rn; r = e - cc * Rn; }
     const int col = c0 + cc;
     if (col < d.Cw) {
       float v = red[cc * RP + r] + red[(BC + cc) * RP + r] + red[(2 * BC + cc) * RP + r] + red[(3 * BC + cc) * RP + r];
-      float* o = d.rank_major ? d.out + (int64_t)r * d.Cw + col : d.out + (int64_t)col * R + r;
+      float* o = d.rank_major ? d.out + (int64_t)(r0 + r) * d.Cw + col : d.out + (int64_t)col * R + r0 + r;
       *o = d.accumulate ? *o + v : v;
     }
   }
@@ -174,10 +181,13 @@ __global__ __launch_bounds__(256) void lora_grad_mfma_kernel(const sdlt_lora_gra
 
 // VALU fallback (odd shapes): a thread owns one column and all Rp ranks (Rp fp32 accumulators); the wave-uniform Q row
 // goes through the scalar cache (SGPR operands of v_fmac).  The 4 waves interleave rows and are reduced through LDS.
-template <int RP>
+template <int RP, bool WIDE = false>
 __global__ __launch_bounds__(256) void lora_grad_valu_kernel(const sdlt_lora_grad_desc* descs, const int32_t* block_desc) {
   __shared__ float red[BC * (RP + 1)];
   const sdlt_lora_grad_desc d = descs[block_desc[blockIdx.x]];
+  const int r0 = WIDE ? (int)blockIdx.y * RP : 0;     // (see the MFMA kernel)
+  if (WIDE && r0 >= d.R) return;
+  const int Rn = WIDE ? (d.R - r0 < RP ? d.R - r0 : RP) : d.R;
   const int cb = blockIdx.x - d.first_block;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -187,7 +197,7 @@ __global__ __launch_bounds__(256) void lora_grad_valu_kernel(const sdlt_lora_gra
 #pragma unroll
   for (int j = 0; j < RP; ++j) a0[j] = 0.f;
   const bf16_t* P = (const bf16_t*)d.P;
-  const bf16_t* Q = (const bf16_t*)d.Q;
+  const bf16_t* Q = (const bf16_t*)d.Q + r0;
   int tap_dy = 0, tap_dx = 0, ci = 0;
   if (d.conv) {
     int tap = c / d.Cin;
@@ -228,13 +238,13 @@ __global__ __launch_bounds__(256) void lora_grad_valu_kernel(const sdlt_lora_gra
     __syncthreads();
   }
   const int R = d.R;
-  for (int e = threadIdx.x; e < BC * R; e += 256) {
+  for (int e = threadIdx.x; e < BC * Rn; e += 256) {
     int cc, r;
-    if (d.rank_major) { r = e / BC; cc = e - r * BC; } else { cc = e / R; r = e - cc * R; }
+    if (d.rank_major) { r = e / BC; cc = e - r * BC; } else { cc = e / Rn; r = e - cc * Rn; }
     const int col = cb * BC + cc;
     if (col < d.Cw) {
       float v = red[cc * (RP + 1) + r];
-      float* o = d.rank_major ? d.out + (int64_t)r * d.Cw + col : d.out + (int64_t)col * R + r;
+      float* o = d.rank_major ? d.out + (int64_t)(r0 + r) * d.Cw + col : d.out + (int64_t)col * R + r0 + r;
       *o = d.accumulate ? *o + v : v;
     }
   }
@@ -247,6 +257,18 @@ void launch(const sdlt_lora_grad_desc* descs, const int32_t* block_desc, int n_b
 }
 
 }  // namespace
+
+extern "C" int sdlt_lora_grad_wide(const sdlt_lora_grad_desc* descs_dev, const int32_t* block_desc_dev,
+                                   int32_t n_blocks, int32_t Rp, int32_t mfma, void* stream) {
+  if (n_blocks <= 0) SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_lora_grad_wide: n_blocks=%d", n_blocks);
+  if (Rp != 128 && Rp != 192 && Rp != 256) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_lora_grad_wide: padded rank %d (128/192/256)", Rp);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(n_blocks, Rp / 64);
+  if (mfma) hipLaunchKernelGGL((lora_grad_mfma_kernel<64, true>), grid, dim3(256), 0, s, descs_dev, block_desc_dev);
+  else hipLaunchKernelGGL((lora_grad_valu_kernel<64, true>), grid, dim3(256), 0, s, descs_dev, block_desc_dev);
+  SDLT_CHECK_LAUNCH();
+  return SDLT_OK;
+}
 
 extern "C" int32_t sdlt_lora_grad_block_cols(void) { return BC; }
 

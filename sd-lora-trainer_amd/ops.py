@@ -289,8 +289,11 @@ def gemm_emits_parts(M, N, K, lora_rank_pad=0, W=None, dora=False):
 
 def gemm(X, W, out, *, X2=None, W2=None, conv=None, lora=None, bias=None, rowbias=None, rows_per_batch=0,
          residual=None, alpha=1.0, Ct=None, tile=0, splitk=0, stages=0, accumulate=False, lora_group_n=0, lora_group_k=0, batch=None,
-         geglu_out=None, geglu_bwd=None, act_out=None, dact_in=None, col_scale=None, ln=None, ln_parts_out=None, rowdot=None, out0=None):
+         geglu_out=None, geglu_bwd=None, act_out=None, dact_in=None, col_scale=None, ln=None, ln_parts_out=None, rowdot=None, out0=None,
+         x2_group_n=0):
     """out[M,N] = alpha*col_scale[n]*(X.W^T [+ X2.W2^T] [+ s*(X.Adown^T).Bup^T]) + bias + rowbias[m//rows_per_batch] + residual.
+    X2 [M, K2] / W2 [N, K2]: second K segment (also behind a convolution, `conv`; no adapter with it).  x2_group_n > 0: grouped second
+    segment - W is a stack of G = N / x2_group_n projections, X2 [M, G*K2], output column n reads X2 columns of group n // x2_group_n.
     out0 [M,N] (with residual, adapter launches): ALSO the value before the residual (DoRA: the magnitude gradient reads the layer's own output) - one launch where the
     product runs on the wave-split-K kernel (sdlt_wsk_gemm_params.Y0), otherwise the product into out0 and an add2d launch.
     col_scale fp32 [N]: DoRA's magnitude / norm factor (adapter launches only; DoraPlan keeps it up to date).
@@ -316,6 +319,9 @@ def gemm(X, W, out, *, X2=None, W2=None, conv=None, lora=None, bias=None, rowbia
     describe problem 0 (shapes, strides, options), every problem's operand pointers come from the batch."""
     lib = _lib.load()
     rp_ = lora[0].shape[0] if lora is not None else 0
+    # wide adapters (padded rank > 64) never reach the fused forms: unet.LoraArena.wide decomposes them into plain / second-segment products
+    assert lora is None or (lora[0].shape[0] if lora_group_k else lora[1].shape[1]) <= 64, "fused adapter products exist for rank pads 16 / 32 / 64"
+    assert X2 is None or lora is None, "a second K segment excludes the fused adapter"
     if out0 is not None:
         assert residual is not None and lora is not None and Ct is None and ln is None and geglu_out is None and act_out is None and tuple(out0.shape) == tuple(out.shape)
     if (WSK and conv is None and X2 is None and rowbias is None and alpha == 1.0 and Ct is None and batch is None and geglu_out is None
@@ -463,8 +469,15 @@ def gemm(X, W, out, *, X2=None, W2=None, conv=None, lora=None, bias=None, rowbia
     p.throughput_hint = int(THROUGHPUT_HINT)
     if X2 is not None:
         _chk2(X2), _chk2(W2)
-        assert X2.shape[0] == M and W2.shape[0] == N and X2.shape[1] == W2.shape[1]
-        p.X2, p.ldx2, p.W2, p.ldw2, p.K2 = _p(X2), _ld(X2), _p(W2), _ld(W2), X2.shape[1]
+        G2 = 1
+        if x2_group_n:
+            assert conv is None and batch is None and N % x2_group_n == 0
+            G2 = N // x2_group_n
+            p.x2_group_n = x2_group_n
+        assert X2.shape[0] == M and W2.shape[0] == N and X2.shape[1] == G2 * W2.shape[1], (X2.shape, W2.shape, x2_group_n)
+        p.X2, p.ldx2, p.W2, p.ldw2, p.K2 = _p(X2), _ld(X2), _p(W2), _ld(W2), W2.shape[1]
+    else:
+        assert not x2_group_n
     if lora is not None:
         Adown, Bup, scale, T_out = lora
         _chk2(Adown), _chk2(Bup)
@@ -863,6 +876,7 @@ class LoraGradPlan:
             block_desc += [i] * blocks
             nb += blocks
             self.keep += [P, Q, out]
+        assert Rp in (16, 32, 64, 128, 192, 256), Rp
         self.n_blocks, self.Rp, self.mfma = nb, Rp, int(mfma)
         raw = bytes(descs)
         self.descs_dev = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
@@ -876,6 +890,10 @@ class LoraGradPlan:
 
     def run(self):
         lib = _lib.load()
+        if self.Rp > 64:      # wide adapters: the rank is walked in 64-column chunks (grid n_blocks x Rp/64)
+            _lib.check(lib.sdlt_lora_grad_wide(_p(self.descs_dev), _p(self.block_desc_dev), self.n_blocks, self.Rp, self.mfma, _stream()),
+                       "sdlt_lora_grad_wide")
+            return
         _lib.check(lib.sdlt_lora_grad_grouped(_p(self.descs_dev), _p(self.block_desc_dev), self.n_blocks, self.Rp, self.mfma, _stream()),
                    "sdlt_lora_grad_grouped")
 

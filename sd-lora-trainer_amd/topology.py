@@ -207,7 +207,7 @@ def hbm_bytes(cfg, B, H, W, rank=16, n_ctx=77):
       lora_grad  the rows the grouped dA / dB launch contracts over tokens: dY [M,N] + T [M,r] and X [M,K] + U [M,r] per adapter
     """
     tot = {"groupnorm": 0.0, "layernorm": 0.0, "geglu": 0.0, "lora_grad": 0.0}
-    Rp = 16 if rank <= 16 else (32 if rank <= 32 else 64)
+    Rp = 16 if rank <= 16 else (32 if rank <= 32 else 64 * ((rank + 63) // 64))
 
     def px(lvl):
         return B * (H >> lvl) * (W >> lvl)

@@ -36,6 +36,22 @@ def _pad_to(x, m):
 
 XATTN_WGS = int(os.environ.get("SDLT_XATTN_WGS", "160"))     # workgroups of a cross-attention backward launch (query splits x heads x batch)
 
+# Wide adapters (DESIGN, "Wide LoRA ranks"): T = s X A^T is its own launch and the up-projection T B^T runs as the second K segment of
+# the base product, instead of the fused in-tile form of the rank pads 16 / 32 / 64.  Padded ranks at or above this value take it (every
+# rank > 64 does); 16, 32 or 64 force it for the narrower ranks (A/B of the two decompositions).
+LORA_WIDE_MIN = int(os.environ.get("SDLT_LORA_WIDE_MIN", "128"))
+LORA_MAX_RANK = 256
+
+
+def padded_rank(rank):
+    """Rank pad of the adapter kernels: 16 / 32 / 64 (fused forms) up to rank 64, then the next multiple of 64 (wide path)."""
+    if rank <= 64:
+        return 16 if rank <= 16 else (32 if rank <= 32 else 64)
+    if rank > LORA_MAX_RANK:
+        raise ValueError(f"LoRA rank {rank} > {LORA_MAX_RANK} is not supported")
+    return 64 * ((rank + 63) // 64)
+
+
 class Runtime:
     """Execution context shared by all layers: device, batch, activation dtype and the op table."""
 
@@ -146,8 +162,14 @@ class LoraArena:
         # LoRA-gradient problems of the adapters in this arena, appended by the layers on their first backward.  The UNet
         # arena shares the runtime's list; the text-encoder arena (step.TextStack) keeps its own, run after the text backward.
         self.problems = rt.lora_problems if problems is None else problems
-        self.Rp = 16 if rank <= 16 else (32 if rank <= 32 else 64)
-        assert rank <= 64, "LoRA rank > 64 not supported by the fused kernels"
+        if rank < 1 or rank > LORA_MAX_RANK:
+            raise ValueError(f"LoRA rank {rank}: supported ranks are 1..{LORA_MAX_RANK}")
+        if self.dora and rank > 64:
+            raise NotImplementedError(f"DoRA (use_dora) with LoRA rank {rank} > 64 is not supported: the DoRA kernels exist for rank pads 16 / 32 / 64")
+        self.Rp = padded_rank(rank)
+        # wide path: T and the up-projection as separate products (LORA_WIDE_MIN); DoRA keeps the fused form
+        self.wide = not self.dora and (self.Rp > 64 or self.Rp >= LORA_WIDE_MIN)
+        self.Wu = max(64, self.Rp)    # channel width of the conv adapters' dX operand Ab_s [Cin, 9 * Wu]
         self.scale = (rank * alpha_multiplier) / rank  # peft: lora_alpha / r, lora_alpha = r * multiplier (optimizer.py:88)
         self.entries = []   # dict(name, kind, offA, offB, N, K, conv)
         self.n = 0
@@ -170,7 +192,7 @@ class LoraArena:
         if conv_cin is None:
             e["At_s"] = rt.zeros(K, Rp)     # backward LoRA-up operand         [K, Rp]
         else:
-            e["Ab_s"] = rt.zeros(conv_cin, 9 * 64)  # dX weights of the 3x3 LoRA-down conv: [Cin, tap*64 + rank]
+            e["Ab_s"] = rt.zeros(conv_cin, 9 * self.Wu)  # dX weights of the 3x3 LoRA-down conv: [Cin, tap*Wu + rank]
         self.entries.append(e)
         return e
 
@@ -196,8 +218,9 @@ class LoraArena:
             else:
                 cin = e["conv_cin"]
                 sh.append((e["offA"], r, K, K, e["A_s"], None))
-                for tap in range(9):   # A[:, tap, :] ([r, Cin], row stride 9*Cin) -> Ab[ci, tap*64 + rank]
-                    sh.append((e["offA"] + tap * cin, r, cin, K, None, e["Ab_s"][:, tap * 64: tap * 64 + 64]))
+                wu = self.Wu
+                for tap in range(9):   # A[:, tap, :] ([r, Cin], row stride 9*Cin) -> Ab[ci, tap*Wu + rank]
+                    sh.append((e["offA"] + tap * cin, r, cin, K, None, e["Ab_s"][:, tap * wu: tap * wu + wu]))
             sh.append((e["offB"], N, r, r, e["B_s"], None if self.dora else e["Bt_s"]))      # DoRA: B^T is written scaled by the refresh
             e["A"] = self.params[e["offA"]: e["offA"] + r * K].view(r, K)
             e["B"] = self.params[e["offB"]: e["offB"] + N * r].view(N, r)
@@ -348,7 +371,7 @@ class Linear(_Module):
         row order of self.W.  keep_plain: the unfolded operand stays too (forward(..., unfolded=True) on the output of the LayerNorm launch) - for the
         consumer whose fold only pays when the producer left row partials (ff.net.0.proj, 26 MB per block of 288 GB)."""
         rt = self.rt
-        assert self.trainer is None and not self.dora and (self.lora is None or self.arena.Rp == 16)
+        assert self.trainer is None and not self.dora and (self.lora is None or (self.arena.Rp == 16 and not self.arena.wide))
         if keep_plain:
             assert self.lora is None
             self.W_plain, self.bias_plain = self.W, self.bias
@@ -370,6 +393,8 @@ class Linear(_Module):
         that LayerNorm's row partials (ops.gemm ln_parts_out), so the consumer GEMM has no statistics to compute."""
         M = x.shape[0]
         y = out if out is not None else self.buf(key, M, self.N)
+        if self.lora is not None and self.arena.wide:
+            return self._forward_wide(x, y, residual=residual, Ct=Ct, geglu_out=geglu_out, act_out=act_out, parts_for=parts_for)
         lora, ln = None, None
         if self.lora is not None:
             T = self.buf("T", M, self.arena.Rp) if train else None
@@ -420,10 +445,44 @@ class Linear(_Module):
             self.rt.ops.gemm(x, W, y, lora=lora, bias=bias, residual=residual, Ct=Ct, **kw)
         return y
 
+    def _forward_wide(self, x, y, *, residual, Ct, geglu_out, act_out, parts_for):
+        """Wide adapter: T = s X A^T [M, Rp] (one launch), then y = X W^T + T B^T (+ bias, residual) with the up-projection as the second
+        K segment of the base product.  Never the wave-split-K kernel (a second segment excludes it) nor a folded LayerNorm."""
+        assert self.ln is None and not self.dora and self.trainer is None, "wide adapters: no folded LayerNorm / DoRA / full fine-tune"
+        ops, M = self.rt.ops, x.shape[0]
+        T = self.buf("T", M, self.arena.Rp)
+        self._x = x
+        if parts_for is not None:
+            parts_for._parts = None
+        ops.gemm(x, self.lora["A_s"], T, alpha=self.arena.scale)
+        kw = {}
+        if geglu_out is not None:
+            kw["geglu_out"] = geglu_out
+        if act_out is not None:
+            kw["act_out"] = act_out
+        ops.gemm(x, self.W, y, X2=T, W2=self.lora["B_s"], bias=self.bias, residual=residual, Ct=Ct, **kw)
+        return y
+
+    def _register_grads(self, dy, U):
+        if not getattr(self, "_registered", False):
+            r = self.arena.rank
+            self.arena.problems += [
+                dict(P=dy, Q=self._b["T"], out=self.lora["gB"], M=dy.shape[0], Cw=self.N, R=r, rank_major=False),
+                dict(P=self._x, Q=U, out=self.lora["gA"], M=dy.shape[0], Cw=self.K, R=r, rank_major=True)]
+            self._registered = True
+
     def backward(self, dy, *, dres=None, Ct=None, key="dx", out=None, dact_in=None, rowdot=None):
         """rowdot: see ops.gemm (attn1.to_out.0: the attention backward's row term as a side output of this dX product)."""
         M = dy.shape[0]
         dx = out if out is not None else self.buf(key, M, self.K)
+        if self.lora is not None and self.arena.wide:
+            # U = s dY B [M, Rp], then dx = dY W + U A (+ dres) with A^T as the second segment (rowdot: left to the attention's pre-pass)
+            U = self.buf("U", M, self.arena.Rp)
+            self._register_grads(dy, U)
+            self.rt.ops.gemm(dy, self.lora["Bt_s"], U, alpha=self.arena.scale)
+            kw = {"dact_in": dact_in} if dact_in is not None else {}
+            self.rt.ops.gemm(dy, self.Wt, dx, X2=U, W2=self.lora["At_s"], residual=dres, Ct=Ct, **kw)
+            return dx
         lora = None
         if self.lora is not None:
             U = self.buf("U", M, self.arena.Rp)
@@ -493,7 +552,9 @@ class StackedLinear(_Module):
                 m.lora["A_s"] = self.A_cat[g * Rp:(g + 1) * Rp]
                 m.lora["B_s"] = self.B_cat[g * N:(g + 1) * N]
             # backward operands of the K-grouped dX GEMM: the members' B^T side by side, their A^T side by side
-            self.kgrouped = self.G <= 4 and N % 64 == 0
+            # (wide adapters: the same operands; dx = dY_cat W_cat + U_cat A_cat is a plain second segment, any G / N)
+            self.wide = self.arena.wide
+            self.kgrouped = self.wide or (self.G <= 4 and N % 64 == 0)
             if self.kgrouped:
                 self.Bt_cat, self.At_cat = rt.zeros(Rp, self.G * N), rt.zeros(K, self.G * Rp)
                 for g, m in enumerate(members):
@@ -510,11 +571,12 @@ class StackedLinear(_Module):
                     self.arena.dora_wts.append(dict(src=self.Wt, dst=self.Wt_d, entries=[m.lora for m in members]))
 
     ln = None
+    wide = False
 
     def fold_ln(self, norm, w32s):
         """Linear.fold_ln for the stack (w32s: the members' fp32 weights): one folded operand, one adapter-constant block per member."""
         rt = self.rt
-        assert self.trainer is None and not self.dora and (not self.has_lora or self.arena.Rp == 16)
+        assert self.trainer is None and not self.dora and (not self.has_lora or (self.arena.Rp == 16 and not self.arena.wide))
         N = self.N
         if getattr(self, "Wt", None) is None:      # the dX operand is built lazily from W: take it from the UNFOLDED weights now
             self.Wt = self.W.t().contiguous()
@@ -557,6 +619,20 @@ class StackedLinear(_Module):
     def forward(self, x, Ct=None):
         """Returns the member outputs as column slices of one [M, G*N] buffer."""
         y, T, outs = self.prepare(x)
+        if self.has_lora and self.wide:
+            # T_cat = s X A_cat^T for every member in one launch, then y = X W_cat^T + the grouped second segment: output column group g reads
+            # T columns [g Rp, (g+1) Rp) against B_cat's rows of that group (sdlt_gemm_params.x2_group_n; member-wise where N is not 64-aligned)
+            assert self.ln is None and not self.dora
+            ops, N, Rp = self.rt.ops, self.N, self.arena.Rp
+            ops.gemm(x, self.A_cat, T, alpha=self.arena.scale)
+            if N % 64 == 0:
+                ops.gemm(x, self.W, y, X2=T, W2=self.B_cat, x2_group_n=N, bias=self.bias, Ct=Ct)
+            else:
+                for g in range(self.G):
+                    cols = slice(g * N, (g + 1) * N)
+                    ops.gemm(x, self.W[cols], y[:, cols], X2=T[:, g * Rp:(g + 1) * Rp], W2=self.B_cat[cols],
+                             bias=self.bias[cols] if self.bias is not None else None, Ct=Ct[cols] if Ct is not None else None)
+            return outs
         lora = (self.A_cat if self.ln is None else self.ln_Ag, self.B_cat, self.arena.scale, T) if self.has_lora else None
         kw = {"col_scale": self.col_scale()} if self.dora else {}
         if self.ln is not None:
@@ -588,6 +664,13 @@ class StackedLinear(_Module):
             return dx
         assert self.kgrouped
         U = self.backward_operands(dy_cat)
+        if self.wide:
+            # U_g = s dY_g B_g per member (K-grouped: G launches), then dx = dY_cat W_cat^T + U_cat A_cat as ONE product with a plain second segment
+            Rp = self.arena.Rp
+            for g in range(G):
+                self.rt.ops.gemm(dy_cat[:, g * N:(g + 1) * N], self.Bt_cat[:, g * N:(g + 1) * N], U[:, g * Rp:(g + 1) * Rp], alpha=self.arena.scale)
+            self.rt.ops.gemm(dy_cat, self.Wt, dx, X2=U, W2=self.At_cat, residual=dres)
+            return dx
         self.rt.ops.gemm(dy_cat, self.Wt_d if self.dora else self.Wt, dx, lora=(self.Bt_cat, self.At_cat, self.arena.scale, U), residual=dres, lora_group_k=N)
         return dx
 
@@ -672,12 +755,20 @@ class Conv3x3(_Module):
         y = out if out is not None else self.buf(key, M, self.Cout)
         lora = None
         if self.lora is not None:
-            T = self.buf("T", M, self.arena.Rp) if train else None
+            T = self.buf("T", M, self.arena.Rp) if (train or self.arena.wide) else None
             lora = (self.lora["A_s"], self.lora["B_s"], self.arena.scale, T)
             self._x, self._g = x, g
         if self.trainer is not None:
             self._x = x
         self._dims = (B, H, W, Hout, Wout)
+        if self.lora is not None and self.arena.wide:
+            # wide adapter: T = conv3x3(X, s A) [M, Rp] (mode-1 product with N = Rp), then y = conv3x3(X, W) + T B^T in ONE launch
+            # (a convolution followed by a plain second K segment; split-K walks both)
+            assert not self.dora and self.stride == 1 and self.ups == 1
+            self.rt.ops.gemm(x, self.lora["A_s"], T, conv=g, alpha=self.arena.scale)
+            self.rt.ops.gemm(x, self.Wf, y, conv=g, X2=T, W2=self.lora["B_s"], bias=self.bias, rowbias=rowbias, rows_per_batch=Hout * Wout,
+                             residual=residual)
+            return y
         if self.dora:       # see Linear.forward
             assert rowbias is None
             y0 = y if residual is None else self.buf(key + "0", M, self.Cout)
@@ -708,12 +799,13 @@ class Conv3x3(_Module):
         if self.lora is None:
             return rt.ops.gemm(dy, self.Wb, dx, conv=gb, residual=dres)
         # LoRA conv (stride 1): U = s * dy . Bup (per pixel);  dx = convT(dy, W) + convT(U, A) (+ dres)
-        M = B * Hout * Wout
-        U64 = self.buf("U64", M, 64, zero=True)
+        # (wide adapters: the same three launches with Wu = Rp channels; DESIGN "Wide LoRA ranks" says why not one fused second conv segment)
+        M, wu = B * Hout * Wout, self.arena.Wu
+        U64 = self.buf("U64", M, wu, zero=True)
         U = U64[:, : self.arena.Rp]
         rt.ops.gemm(dy, self.lora["Bt_s"], U, alpha=self.arena.scale)
         rt.ops.gemm(dy, self.Wb_d if self.dora else self.Wb, dx, conv=gb, residual=dres)
-        rt.ops.gemm(U64, self.lora["Ab_s"], dx, conv=_ops.ConvGeom(B, Hout, Wout, 64, H, W, flip=1), residual=dx)
+        rt.ops.gemm(U64, self.lora["Ab_s"], dx, conv=_ops.ConvGeom(B, Hout, Wout, wu, H, W, flip=1), residual=dx)
         if not getattr(self, "_registered", False):
             r = self.arena.rank
             self.arena.problems += [
@@ -873,6 +965,7 @@ class Attention(_Module):
         # self-attention whose to_out.0 input gradient runs on the wave-split-K kernel: that product leaves the backward's row term D = rowsum(dO o O) as a side output
         # (no D pre-pass launch); its slots are cleared here, by the forward kernel's epilogue
         self._rowdot = (not self.cross and getattr(self, "_rowdot_ok", True) and self.to_out.trainer is None
+                        and not (self.to_out.lora is not None and self.to_out.arena.wide)
                         and getattr(rt.ops, "wsk_rowdot_shape", None) is not None and rt.ops.wsk_rowdot_shape(Mq, C, C, self.to_out.lora is not None, self.d))
         kwz = {"zero_D": self.buf("D", B * self.heads * N, dtype=F32)} if self._rowdot else {}
         rt.ops.attn_fwd(q, k, v, None, O, L, B=B, H=self.heads, Nq=N, Nk=Nk, Nqp=N, Nkp=Nkp, d=self.d, scale=self.scale, **kwz)
@@ -1004,9 +1097,9 @@ class TransformerBlock(_Module):
             w = lambda n: sd[n + ".weight"].float()
             a1 = self.attn1
             ok = lambda l: l.trainer is None and not l.dora        # (the folded kernel variants exist for rank-16 adapter products and for ff.net.0.proj + GEGLU)
-            if (LN_FOLD & 1) and arena.Rp == 16 and ok(a1.to_q):
+            if (LN_FOLD & 1) and arena.Rp == 16 and not arena.wide and ok(a1.to_q):
                 a1.stack.fold_ln(self.norm1, [w(m.name) for m in a1.stack.members])
-            if (LN_FOLD & 2) and arena.Rp == 16 and ok(self.attn2.to_q):
+            if (LN_FOLD & 2) and arena.Rp == 16 and not arena.wide and ok(self.attn2.to_q):
                 self.attn2.to_q.fold_ln(self.norm2, w(self.attn2.to_q.name))
             if self.fused_geglu and (LN_FOLD & 4) and ok(self.ff1):      # (no adapter on ff.net.0.proj: any rank, DoRA too - round 6)
                 w3 = w(self.ff1.name).to(rt.device)
@@ -1212,7 +1305,7 @@ class UNet(_Module):
         # group in forward, and one for all their input gradients in backward (instead of 2 x 70 M = 128 GEMMs)
         tfs = [t for (_, att, _) in self.down for t in att] + [self.mid[1]] + [t for (_, att, _) in self.up for t in att]
         self.cross_attns = [blk.attn2 for t in tfs for blk in t.blocks]
-        ok = all(a.stack.has_lora and a.stack.kgrouped for a in self.cross_attns) and len(self.cross_attns) > 1
+        ok = all(a.stack.has_lora and a.stack.kgrouped and not a.stack.wide for a in self.cross_attns) and len(self.cross_attns) > 1
         self._kv_groups = None
         for a in self.cross_attns:
             a.kv_batched = ok
