@@ -20,7 +20,7 @@ extern "C" {
 
 const char* sdlt_last_error(void);
 int sdlt_abi_version(void);
-int sdlt_struct_size(int which); /* 0 gemm, 1 lora_grad_desc, 2 attn, 3 groupnorm, 4 shadow_desc, 5 gemm_batch_item, 6 dora_desc, 7 dora_wt_desc, 8 dora_grad_desc, 9 splitsum_desc */
+int sdlt_struct_size(int which); /* 0 gemm, 1 lora_grad_desc, 2 attn, 3 groupnorm, 4 shadow_desc, 5 gemm_batch_item, 6 dora_desc, 7 dora_wt_desc, 8 dora_grad_desc, 9 splitsum_desc ... 19 merge_desc */
 
 /* ------------------------------------------------------------------------------------------------
  * sdlt_gemm_bf16 : C = alpha*(X.W^T [+ X2.W2^T] [+ s*(X.Adown^T).Bup^T]) + bias + rowbias + R
@@ -469,6 +469,30 @@ int sdlt_dora_scale_wt(const sdlt_dora_wt_desc* descs_dev, const int32_t* block_
                        void* stream);
 int sdlt_dora_mag_grad(const sdlt_dora_grad_desc* descs_dev, const int32_t* block_desc_dev, const int32_t* block_first_dev, int32_t n_blocks,
                        const int32_t* fin_block_desc_dev, const int32_t* fin_block_first_dev, int32_t n_fin_blocks, float* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------------------ adapter merge
+ * sdlt_lora_merge : the trained adapters baked into the base weights (export of a standalone model; the reference's inference script
+ * calls `pipe.fuse_lora()`, scripts/test_inference.py:53), every adapted layer of an arena in one launch over a descriptor table:
+ *     LoRA (phase 0):      out = W + s B A
+ *     DoRA (phase 1, 2):   out = (mag[n] / ||W_n + s B_n A||) (W_n + s B_n A)   (peft _apply_dora, per output row n)
+ * W [N, K] in w_dtype (0 bf16, 1 fp16, 2 fp32; 3x3 conv: the tap-major [Cout, 9 Cin] layout of the arena), A [rank, K] and B [N, rank] the
+ * fp32 masters (rank <= 256), out [N, K] in out_dtype (same codes), rounded once; products accumulate in fp32.  One workgroup per 64 x 64 tile:
+ * layer d owns ceil(N / 64) * ceil(K / 64) consecutive blocks (block_desc[b] = descriptor of block b, block_first[d] = its first block).
+ * DoRA runs the same table twice: phase 1 writes the tiles' fp32 row sums of squares to ws [N, ceil(K / 64)] (out untouched), phase 2 adds
+ * them in tile order and writes the scaled rows.  mag / ws are read only by the DoRA phases. */
+typedef struct sdlt_merge_desc {
+  const void* W; int64_t ldw;
+  const float* A; int64_t lda;
+  const float* B; int64_t ldb;
+  const float* mag;                  /* fp32 [N] (DoRA) or NULL */
+  float* ws;                         /* fp32 [N, ceil(K / 64)] (DoRA) or NULL */
+  void* out; int64_t ldo;
+  int32_t N, K, rank, w_dtype;
+  float s;                           /* lora_alpha / r times the render scale */
+  int32_t pad_;
+} sdlt_merge_desc;
+int sdlt_lora_merge(const sdlt_merge_desc* descs_dev, const int32_t* block_desc_dev, const int32_t* block_first_dev, int32_t n_blocks,
+                    int32_t out_dtype, int32_t phase, void* stream);
 
 /* out[M,C] = a + b on strided 2-D bf16 views (gradient fan-in of the UNet skip connections). */
 int sdlt_add2d(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int32_t M, int32_t C, void* stream);

@@ -16,6 +16,7 @@ the name diffusers' convert_state_dict_to_kohya and the kohya / ComfyUI loaders 
 """
 import json
 import os
+import shutil
 
 import torch
 from safetensors.torch import load_file, save_file
@@ -102,6 +103,55 @@ def save_checkpoint(output_dir, global_step, arena, ti_rows, token_dict, name, p
             json.dump(topology.diffusers_unet_config(topology.CONFIGS[pretrained_model_version]), f, indent=2, sort_keys=True)
     if config is not None:
         config.save_as_json(os.path.join(output_dir, "training_args.json"))
+    return files
+
+
+TEXT_PREFIXES = ("text_encoder.", "text_encoder_2.")
+TEXT_DIRS = ("text_encoder", "text_encoder_2")
+
+
+def save_merged(output_dir, base_sd, arena, pretrained_model_version, *, scale=1.0, text_arena=None, te_base_sds=None, dtype=torch.bfloat16,
+                checkpoint_dir=None):
+    """A standalone model with the adapters merged in (LoraArena.merged, sdlt_lora_merge) - the `pipe.fuse_lora()` of the reference's
+    inference script (scripts/test_inference.py:53):
+      diffusion_pytorch_model.safetensors + config.json   the full fine-tune writer's format (save_checkpoint's unet_weights): EVERY tensor of
+                                                           base_sd under its own name, adapted ones merged, the others cast to `dtype`
+      text_encoder[_2]/model.safetensors                   (text_arena) the same for the Hugging Face text-encoder state dicts te_base_sds
+      *_embeddings.safetensors, special_params.json        copied unchanged from checkpoint_dir (the TI tokens are not merged)
+    The UNet file loads back as `pretrained_model["path"]` of a train() job and through unet.UNet(rt, cfg, sd) without adapters."""
+    from . import topology
+    os.makedirs(output_dir, exist_ok=True)
+    files = {}
+
+    def write(sd, merged, path):
+        out = {}
+        for k, v in sd.items():
+            t = merged[k] if k in merged else v
+            out[k] = t.detach().to("cpu", dtype).contiguous()
+        save_file(out, path)
+        return path
+
+    m = arena.merged(base_sd, scale=scale, dtype=dtype)
+    assert set(m) <= set(base_sd), sorted(set(m) - set(base_sd))[:4]
+    files["unet"] = write(base_sd, m, os.path.join(output_dir, "diffusion_pytorch_model.safetensors"))
+    del m
+    with open(os.path.join(output_dir, "config.json"), "w") as f:
+        json.dump(topology.diffusers_unet_config(topology.CONFIGS[pretrained_model_version]), f, indent=2, sort_keys=True)
+    if text_arena is not None:
+        assert te_base_sds, "text-encoder adapters need the text encoders' base state dicts"
+        view = {}
+        for pre, sd in zip(TEXT_PREFIXES, te_base_sds):
+            view.update({pre + k: v for k, v in sd.items()})
+        m = text_arena.merged(view, scale=scale, dtype=dtype)
+        for i, (pre, d, sd) in enumerate(zip(TEXT_PREFIXES, TEXT_DIRS, te_base_sds)):
+            os.makedirs(os.path.join(output_dir, d), exist_ok=True)
+            mi = {k[len(pre):]: v for k, v in m.items() if k.startswith(pre)}
+            files[d] = write(sd, mi, os.path.join(output_dir, d, "model.safetensors"))
+    if checkpoint_dir is not None:
+        for f in sorted(os.listdir(checkpoint_dir)):
+            if f.endswith("_embeddings.safetensors") or f == "special_params.json":
+                shutil.copy(os.path.join(checkpoint_dir, f), os.path.join(output_dir, f))
+                files[f] = os.path.join(output_dir, f)
     return files
 
 

@@ -39,6 +39,7 @@ extern "C" int sdlt_struct_size(int which) {
     case 16: return (int)sizeof(sdlt_ln_fold_desc);
     case 17: return (int)sizeof(sdlt_colsum_finish_desc);
     case 18: return (int)sizeof(sdlt_wsk_gemm_params);
+    case 19: return (int)sizeof(sdlt_merge_desc);
   }
   return -1;
 }

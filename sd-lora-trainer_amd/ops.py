@@ -1403,6 +1403,55 @@ class DoraPlan:
                                                       self.nb_g2, _p(self.ws), _stream()), "sdlt_dora_mag_grad")
 
 
+MERGE_DTYPES = {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}
+
+
+class MergePlan:
+    """Descriptor table of sdlt_lora_merge: every adapted layer of an arena merged into its base weight, one launch for all of them (DoRA: two -
+    the row norms of the merged values, then the scaled rows).  layers: dict(W [N, K] bf16 / fp16 / fp32 (3x3 conv: tap-major), A fp32 [rank, K],
+    B fp32 [N, rank] (the arena's masters), out [N, K] in out_dtype, s, mag fp32 [N] (DoRA) or None); all on `device`, unit column stride."""
+
+    def __init__(self, layers, out_dtype, device):
+        self.keep, self.device = layers, device
+        self.out_dtype = MERGE_DTYPES[out_dtype]
+        kinds = {L.get("mag") is not None for L in layers}
+        assert len(kinds) <= 1, "a merge plan is all LoRA or all DoRA"
+        self.dora = kinds == {True}
+        arr = (_lib.MergeDesc * max(len(layers), 1))()
+        counts, ws_off = [], []
+        off = 0
+        for L in layers:
+            N, K = L["W"].shape
+            tk = (K + 63) // 64
+            counts.append(((N + 63) // 64) * tk)
+            ws_off.append(off)
+            off += N * tk if self.dora else 0
+        self.ws = torch.empty(max(off, 1), dtype=F32, device=device) if self.dora else None
+        for d, L, wo in zip(arr, layers, ws_off):
+            W, A, B, out = L["W"], L["A"], L["B"], L["out"]
+            _chk2(W, W.dtype), _chk2(A, F32), _chk2(B, F32), _chk2(out, out_dtype)
+            assert W.dtype in MERGE_DTYPES, W.dtype
+            N, K = W.shape
+            r = A.shape[0]
+            assert 1 <= r <= 256 and tuple(A.shape) == (r, K) and tuple(B.shape) == (N, r) and tuple(out.shape) == (N, K), (W.shape, A.shape, B.shape, out.shape)
+            d.W, d.ldw, d.A, d.lda, d.B, d.ldb, d.out, d.ldo = _p(W), _ld(W), _p(A), _ld(A), _p(B), _ld(B), _p(out), _ld(out)
+            d.N, d.K, d.rank, d.w_dtype, d.s = N, K, r, MERGE_DTYPES[W.dtype], float(L["s"])
+            if self.dora:
+                mag = L["mag"]
+                _chk2(mag, F32)
+                assert mag.numel() == N and mag.is_contiguous()
+                d.mag, d.ws = _p(mag), self.ws.data_ptr() + 4 * wo
+        self.n_blocks, self.bd, self.bf = _block_table(counts, device)
+        self.dev = _to_dev(arr, device)
+
+    def run(self):
+        if not self.n_blocks:
+            return
+        lib = _lib.load()
+        for phase in ((1, 2) if self.dora else (0,)):
+            _lib.check(lib.sdlt_lora_merge(_p(self.dev), _p(self.bd), _p(self.bf), self.n_blocks, self.out_dtype, phase, _stream()), "sdlt_lora_merge")
+
+
 def _shadow_adamw(self, p, g, m, v, hyper):
     """AdamW step fused into the refresh tiles (sdlt_adamw_shadow_refresh); covers exactly the elements the plan's descriptors tile."""
     lib = _lib.load()

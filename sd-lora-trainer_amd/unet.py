@@ -171,6 +171,7 @@ class LoraArena:
         self.wide = not self.dora and (self.Rp > 64 or self.Rp >= LORA_WIDE_MIN)
         self.Wu = max(64, self.Rp)    # channel width of the conv adapters' dX operand Ab_s [Cin, 9 * Wu]
         self.scale = (rank * alpha_multiplier) / rank  # peft: lora_alpha / r, lora_alpha = r * multiplier (optimizer.py:88)
+        self.alpha_scale = self.scale                  # lora_alpha / r as trained (set_scale moves `scale` only; merged() starts from this)
         self.entries = []   # dict(name, kind, offA, offB, N, K, conv)
         self.n = 0
         self._shadow_entries = []
@@ -294,6 +295,40 @@ class LoraArena:
             e["A"].copy_(A.to(self.rt.device, F32))
             e["B"].copy_(B.to(self.rt.device, F32))
         self.refresh_shadows()
+
+    def merged(self, base_sd, scale=1.0, dtype=torch.bfloat16):
+        """The adapters baked into the base weights (export of a standalone model): {weight name: merged tensor} for every adapted layer,
+        W' = W + s B A (DoRA: (m / ||W + s B A||_row) (W + s B A)), s = lora_alpha / r * scale (`scale`: the render scale of
+        sampler.LatentSampler.set_lora_scale).  W comes from the CALLER's state dict `base_sd` (the engine's forward operands may be folded,
+        stacked or rounded); the text-encoder arena looks its entries up under their prefixed names ("text_encoder.<Hugging Face name>",
+        "text_encoder_2.<...>": checkpoint.save_merged builds that view).  One sdlt_lora_merge launch over all layers (DoRA: two) on the fp32
+        masters; nothing of the training state (params, moments, shadows, DoRA factors, `scale`) changes.  Returned tensors live on the device
+        in `dtype`, in the base weight's shape (3x3 conv: [Cout, Cin, 3, 3] as a view of the tap-major result)."""
+        rt = self.rt
+        s = self.alpha_scale * float(scale)
+        layers, result = [], {}
+        for e in self.entries:
+            key = e["name"] + ".weight"
+            w = base_sd[key]
+            N, K = e["N"], e["K"]
+            if e["conv_cin"] is not None:
+                assert tuple(w.shape) == (N, e["conv_cin"], 3, 3), (key, tuple(w.shape))
+                w = w.to(rt.device).permute(0, 2, 3, 1).reshape(N, K)      # tap-major [Cout, (tap, ci)], the arena's A layout
+            else:
+                assert w.numel() == N * K and w.shape[0] == N, (key, tuple(w.shape))
+                w = w.to(rt.device).reshape(N, K)
+            if w.dtype not in (torch.bfloat16, torch.float16, F32):
+                w = w.float()
+            w = w.contiguous()
+            out = torch.empty(N, K, dtype=dtype, device=rt.device)
+            layers.append(dict(W=w, A=e["A"], B=e["B"], out=out, s=s, mag=e["M"] if self.dora else None))
+            if e["conv_cin"] is not None:
+                result[key] = out.view(N, 3, 3, e["conv_cin"]).permute(0, 3, 1, 2)
+            else:
+                result[key] = out.view(base_sd[key].shape)
+        if layers:
+            rt.ops.MergePlan(layers, dtype, rt.device).run()
+        return result
 
     def export(self, which="params"):
         out = {}
