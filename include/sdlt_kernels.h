@@ -20,7 +20,7 @@ extern "C" {
 
 const char* sdlt_last_error(void);
 int sdlt_abi_version(void);
-int sdlt_struct_size(int which); /* 0 gemm, 1 lora_grad_desc, 2 attn, 3 groupnorm, 4 shadow_desc, 5 gemm_batch_item, 6 dora_desc, 7 dora_wt_desc, 8 dora_grad_desc, 9 splitsum_desc ... 19 merge_desc */
+int sdlt_struct_size(int which); /* 0 gemm, 1 lora_grad_desc, 2 attn, 3 groupnorm, 4 shadow_desc, 5 gemm_batch_item, 6 dora_desc, 7 dora_wt_desc, 8 dora_grad_desc, 9 splitsum_desc ... 19 merge_desc, 20 sampler_params */
 
 /* ------------------------------------------------------------------------------------------------
  * sdlt_gemm_bf16 : C = alpha*(X.W^T [+ X2.W2^T] [+ s*(X.Adown^T).Bup^T]) + bias + rowbias + R
@@ -493,6 +493,31 @@ typedef struct sdlt_merge_desc {
 } sdlt_merge_desc;
 int sdlt_lora_merge(const sdlt_merge_desc* descs_dev, const int32_t* block_desc_dev, const int32_t* block_first_dev, int32_t n_blocks,
                     int32_t out_dtype, int32_t phase, void* stream);
+
+/* ------------------------------------------------------------------------------------------------ latent sampler
+ * sdlt_sampler_step : the one launch between two UNet forwards of the classifier-free-guidance Euler sampler, for n images sampled
+ * together (UNet batch 2n: image j = rows 2j negative, 2j + 1 positive):
+ *     e = eps_neg + g (eps_pos - eps_neg) ;  d = e (epsilon) | (x - (e * (-s / sqrt(s^2 + 1)) + x / (s^2 + 1))) / s (v prediction)
+ *     x += d (sigma_next - sigma)  in place ;  xin[both rows of the pair, columns 0..3] = bf16(x / sqrt(sigma_next^2 + 1))
+ *     timesteps[0 .. 2n) = next timestep ;  ctr[0] = (ctr[0] + 1) mod steps
+ * init != 0:  x = noise * init_noise_sigma, the first model input and timestep, ctr[0] = 0  (noise may alias x; eps is not read).
+ * What a sampling call chooses lives in DEVICE memory (a captured graph bakes nothing of it): table fp32 [table_rows, 4] with
+ *     row 0: guidance scale g, init_noise_sigma, 1 / sqrt(sigma_0^2 + 1), timestep 0     row 1: steps, v prediction (0 / 1), 0, 0
+ *     row 2 + i: sigma_i, sigma_{i+1}, 1 / sqrt(sigma_{i+1}^2 + 1), timestep of step i + 1
+ * (steps is clamped to table_rows - 2, the counter to steps - 1) and ctr int32 [2] = {step i, ticket}: both zero before the first launch;
+ * the workgroup that finishes last advances the counter, after every workgroup has read it.  Columns 4.. of xin are never written.
+ * All arithmetic fp32, one rounding per operation.  eps 16-byte aligned, xin 8-byte aligned with ld_xin % 4 == 0. */
+typedef struct sdlt_sampler_params {
+  const float* eps;                  /* fp32 [2n * hw, 4]: UNet.forward's output */
+  float* x;                          /* fp32 [n, 4, hw] latent state, in place */
+  const float* noise;                /* fp32 [n, 4, hw], init only */
+  void* xin; int64_t ld_xin;         /* bf16 [2n * hw, ld_xin] NHWC model input */
+  float* timesteps;                  /* fp32 [2n] */
+  const float* table;
+  int32_t* ctr;
+  int32_t n, hw, table_rows, init;
+} sdlt_sampler_params;
+int sdlt_sampler_step(const sdlt_sampler_params* p, void* stream);
 
 /* out[M,C] = a + b on strided 2-D bf16 views (gradient fan-in of the UNet skip connections). */
 int sdlt_add2d(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int32_t M, int32_t C, void* stream);

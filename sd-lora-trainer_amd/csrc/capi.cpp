@@ -40,6 +40,7 @@ extern "C" int sdlt_struct_size(int which) {
     case 17: return (int)sizeof(sdlt_colsum_finish_desc);
     case 18: return (int)sizeof(sdlt_wsk_gemm_params);
     case 19: return (int)sizeof(sdlt_merge_desc);
+    case 20: return (int)sizeof(sdlt_sampler_params);
   }
   return -1;
 }

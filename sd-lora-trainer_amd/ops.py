@@ -1215,6 +1215,30 @@ def add_noise_nhwc(x0, noise, timesteps, alphas_cumprod, out, noisy_nchw=None):
     return out
 
 
+def sampler_step(eps, x, xin, timesteps, table, ctr, *, noise=None):
+    """sdlt_sampler_step: guidance + Euler update + repack of the next model input for the n = x.shape[0] images of a UNet batch 2n (image j =
+    rows 2j negative, 2j + 1 positive).  eps fp32 [2n hw, 4] (None with `noise`: the init entry, x = noise * init_noise_sigma), x fp32
+    [n, 4, h, w] in place, xin bf16 [2n hw, >= 4] (columns 0..3 written), timesteps fp32 [2n], table fp32 [rows, 4] (sampler.step_table),
+    ctr int32 [2] = {step, ticket}.  Guidance scale, prediction type, step count and the step itself are read from table / ctr on the device."""
+    lib = _lib.load()
+    n, c4, h, w = x.shape
+    init = noise is not None
+    _chk2(x, F32), _chk2(xin), _chk2(timesteps, F32), _chk2(table, F32), _chk2(ctr, torch.int32)
+    assert c4 == 4 and x.is_contiguous() and table.is_contiguous() and table.dim() == 2 and table.shape[1] == 4 and ctr.numel() >= 2
+    assert xin.shape[0] == 2 * n * h * w and timesteps.numel() >= 2 * n and timesteps.is_contiguous()
+    if init:
+        _chk2(noise, F32)
+        assert noise.shape == x.shape and noise.is_contiguous()
+    else:
+        _chk2(eps, F32)
+        assert eps.is_contiguous() and tuple(eps.shape) == (2 * n * h * w, 4)
+    p = _lib.SamplerParams(eps=None if init else eps.data_ptr(), x=x.data_ptr(), noise=noise.data_ptr() if init else None, xin=xin.data_ptr(),
+                           ld_xin=_ld(xin), timesteps=timesteps.data_ptr(), table=table.data_ptr(), ctr=ctr.data_ptr(), n=n, hw=h * w,
+                           table_rows=table.shape[0], init=int(init))
+    _lib.check(lib.sdlt_sampler_step(C.byref(p), _stream()), "sdlt_sampler_step")
+    return x
+
+
 def masked_mse_fwd_bwd(pred, noise, noisy, mask, timesteps, alphas_cumprod, sums, loss_out, dpred, *, snr_gamma, v_prediction=False,
                        loss_scale=1.0):
     lib = _lib.load()

@@ -1,0 +1,240 @@
+"""Render from a saved checkpoint: what a user does first when a job has ended - load the checkpoint directory train() wrote and make pictures with
+prompts of their own (the reference's trainer/checkpoint.py:223 `load_checkpoint`, trainer/inference.py:409-493 `render_images_eval` and
+scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-square `render_size`, own step count / guidance / seeds).
+
+    python -m sd_lora_trainer_amd.render --checkpoint DIR --out DIR [--prompt TEXT ...] [--n-validation N] [--lora-scale X ...] [--size W H]
+                                         [--steps N] [--guidance G] [--seed S] [--images-per-batch N] [--eager]
+                                         [--unet F] [--text-encoder F] [--text-encoder-2 F] [--vae F] [--tokenizer DIR]
+
+DIR is a checkpoint directory of train(): training_args.json (the job's TrainingConfig), adapter_config.json + the kohya adapter file
+(`*_lora.safetensors`, `lora_te1_ / lora_te2_` keys for text-encoder adapters, `.dora_scale` for DoRA), the embeddings file and
+special_params.json; a full fine-tune (`is_lora` false) has diffusion_pytorch_model.safetensors instead of the adapter files.  The base model is
+the job's `pretrained_model` unless given (anything train() accepts, "synthetic:<version>" included).  The sampler runs each denoising iteration
+as one replayed hipGraph (sampler.LatentSampler.sample(graph=True)); --eager issues the same kernels from Python.
+"""
+import argparse
+import json
+import os
+
+import torch
+from safetensors.torch import load_file
+
+from . import checkpoint as ckpt
+from . import merge as MG
+from . import prompts as P
+from . import topology
+from .config import TrainingConfig
+
+
+class Loaded:
+    """A checkpoint ready to render: the job's config, the train.RenderStack holding the inference models, and what was read (for inspection)."""
+
+    def __init__(self, config, models, stack, checkpoint_dir, lora, te_lora, embeddings):
+        self.config, self.models, self.stack, self.checkpoint_dir = config, models, stack, checkpoint_dir
+        self.lora, self.te_lora, self.embeddings = lora, te_lora, embeddings
+        self.shape = None                       # (images per batch, h, w) the UNet's buffers were allocated for
+
+    def load_adapters(self):
+        """The checkpoint's adapters into the (re)built UNet."""
+        if self.lora is not None:
+            self.stack.unet.arena.load(self.lora)
+
+    def prepare(self, n_images, h, w):
+        """The UNet's activation buffers belong to the first latent shape it runs: another batch or size starts from fresh instances."""
+        if self.shape is not None and self.shape != (n_images, h, w) or n_images != self.stack.n_images:
+            self.stack.build_sampler(n_images)
+            self.load_adapters()
+        self.shape = (n_images, h, w)
+
+
+def _find(checkpoint_dir, suffix):
+    return next((os.path.join(checkpoint_dir, f) for f in sorted(os.listdir(checkpoint_dir)) if f.endswith(suffix)), None)
+
+
+def load_for_inference(checkpoint_dir, pretrained_model=None, device="cuda:0", runtime=None):
+    """-> Loaded.  pretrained_model: None (the job's own), a UNet path / "synthetic:<version>", or the dict train() takes; runtime: a unet.Runtime
+    whose device and op table the inference instances use (default: `device` with the HIP kernels)."""
+    from . import train as T
+    from . import unet as M
+    args_path = os.path.join(checkpoint_dir, "training_args.json")
+    if not os.path.exists(args_path):
+        raise FileNotFoundError(f"{checkpoint_dir}: no training_args.json (not a checkpoint directory of train())")
+    with open(args_path) as f:
+        data = json.load(f)
+    for k in ("concept_mode", "n_tokens", "is_lora", "lora_rank", "lora_alpha_multiplier", "use_dora", "pretrained_model"):
+        if k not in data:
+            raise KeyError(f"{args_path}: key '{k}' is missing")
+    config = TrainingConfig(**dict(data, _make_dirs=False))
+    config.name, config.seed = data.get("name", config.name), data.get("seed", config.seed)
+    if pretrained_model is not None:
+        pm = {"path": pretrained_model} if isinstance(pretrained_model, str) else dict(pretrained_model)
+        config.pretrained_model = dict({k: v for k, v in (data.get("pretrained_model") or {}).items() if k == "version"}, **pm)
+    config.sd_model_version = data.get("sd_model_version") or config.sd_model_version
+    pm = config.pretrained_model or {}
+    synthetic = str(pm.get("path", "")).startswith("synthetic:")
+    # ---- what the directory must hold
+    lora_file = acfg = lora_sd = None
+    unet_file = os.path.join(checkpoint_dir, "diffusion_pytorch_model.safetensors")
+    if config.is_lora:
+        lora_file = _find(checkpoint_dir, "_lora.safetensors")
+        if lora_file is None:
+            raise FileNotFoundError(f"{checkpoint_dir}: no *_lora.safetensors adapter file")
+        acfg_path = os.path.join(checkpoint_dir, "adapter_config.json")
+        if not os.path.exists(acfg_path):
+            raise FileNotFoundError(f"{checkpoint_dir}: no adapter_config.json")
+        with open(acfg_path) as f:
+            acfg = json.load(f)
+        for k in ("r", "lora_alpha"):
+            if k not in acfg:
+                raise KeyError(f"{acfg_path}: key '{k}' is missing")
+        lora_sd = load_file(lora_file)
+    elif not os.path.exists(unet_file):
+        raise FileNotFoundError(f"{checkpoint_dir}: no diffusion_pytorch_model.safetensors (the job trained the whole UNet: is_lora is false)")
+    text_lora = bool(lora_sd) and any(k.startswith("lora_te") for k in lora_sd)
+    if not synthetic:
+        for i, key in enumerate(("text_encoder_path", "text_encoder_2_path")[: 2 if (config.sd_model_version == "sdxl") else 1]):
+            if not pm.get(key):
+                raise ValueError(f"pretrained_model['{key}'] is missing: rendering needs the weights of the text encoder(s)"
+                                 + (" - the checkpoint holds text-encoder adapters (lora_te* keys) that are applied to them" if text_lora else ""))
+    if config.is_lora:
+        config.lora_rank = int(acfg["r"])
+        config.lora_alpha_multiplier = float(acfg["lora_alpha"]) / float(acfg["r"])          # the kohya file's alpha is r whatever the multiplier was
+        config.use_dora = bool(acfg.get("use_dora", config.use_dora))
+    rt = runtime or M.Runtime(device, 1)
+    models = T.Models(config, rt, build=False)
+    if models.tokenizers is None:
+        raise ValueError("rendering needs the tokenizer files: pretrained_model['tokenizer_path'] (vocab.json + merges.txt)")
+    if models.vae_state() is None:
+        raise ValueError("rendering needs the VAE weights: pretrained_model['vae_path']")
+    if not config.is_lora:                      # the fine-tuned UNet is the checkpoint's own file
+        models.unet_state = lambda: load_file(unet_file)
+    te_rank = None
+    te_lora = {}
+    if text_lora:
+        for i, pre in enumerate(ckpt.TEXT_PREFIXES[: len(models.kinds)]):
+            te_lora.update(MG._load_text_lora(lora_sd, models.clip_state(i), pre))
+        if not te_lora:
+            raise KeyError(f"{lora_file}: lora_te* keys that match no module of the text encoder(s)")
+        te_rank = next(iter(te_lora.values()))[0].shape[0]
+        config.text_encoder_lora_rank = int(te_rank)
+    stack = T.RenderStack(config, models, text_lora=text_lora, is_lora=config.is_lora)
+    lora = None
+    if config.is_lora:
+        targets = topology.lora_targets(models.cfg)
+        missing = [m for m in targets if ckpt.kohya_key(m) + ".lora_down.weight" not in lora_sd]
+        if missing:
+            raise KeyError(f"{lora_file}: key '{ckpt.kohya_key(missing[0])}.lora_down.weight' is missing ({len(missing)} of {len(targets)} adapted modules)")
+        lora = ckpt.load_lora(lora_file, targets)
+    if text_lora:
+        stack.te_arena.load(te_lora)
+    emb_file = _find(checkpoint_dir, "_embeddings.safetensors")
+    rows = None
+    if emb_file is not None:
+        rows = ckpt.load_embeddings(emb_file)
+        for enc, r in zip(stack.encoders, rows):
+            assert r.shape[0] == config.n_tokens, (tuple(r.shape), config.n_tokens)
+            enc.table[enc.V - config.n_tokens:].copy_(r.to(enc.table.device, enc.table.dtype))
+    elif not config.disable_ti:
+        raise FileNotFoundError(f"{checkpoint_dir}: no *_embeddings.safetensors (the job trained its trigger tokens)")
+    loaded = Loaded(config, models, stack, checkpoint_dir, lora, te_lora or None, rows)
+    loaded.load_adapters()
+    return loaded
+
+
+def _scale_tag(s):
+    return f"{s:.2f}"
+
+
+@torch.no_grad()
+def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, guidance_scale=8.0, seed=None, images_per_batch=1, token_scale=None,
+           graph=True, n_validation=4):
+    """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
+    VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
+    seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
+    graph=False is the eager loop with the same fused kernel.  -> {scale: [paths]}."""
+    from . import train as T
+    from . import vae as _vae
+    from PIL import Image
+    config, stack = loaded.config, loaded.stack
+    cfg = loaded.models.cfg
+    dev = stack.rt.device
+    if prompts is None:
+        lists = (config.training_attributes or {}).get("validation_prompts")
+        prompts = P.validation_prompts(config.concept_mode, n_validation, config.seed, config.prompt_modifier, lists if isinstance(lists, dict) else None)
+    prompts = list(prompts)
+    if lora_scales is None:
+        lora_scales = [config.sample_imgs_lora_scale or (0.75 if cfg["addition"] else 0.85)]
+    if size is None:
+        size = config.validation_img_size or (1024 if cfg["addition"] else 768)
+    size = (size, size) if isinstance(size, int) else tuple(size)
+    seed = config.seed if seed is None else seed
+    f = 2 ** (len(stack.decoder.ups) - 1) if hasattr(stack.decoder, "ups") else 8      # 8 for the SD / SDXL VAE
+    w, h = size[0] // f, size[1] // f
+    n = images_per_batch
+    loaded.prepare(n, h, w)
+    smp, fused = stack.sampler, hasattr(stack.rt.ops, "sampler_step")
+    graph = graph and dev.type == "cuda"
+    os.makedirs(out_dir, exist_ok=True)
+    result = {}
+    try:
+        for scale in lora_scales:
+            smp.set_lora_scale(scale)
+            embeds = [stack.conditioning(p, scale, token_scale)[0] for p in prompts]
+            paths = []
+            for s0 in range(0, len(prompts), n):
+                idx = [min(s0 + j, len(prompts) - 1) for j in range(n)]          # a short last batch repeats its last prompt
+                noise = torch.cat([torch.randn(1, 4, h, w, generator=torch.Generator(device=dev).manual_seed(seed + i), device=dev) for i in idx])
+                if fused:
+                    lat = smp.sample([embeds[i] for i in idx] if n > 1 else embeds[idx[0]], h, w, steps=steps, guidance_scale=guidance_scale,
+                                     size=(size[1], size[0]), latents=noise, graph=graph, fused=True, n_images=n)
+                else:                                                            # an op table without the fused kernel: the torch loop, image by image
+                    lat = torch.cat([smp.sample(embeds[i], h, w, steps=steps, guidance_scale=guidance_scale, size=(size[1], size[0]),
+                                                latents=noise[j:j + 1]) for j, i in enumerate(idx)])
+                for j, i in enumerate(idx[: len(prompts) - s0]):
+                    img = _vae.postprocess(stack.decoder.decode(lat[j:j + 1] / cfg["scaling_factor"]))[0].permute(1, 2, 0)
+                    arr = (img.float().cpu().numpy() * 255).round().astype("uint8")
+                    paths.append(os.path.join(out_dir, f"img_{i:02d}_seed{seed + i}_scale{_scale_tag(scale)}.jpg"))
+                    Image.fromarray(arr).save(paths[-1], format="JPEG", quality=95)
+            T.make_validation_img_grid(paths, os.path.join(out_dir, f"grid_scale{_scale_tag(scale)}.jpg"))
+            result[scale] = paths
+    finally:
+        smp.set_lora_scale(1.0)
+    with open(os.path.join(out_dir, "prompts.json"), "w") as fh:
+        json.dump(dict(prompts=prompts, lora_scales=list(lora_scales), size=list(size), steps=steps, guidance_scale=guidance_scale, seed=seed), fh, indent=2)
+    return result
+
+
+def main(argv=None, runtime=None):
+    ap = argparse.ArgumentParser(prog="python -m sd_lora_trainer_amd.render", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--checkpoint", required=True, help="checkpoint directory written by train()")
+    ap.add_argument("--out", required=True, help="output directory")
+    ap.add_argument("--prompt", action="append", default=None, help="a prompt (repeatable; <concept> marks the learned concept); default: validation prompts")
+    ap.add_argument("--n-validation", type=int, default=4, help="number of validation prompts when no --prompt is given")
+    ap.add_argument("--lora-scale", type=float, action="append", default=None, help="adapter weight (repeatable: a sweep); default: the job's sample_imgs_lora_scale")
+    ap.add_argument("--size", type=int, nargs=2, metavar=("W", "H"), default=None, help="image size in pixels; default: the job's validation_img_size")
+    ap.add_argument("--steps", type=int, default=25)
+    ap.add_argument("--guidance", type=float, default=8.0)
+    ap.add_argument("--seed", type=int, default=None, help="image i starts from seed + i; default: the job's seed")
+    ap.add_argument("--images-per-batch", type=int, default=1, help="images sampled together (UNet batch 2 N)")
+    ap.add_argument("--eager", action="store_true", help="issue every launch from Python instead of replaying one hipGraph per iteration (same kernels)")
+    ap.add_argument("--device", default="cuda:0")
+    for flag, key, what in (("--unet", "path", "base UNet weights or synthetic:<version>"), ("--text-encoder", "text_encoder_path", "text encoder state dict"),
+                            ("--text-encoder-2", "text_encoder_2_path", "SDXL's second text encoder"), ("--vae", "vae_path", "AutoencoderKL state dict"),
+                            ("--tokenizer", "tokenizer_path", "directory with vocab.json + merges.txt")):
+        ap.add_argument(flag, dest=key, default=None, help=what + " (default: the job's)")
+    a = ap.parse_args(argv)
+    over = {k: getattr(a, k) for k in ("path", "text_encoder_path", "text_encoder_2_path", "vae_path", "tokenizer_path") if getattr(a, k)}
+    pm = None
+    if over and os.path.exists(os.path.join(a.checkpoint, "training_args.json")):
+        with open(os.path.join(a.checkpoint, "training_args.json")) as f:
+            pm = dict(json.load(f).get("pretrained_model") or {}, **over)
+    loaded = load_for_inference(a.checkpoint, pm, device=a.device, runtime=runtime)
+    res = render(loaded, a.prompt, a.out, lora_scales=a.lora_scale, size=a.size, steps=a.steps, guidance_scale=a.guidance, seed=a.seed,
+                 images_per_batch=a.images_per_batch, graph=not a.eager, n_validation=a.n_validation)
+    for scale, paths in res.items():
+        print(f"lora_scale {scale}: {len(paths)} image(s), {os.path.join(a.out, 'grid_scale' + _scale_tag(scale) + '.jpg')}")
+    return res
+
+
+if __name__ == "__main__":
+    main()

@@ -57,18 +57,41 @@ class EulerDiscrete:
         return x + d * (sn - s)
 
 
+TABLE_ROWS = 2 + 1000      # rows of the device step table: two header rows + at most one step per training timestep
+MAX_GRAPHS = 4             # captured iterations kept per sampler (one per shape and adapter scale)
+
+
+def step_table(sched, guidance_scale):
+    """The device table of ops.sampler_step for a scheduler whose set_timesteps(n) has run: fp32 [2 + n, 4],
+    row 0 (guidance scale, init_noise_sigma, 1 / sqrt(sigma_0^2 + 1), timestep 0), row 1 (n, v prediction, 0, 0),
+    row 2 + i (sigma_i, sigma_{i+1}, 1 / sqrt(sigma_{i+1}^2 + 1), timestep of step i + 1; after the last step: timestep 0 again).
+    The factors are the fp32 roundings of the fp64 values of the fp32 sigmas (what scale_model_input divides by)."""
+    sig, ts = sched.sigmas.astype(np.float64), sched.timesteps
+    n = len(ts)
+    inv = 1.0 / np.sqrt(sig ** 2 + 1.0)
+    tab = np.zeros((2 + n, 4), dtype=np.float32)
+    tab[0] = (guidance_scale, sched.init_noise_sigma, inv[0], ts[0])
+    tab[1] = (n, 1.0 if sched.prediction_type == "v_prediction" else 0.0, 0.0, 0.0)
+    tab[2:, 0], tab[2:, 1], tab[2:, 2] = sig[:-1], sig[1:], inv[1:]
+    tab[2:, 3] = np.concatenate([ts[1:], ts[:1]])
+    return torch.from_numpy(tab)
+
+
 class LatentSampler:
     """`pipe(prompt_embeds=c, negative_prompt_embeds=uc, ..., num_inference_steps, guidance_scale, generator)` of the
     reference's render loop, up to the latents.  `unet` is an inference instance built for batch 2 (negative | positive, the
     order diffusers concatenates them in); its LoRA arena holds the trained adapters."""
 
     def __init__(self, rt, unet, prediction_type="epsilon"):
-        assert rt.B == 2, "classifier-free guidance runs the negative and the positive prompt as one batch of 2"
+        assert rt.B >= 2 and rt.B % 2 == 0, "classifier-free guidance runs the negative and the positive prompt of every image as one pair: an even batch"
         self.rt, self.unet = rt, unet
+        self.n = rt.B // 2                 # images sampled together (fused / graph path); image j = rows 2j (negative), 2j + 1 (positive)
         self.sched = EulerDiscrete(prediction_type=prediction_type)
         cfg = unet.cfg
-        self.ctx = rt.zeros(2 * CTX_PAD, cfg["cross_dim"])
-        self.pooled = rt.zeros(2, cfg["proj_class_in"] - 6 * cfg["addition_time_embed_dim"]) if cfg["addition"] else None
+        self.ctx = rt.zeros(rt.B * CTX_PAD, cfg["cross_dim"])
+        self.pooled = rt.zeros(rt.B, cfg["proj_class_in"] - 6 * cfg["addition_time_embed_dim"]) if cfg["addition"] else None
+        self._fused = None                 # persistent device state of the fused / graph path, built on first use
+        self._graphs = {}                  # (h, w, n, adapter scale in effect, DoRA) -> hipGraph of one denoising iteration
 
     def set_lora_scale(self, lora_scale, train_scale=None):
         """set_adapter_scales (checkpoint.py:31-55): every adapter's contribution is multiplied by lora_scale."""
@@ -79,9 +102,15 @@ class LatentSampler:
             a.set_scale(a._train_scale * lora_scale)      # (DoRA: the column factors follow the scale in effect)
 
     @torch.no_grad()
-    def sample(self, embeds, h, w, *, steps=25, guidance_scale=8.0, generator=None, size=None, latents=None):
+    def sample(self, embeds, h, w, *, steps=25, guidance_scale=8.0, generator=None, size=None, latents=None, graph=False, fused=False, n_images=1):
         """embeds = (c [1,77,D], uc [1,77,D], pc [1,P] | None, puc | None); h, w latent size.  Returns latents [1,4,h,w] fp32
-        (still multiplied by the VAE scaling factor, as the pipeline holds them before `vae.decode(latents / scaling_factor)`)."""
+        (still multiplied by the VAE scaling factor, as the pipeline holds them before `vae.decode(latents / scaling_factor)`).
+        fused: guidance, the Euler update and the next model input are ONE kernel between two forwards (ops.sampler_step) instead of torch
+        element-wise launches; graph: that iteration additionally replayed as a hipGraph (implies fused).  Both sample n_images images together
+        on a runtime of batch 2 n_images: embeds is then a list of n_images 4-tuples and the result [n_images, 4, h, w]."""
+        if graph or fused:
+            return self._sample_fused(embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images)
+        assert n_images == 1 and self.rt.B == 2, "the torch loop samples one image on a batch-2 runtime; several images together: fused=True or graph=True"
         rt, u, cfg = self.rt, self.unet, self.unet.cfg
         dev = rt.device
         c, uc, pc, puc = (tuple(embeds) + (None, None))[:4]
@@ -106,6 +135,107 @@ class LatentSampler:
             e = eps[0:1] + guidance_scale * (eps[1:2] - eps[0:1])
             x = s.step(e, i, x)
         return x
+
+    # ---- fused / graph path ---------------------------------------------------------------------------------------------------
+    def _scope(self):
+        """This sampler's own split-K / norm scratch (ops.workspace_owner), as the training step keeps its own: a captured launch holds the pointers."""
+        own = getattr(self.rt.ops, "workspace_owner", None)
+        if own is None:
+            import contextlib
+            return contextlib.nullcontext()
+        return own(id(self))
+
+    def _state(self, h, w):
+        rt, n = self.rt, self.n
+        if self._fused is None:
+            self._fused = dict(tf=rt.zeros(2 * n, dtype=F32), tid=rt.zeros(2 * n * 6, dtype=F32), table=rt.zeros(TABLE_ROWS, 4, dtype=F32),
+                               ctr=torch.zeros(2, dtype=torch.int32, device=rt.device), shapes={})
+        st = self._fused
+        if (h, w) not in st["shapes"]:
+            st["shapes"][(h, w)] = dict(x=rt.zeros(n, 4, h, w, dtype=F32), x64=rt.zeros(2 * n * h * w, 64))
+        return st, st["shapes"][(h, w)]
+
+    def _iteration(self, st, sh, h, w):
+        u = self.unet
+        eps = u.forward(sh["x64"], st["tf"], self.ctx, self.pooled, st["tid"] if u.cfg["addition"] else None, B=2 * self.n, H=h, W=w)
+        self.rt.ops.sampler_step(eps, sh["x"], sh["x64"], st["tf"], st["table"], st["ctr"])
+
+    def _graph(self, st, sh, h, w):
+        """The hipGraph of one iteration for this shape and the adapter scale in effect.  The scale is a launch argument of every adapted GEMM
+        (baked by capture), hence part of the key; adapters, DoRA factors, token rows, conditioning, table and counter are device memory."""
+        a = self.unet.arena
+        key = (h, w, self.n, None if a is None else float(a.scale), bool(a is not None and a.dora))
+        g = self._graphs.get(key)
+        if g is not None:
+            return g
+        while len(self._graphs) >= MAX_GRAPHS:            # a sweep over many scales: the oldest capture goes
+            self._graphs.pop(next(iter(self._graphs)))
+        ops = self.rt.ops
+        prefetch = hasattr(ops, "pf_record_begin") and getattr(ops, "WSK_PREFETCH", False)
+        side = torch.cuda.Stream(device=self.rt.device)
+        side.wait_stream(torch.cuda.current_stream())
+        seq = None
+        with torch.cuda.stream(side):
+            self._iteration(st, sh, h, w)                 # eager warm-up: every persistent buffer and packed-weight copy exists before the capture
+            if prefetch:                                  # next-weight hints of the wave-split-K products, recorded from one eager pass (step.TrainStep.capture)
+                ops.pf_record_begin()
+                try:
+                    self._iteration(st, sh, h, w)
+                finally:
+                    seq = ops.pf_record_end()
+        torch.cuda.current_stream().wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            if seq:
+                ops.pf_replay_begin(seq)
+            try:
+                self._iteration(st, sh, h, w)
+            finally:
+                if seq:
+                    ops.pf_replay_end()
+        self._graphs[key] = g
+        return g
+
+    def _sample_fused(self, embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images):
+        rt, cfg, n = self.rt, self.unet.cfg, self.n
+        if not hasattr(rt.ops, "sampler_step"):
+            raise NotImplementedError("this op table has no sampler_step kernel: sample(graph=False, fused=False) is the torch loop")
+        assert n_images == n, f"the runtime's batch {rt.B} samples {n} image(s) together, not {n_images}"
+        assert 1 <= steps <= TABLE_ROWS - 2
+        dev = rt.device
+        per_image = [embeds] if (n == 1 and not isinstance(embeds[0], (tuple, list))) else list(embeds)
+        assert len(per_image) == n, "one (c, uc[, pc, puc]) per image"
+        cv = self.ctx.view(2 * n, CTX_PAD, -1)
+        st, sh = self._state(h, w)
+        for j, e in enumerate(per_image):
+            c, uc, pc, puc = (tuple(e) + (None, None))[:4]
+            cv[2 * j, :77].copy_(uc[0])
+            cv[2 * j + 1, :77].copy_(c[0])
+            if cfg["addition"]:
+                self.pooled[2 * j].copy_(puc[0])
+                self.pooled[2 * j + 1].copy_(pc[0])
+        if cfg["addition"]:
+            H, W = size if size is not None else (8 * h, 8 * w)
+            st["tid"].copy_(torch.tensor([float(H), float(W), 0.0, 0.0, float(H), float(W)] * (2 * n)))
+        s = self.sched.set_timesteps(steps)
+        tab = step_table(s, guidance_scale)
+        st["table"][: tab.shape[0]].copy_(tab)
+        noise = latents if latents is not None else torch.randn(n, 4, h, w, generator=generator, device=dev, dtype=F32)
+        noise = noise.to(dev, F32).contiguous()
+        assert tuple(noise.shape) == (n, 4, h, w)
+        x, x64 = sh["x"], sh["x64"]
+        with self._scope():
+            g = None
+            if graph:
+                rt.ops.sampler_step(None, x, x64, st["tf"], st["table"], st["ctr"], noise=noise)     # (a defined state for the warm-up passes)
+                g = self._graph(st, sh, h, w)
+            rt.ops.sampler_step(None, x, x64, st["tf"], st["table"], st["ctr"], noise=noise)
+            for _ in range(steps):                        # no host read in here: the step index lives in ctr, its scalars in the table
+                if g is not None:
+                    g.replay()
+                else:
+                    self._iteration(st, sh, h, w)
+        return x.clone()
 
 
 def render_images(sampler, decoder, embeds_list, render_size, out_dir, train_step, seed, *, scaling_factor, lora_scale,

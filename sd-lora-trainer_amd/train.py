@@ -69,7 +69,8 @@ def _rank_world():
 class Models:
     """What `load_models` returns in the reference (trainer/models.py:7-54), for the parts this engine runs."""
 
-    def __init__(self, config, rt):
+    def __init__(self, config, rt, build=True):
+        """build=False: the model choice, the tokenizers and the state-dict sources only (render.load_for_inference builds inference instances from them)."""
         from . import clip as CL
         from . import step as S
         from . import unet as M
@@ -99,6 +100,10 @@ class Models:
             for t in toks:
                 t.add_tokens(config.inserting_list_tokens)
             self.tokenizers = toks
+        if not build:
+            self.unet = self.text = None
+            self.encoders = []
+            return
         # ---- UNet
         if self.synthetic:
             sd = _random_state(topology.param_shapes(cfg), rt.device, seed=config.seed)
@@ -259,41 +264,87 @@ def load_data(config, models, rt, h, w):
     return cache
 
 
-class Renderer:
+class RenderStack:
+    """The inference side of a render, shared by the training-time Renderer below and render.load_for_inference: an inference instance of the
+    UNet (batch 2 per image sampled together) with its LatentSampler, the VAE decoder, inference instances of the text encoders (with their own
+    adapter arena when the job trains text-encoder LoRA) and prompt -> conditioning.  `models`: cfg, rt, kinds, tokenizers, unet_state(),
+    clip_state(i), vae_state() (train.Models)."""
+
+    def __init__(self, config, models, text_lora, n_images=1, is_lora=True):
+        from . import clip as CL
+        from . import step as S
+        from . import unet as M
+        self.config, self.models, self.is_lora = config, models, is_lora
+        cfg = models.cfg
+        dev = models.rt.device
+        self.build_sampler(n_images)
+        self.rt_text = self.rt if n_images == 1 else M.Runtime(dev, 2, ops=models.rt.ops)      # a prompt is encoded as (negative, prompt): batch 2
+        xl = bool(cfg["addition"])
+        self.encoders = []
+        # text-encoder LoRA (text_encoder_lora_optimizer): the reference renders with the pipe's own peft-wrapped text encoders
+        # (inference.py:345-356), so the inference encoders carry the same adapters
+        self.te_arena = None
+        if text_lora:
+            self.te_arena = M.LoraArena(self.rt_text, config.text_encoder_lora_rank, config.lora_alpha_multiplier, problems=[], dora=config.use_dora)
+        for i, kd in enumerate(models.kinds):
+            c = topology.CLIP_CONFIGS[kd]
+            self.encoders.append(CL.ClipTextEncoder(self.rt_text, f"rte{i + 1}", models.clip_state(i), heads=c["heads"], act=c["act"],
+                                                    mode="penultimate" if xl else "last", with_projection=bool(c["proj"]), n_train=config.n_tokens,
+                                                    arena=self.te_arena, lora_prefix="text_encoder." if i == 0 else "text_encoder_2."))
+        if self.te_arena is not None:
+            self.te_arena.finalize()
+        self.text = S.TextStack(self.rt_text, self.encoders, pool_mode="argmax", arena=self.te_arena)
+        self.ctx = self.rt_text.zeros(2 * M.CTX_PAD, cfg["cross_dim"])
+
+    def build_sampler(self, n_images):
+        """(Re)build the UNet, its sampler and the VAE decoder for n_images images sampled together.  Their activation buffers are allocated for
+        the first latent shape they run, so a render at another size or batch starts from fresh instances (the caller reloads the adapters)."""
+        from . import sampler as SM
+        from . import unet as M
+        from . import vae as V
+        config, models = self.config, self.models
+        dev = models.rt.device
+        self.n_images = n_images
+        self.unet = self.sampler = self.decoder = None
+        self.rt = M.Runtime(dev, 2 * n_images, ops=models.rt.ops)
+        kw = dict(lora_rank=config.lora_rank, lora_alpha_multiplier=config.lora_alpha_multiplier, use_dora=config.use_dora) if self.is_lora else {}
+        self.unet = M.UNet(self.rt, models.cfg, models.unet_state(), **kw)
+        self.sampler = SM.LatentSampler(self.rt, self.unet)
+        self.decoder = V.VaeDecoder(M.Runtime(dev, 1, ops=models.rt.ops), models.vae_state())
+
+    def encode(self, prompt, negative):
+        """pipe.encode_prompt(prompt, do_classifier_free_guidance=True, negative_prompt=...) -> (c, uc[, pc, puc]); batch row 0 = negative."""
+        from .unet import CTX_PAD
+        ids = [torch.tensor(t([negative, prompt]), dtype=torch.int64) for t in self.models.tokenizers]
+        self.text.set_ids([i.to(self.rt_text.device) for i in ids])
+        pooled = self.text.forward(self.ctx)
+        cv = self.ctx.view(2, CTX_PAD, -1)[:, :77].float().clone()
+        out = (cv[1:2], cv[0:1])
+        if pooled is not None:
+            pf = pooled.float().clone()
+            out += (pf[1:2], pf[0:1])
+        return out
+
+    def conditioning(self, prompt, lora_scale, token_scale=None):
+        """encode_prompt_advanced + blend_conditions for one raw prompt -> (conditioning 4-tuple, the prompt with the learned tokens)."""
+        from . import sampler as SM
+        config = self.config
+        trig = (config.training_attributes or {}).get("trigger_text", "TOK")
+        lora_p, zero_p = P.prompt_pair(prompt, config.token_dict, trig, config.name, config.concept_mode, use_lora=not config.disable_ti)
+        # render_images passes token_scale = 0 with disable_ti (inference.py:289-385): the conditioning is the zero prompt's alone
+        e, _ = SM.blend_conditions(self.encode(zero_p, P.NEGATIVE_PROMPT), self.encode(lora_p, P.NEGATIVE_PROMPT), lora_scale,
+                                   token_scale=0.0 if config.disable_ti else token_scale)
+        return e, lora_p
+
+
+class Renderer(RenderStack):
     """`render_images` (trainer/inference.py:289-406) on this engine: validation prompts -> with / without-concept conditionings
     (encode_prompt_advanced + blend_conditions) -> Euler-trailing CFG sampler on an inference instance of the UNet (batch 2) with the
     current adapters -> VAE decode -> JPEGs + validation grid.  Built lazily at the first checkpoint."""
 
     def __init__(self, config, models, train_unet):
-        from . import clip as CL
-        from . import sampler as SM
-        from . import step as S
-        from . import unet as M
-        from . import vae as V
-        self.config, self.models, self.train_unet = config, models, train_unet
-        cfg = models.cfg
-        dev = models.rt.device
-        self.rt = M.Runtime(dev, 2)
-        self.unet = M.UNet(self.rt, cfg, models.unet_state(), lora_rank=config.lora_rank, lora_alpha_multiplier=config.lora_alpha_multiplier,
-                           use_dora=config.use_dora)
-        self.sampler = SM.LatentSampler(self.rt, self.unet)
-        self.decoder = V.VaeDecoder(M.Runtime(dev, 1), models.vae_state())
-        xl = bool(cfg["addition"])
-        self.encoders = []
-        # text-encoder LoRA (text_encoder_lora_optimizer): the reference renders with the pipe's own peft-wrapped text encoders
-        # (inference.py:345-356), so the inference encoders carry the same adapters, refreshed from the training arena in sync()
-        self.te_arena = None
-        if models.text.arena is not None:
-            self.te_arena = M.LoraArena(self.rt, config.text_encoder_lora_rank, config.lora_alpha_multiplier, problems=[], dora=config.use_dora)
-        for i, kd in enumerate(models.kinds):
-            c = topology.CLIP_CONFIGS[kd]
-            self.encoders.append(CL.ClipTextEncoder(self.rt, f"rte{i + 1}", models.clip_state(i), heads=c["heads"], act=c["act"],
-                                                    mode="penultimate" if xl else "last", with_projection=bool(c["proj"]), n_train=config.n_tokens,
-                                                    arena=self.te_arena, lora_prefix="text_encoder." if i == 0 else "text_encoder_2."))
-        if self.te_arena is not None:
-            self.te_arena.finalize()
-        self.text = S.TextStack(self.rt, self.encoders, pool_mode="argmax", arena=self.te_arena)
-        self.ctx = self.rt.zeros(2 * M.CTX_PAD, cfg["cross_dim"])
+        super().__init__(config, models, text_lora=models.text.arena is not None)
+        self.train_unet = train_unet
 
     def sync(self):
         """Current adapters and token rows of the training instance -> the inference instance."""
@@ -306,19 +357,6 @@ class Renderer:
         for dst, src in zip(self.encoders, self.models.encoders):
             dst.table[dst.V - n:].copy_(src.table[src.V - n:])
 
-    def encode(self, prompt, negative):
-        """pipe.encode_prompt(prompt, do_classifier_free_guidance=True, negative_prompt=...) -> (c, uc[, pc, puc]); batch row 0 = negative."""
-        from .unet import CTX_PAD
-        ids = [torch.tensor(t([negative, prompt]), dtype=torch.int64) for t in self.models.tokenizers]
-        self.text.set_ids([i.to(self.rt.device) for i in ids])
-        pooled = self.text.forward(self.ctx)
-        cv = self.ctx.view(2, CTX_PAD, -1)[:, :77].float().clone()
-        out = (cv[1:2], cv[0:1])
-        if pooled is not None:
-            pf = pooled.float().clone()
-            out += (pf[1:2], pf[0:1])
-        return out
-
     @torch.no_grad()
     def render(self, out_dir, train_step, n_steps=25):
         from . import sampler as SM
@@ -326,15 +364,7 @@ class Renderer:
         self.sync()
         lists = (config.training_attributes or {}).get("validation_prompts")
         raw = P.validation_prompts(config.concept_mode, config.n_sample_imgs, config.seed, config.prompt_modifier, lists if isinstance(lists, dict) else None)
-        trig = (config.training_attributes or {}).get("trigger_text", "TOK")
-        embeds, used = [], []
-        for p in raw:
-            lora_p, zero_p = P.prompt_pair(p, config.token_dict, trig, config.name, config.concept_mode, use_lora=not config.disable_ti)
-            # render_images passes token_scale = 0 with disable_ti (inference.py:289-385): the conditioning is the zero prompt's alone
-            e, _ = SM.blend_conditions(self.encode(zero_p, P.NEGATIVE_PROMPT), self.encode(lora_p, P.NEGATIVE_PROMPT), config.sample_imgs_lora_scale,
-                                       token_scale=0.0 if config.disable_ti else None)
-            embeds.append(e)
-            used.append(lora_p)
+        embeds = [self.conditioning(p, config.sample_imgs_lora_scale)[0] for p in raw]
         size = config.validation_img_size
         size = (size, size) if isinstance(size, int) else tuple(size)
         paths = SM.render_images(self.sampler, self.decoder, embeds, size, out_dir, train_step, config.seed, scaling_factor=cfg["scaling_factor"],

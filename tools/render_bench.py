@@ -1,0 +1,107 @@
+"""What the validation sampler costs per denoising iteration, three ways in ONE session (alternated, so that clocks and neighbours hit all of
+them alike): (a) LatentSampler.sample as train() uses it (torch element-wise launches between the forwards), (b) the eager loop with the fused
+sdlt_sampler_step kernel, (c) one replayed hipGraph per iteration.  SDXL topology (random weights), 128 x 128 latent, rank-16 adapters, 25 steps,
+n = 1 and n = 2 images per batch ((a) samples the n images one after the other on its batch-2 instance).
+
+    python tools/render_bench.py [--out FILE] [--rounds 5] [--version sdxl] [--latent 128] [--n 1 2]
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/render_bench.py --trace-iteration --n 1      # kernel time of one iteration: sum the stats
+
+Prints one table: wall milliseconds per iteration (median over the rounds, min .. max) per variant and n, per image in brackets.
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def build(version, n, rank):
+    import sd_lora_trainer_amd.unet as M
+    from sd_lora_trainer_amd import sampler, topology
+    from sd_lora_trainer_amd.train import _random_state
+    cfg = topology.CONFIGS[version]
+    sd = _random_state(topology.param_shapes(cfg), "cuda:0", seed=0)
+    rt = M.Runtime("cuda:0", 2 * n)
+    unet = M.UNet(rt, cfg, sd, lora_rank=rank)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    for e in unet.arena.entries:
+        e["A"].copy_(torch.randn(e["A"].shape, generator=g, device="cuda") / rank)
+        e["B"].copy_(torch.randn(e["B"].shape, generator=g, device="cuda") * 0.02)
+    unet.arena.refresh_shadows()
+    smp = sampler.LatentSampler(rt, unet)
+    smp.set_lora_scale(0.75)
+    return cfg, smp
+
+
+def embeds(cfg, n):
+    g = torch.Generator(device="cuda").manual_seed(2)
+    D = cfg["cross_dim"]
+    P = cfg["proj_class_in"] - 6 * cfg["addition_time_embed_dim"] if cfg["addition"] else 0
+    mk = lambda *s: torch.randn(*s, generator=g, device="cuda")  # noqa: E731
+    return [(mk(1, 77, D), mk(1, 77, D)) + ((mk(1, P), mk(1, P)) if cfg["addition"] else (None, None)) for _ in range(n)]
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--version", default="sdxl")
+    ap.add_argument("--latent", type=int, default=128)
+    ap.add_argument("--rank", type=int, default=16)
+    ap.add_argument("--steps", type=int, default=25)
+    ap.add_argument("--n", type=int, nargs="+", default=[1, 2])
+    ap.add_argument("--trace-iteration", action="store_true", help="run the eager fused loop once and exit (under rocprofv3 --kernel-trace --stats: kernel time per iteration = total / steps, without the one-off pack kernels)")
+    a = ap.parse_args()
+    h = a.latent
+    lines = [f"# {a.version} topology, {h} x {h} latent, rank {a.rank}, {a.steps} steps, guidance 8; wall ms per denoising iteration: median (min .. max) of {a.rounds} rounds, alternated",
+             f"# {torch.cuda.get_device_name(0)}, torch {torch.__version__}",
+             f"{'n':>2} {'variant':<28} {'ms / iteration':>16} {'min':>8} {'max':>8} {'ms / iteration / image':>24}"]
+    cfg1, smp1 = build(a.version, 1, a.rank)               # (a): today's loop, always a batch-2 instance
+    for n in a.n:
+        cfg, smp = (cfg1, smp1) if n == 1 else build(a.version, n, a.rank)
+        em = embeds(cfg, n)
+        noise = torch.randn(n, 4, h, h, device="cuda", generator=torch.Generator(device="cuda").manual_seed(3))
+        one = lambda **kw: smp.sample(em if n > 1 else em[0], h, h, steps=a.steps, latents=noise, n_images=n, **kw)  # noqa: E731
+        variants = {
+            "a torch loop (train())": lambda: [smp1.sample(em[j], h, h, steps=a.steps, latents=noise[j:j + 1]) for j in range(n)],
+            "b eager + fused kernel": lambda: one(fused=True),
+            "c hipGraph per iteration": lambda: one(graph=True),
+        }
+        if a.trace_iteration:                               # the kernels of `steps` eager iterations (+ the one-off weight packing of the first)
+            one(fused=True)
+            torch.cuda.synchronize()
+            return
+        for fn in variants.values():                        # warm-up: buffers, packed weights, the capture
+            fn()
+        times = {k: [] for k in variants}
+        for _ in range(a.rounds):
+            for k, fn in variants.items():
+                times[k].append(timed(fn) * 1e3 / a.steps)
+        for k, t in times.items():
+            med = statistics.median(t)
+            lines.append(f"{n:>2} {k:<28} {med:>16.3f} {min(t):>8.3f} {max(t):>8.3f} {med / n:>24.3f}")
+        if n != 1:
+            del smp
+            torch.cuda.empty_cache()
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text)
+
+
+if __name__ == "__main__":
+    main()
