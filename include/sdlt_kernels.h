@@ -20,7 +20,7 @@ extern "C" {
 
 const char* sdlt_last_error(void);
 int sdlt_abi_version(void);
-int sdlt_struct_size(int which); /* 0 gemm, 1 lora_grad_desc, 2 attn, 3 groupnorm, 4 shadow_desc, 5 gemm_batch_item, 6 dora_desc, 7 dora_wt_desc, 8 dora_grad_desc, 9 splitsum_desc ... 19 merge_desc, 20 sampler_params */
+int sdlt_struct_size(int which); /* 0 gemm, 1 lora_grad_desc, 2 attn, 3 groupnorm, 4 shadow_desc, 5 gemm_batch_item, 6 dora_desc, 7 dora_wt_desc, 8 dora_grad_desc, 9 splitsum_desc ... 19 merge_desc, 20 sampler_params, 21 delta_desc */
 
 /* ------------------------------------------------------------------------------------------------
  * sdlt_gemm_bf16 : C = alpha*(X.W^T [+ X2.W2^T] [+ s*(X.Adown^T).Bup^T]) + bias + rowbias + R
@@ -493,6 +493,27 @@ typedef struct sdlt_merge_desc {
 } sdlt_merge_desc;
 int sdlt_lora_merge(const sdlt_merge_desc* descs_dev, const int32_t* block_desc_dev, const int32_t* block_first_dev, int32_t n_blocks,
                     int32_t out_dtype, int32_t phase, void* stream);
+
+/* ------------------------------------------------------------------------------------------------ adapter extraction
+ * sdlt_delta_matmul : products with the difference of a tuned and a base weight (the inverse of sdlt_lora_merge: the range finder of
+ * python -m sd_lora_trainer_amd.extract), every layer of a descriptor table in one launch:
+ *     transposed == 0:  Y[N, L] = (W1 - W0) X[K, L]          transposed != 0:  Y[K, L] = (W1 - W0)^T X[N, L]
+ * W0 / W1 [N, K]: dtype 0 bf16, 1 fp16, 2 fp32, chosen independently (3x3 conv: the tap-major [Cout, 9 Cin] operand), unit column stride;
+ * 16-byte loads where base and row stride are 16-byte aligned, element loads otherwise.  X / Y fp32 with 16-byte aligned rows (base
+ * aligned, ld % 4 == 0).  L (one value per launch): a multiple of 16, 16..272.  The difference is taken in fp32 registers and never
+ * stored; the product is the f32-input MFMA's k-ordered fp32 fmaf chain.  Layer d owns ceil(rows of Y / 64) consecutive blocks
+ * (block_desc[b] = descriptor of block b, block_first[d] = its first block); the reduction is not split, so runs are bitwise reproducible.
+ * rowsq (optional, forward only): fp32 [N] = sum_k (W1 - W0)[n, k]^2. */
+typedef struct sdlt_delta_desc {
+  const void* W0; int64_t ldw0;
+  const void* W1; int64_t ldw1;
+  const float* X; int64_t ldx;
+  float* Y; int64_t ldy;
+  float* rowsq;
+  int32_t N, K, dtype0, dtype1, transposed, pad_;
+} sdlt_delta_desc;
+int sdlt_delta_matmul(const sdlt_delta_desc* descs_dev, const int32_t* block_desc_dev, const int32_t* block_first_dev, int32_t n_blocks,
+                      int32_t L, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ latent sampler
  * sdlt_sampler_step : the one launch between two UNet forwards of the classifier-free-guidance Euler sampler, for n images sampled

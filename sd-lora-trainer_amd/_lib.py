@@ -153,6 +153,11 @@ class MergeDesc(C.Structure):
                 ("N", i32), ("K", i32), ("rank", i32), ("w_dtype", i32), ("s", f32), ("pad_", i32)]
 
 
+class DeltaDesc(C.Structure):
+    _fields_ = [("W0", vp), ("ldw0", i64), ("W1", vp), ("ldw1", i64), ("X", vp), ("ldx", i64), ("Y", vp), ("ldy", i64), ("rowsq", vp),
+                ("N", i32), ("K", i32), ("dtype0", i32), ("dtype1", i32), ("transposed", i32), ("pad_", i32)]
+
+
 class SamplerParams(C.Structure):
     _fields_ = [("eps", vp), ("x", vp), ("noise", vp), ("xin", vp), ("ld_xin", i64), ("timesteps", vp), ("table", vp), ("ctr", vp),
                 ("n", i32), ("hw", i32), ("table_rows", i32), ("init", i32)]
@@ -207,6 +212,7 @@ SYMBOLS = {
     "sdlt_dora_scale_wt": (i32, [vp, vp, vp, i32, vp]),
     "sdlt_dora_mag_grad": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, vp]),
     "sdlt_lora_merge": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "sdlt_delta_matmul": (i32, [vp, vp, vp, i32, i32, vp]),
     "sdlt_sampler_step": (i32, [C.POINTER(SamplerParams), vp]),
     "sdlt_strip_gemm": (i32, [C.POINTER(StripParams), vp]),
     "sdlt_strip_gemm_pair": (i32, [C.POINTER(StripParams), C.POINTER(StripParams), vp]),
@@ -267,7 +273,8 @@ def struct_sizes():
     mirrored = (GemmParams, LoraGradDesc, AttnParams, GroupNormParams, ShadowDesc, GemmBatchItem, DoraDesc, DoraWtDesc, DoraGradDesc, SplitsumDesc, StripParams,
                 TaParams, LnSlabsParams, TaGroup)
     return [(c.__name__, C.sizeof(c)) for c in mirrored] + [("sdlt_affine_grad_item", 8 * 8), ("sdlt_wgrad_tr_item", 3 * 8), ("LnFoldDesc", C.sizeof(LnFoldDesc)), ("ColsumFinishDesc", C.sizeof(ColsumFinishDesc)),
-                                                               ("WskGemmParams", C.sizeof(WskGemmParams)), ("MergeDesc", C.sizeof(MergeDesc)), ("SamplerParams", C.sizeof(SamplerParams))]
+                                                               ("WskGemmParams", C.sizeof(WskGemmParams)), ("MergeDesc", C.sizeof(MergeDesc)), ("SamplerParams", C.sizeof(SamplerParams)),
+                                                               ("DeltaDesc", C.sizeof(DeltaDesc))]
 
 
 def check(rc, what):

@@ -41,6 +41,7 @@ extern "C" int sdlt_struct_size(int which) {
     case 18: return (int)sizeof(sdlt_wsk_gemm_params);
     case 19: return (int)sizeof(sdlt_merge_desc);
     case 20: return (int)sizeof(sdlt_sampler_params);
+    case 21: return (int)sizeof(sdlt_delta_desc);
   }
   return -1;
 }

@@ -1476,6 +1476,67 @@ class MergePlan:
             _lib.check(lib.sdlt_lora_merge(_p(self.dev), _p(self.bd), _p(self.bf), self.n_blocks, self.out_dtype, phase, _stream()), "sdlt_lora_merge")
 
 
+def _delta_table(items, L, device):
+    """(descriptor table, n_blocks, block_desc, block_first) of one sdlt_delta_matmul launch.  items: dict(W0, W1 [N, K] bf16 / fp16 / fp32,
+    X fp32 [K, L] ([N, L] transposed), Y fp32 [N, L] ([K, L] transposed), transposed, rowsq fp32 [N] or None)."""
+    assert L % 16 == 0 and 16 <= L <= 272, f"L = {L}: a multiple of 16, 16..272"
+    arr = (_lib.DeltaDesc * max(len(items), 1))()
+    counts = []
+    for d, it in zip(arr, items):
+        W0, W1, X, Y, tr = it["W0"], it["W1"], it["X"], it["Y"], bool(it.get("transposed"))
+        _chk2(W0, W0.dtype), _chk2(W1, W1.dtype), _chk2(X, F32), _chk2(Y, F32)
+        assert W0.dtype in MERGE_DTYPES and W1.dtype in MERGE_DTYPES, (W0.dtype, W1.dtype)
+        N, K = W0.shape
+        rows_in, rows_out = (N, K) if tr else (K, N)
+        assert tuple(W1.shape) == (N, K) and tuple(X.shape) == (rows_in, L) and tuple(Y.shape) == (rows_out, L), (W0.shape, W1.shape, X.shape, Y.shape, tr)
+        for t in (X, Y):
+            assert t.data_ptr() % 16 == 0 and _ld(t) % 4 == 0, "X / Y rows must be 16-byte aligned"
+        d.W0, d.ldw0, d.W1, d.ldw1, d.X, d.ldx, d.Y, d.ldy = _p(W0), _ld(W0), _p(W1), _ld(W1), _p(X), _ld(X), _p(Y), _ld(Y)
+        d.N, d.K, d.dtype0, d.dtype1, d.transposed = N, K, MERGE_DTYPES[W0.dtype], MERGE_DTYPES[W1.dtype], int(tr)
+        rs = it.get("rowsq")
+        if rs is not None:
+            _chk2(rs, F32)
+            assert not tr and rs.numel() == N and rs.is_contiguous()
+            d.rowsq = _p(rs)
+        counts.append((rows_out + 63) // 64)
+    nb, bd, bf = _block_table(counts, device)
+    return _to_dev(arr, device), nb, bd, bf
+
+
+def _delta_launch(table, L):
+    dev, nb, bd, bf = table
+    if nb:
+        _lib.check(_lib.load().sdlt_delta_matmul(_p(dev), _p(bd), _p(bf), nb, L, _stream()), "sdlt_delta_matmul")
+
+
+def delta_matmul(items, device=None):
+    """One sdlt_delta_matmul launch over `items` (see _delta_table; every item chooses its orientation): Y = (W1 - W0) X or (W1 - W0)^T X in
+    fp32, the difference formed in registers."""
+    if not items:
+        return
+    L = items[0]["X"].shape[1]
+    table = _delta_table(items, L, device or items[0]["X"].device)
+    _delta_launch(table, L)
+    return table          # (the caller keeps it alive until the stream has run the launch)
+
+
+class DeltaPlan:
+    """Descriptor tables of sdlt_delta_matmul for one (base, tuned) model pair, built once: layers = dict(W0, W1 [N, K], Pk fp32 [K, L],
+    Pn fp32 [N, L][, rowsq fp32 [N]]).  forward(): Pn = (W1 - W0) Pk (and rowsq) ; transposed(): Pk = (W1 - W0)^T Pn - one launch each
+    for all layers."""
+
+    def __init__(self, layers, L, device):
+        self.keep, self.L = layers, L
+        self.fwd = _delta_table([dict(W0=l["W0"], W1=l["W1"], X=l["Pk"], Y=l["Pn"], rowsq=l.get("rowsq")) for l in layers], L, device)
+        self.tr = _delta_table([dict(W0=l["W0"], W1=l["W1"], X=l["Pn"], Y=l["Pk"], transposed=True) for l in layers], L, device)
+
+    def forward(self):
+        _delta_launch(self.fwd, self.L)
+
+    def transposed(self):
+        _delta_launch(self.tr, self.L)
+
+
 def _shadow_adamw(self, p, g, m, v, hyper):
     """AdamW step fused into the refresh tiles (sdlt_adamw_shadow_refresh); covers exactly the elements the plan's descriptors tile."""
     lib = _lib.load()
