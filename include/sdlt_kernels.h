@@ -20,7 +20,7 @@ extern "C" {
 
 const char* sdlt_last_error(void);
 int sdlt_abi_version(void);
-int sdlt_struct_size(int which); /* 0 gemm, 1 lora_grad_desc, 2 attn, 3 groupnorm, 4 shadow_desc, 5 gemm_batch_item, 6 dora_desc, 7 dora_wt_desc, 8 dora_grad_desc, 9 splitsum_desc ... 19 merge_desc, 20 sampler_params, 21 delta_desc */
+int sdlt_struct_size(int which); /* 0 gemm, 1 lora_grad_desc, 2 attn, 3 groupnorm, 4 shadow_desc, 5 gemm_batch_item, 6 dora_desc, 7 dora_wt_desc, 8 dora_grad_desc, 9 splitsum_desc ... 19 merge_desc, 20 sampler_params, 21 delta_desc, 22 sampler_img_params */
 
 /* ------------------------------------------------------------------------------------------------
  * sdlt_gemm_bf16 : C = alpha*(X.W^T [+ X2.W2^T] [+ s*(X.Adown^T).Bup^T]) + bias + rowbias + R
@@ -539,6 +539,28 @@ typedef struct sdlt_sampler_params {
   int32_t n, hw, table_rows, init;
 } sdlt_sampler_params;
 int sdlt_sampler_step(const sdlt_sampler_params* p, void* stream);
+
+/* sdlt_sampler_step_img : the same launch for a trajectory that starts from an init image (img2img) and, with a mask, keeps a known region
+ * (inpainting).  x0 fp32 [n, 4, hw]: the encoded init latents times the scaling factor; noise fp32 [n, 4, hw]: ONE draw for the whole
+ * trajectory; mask fp32 [n, hw] or NULL: 1 regenerate, 0 keep.  Table, counter, ticket, repack and timesteps as sdlt_sampler_step, with
+ * row 0 column 1 = the FIRST USED sigma (the host skips the head of the schedule: strength and step count live in the table).
+ *     init != 0:  x = x0 + noise * sigma_0 ;  xin = bf16(x / sqrt(sigma_0^2 + 1)) ;  ctr[0] = 0   (eps and mask are not read)
+ *     init == 0:  xn = x + d (sigma_next - sigma) as above ;  with a mask: k = x0 + noise * sigma_next, xn = k + m (xn - k) ;  x = xn, xin, timesteps, ctr
+ * m = 0 gives k exactly, and k = x0 exactly after the last step (sigma_next = 0).  Without a mask a step reads neither x0 nor noise.
+ * All arithmetic fp32, one rounding per operation, in the order written.  x0 and noise may not alias x.  Alignment as sdlt_sampler_step. */
+typedef struct sdlt_sampler_img_params {
+  const float* eps;                  /* fp32 [2n * hw, 4]: UNet.forward's output (step only) */
+  float* x;                          /* fp32 [n, 4, hw] latent state, in place */
+  const float* x0;                   /* fp32 [n, 4, hw]: init, and every step with a mask */
+  const float* noise;                /* fp32 [n, 4, hw]: init, and every step with a mask */
+  const float* mask;                 /* fp32 [n, hw] or NULL */
+  void* xin; int64_t ld_xin;         /* bf16 [2n * hw, ld_xin] NHWC model input */
+  float* timesteps;                  /* fp32 [2n] */
+  const float* table;
+  int32_t* ctr;
+  int32_t n, hw, table_rows, init;
+} sdlt_sampler_img_params;
+int sdlt_sampler_step_img(const sdlt_sampler_img_params* p, void* stream);
 
 /* out[M,C] = a + b on strided 2-D bf16 views (gradient fan-in of the UNet skip connections). */
 int sdlt_add2d(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int32_t M, int32_t C, void* stream);

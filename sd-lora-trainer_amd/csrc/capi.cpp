@@ -42,6 +42,7 @@ extern "C" int sdlt_struct_size(int which) {
     case 19: return (int)sizeof(sdlt_merge_desc);
     case 20: return (int)sizeof(sdlt_sampler_params);
     case 21: return (int)sizeof(sdlt_delta_desc);
+    case 22: return (int)sizeof(sdlt_sampler_img_params);
   }
   return -1;
 }

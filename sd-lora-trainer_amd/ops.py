@@ -1239,6 +1239,31 @@ def sampler_step(eps, x, xin, timesteps, table, ctr, *, noise=None):
     return x
 
 
+def sampler_step_img(eps, x, xin, timesteps, table, ctr, *, x0, noise, mask=None, init=False):
+    """sdlt_sampler_step_img: sampler_step for a trajectory that starts from init latents.  x0, noise fp32 [n, 4, h, w] (the encoded image times the
+    scaling factor; ONE noise draw for all steps), mask fp32 [n, 1, h, w] or None (1 regenerate, 0 keep), table from sampler.step_table_img.
+    init: x = x0 + noise * (first used sigma), eps is not read (None); otherwise the Euler step and, with a mask, the blend with x0 noised to the
+    next sigma.  The other operands as sampler_step."""
+    lib = _lib.load()
+    n, c4, h, w = x.shape
+    _chk2(x, F32), _chk2(xin), _chk2(timesteps, F32), _chk2(table, F32), _chk2(ctr, torch.int32), _chk2(x0, F32), _chk2(noise, F32)
+    assert c4 == 4 and x.is_contiguous() and table.is_contiguous() and table.dim() == 2 and table.shape[1] == 4 and ctr.numel() >= 2
+    assert xin.shape[0] == 2 * n * h * w and timesteps.numel() >= 2 * n and timesteps.is_contiguous()
+    assert x0.shape == x.shape and x0.is_contiguous() and noise.shape == x.shape and noise.is_contiguous()
+    assert x0.data_ptr() != x.data_ptr() and noise.data_ptr() != x.data_ptr(), "x0 and noise are read at every step: they may not alias x"
+    if mask is not None:
+        _chk2(mask, F32)
+        assert tuple(mask.shape) == (n, 1, h, w) and mask.is_contiguous()
+    if not init:
+        _chk2(eps, F32)
+        assert eps.is_contiguous() and tuple(eps.shape) == (2 * n * h * w, 4)
+    p = _lib.SamplerImgParams(eps=None if init else eps.data_ptr(), x=x.data_ptr(), x0=x0.data_ptr(), noise=noise.data_ptr(),
+                              mask=None if mask is None else mask.data_ptr(), xin=xin.data_ptr(), ld_xin=_ld(xin), timesteps=timesteps.data_ptr(),
+                              table=table.data_ptr(), ctr=ctr.data_ptr(), n=n, hw=h * w, table_rows=table.shape[0], init=int(init))
+    _lib.check(lib.sdlt_sampler_step_img(C.byref(p), _stream()), "sdlt_sampler_step_img")
+    return x
+
+
 def masked_mse_fwd_bwd(pred, noise, noisy, mask, timesteps, alphas_cumprod, sums, loss_out, dpred, *, snr_gamma, v_prediction=False,
                        loss_scale=1.0):
     lib = _lib.load()

@@ -4,6 +4,7 @@ scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-squ
 
     python -m sd_lora_trainer_amd.render --checkpoint DIR --out DIR [--prompt TEXT ...] [--n-validation N] [--lora-scale X ...] [--size W H]
                                          [--steps N] [--guidance G] [--seed S] [--images-per-batch N] [--eager]
+                                         [--init-image PATH [--strength S] [--mask PATH]]
                                          [--unet F] [--text-encoder F] [--text-encoder-2 F] [--vae F] [--tokenizer DIR]
 
 DIR is a checkpoint directory of train(): training_args.json (the job's TrainingConfig), adapter_config.json + the kohya adapter file
@@ -11,6 +12,11 @@ DIR is a checkpoint directory of train(): training_args.json (the job's Training
 special_params.json; a full fine-tune (`is_lora` false) has diffusion_pytorch_model.safetensors instead of the adapter files.  The base model is
 the job's `pretrained_model` unless given (anything train() accepts, "synthetic:<version>" included).  The sampler runs each denoising iteration
 as one replayed hipGraph (sampler.LatentSampler.sample(graph=True)); --eager issues the same kernels from Python.
+
+--init-image starts every image from that picture instead of pure noise (img2img): it is resized to --size (bicubic), encoded by the VAE encoder
+of the loaded stack (the posterior's mean times the scaling factor: deterministic) and noised to the point of the schedule that --strength
+selects (default 0.6; the last int(steps * strength) steps run).  --mask (white: regenerate, black: keep; nearest-resized to the latent grid)
+keeps the black region of the init image: it is put back after every step, and comes out as the encoded image exactly.
 """
 import argparse
 import json
@@ -145,13 +151,41 @@ def _scale_tag(s):
     return f"{s:.2f}"
 
 
+def _open(image):
+    from PIL import Image
+    return Image.open(image) if isinstance(image, (str, os.PathLike)) else image
+
+
+@torch.no_grad()
+def encode_init(loaded, init_image, mask_image, size, latent_hw):
+    """-> (init latents [1, 4, h, w] fp32 = posterior mean of the image, resized to `size` = (width, height), times the scaling factor;
+    mask [1, 1, h, w] fp32 | None: dataset.latent_mask's resize, 1 regenerate / 0 keep).  Images are paths or PIL images."""
+    from . import dataset as D
+    from . import unet as M
+    from . import vae as V
+    stack, cfg = loaded.stack, loaded.models.cfg
+    rt = stack.rt
+    enc = V.VaeEncoder(M.Runtime(rt.device, 1, act_dtype=rt.act, ops=rt.ops), loaded.models.vae_state())
+    f = 2 ** (len(enc.downs) - 1)
+    h, w = latent_hw
+    if (size[0], size[1]) != (f * w, f * h):
+        raise ValueError(f"an init image needs a size that is a multiple of {f}, got {size[0]} x {size[1]}")
+    mom = enc.encode_moments(D.prepare_image(_open(init_image).convert("RGB"), size[0], size[1]))
+    x0 = mom[:, : mom.shape[1] // 2].float() * cfg["scaling_factor"]
+    mask = None
+    if mask_image is not None:
+        mask = D.latent_mask(_open(mask_image), size, (h, w), channels=1).reshape(1, 1, h, w).to(rt.device)
+    return x0.contiguous(), mask
+
+
 @torch.no_grad()
 def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, guidance_scale=8.0, seed=None, images_per_batch=1, token_scale=None,
-           graph=True, n_validation=4):
+           graph=True, n_validation=4, init_image=None, strength=None, mask_image=None):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
     seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
-    graph=False is the eager loop with the same fused kernel.  -> {scale: [paths]}."""
+    graph=False is the eager loop with the same fused kernel.  init_image (path or PIL image): every image starts from it (encode_init) at
+    `strength` (default 0.6) instead of from pure noise, each with its own noise; mask_image: white regenerate, black keep.  -> {scale: [paths]}."""
     from . import train as T
     from . import vae as _vae
     from PIL import Image
@@ -171,6 +205,18 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     f = 2 ** (len(stack.decoder.ups) - 1) if hasattr(stack.decoder, "ups") else 8      # 8 for the SD / SDXL VAE
     w, h = size[0] // f, size[1] // f
     n = images_per_batch
+    img_kw = {}
+    if init_image is None:
+        if mask_image is not None:
+            raise ValueError("mask_image needs init_image: the region to keep is taken from it")
+        if strength is not None:
+            raise ValueError("strength needs init_image")
+    else:
+        from . import sampler as SM
+        strength = 0.6 if strength is None else strength
+        SM.img2img_steps(steps, strength)               # (raises before anything is built)
+        x0, mask = encode_init(loaded, init_image, mask_image, size, (h, w))
+        img_kw = dict(init_latents=x0, strength=strength, mask=mask)
     loaded.prepare(n, h, w)
     smp, fused = stack.sampler, hasattr(stack.rt.ops, "sampler_step")
     graph = graph and dev.type == "cuda"
@@ -186,10 +232,10 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
                 noise = torch.cat([torch.randn(1, 4, h, w, generator=torch.Generator(device=dev).manual_seed(seed + i), device=dev) for i in idx])
                 if fused:
                     lat = smp.sample([embeds[i] for i in idx] if n > 1 else embeds[idx[0]], h, w, steps=steps, guidance_scale=guidance_scale,
-                                     size=(size[1], size[0]), latents=noise, graph=graph, fused=True, n_images=n)
+                                     size=(size[1], size[0]), latents=noise, graph=graph, fused=True, n_images=n, **img_kw)
                 else:                                                            # an op table without the fused kernel: the torch loop, image by image
                     lat = torch.cat([smp.sample(embeds[i], h, w, steps=steps, guidance_scale=guidance_scale, size=(size[1], size[0]),
-                                                latents=noise[j:j + 1]) for j, i in enumerate(idx)])
+                                                latents=noise[j:j + 1], **img_kw) for j, i in enumerate(idx)])
                 for j, i in enumerate(idx[: len(prompts) - s0]):
                     img = _vae.postprocess(stack.decoder.decode(lat[j:j + 1] / cfg["scaling_factor"]))[0].permute(1, 2, 0)
                     arr = (img.float().cpu().numpy() * 255).round().astype("uint8")
@@ -200,7 +246,10 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     finally:
         smp.set_lora_scale(1.0)
     with open(os.path.join(out_dir, "prompts.json"), "w") as fh:
-        json.dump(dict(prompts=prompts, lora_scales=list(lora_scales), size=list(size), steps=steps, guidance_scale=guidance_scale, seed=seed), fh, indent=2)
+        meta = dict(prompts=prompts, lora_scales=list(lora_scales), size=list(size), steps=steps, guidance_scale=guidance_scale, seed=seed)
+        if init_image is not None:
+            meta.update(strength=strength, masked=mask_image is not None)
+        json.dump(meta, fh, indent=2)
     return result
 
 
@@ -217,12 +266,19 @@ def main(argv=None, runtime=None):
     ap.add_argument("--seed", type=int, default=None, help="image i starts from seed + i; default: the job's seed")
     ap.add_argument("--images-per-batch", type=int, default=1, help="images sampled together (UNet batch 2 N)")
     ap.add_argument("--eager", action="store_true", help="issue every launch from Python instead of replaying one hipGraph per iteration (same kernels)")
+    ap.add_argument("--init-image", default=None, help="start from this picture instead of pure noise (img2img); resized to --size")
+    ap.add_argument("--strength", type=float, default=None, help="how much of the schedule runs on the init image, in (0, 1]; default 0.6 with --init-image")
+    ap.add_argument("--mask", default=None, help="inpainting mask for --init-image: white is regenerated, black is kept")
     ap.add_argument("--device", default="cuda:0")
     for flag, key, what in (("--unet", "path", "base UNet weights or synthetic:<version>"), ("--text-encoder", "text_encoder_path", "text encoder state dict"),
                             ("--text-encoder-2", "text_encoder_2_path", "SDXL's second text encoder"), ("--vae", "vae_path", "AutoencoderKL state dict"),
                             ("--tokenizer", "tokenizer_path", "directory with vocab.json + merges.txt")):
         ap.add_argument(flag, dest=key, default=None, help=what + " (default: the job's)")
     a = ap.parse_args(argv)
+    if a.init_image is None and (a.mask is not None or a.strength is not None):
+        ap.error("--mask and --strength need --init-image")
+    if a.strength is not None and not 0.0 < a.strength <= 1.0:
+        ap.error(f"--strength must be in (0, 1], got {a.strength}")
     over = {k: getattr(a, k) for k in ("path", "text_encoder_path", "text_encoder_2_path", "vae_path", "tokenizer_path") if getattr(a, k)}
     pm = None
     if over and os.path.exists(os.path.join(a.checkpoint, "training_args.json")):
@@ -230,7 +286,8 @@ def main(argv=None, runtime=None):
             pm = dict(json.load(f).get("pretrained_model") or {}, **over)
     loaded = load_for_inference(a.checkpoint, pm, device=a.device, runtime=runtime)
     res = render(loaded, a.prompt, a.out, lora_scales=a.lora_scale, size=a.size, steps=a.steps, guidance_scale=a.guidance, seed=a.seed,
-                 images_per_batch=a.images_per_batch, graph=not a.eager, n_validation=a.n_validation)
+                 images_per_batch=a.images_per_batch, graph=not a.eager, n_validation=a.n_validation, init_image=a.init_image, strength=a.strength,
+                 mask_image=a.mask)
     for scale, paths in res.items():
         print(f"lora_scale {scale}: {len(paths)} image(s), {os.path.join(a.out, 'grid_scale' + _scale_tag(scale) + '.jpg')}")
     return res

@@ -10,6 +10,11 @@ reference builds (`from_config(training scheduler config, timestep_spacing="trai
 v prediction, no Karras sigmas): sigma_t = sqrt((1 - abar_t) / abar_t), timesteps = round(arange(T, 0, -T/n)) - 1, sigmas
 interpolated at those timesteps plus a final 0, initial noise scaled by sigma_max (trailing spacing), model input x / sqrt(sigma^2 + 1),
 x_next = x + d * (sigma_next - sigma) with d = eps (epsilon prediction).
+
+From an init image (`sample(init_latents=, strength=, mask=)`): diffusers' img2img rule keeps the last k = min(int(steps * strength), steps)
+entries of the trailing schedule (StableDiffusionImg2ImgPipeline.get_timesteps) and starts from x0 + noise * sigma of the first kept entry
+(EulerDiscreteScheduler.add_noise); with a mask (1 regenerate, 0 keep) the known region is put back after every step, noised to the sigma the
+step arrived at, from the same noise draw (the legacy inpainting loop of diffusers: latents = init_latents_proper * (1 - mask) + latents * mask).
 """
 import numpy as np
 import torch
@@ -34,8 +39,10 @@ class EulerDiscrete:
         self.sigmas_all = np.sqrt((1 - acp) / acp)
         self.T, self.prediction_type = num_train_timesteps, prediction_type
 
-    def set_timesteps(self, n):
-        ts = np.round(np.arange(self.T, 0, -self.T / n)) - 1                       # "trailing"
+    def set_timesteps(self, n, start=0):
+        """start: skip the first `start` entries of the schedule (img2img: the trajectory begins at timesteps[start] of the n-step schedule)."""
+        assert 0 <= start < n
+        ts = np.round(np.arange(self.T, 0, -self.T / n))[start:] - 1               # "trailing"
         sig = np.interp(ts, np.arange(self.T), self.sigmas_all)
         self.timesteps = ts.astype(np.float32)
         self.sigmas = np.concatenate([sig, [0.0]]).astype(np.float32)
@@ -77,6 +84,24 @@ def step_table(sched, guidance_scale):
     return torch.from_numpy(tab)
 
 
+def img2img_steps(steps, strength):
+    """diffusers' img2img rule -> (k steps to run, index of the first one in the `steps`-entry schedule)."""
+    if not (isinstance(strength, (int, float)) and 0.0 < strength <= 1.0):
+        raise ValueError(f"strength must be in (0, 1], got {strength!r}")
+    k = min(int(steps * strength), steps)
+    if k < 1:
+        raise ValueError(f"strength {strength} of {steps} steps leaves no step to run (int(steps * strength) = {k})")
+    return k, steps - k
+
+
+def step_table_img(sched, guidance_scale):
+    """step_table for ops.sampler_step_img, for a scheduler whose set_timesteps(n, start) has run: the rows of the k = n - start steps that run, and
+    row 0 column 1 = the FIRST USED sigma (x = x0 + noise * sigma_0) instead of init_noise_sigma."""
+    tab = step_table(sched, guidance_scale)
+    tab[0, 1] = float(sched.sigmas[0])
+    return tab
+
+
 class LatentSampler:
     """`pipe(prompt_embeds=c, negative_prompt_embeds=uc, ..., num_inference_steps, guidance_scale, generator)` of the
     reference's render loop, up to the latents.  `unet` is an inference instance built for batch 2 (negative | positive, the
@@ -92,6 +117,7 @@ class LatentSampler:
         self.pooled = rt.zeros(rt.B, cfg["proj_class_in"] - 6 * cfg["addition_time_embed_dim"]) if cfg["addition"] else None
         self._fused = None                 # persistent device state of the fused / graph path, built on first use
         self._graphs = {}                  # (h, w, n, adapter scale in effect, DoRA) -> hipGraph of one denoising iteration
+        self._img_graphs = {}              # the same key + (masked,) -> hipGraph of one iteration whose step launch is ops.sampler_step_img
 
     def set_lora_scale(self, lora_scale, train_scale=None):
         """set_adapter_scales (checkpoint.py:31-55): every adapter's contribution is multiplied by lora_scale."""
@@ -102,14 +128,20 @@ class LatentSampler:
             a.set_scale(a._train_scale * lora_scale)      # (DoRA: the column factors follow the scale in effect)
 
     @torch.no_grad()
-    def sample(self, embeds, h, w, *, steps=25, guidance_scale=8.0, generator=None, size=None, latents=None, graph=False, fused=False, n_images=1):
+    def sample(self, embeds, h, w, *, steps=25, guidance_scale=8.0, generator=None, size=None, latents=None, graph=False, fused=False, n_images=1,
+               init_latents=None, strength=1.0, mask=None):
         """embeds = (c [1,77,D], uc [1,77,D], pc [1,P] | None, puc | None); h, w latent size.  Returns latents [1,4,h,w] fp32
         (still multiplied by the VAE scaling factor, as the pipeline holds them before `vae.decode(latents / scaling_factor)`).
         fused: guidance, the Euler update and the next model input are ONE kernel between two forwards (ops.sampler_step) instead of torch
         element-wise launches; graph: that iteration additionally replayed as a hipGraph (implies fused).  Both sample n_images images together
-        on a runtime of batch 2 n_images: embeds is then a list of n_images 4-tuples and the result [n_images, 4, h, w]."""
+        on a runtime of batch 2 n_images: embeds is then a list of n_images 4-tuples and the result [n_images, 4, h, w].
+        init_latents [n_images | 1, 4, h, w] (the encoded image times the scaling factor): img2img - the last min(int(steps * strength), steps) steps of
+        the schedule, from init_latents noised to the first of them (`latents` / `generator` give the noise, as above).  mask [n_images | 1, 1, h, w] in
+        [0, 1]: 1 regenerate, 0 keep - the kept region is re-injected after every step and equals init_latents exactly at the end.  strength 1 without a
+        mask is txt2img from the noise; a mask of ones is no mask."""
+        img = self._img_args(init_latents, strength, mask, steps, h, w, n_images)
         if graph or fused:
-            return self._sample_fused(embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images)
+            return self._sample_fused(embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img)
         assert n_images == 1 and self.rt.B == 2, "the torch loop samples one image on a batch-2 runtime; several images together: fused=True or graph=True"
         rt, u, cfg = self.rt, self.unet, self.unet.cfg
         dev = rt.device
@@ -123,9 +155,14 @@ class LatentSampler:
             self.pooled[1].copy_(pc[0])
             H, W = size if size is not None else (8 * h, 8 * w)
             tid = torch.tensor([float(H), float(W), 0.0, 0.0, float(H), float(W)] * 2, device=dev)   # original_size, crop, target_size
-        s = self.sched.set_timesteps(steps)
+        x0, m, start = img if img is not None else (None, None, 0)
+        s = self.sched.set_timesteps(steps, start) if img is not None else self.sched.set_timesteps(steps)
         x = latents if latents is not None else torch.randn(1, 4, h, w, generator=generator, device=dev, dtype=F32)
-        x = x.to(dev, F32) * s.init_noise_sigma
+        if img is None:
+            x = x.to(dev, F32) * s.init_noise_sigma
+        else:
+            noise = x.to(dev, F32)
+            x = x0 + noise * float(s.sigmas[0])
         x64 = rt.zeros(2 * h * w, 64)
         for i, t in enumerate(s.timesteps):
             xin = s.scale_model_input(x, i)
@@ -134,7 +171,36 @@ class LatentSampler:
             eps = u.forward(x64, tf, self.ctx, self.pooled, tid, B=2, H=h, W=w).view(2, h, w, 4).permute(0, 3, 1, 2)
             e = eps[0:1] + guidance_scale * (eps[1:2] - eps[0:1])
             x = s.step(e, i, x)
+            if m is not None:                      # the known region, noised to the sigma this step arrived at (0 after the last: init_latents itself)
+                k = x0 + noise * float(s.sigmas[i + 1])
+                x = k + m * (x - k)
         return x
+
+    def _img_args(self, init_latents, strength, mask, steps, h, w, n):
+        """-> None (txt2img: no init_latents, or strength 1 without a mask) | (x0 [n, 4, h, w], mask [n, 1, h, w] | None, first step) on the device."""
+        if init_latents is None:
+            if mask is not None:
+                raise ValueError("mask needs init_latents: the region to keep is taken from them")
+            if strength != 1.0:
+                raise ValueError("strength needs init_latents")
+            return None
+        _, start = img2img_steps(steps, strength)
+        dev = self.rt.device
+        if init_latents.dim() != 4 or tuple(init_latents.shape[1:]) != (4, h, w) or init_latents.shape[0] not in (1, n):
+            raise ValueError(f"init_latents {tuple(init_latents.shape)}: expected [{n} or 1, 4, {h}, {w}]")
+        x0 = init_latents.to(dev, F32).expand(n, 4, h, w).contiguous()
+        if mask is not None:
+            if mask.dim() != 4 or tuple(mask.shape[1:]) != (1, h, w) or mask.shape[0] not in (1, n):
+                raise ValueError(f"mask {tuple(mask.shape)}: expected [{n} or 1, 1, {h}, {w}]")
+            mask = mask.to(dev, F32)
+            lo, hi = float(mask.min()), float(mask.max())
+            if not (lo >= 0.0 and hi <= 1.0):
+                raise ValueError(f"mask values must lie in [0, 1] (1 regenerate, 0 keep), got [{lo}, {hi}]")
+            # ones everywhere: nothing to keep.  (k + 1 (x - k) rounds twice where the plain step does not, so it is not left to the blend.)
+            mask = None if lo == 1.0 else mask.expand(n, 1, h, w).contiguous()
+        if mask is None and start == 0:
+            return None
+        return x0, mask, start
 
     # ---- fused / graph path ---------------------------------------------------------------------------------------------------
     def _scope(self):
@@ -155,32 +221,50 @@ class LatentSampler:
             st["shapes"][(h, w)] = dict(x=rt.zeros(n, 4, h, w, dtype=F32), x64=rt.zeros(2 * n * h * w, 64))
         return st, st["shapes"][(h, w)]
 
-    def _iteration(self, st, sh, h, w):
+    def _img_state(self, sh, h, w):
+        """The persistent init latents, noise and mask of a shape: a captured ops.sampler_step_img launch holds their pointers."""
+        if "img" not in sh:
+            rt, n = self.rt, self.n
+            sh["img"] = dict(x0=rt.zeros(n, 4, h, w, dtype=F32), noise=rt.zeros(n, 4, h, w, dtype=F32), mask=rt.zeros(n, 1, h, w, dtype=F32))
+        return sh["img"]
+
+    def _iteration(self, st, sh, h, w, masked=None):
+        """masked None: txt2img; False / True: from init latents, without / with the mask (sh["img"] holds them)."""
         u = self.unet
         eps = u.forward(sh["x64"], st["tf"], self.ctx, self.pooled, st["tid"] if u.cfg["addition"] else None, B=2 * self.n, H=h, W=w)
-        self.rt.ops.sampler_step(eps, sh["x"], sh["x64"], st["tf"], st["table"], st["ctr"])
+        if masked is None:
+            self.rt.ops.sampler_step(eps, sh["x"], sh["x64"], st["tf"], st["table"], st["ctr"])
+        else:
+            im = sh["img"]
+            self.rt.ops.sampler_step_img(eps, sh["x"], sh["x64"], st["tf"], st["table"], st["ctr"], x0=im["x0"], noise=im["noise"],
+                                         mask=im["mask"] if masked else None)
 
-    def _graph(self, st, sh, h, w):
+    def _graph(self, st, sh, h, w, masked=None):
         """The hipGraph of one iteration for this shape and the adapter scale in effect.  The scale is a launch argument of every adapted GEMM
-        (baked by capture), hence part of the key; adapters, DoRA factors, token rows, conditioning, table and counter are device memory."""
+        (baked by capture), hence part of the key; adapters, DoRA factors, token rows, conditioning, table and counter are device memory.
+        From init latents (masked False / True) the step launch is another kernel: those captures live in a dict of their own, keyed by the mask
+        pointer's presence as well; strength and step count are in the table, init latents, noise and mask in persistent buffers."""
         a = self.unet.arena
         key = (h, w, self.n, None if a is None else float(a.scale), bool(a is not None and a.dora))
-        g = self._graphs.get(key)
+        graphs = self._graphs
+        if masked is not None:
+            key, graphs = key + (bool(masked),), self._img_graphs
+        g = graphs.get(key)
         if g is not None:
             return g
-        while len(self._graphs) >= MAX_GRAPHS:            # a sweep over many scales: the oldest capture goes
-            self._graphs.pop(next(iter(self._graphs)))
+        while len(graphs) >= MAX_GRAPHS:                  # a sweep over many scales: the oldest capture goes
+            graphs.pop(next(iter(graphs)))
         ops = self.rt.ops
         prefetch = hasattr(ops, "pf_record_begin") and getattr(ops, "WSK_PREFETCH", False)
         side = torch.cuda.Stream(device=self.rt.device)
         side.wait_stream(torch.cuda.current_stream())
         seq = None
         with torch.cuda.stream(side):
-            self._iteration(st, sh, h, w)                 # eager warm-up: every persistent buffer and packed-weight copy exists before the capture
+            self._iteration(st, sh, h, w, masked)         # eager warm-up: every persistent buffer and packed-weight copy exists before the capture
             if prefetch:                                  # next-weight hints of the wave-split-K products, recorded from one eager pass (step.TrainStep.capture)
                 ops.pf_record_begin()
                 try:
-                    self._iteration(st, sh, h, w)
+                    self._iteration(st, sh, h, w, masked)
                 finally:
                     seq = ops.pf_record_end()
         torch.cuda.current_stream().wait_stream(side)
@@ -189,17 +273,19 @@ class LatentSampler:
             if seq:
                 ops.pf_replay_begin(seq)
             try:
-                self._iteration(st, sh, h, w)
+                self._iteration(st, sh, h, w, masked)
             finally:
                 if seq:
                     ops.pf_replay_end()
-        self._graphs[key] = g
+        graphs[key] = g
         return g
 
-    def _sample_fused(self, embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images):
+    def _sample_fused(self, embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img=None):
         rt, cfg, n = self.rt, self.unet.cfg, self.n
         if not hasattr(rt.ops, "sampler_step"):
             raise NotImplementedError("this op table has no sampler_step kernel: sample(graph=False, fused=False) is the torch loop")
+        if img is not None and not hasattr(rt.ops, "sampler_step_img"):
+            raise NotImplementedError("this op table has no sampler_step_img kernel: sample(init_latents=..., graph=False, fused=False) is the torch loop")
         assert n_images == n, f"the runtime's batch {rt.B} samples {n} image(s) together, not {n_images}"
         assert 1 <= steps <= TABLE_ROWS - 2
         dev = rt.device
@@ -217,24 +303,39 @@ class LatentSampler:
         if cfg["addition"]:
             H, W = size if size is not None else (8 * h, 8 * w)
             st["tid"].copy_(torch.tensor([float(H), float(W), 0.0, 0.0, float(H), float(W)] * (2 * n)))
-        s = self.sched.set_timesteps(steps)
-        tab = step_table(s, guidance_scale)
+        if img is None:
+            s = self.sched.set_timesteps(steps)
+            tab = step_table(s, guidance_scale)
+        else:
+            s = self.sched.set_timesteps(steps, img[2])
+            tab = step_table_img(s, guidance_scale)
+            steps -= img[2]                                 # the steps that run: the table holds their rows only
         st["table"][: tab.shape[0]].copy_(tab)
         noise = latents if latents is not None else torch.randn(n, 4, h, w, generator=generator, device=dev, dtype=F32)
         noise = noise.to(dev, F32).contiguous()
         assert tuple(noise.shape) == (n, 4, h, w)
         x, x64 = sh["x"], sh["x64"]
+        masked = None
+        if img is None:
+            init = lambda: rt.ops.sampler_step(None, x, x64, st["tf"], st["table"], st["ctr"], noise=noise)  # noqa: E731
+        else:
+            im, masked = self._img_state(sh, h, w), img[1] is not None
+            im["x0"].copy_(img[0])
+            im["noise"].copy_(noise)
+            if masked:
+                im["mask"].copy_(img[1])
+            init = lambda: rt.ops.sampler_step_img(None, x, x64, st["tf"], st["table"], st["ctr"], x0=im["x0"], noise=im["noise"], init=True)  # noqa: E731
         with self._scope():
             g = None
             if graph:
-                rt.ops.sampler_step(None, x, x64, st["tf"], st["table"], st["ctr"], noise=noise)     # (a defined state for the warm-up passes)
-                g = self._graph(st, sh, h, w)
-            rt.ops.sampler_step(None, x, x64, st["tf"], st["table"], st["ctr"], noise=noise)
+                init()                                    # (a defined state for the warm-up passes)
+                g = self._graph(st, sh, h, w, masked)
+            init()
             for _ in range(steps):                        # no host read in here: the step index lives in ctr, its scalars in the table
                 if g is not None:
                     g.replay()
                 else:
-                    self._iteration(st, sh, h, w)
+                    self._iteration(st, sh, h, w, masked)
         return x.clone()
 
 

@@ -1003,7 +1003,10 @@ class Attention(_Module):
                         and not (self.to_out.lora is not None and self.to_out.arena.wide)
                         and getattr(rt.ops, "wsk_rowdot_shape", None) is not None and rt.ops.wsk_rowdot_shape(Mq, C, C, self.to_out.lora is not None, self.d))
         kwz = {"zero_D": self.buf("D", B * self.heads * N, dtype=F32)} if self._rowdot else {}
-        rt.ops.attn_fwd(q, k, v, None, O, L, B=B, H=self.heads, Nq=N, Nk=Nk, Nqp=N, Nkp=Nkp, d=self.d, scale=self.scale, **kwz)
+        if N % 8:
+            self._attn_fwd_padded(q, k, v, O, L, B, N, Nk, Nkp)
+        else:
+            rt.ops.attn_fwd(q, k, v, None, O, L, B=B, H=self.heads, Nq=N, Nk=Nk, Nqp=N, Nkp=Nkp, d=self.d, scale=self.scale, **kwz)
         if self.cross and self.hooked:
             # DAAM side output (ti_cross_attn_loss.py:201-212): sum over heads of Q_h K_h^T / sqrt(d) = Q K^T / sqrt(d).
             # The token-attention loss only ever uses the MEAN over layers of these maps (loss.py:23-52), so the layers
@@ -1025,6 +1028,23 @@ class Attention(_Module):
                     rt.ops.gemm(q[b * N:(b + 1) * N], k[b * Nkp:(b + 1) * Nkp], S[b * N:(b + 1) * N], alpha=self.scale)
                 rt.daam.append((self.name, S.view(B, N, CTX_PAD)))
         return self.to_out.forward(O, residual=residual, parts_for=parts_for)
+
+    def _attn_fwd_padded(self, q, k, v, O, L, B, N, Nk, Nkp):
+        """A map of 4 or 6 tokens per image (the innermost level of the toy topologies at an 8 x 8 / 8 x 12 latent; no real model gets here): the kernel
+        wants every batch to start on an 8-row boundary, so q - and k | v of self-attention - move into zeroed padded rows (keys past Nk are masked and
+        their V rows meet P == 0) and the N real rows of O come back.  Forward only: the backward kernels refuse such a map (sdlt_attn_bwd's own row check)."""
+        C, Np = self.C, _pad_to(N, 8)
+        self._rowdot = False
+        qp = self.buf("q_pad", B * Np, C, zero=True)
+        qp.view(B, Np, C)[:, :N].copy_(q.reshape(B, N, C))
+        if not self.cross:
+            kvp = self.buf("kv_pad", 2, B * Np, C, zero=True)
+            for dst, src in zip(kvp, (k, v)):
+                dst.view(B, Np, C)[:, :N].copy_(src.reshape(B, N, C))
+            k, v, Nkp = kvp[0], kvp[1], Np
+        Op = self.buf("O_pad", B * Np, C)
+        self.rt.ops.attn_fwd(qp, k, v, None, Op, L, B=B, H=self.heads, Nq=N, Nk=Nk, Nqp=Np, Nkp=Nkp, d=self.d, scale=self.scale)
+        O.view(B, N, C).copy_(Op.view(B, Np, C)[:, :N])
 
     def backward(self, dout, dctx=None):
         """dout = grad of (residual + to_out(attn)); returns d(attention input) WITHOUT the residual path."""

@@ -1,9 +1,11 @@
 """What the validation sampler costs per denoising iteration, three ways in ONE session (alternated, so that clocks and neighbours hit all of
 them alike): (a) LatentSampler.sample as train() uses it (torch element-wise launches between the forwards), (b) the eager loop with the fused
 sdlt_sampler_step kernel, (c) one replayed hipGraph per iteration.  SDXL topology (random weights), 128 x 128 latent, rank-16 adapters, 25 steps,
-n = 1 and n = 2 images per batch ((a) samples the n images one after the other on its batch-2 instance).
+n = 1 and n = 2 images per batch ((a) samples the n images one after the other on its batch-2 instance).  --img2img adds the replayed graph
+whose step launch is sdlt_sampler_step_img: (d) from init latents at strength 0.6 (15 of the 25 iterations run, no mask) and (e) masked inpainting at
+strength 1 (all 25, the mask blend in every one); their time is divided by the iterations that ran.
 
-    python tools/render_bench.py [--out FILE] [--rounds 5] [--version sdxl] [--latent 128] [--n 1 2]
+    python tools/render_bench.py [--out FILE] [--rounds 5] [--version sdxl] [--latent 128] [--n 1 2] [--img2img]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/render_bench.py --trace-iteration --n 1      # kernel time of one iteration: sum the stats
 
 Prints one table: wall milliseconds per iteration (median over the rounds, min .. max) per variant and n, per image in brackets.
@@ -63,6 +65,8 @@ def main():
     ap.add_argument("--steps", type=int, default=25)
     ap.add_argument("--n", type=int, nargs="+", default=[1, 2])
     ap.add_argument("--trace-iteration", action="store_true", help="run the eager fused loop once and exit (under rocprofv3 --kernel-trace --stats: kernel time per iteration = total / steps, without the one-off pack kernels)")
+    ap.add_argument("--img2img", action="store_true", help="also time the graph sampler from init latents: strength 0.6 without a mask, strength 1 with a mask "
+                    "(with --trace-iteration: run the masked eager loop instead of the txt2img one)")
     a = ap.parse_args()
     h = a.latent
     lines = [f"# {a.version} topology, {h} x {h} latent, rank {a.rank}, {a.steps} steps, guidance 8; wall ms per denoising iteration: median (min .. max) of {a.rounds} rounds, alternated",
@@ -79,8 +83,17 @@ def main():
             "b eager + fused kernel": lambda: one(fused=True),
             "c hipGraph per iteration": lambda: one(graph=True),
         }
+        ran = {k: a.steps for k in variants}                # iterations a call runs
+        x0 = mask = None
+        if a.img2img:
+            g = torch.Generator(device="cuda").manual_seed(4)
+            x0 = 0.8 * torch.randn(n, 4, h, h, device="cuda", generator=g)
+            mask = (torch.rand(n, 1, h, h, device="cuda", generator=g) > 0.5).float()
+            variants["d graph, init latents 0.6"] = lambda: one(graph=True, init_latents=x0, strength=0.6)
+            variants["e graph, inpaint 1.0"] = lambda: one(graph=True, init_latents=x0, strength=1.0, mask=mask)
+            ran["d graph, init latents 0.6"], ran["e graph, inpaint 1.0"] = min(int(a.steps * 0.6), a.steps), a.steps
         if a.trace_iteration:                               # the kernels of `steps` eager iterations (+ the one-off weight packing of the first)
-            one(fused=True)
+            one(fused=True, **(dict(init_latents=x0, strength=1.0, mask=mask) if a.img2img else {}))
             torch.cuda.synchronize()
             return
         for fn in variants.values():                        # warm-up: buffers, packed weights, the capture
@@ -88,7 +101,7 @@ def main():
         times = {k: [] for k in variants}
         for _ in range(a.rounds):
             for k, fn in variants.items():
-                times[k].append(timed(fn) * 1e3 / a.steps)
+                times[k].append(timed(fn) * 1e3 / ran[k])
         for k, t in times.items():
             med = statistics.median(t)
             lines.append(f"{n:>2} {k:<28} {med:>16.3f} {min(t):>8.3f} {max(t):>8.3f} {med / n:>24.3f}")
