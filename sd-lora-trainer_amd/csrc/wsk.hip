@@ -266,9 +266,6 @@ __global__ __launch_bounds__(64 * NW) void wsk_kernel(const wsk_params p) {
   const float* bsrc = (p.bias ? p.bias : (const float*)p.X) + n0 + 4 * g;       // (N floats <= 64 rows of X: K >= 256 columns)
   uint2 rpre[JN];
   f32x4 bpre[JN], c1pre[LN ? JN : 1];
-  // RG = 4 (rank pad 64): the LoRA-up fragments and the column factors (60 registers) would not fit beside the K walk's 512 - they are requested behind it, in front of the
-  // reduction's first barrier, which covers most of their round trip
-  constexpr bool LATE = RG >= 4;
   uint2 bupf[JN][TG];
   [[maybe_unused]] f32x4 cspre[LORA ? JN : 1];
   [[maybe_unused]] const float* cssrc = nullptr;
@@ -277,7 +274,7 @@ __global__ __launch_bounds__(64 * NW) void wsk_kernel(const wsk_params p) {
   for (int q = 0; q < JN; ++q) {
     rpre[q] = *(const uint2*)(rsrc + 16 * q);
     bpre[q] = *(const f32x4*)(bsrc + 16 * q);
-    if constexpr (LORA && !LATE) cspre[q] = *(const f32x4*)(cssrc + 16 * q);
+    if constexpr (LORA) cspre[q] = *(const f32x4*)(cssrc + 16 * q);
     if constexpr (LN) c1pre[q] = *(const f32x4*)(p.ln_c1 + n0 + 16 * q + 4 * g);
   }
   [[maybe_unused]] uint2 rbpre[JN];
@@ -295,7 +292,7 @@ __global__ __launch_bounds__(64 * NW) void wsk_kernel(const wsk_params p) {
 #pragma unroll
       for (int tg = 0; tg < TG; ++tg) bupf[q][tg] = *(const uint2*)(bu + (int64_t)(16 * q) * p.ld_bup + (tg < ngrp0 ? 16 * tg : 0));
   };
-  if constexpr (LORA && !LATE) load_bup();
+  if constexpr (LORA) load_bup();
   WTR(14);
   [[maybe_unused]] f32x4 lnca[TG], lnab[TG];      // adapter constants of this lane's four rank rows 4g .. 4g+3 of every rank group (cA[16] | abeta[16] per group)
   if constexpr (LN && LORA) {
@@ -472,11 +469,6 @@ __global__ __launch_bounds__(64 * NW) void wsk_kernel(const wsk_params p) {
       const char* a = p.pf_ptr + (int64_t)((xcdp & 3) * pcp + t) * p.pf_tile_bytes + (int64_t)o * 128;
       asm volatile("global_load_dword %0, %1, off" : "+v"(pf_tmp) : "v"(a) : "memory");
     }
-  }
-  if constexpr (LORA && LATE) {
-    load_bup();
-#pragma unroll
-    for (int q = 0; q < JN; ++q) cspre[q] = *(const f32x4*)(cssrc + 16 * q);
   }
   __syncthreads();
   WTR(9);
@@ -665,100 +657,112 @@ extern "C" int sdlt_wsk_pack_weight(const void* W, int64_t ldw, int32_t N, int32
 extern "C" int sdlt_wsk_trace_read(long long* out16) { return (int)hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_wsk_tr), sizeof(long long) * 16); }
 #endif
 
-static int wsk_gemm_impl(const void* X, int64_t ldx, const void* W, int64_t ldw, int32_t M, int32_t N, int32_t K, const float* bias,
-                         const void* R, int64_t ldr, void* Y, int64_t ldy, const void* Adown, int64_t ld_adown, const void* Bup, int64_t ld_bup,
-                         float lora_scale, void* T_out, int64_t ld_t, int32_t lora_group_k, const float* ln_c1, float* ln_stats, float ln_eps,
-                         const float* ln_adapter, void* ln_parts, void* stream, float* dotD = nullptr, int32_t dot_nq = 0, int32_t lora_rp = 16,
-                         const float* col_scale = nullptr, void* Y0 = nullptr, int64_t ldy0 = 0,
-                         const void* pf_w = nullptr, int32_t pf_n = 0, int32_t pf_k = 0, int32_t pf_steps = 0) {
-  if (M <= 0 || N <= 0 || K <= 0 || (M % 64) || (N % 80) || ((N / 80) % 8) || (K % 256))
-    SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_wsk_gemm: M=%d N=%d K=%d (M %% 64, N %% 640, K %% 256 == 0)", M, N, K);
-  const bool packed = ldw == 0;          // W is sdlt_wsk_pack_weight's output
-  if (!X || !W || !Y || (ldx % 8) || (ldw % 8) || (ldy % 4) || ((uintptr_t)X & 15) || ((uintptr_t)W & 15) || ((uintptr_t)Y & 7) || (R && ((ldr % 4) || ((uintptr_t)R & 7))) ||
-      (bias && ((uintptr_t)bias & 15)))
+// The fields the product and the convolution share - operands, adapter, the 2D XCD map, the refill stagger -, by name; the rest stays zero / NULL until its owner sets it
+static wsk_params wsk_shared_params(const sdlt_wsk_gemm_params& q) {
+  static const int stagger_env = getenv("SDLT_WSK_STAGGER") ? atoi(getenv("SDLT_WSK_STAGGER")) : 1;   // (read once: A/B switch)
+  wsk_params p{};
+  p.X = (const bf16_t*)q.X; p.ldx = q.ldx; p.W = (const bf16_t*)q.W; p.ldw = q.ldw;
+  p.Wp = q.ldw == 0 ? p.W : nullptr;          // ldw == 0: W is sdlt_wsk_pack_weight's output
+  p.bias = q.bias; p.R = (const bf16_t*)q.R; p.ldr = q.ldr; p.Y = (bf16_t*)q.Y; p.ldy = q.ldy; p.M = q.M; p.N = q.N; p.K = q.K; p.map2d = 1;
+  p.Adown = (const bf16_t*)q.Adown; p.ld_adown = q.ld_adown; p.Bup = (const bf16_t*)q.Bup; p.ld_bup = q.ld_bup;
+  p.T_out = (bf16_t*)q.T_out; p.ld_t = q.ld_t; p.lora_scale = q.lora_scale; p.group_k = q.lora_group_k; p.stagger = stagger_env;
+  return p;
+}
+
+// One ladder for every kernel.  WP: packed weights, a register ring of 3 stages (probed 2 / 3 / 4 in round 5: 3 wins on every shape; 4 runs out of registers with an
+// adapter); row-major weights ride a 2-slot LDS ring.  rp: the adapter's padded rank (16, or 32: packed weights only).
+template <bool WP, bool CONV>
+static int wsk_dispatch(const wsk_params& p, int rp, hipStream_t s) {
+  constexpr int R = WP ? 3 : 2;
+  if constexpr (CONV) return p.Adown ? launch_wsk<4, 5, R, 1, false, WP, true>(p, s) : launch_wsk<4, 5, R, 0, false, WP, true>(p, s);
+  if constexpr (WP) if (p.Adown && rp == 32) return launch_wsk<4, 5, R, 1, false, true, false, 2>(p, s);
+  if (p.ln_c1) return p.Adown ? launch_wsk<4, 5, R, 1, true, WP>(p, s) : launch_wsk<4, 5, R, 0, true, WP>(p, s);
+  if (!p.Adown) return launch_wsk<4, 5, R, 0, false, WP>(p, s);
+  if (p.group_k <= 0) return launch_wsk<4, 5, R, 1, false, WP>(p, s);
+  const int G = p.K / p.group_k;
+  if ((p.group_k % 64) || G * p.group_k != p.K || G < 2 || G > 3) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_wsk_gemm: lora_group_k=%d with K=%d (2 or 3 groups of a multiple of 64 columns)", p.group_k, p.K);
+  return launch_wsk<4, 5, R, 3, false, WP>(p, s);
+}
+
+static int wsk_gemm_impl(const sdlt_wsk_gemm_params& q, void* stream) {
+  if (q.M <= 0 || q.N <= 0 || q.K <= 0 || (q.M % 64) || (q.N % 80) || ((q.N / 80) % 8) || (q.K % 256))
+    SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_wsk_gemm: M=%d N=%d K=%d (M %% 64, N %% 640, K %% 256 == 0)", q.M, q.N, q.K);
+  if (!q.X || !q.W || !q.Y || (q.ldx % 8) || (q.ldw % 8) || (q.ldy % 4) || ((uintptr_t)q.X & 15) || ((uintptr_t)q.W & 15) || ((uintptr_t)q.Y & 7) ||
+      (q.R && ((q.ldr % 4) || ((uintptr_t)q.R & 7))) || (q.bias && ((uintptr_t)q.bias & 15)))
     SDLT_FAIL(SDLT_ERR_ALIGN, "sdlt_wsk_gemm: operand alignment");
-  if (Adown && (!Bup || (ld_adown % 8) || ((uintptr_t)Adown & 15) || (ld_bup % 4) || ((uintptr_t)Bup & 7) || (T_out && ((ld_t % 4) || ((uintptr_t)T_out & 7)))))
+  if (q.Adown && (!q.Bup || (q.ld_adown % 8) || ((uintptr_t)q.Adown & 15) || (q.ld_bup % 4) || ((uintptr_t)q.Bup & 7) || (q.T_out && ((q.ld_t % 4) || ((uintptr_t)q.T_out & 7)))))
     SDLT_FAIL(SDLT_ERR_ALIGN, "sdlt_wsk_gemm: adapter operands (Adown [16, K] 16-byte rows, Bup [N, 16] / T_out [M, 16] 8-byte rows)");
-  if (lora_rp <= 0) lora_rp = 16;
+  const int lora_rp = q.lora_rp <= 0 ? 16 : q.lora_rp;
   // (rank pad 64 - four groups - was built and dropped in round 6: with 64 T accumulators beside the 80 of the tile and the weight ring the kernel needs all 512 registers, hipcc
   // starts moving values between VGPRs and AGPRs around the hand-issued weight loads - whose destinations it believes to be ready at once - and the launch faults; the tiled
   // kernel keeps those products)
-  if (Adown && lora_rp != 16 && (lora_rp != 32 || lora_group_k > 0 || ldw != 0))
+  if (q.Adown && lora_rp != 16 && (lora_rp != 32 || q.lora_group_k > 0 || q.ldw != 0))
     SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_wsk_gemm_p: lora_rp=%d (16; 32 with ONE adapter and a packed weight, ldw == 0)", lora_rp);
-  if (Adown && lora_rp != 16 && ln_c1) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_wsk_gemm_p: the folded LayerNorm exists for rank pad 16 only");
-  if (col_scale && (!Adown || ((uintptr_t)col_scale & 15) || ln_c1)) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_wsk_gemm_p: col_scale (DoRA) needs an adapter, 16-byte alignment and no folded LayerNorm");
-  if (Y0 && (!Adown || (ldy0 % 4) || ((uintptr_t)Y0 & 7))) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_wsk_gemm_p: Y0 (the output before the residual) exists for adapter launches; 8-byte aligned rows");
-  if (ln_c1 && (((uintptr_t)ln_c1 & 15) || ((uintptr_t)ln_stats & 7) || lora_group_k > 0 || (Adown && (!ln_adapter || ((uintptr_t)ln_adapter & 15)))))
+  if (q.Adown && lora_rp != 16 && q.ln_c1) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_wsk_gemm_p: the folded LayerNorm exists for rank pad 16 only");
+  if (q.col_scale && (!q.Adown || ((uintptr_t)q.col_scale & 15) || q.ln_c1)) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_wsk_gemm_p: col_scale (DoRA) needs an adapter, 16-byte alignment and no folded LayerNorm");
+  if (q.Y0 && (!q.Adown || (q.ldy0 % 4) || ((uintptr_t)q.Y0 & 7))) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_wsk_gemm_p: Y0 (the output before the residual) exists for adapter launches; 8-byte aligned rows");
+  if (q.ln_c1 && (((uintptr_t)q.ln_c1 & 15) || ((uintptr_t)q.ln_stats & 7) || q.lora_group_k > 0 || (q.Adown && (!q.ln_adapter || ((uintptr_t)q.ln_adapter & 15)))))
     SDLT_FAIL(SDLT_ERR_ALIGN, "sdlt_wsk_gemm_ln: c1 [N] / ln_adapter [32] 16-byte aligned, stats [M, 2] 8-byte aligned, no K-grouped adapters");
-  static const int stagger_env = getenv("SDLT_WSK_STAGGER") ? atoi(getenv("SDLT_WSK_STAGGER")) : 1;   // (read once: A/B switch)
-  wsk_params p{(const bf16_t*)X, ldx, (const bf16_t*)W, ldw, bias, (const bf16_t*)R, ldr, (bf16_t*)Y, ldy, M, N, K, 1,
-               (const bf16_t*)Adown, ld_adown, (const bf16_t*)Bup, ld_bup, (bf16_t*)T_out, ld_t, lora_scale, lora_group_k, stagger_env,
-               ln_c1, ln_stats, ln_adapter, ln_eps, (float2*)ln_parts, packed ? (const bf16_t*)W : nullptr, 0, 0, 0, 0, nullptr, nullptr, 0, dotD, dot_nq, col_scale, (bf16_t*)Y0, ldy0, nullptr, 0, 0, 0};
-  if (pf_w && pf_steps > 0) {      // (a hint: anything that does not fit the scheme is ignored, never an error)
-    if (pf_n > 0 && pf_k > 0 && (pf_n % 320) == 0 && (pf_k % 64) == 0 && !((uintptr_t)pf_w & 127)) {
-      const int steps = pf_steps < (pf_k >> 6) ? pf_steps : (pf_k >> 6);
-      p.pf_ptr = (const char*)pf_w; p.pf_tile_bytes = (pf_k >> 6) * 10240; p.pf_head_bytes = steps * 10240; p.pf_ntn = pf_n / 80;
-    }
-  }
-  if (((uintptr_t)ln_parts) & 7) SDLT_FAIL(SDLT_ERR_ALIGN, "sdlt_wsk_gemm: ln_parts must be 8-byte aligned");
-  if (dotD && (!R || ln_c1 || (N % 64) || dot_nq <= 0 || (M % dot_nq) || ((uintptr_t)dotD & 3)))
+  if (((uintptr_t)q.ln_parts) & 7) SDLT_FAIL(SDLT_ERR_ALIGN, "sdlt_wsk_gemm: ln_parts must be 8-byte aligned");
+  if (q.dotD && (!q.R || q.ln_c1 || (q.N % 64) || q.dot_nq <= 0 || (q.M % q.dot_nq) || ((uintptr_t)q.dotD & 3)))
     SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_wsk_gemm_rowdot: O is required, N %% 64 == 0 (64-wide heads), M = B * Nq, no folded LayerNorm");
-  hipStream_t s = (hipStream_t)stream;
-  if (packed) {          // register ring of 3 stages (probed 2 / 3 / 4 in round 5: 3 wins on every shape; 4 runs out of registers with an adapter)
-#define WSK_WP(KG_, LN_) launch_wsk<4, 5, 3, KG_, LN_, true>(p, s)
-    if (Adown && lora_rp == 32) return launch_wsk<4, 5, 3, 1, false, true, false, 2>(p, s);
-    if (ln_c1) return Adown ? WSK_WP(1, true) : WSK_WP(0, true);
-    if (!Adown) return WSK_WP(0, false);
-    if (lora_group_k <= 0) return WSK_WP(1, false);
-    const int G = K / lora_group_k;
-    if ((lora_group_k % 64) || G * lora_group_k != K || G < 2 || G > 3) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_wsk_gemm: lora_group_k=%d with K=%d (2 or 3 groups of a multiple of 64 columns)", lora_group_k, K);
-    return WSK_WP(3, false);
-#undef WSK_WP
+  wsk_params p = wsk_shared_params(q);
+  p.ln_c1 = q.ln_c1; p.ln_stats = q.ln_stats; p.ln_adapter = q.ln_adapter; p.ln_eps = q.ln_eps; p.ln_parts = (float2*)q.ln_parts;
+  p.dotD = q.dotD; p.dot_nq = q.dot_nq; p.col_scale = q.col_scale; p.Y0 = (bf16_t*)q.Y0; p.ldy0 = q.ldy0;
+  // the prefetch is a hint: anything that does not fit the scheme is ignored, never an error
+  if (q.pf_next_w && q.pf_steps > 0 && q.pf_next_n > 0 && q.pf_next_k > 0 && (q.pf_next_n % 320) == 0 && (q.pf_next_k % 64) == 0 && !((uintptr_t)q.pf_next_w & 127)) {
+    const int ksteps = q.pf_next_k >> 6;
+    p.pf_ptr = (const char*)q.pf_next_w; p.pf_tile_bytes = ksteps * 10240; p.pf_head_bytes = (q.pf_steps < ksteps ? q.pf_steps : ksteps) * 10240; p.pf_ntn = q.pf_next_n / 80;
   }
-  if (ln_c1) return Adown ? launch_wsk<4, 5, 2, 1, true>(p, s) : launch_wsk<4, 5, 2, 0, true>(p, s);
-  if (!Adown) return launch_wsk<4, 5, 2, 0>(p, s);
-  if (lora_group_k <= 0) return launch_wsk<4, 5, 2, 1>(p, s);
-  const int G = K / lora_group_k;
-  if ((lora_group_k % 64) || G * lora_group_k != K || G < 2 || G > 3) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_wsk_gemm: lora_group_k=%d with K=%d (2 or 3 groups of a multiple of 64 columns)", lora_group_k, K);
-  return launch_wsk<4, 5, 2, 3>(p, s);
+  return p.Wp ? wsk_dispatch<true, false>(p, lora_rp, (hipStream_t)stream) : wsk_dispatch<false, false>(p, lora_rp, (hipStream_t)stream);
+}
+
+// what the flat entry points (and the convolution) share, as a parameter block whose other fields are zero / NULL
+static sdlt_wsk_gemm_params wsk_flat_params(const void* X, int64_t ldx, const void* W, int64_t ldw, int32_t M, int32_t N, int32_t K, const float* bias,
+                                            const void* R, int64_t ldr, void* Y, int64_t ldy, const void* Adown, int64_t ld_adown, const void* Bup, int64_t ld_bup,
+                                            float lora_scale, void* T_out, int64_t ld_t, int32_t lora_group_k) {
+  sdlt_wsk_gemm_params q{};
+  q.X = X; q.ldx = ldx; q.W = W; q.ldw = ldw; q.M = M; q.N = N; q.K = K; q.bias = bias; q.R = R; q.ldr = ldr; q.Y = Y; q.ldy = ldy;
+  q.Adown = Adown; q.ld_adown = ld_adown; q.Bup = Bup; q.ld_bup = ld_bup; q.lora_scale = lora_scale; q.T_out = T_out; q.ld_t = ld_t; q.lora_group_k = lora_group_k;
+  return q;
 }
 
 extern "C" int sdlt_wsk_gemm(const void* X, int64_t ldx, const void* W, int64_t ldw, int32_t M, int32_t N, int32_t K, const float* bias,
                              const void* R, int64_t ldr, void* Y, int64_t ldy, const void* Adown, int64_t ld_adown, const void* Bup, int64_t ld_bup,
                              float lora_scale, void* T_out, int64_t ld_t, int32_t lora_group_k, void* stream) {
-  return wsk_gemm_impl(X, ldx, W, ldw, M, N, K, bias, R, ldr, Y, ldy, Adown, ld_adown, Bup, ld_bup, lora_scale, T_out, ld_t, lora_group_k,
-                       nullptr, nullptr, 0.f, nullptr, nullptr, stream);
+  return wsk_gemm_impl(wsk_flat_params(X, ldx, W, ldw, M, N, K, bias, R, ldr, Y, ldy, Adown, ld_adown, Bup, ld_bup, lora_scale, T_out, ld_t, lora_group_k), stream);
 }
 
 extern "C" int sdlt_wsk_gemm_rowdot(const void* X, int64_t ldx, const void* W, int64_t ldw, int32_t M, int32_t N, int32_t K, const float* bias,
                                     const void* O, int64_t ldo, void* Y, int64_t ldy, const void* Adown, int64_t ld_adown, const void* Bup, int64_t ld_bup,
                                     float lora_scale, void* T_out, int64_t ld_t, int32_t lora_group_k, float* D, int32_t Nq, void* stream) {
   if (!D) SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_wsk_gemm_rowdot: D == NULL");
-  return wsk_gemm_impl(X, ldx, W, ldw, M, N, K, bias, O, ldo, Y, ldy, Adown, ld_adown, Bup, ld_bup, lora_scale, T_out, ld_t, lora_group_k,
-                       nullptr, nullptr, 0.f, nullptr, nullptr, stream, D, Nq);
+  sdlt_wsk_gemm_params q = wsk_flat_params(X, ldx, W, ldw, M, N, K, bias, O, ldo, Y, ldy, Adown, ld_adown, Bup, ld_bup, lora_scale, T_out, ld_t, lora_group_k);
+  q.dotD = D; q.dot_nq = Nq;
+  return wsk_gemm_impl(q, stream);
 }
 
 extern "C" int sdlt_wsk_gemm_parts(const void* X, int64_t ldx, const void* W, int64_t ldw, int32_t M, int32_t N, int32_t K, const float* bias,
                                    const void* R, int64_t ldr, void* Y, int64_t ldy, const void* Adown, int64_t ld_adown, const void* Bup, int64_t ld_bup,
                                    float lora_scale, void* T_out, int64_t ld_t, int32_t lora_group_k, void* ln_parts, void* stream) {
-  return wsk_gemm_impl(X, ldx, W, ldw, M, N, K, bias, R, ldr, Y, ldy, Adown, ld_adown, Bup, ld_bup, lora_scale, T_out, ld_t, lora_group_k,
-                       nullptr, nullptr, 0.f, nullptr, ln_parts, stream);
+  sdlt_wsk_gemm_params q = wsk_flat_params(X, ldx, W, ldw, M, N, K, bias, R, ldr, Y, ldy, Adown, ld_adown, Bup, ld_bup, lora_scale, T_out, ld_t, lora_group_k);
+  q.ln_parts = ln_parts;
+  return wsk_gemm_impl(q, stream);
 }
 
 extern "C" int sdlt_wsk_gemm_ln(const void* X, int64_t ldx, const void* W, int64_t ldw, int32_t M, int32_t N, int32_t K, const float* c2,
                                 const void* R, int64_t ldr, void* Y, int64_t ldy, const void* Adown, int64_t ld_adown, const void* Bup, int64_t ld_bup,
-                                float lora_scale, void* T_out, int64_t ld_t, const float* ln_c1, float* ln_stats, float ln_eps,
-                                const float* ln_adapter, void* stream) {
+                                float lora_scale, void* T_out, int64_t ld_t, const float* ln_c1, float* ln_stats, float ln_eps, const float* ln_adapter, void* stream) {
   if (!ln_c1) SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_wsk_gemm_ln: c1 is required");
-  return wsk_gemm_impl(X, ldx, W, ldw, M, N, K, c2, R, ldr, Y, ldy, Adown, ld_adown, Bup, ld_bup, lora_scale, T_out, ld_t, 0,
-                       ln_c1, ln_stats, ln_eps, ln_adapter, nullptr, stream);
+  sdlt_wsk_gemm_params q = wsk_flat_params(X, ldx, W, ldw, M, N, K, c2, R, ldr, Y, ldy, Adown, ld_adown, Bup, ld_bup, lora_scale, T_out, ld_t, 0);
+  q.ln_c1 = ln_c1; q.ln_stats = ln_stats; q.ln_eps = ln_eps; q.ln_adapter = ln_adapter;
+  return wsk_gemm_impl(q, stream);
 }
 
 extern "C" int sdlt_wsk_gemm_p(const sdlt_wsk_gemm_params* q, void* stream) {
   if (!q) SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_wsk_gemm_p: params == NULL");
   if (q->dotD && (q->ln_c1 || q->ln_parts)) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_wsk_gemm_p: the row-dot side output excludes the folded LayerNorm / row partials");
-  return wsk_gemm_impl(q->X, q->ldx, q->W, q->ldw, q->M, q->N, q->K, q->bias, q->R, q->ldr, q->Y, q->ldy, q->Adown, q->ld_adown, q->Bup, q->ld_bup, q->lora_scale,
-                       q->T_out, q->ld_t, q->lora_group_k, q->ln_c1, q->ln_stats, q->ln_eps, q->ln_adapter, q->ln_parts, stream, q->dotD, q->dot_nq, q->lora_rp, q->col_scale, q->Y0, q->ldy0, q->pf_next_w, q->pf_next_n, q->pf_next_k, q->pf_steps);
+  return wsk_gemm_impl(*q, stream);
 }
 
 extern "C" int sdlt_wsk_conv(const void* X, int64_t ldx, const void* W, int64_t ldw, int32_t B, int32_t H, int32_t Wd, int32_t Cin, int32_t N, int32_t flip,
@@ -769,17 +773,12 @@ extern "C" int sdlt_wsk_conv(const void* X, int64_t ldx, const void* W, int64_t 
   const int32_t M = (int32_t)M64, K = 9 * Cin;
   if (B <= 0 || H <= 0 || Wd <= 0 || Cin <= 0 || N <= 0 || M64 >= (1ll << 22) || (M % 64) || (N % 80) || ((N / 80) % 8) || (Cin % 64) || K >= (1 << 22) || H >= 32768 || Wd >= 32768)
     SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_wsk_conv: B=%d H=%d W=%d Cin=%d N=%d (B H W %% 64, N %% 640, Cin %% 64 == 0)", B, H, Wd, Cin, N);
-  const bool packed = ldw == 0;
   if (!X || !W || !Y || !zero || (ldx % 8) || (ldw % 8) || (ldy % 4) || ((uintptr_t)X & 15) || ((uintptr_t)W & 15) || ((uintptr_t)Y & 7) || ((uintptr_t)zero & 15) ||
       (R && ((ldr % 4) || ((uintptr_t)R & 7))) || (bias && ((uintptr_t)bias & 15)) || (rowbias && ((ld_rowbias % 4) || ((uintptr_t)rowbias & 7))))
     SDLT_FAIL(SDLT_ERR_ALIGN, "sdlt_wsk_conv: operand alignment (zero: a >= 128-byte zero page)");
   if (Adown && (!Bup || (ld_adown % 8) || ((uintptr_t)Adown & 15) || (ld_bup % 4) || ((uintptr_t)Bup & 7) || (T_out && ((ld_t % 4) || ((uintptr_t)T_out & 7)))))
     SDLT_FAIL(SDLT_ERR_ALIGN, "sdlt_wsk_conv: adapter operands (Adown [16, 9 Cin] 16-byte rows, Bup [N, 16] / T_out [M, 16] 8-byte rows)");
-  static const int stagger_env = getenv("SDLT_WSK_STAGGER") ? atoi(getenv("SDLT_WSK_STAGGER")) : 1;
-  wsk_params p{(const bf16_t*)X, ldx, (const bf16_t*)W, ldw, bias, (const bf16_t*)R, ldr, (bf16_t*)Y, ldy, M, N, K, 1,
-               (const bf16_t*)Adown, ld_adown, (const bf16_t*)Bup, ld_bup, (bf16_t*)T_out, ld_t, lora_scale, 0, stagger_env,
-               nullptr, nullptr, nullptr, 0.f, nullptr, packed ? (const bf16_t*)W : nullptr, H, Wd, Cin, flip ? 1 : 0, (const bf16_t*)zero, (const bf16_t*)rowbias, ld_rowbias};
-  hipStream_t s = (hipStream_t)stream;
-  if (packed) return Adown ? launch_wsk<4, 5, 3, 1, false, true, true>(p, s) : launch_wsk<4, 5, 3, 0, false, true, true>(p, s);
-  return Adown ? launch_wsk<4, 5, 2, 1, false, false, true>(p, s) : launch_wsk<4, 5, 2, 0, false, false, true>(p, s);
+  wsk_params p = wsk_shared_params(wsk_flat_params(X, ldx, W, ldw, M, N, K, bias, R, ldr, Y, ldy, Adown, ld_adown, Bup, ld_bup, lora_scale, T_out, ld_t, 0));
+  p.Hc = H; p.Wc = Wd; p.Cin = Cin; p.flip = flip ? 1 : 0; p.zero = (const bf16_t*)zero; p.rowbias = (const bf16_t*)rowbias; p.ld_rowbias = ld_rowbias;
+  return p.Wp ? wsk_dispatch<true, true>(p, 16, (hipStream_t)stream) : wsk_dispatch<false, true>(p, 16, (hipStream_t)stream);
 }

@@ -149,7 +149,8 @@ def wsk_rowdot_shape(M, N, K, lora, d):
 
 WSK_PACK = os.environ.get("SDLT_WSK_PACK", "1") != "0"
 WSK_DORA = os.environ.get("SDLT_WSK_DORA", "1") != "0"        # DoRA's column factor in the wave-split-K epilogue (A/B switch: 0 = the tiled kernel, round 5)
-WSK_RANKS = tuple(int(x) for x in os.environ.get("SDLT_WSK_RANKS", "16,32").split(","))      # padded adapter ranks the wave-split-K kernel takes (A/B switch: "16" = round 5; 64 does not exist: csrc/wsk.hip says why)
+# padded adapter ranks the wave-split-K kernel takes (A/B switch: "16" = round 5), clamped to the pads it has: 64 does not exist (csrc/wsk.hip says why) and stays on the tiled kernel
+WSK_RANKS = tuple(r for r in (int(x) for x in os.environ.get("SDLT_WSK_RANKS", "16,32").split(",")) if r in (16, 32))
 _WSK_FROZEN = {}         # data_ptr of a weight declared frozen -> weakref of the tensor
 _WSK_PACKED = {}         # data_ptr -> (fragment-major copy (sdlt_wsk_pack_weight's layout), N, K, ld, weakref of the tensor, W._version at pack time)
 
@@ -287,169 +288,110 @@ def gemm_emits_parts(M, N, K, lora_rank_pad=0, W=None, dora=False):
     return N // 80 if ok else 0
 
 
-def gemm(X, W, out, *, X2=None, W2=None, conv=None, lora=None, bias=None, rowbias=None, rows_per_batch=0,
-         residual=None, alpha=1.0, Ct=None, tile=0, splitk=0, stages=0, accumulate=False, lora_group_n=0, lora_group_k=0, batch=None,
-         geglu_out=None, geglu_bwd=None, act_out=None, dact_in=None, col_scale=None, ln=None, ln_parts_out=None, rowdot=None, out0=None,
-         x2_group_n=0):
-    """out[M,N] = alpha*col_scale[n]*(X.W^T [+ X2.W2^T] [+ s*(X.Adown^T).Bup^T]) + bias + rowbias[m//rows_per_batch] + residual.
-    X2 [M, K2] / W2 [N, K2]: second K segment (also behind a convolution, `conv`; no adapter with it).  x2_group_n > 0: grouped second
-    segment - W is a stack of G = N / x2_group_n projections, X2 [M, G*K2], output column n reads X2 columns of group n // x2_group_n.
-    out0 [M,N] (with residual, adapter launches): ALSO the value before the residual (DoRA: the magnitude gradient reads the layer's own output) - one launch where the
-    product runs on the wave-split-K kernel (sdlt_wsk_gemm_params.Y0), otherwise the product into out0 and an add2d launch.
-    col_scale fp32 [N]: DoRA's magnitude / norm factor (adapter launches only; DoraPlan keeps it up to date).
-    act_out = (kind, A [M,N]): also writes A = act(out), kind "gelu" | "quick_gelu" (the CLIP MLP's fc1).
-    dact_in = (kind, P [M,N]): out = (...) * act'(P), P = the forward pre-activation (the dX of the CLIP MLP's fc2).
-    geglu_out [M, N/2]: this GEMM is ff.net.0.proj in the interleaved-16 layout (geglu_perm) - also writes hidden * gelu(gate).
-    geglu_bwd = (F1 [M, 2N], dF1 [M, 2N]): this GEMM is the dX of ff.net.2 - writes GEGLU's input gradient instead of `out` (None).
-    lora = (Adown [Rp,K], Bup [N,Rp], scale, T_out [M,Rp] or None).  out dtype bf16 or fp32.  Ct: optional
-    transposed bf16 copy [N, >=M].  conv: ConvGeom -> X is the NHWC activation [B*Hin*Win, Cin].
-    lora_group_n > 0: W is a stack of G = N / lora_group_n projections with one adapter each:
-    Adown [G*Rp, K] (group-major), Bup [N, Rp], T_out [M, G*Rp].
-    lora_group_k > 0: X is a stack of G = K / lora_group_k gradients (the dX of such a stack): Adown [Rp, K], Bup [N, G*Rp],
-    T_out [M, G*Rp].
-    ln = (c1 fp32 [N], stats fp32 [M, 2] or None, eps, adapter constants fp32 [G*32] or None): the LayerNorm in front of this product is
-    folded in (fold_layernorm: X = the raw rows, W = W o gamma, bias = c2; with an adapter Adown = A o gamma, LnFoldPlan) - sdlt_gemm_params.ln_c1.
-    ... optionally followed by (parts fp32 [M, P, 2], P): the row partials the PRODUCER of X left (ln_parts_out of that call).
-    ln_parts_out fp32 [M, N / 80, 2]: also leave the row partials (sum, centred sum of squares of the rounded output row per 80-column tile) for the
-    LayerNorm that reads `out` next - only where this call runs on the wave-split-K kernel (gemm_emits_parts says so; asserted).
-    rowdot = dict(O bf16 [M, N], D fp32 [B * N / 64 * Nq], Nq): `out` is the gradient dO of a self-attention with 64-wide heads; where this call runs on the wave-split-K
-    kernel it also accumulates D[b, h, q] += sum_n rounded(out[m, n]) O[m, n] over each head's columns and sets rowdot["done"] = True (attn_bwd(d_ready=True) then skips its
-    D pre-pass); otherwise the dict is left alone and the caller keeps the pre-pass.  D must be zero on entry (attn_fwd(zero_D=)).
-    batch: a GemmBatch - the launch runs len(batch) problems of identical shape / leading dimensions; the tensor arguments
-    describe problem 0 (shapes, strides, options), every problem's operand pointers come from the batch."""
-    lib = _lib.load()
+def _wsk_gemm_route(X, W, lora, *, conv, rowbias, col_scale, lora_group_k, ln):
+    """Does a product whose epilogue is plain (gemm() checks that) run on the wave-split-K kernel?  Rank pad 16: one adapter or 2 / 3 K groups; rank pad 32: one adapter, no folded
+    LayerNorm, the packed copy of a frozen weight."""
     rp_ = lora[0].shape[0] if lora is not None else 0
-    # wide adapters (padded rank > 64) never reach the fused forms: unet.LoraArena.wide decomposes them into plain / second-segment products
-    assert lora is None or (lora[0].shape[0] if lora_group_k else lora[1].shape[1]) <= 64, "fused adapter products exist for rank pads 16 / 32 / 64"
-    assert X2 is None or lora is None, "a second K segment excludes the fused adapter"
-    if out0 is not None:
-        assert residual is not None and lora is not None and Ct is None and ln is None and geglu_out is None and act_out is None and tuple(out0.shape) == tuple(out.shape)
-    if (WSK and conv is None and X2 is None and rowbias is None and alpha == 1.0 and Ct is None and batch is None and geglu_out is None
-            and geglu_bwd is None and act_out is None and dact_in is None and (col_scale is None or (lora is not None and ln is None and WSK_DORA)) and not accumulate and tile == 0 and splitk == 0
-            and not lora_group_n and out is not None and out.dtype == BF16 and not THROUGHPUT_HINT and (ln is None or not lora_group_k)
+    return (WSK and conv is None and rowbias is None and (col_scale is None or (lora is not None and ln is None and WSK_DORA)) and (ln is None or not lora_group_k)
             and (lora is None or (rp_ == 16 and ((not lora_group_k and lora[1].shape[1] == 16) or
                                                  (lora_group_k and lora_group_k % 64 == 0 and W.shape[1] // lora_group_k in (2, 3))))
-                 or (rp_ in WSK_RANKS and rp_ > 16 and not lora_group_k and ln is None and lora[1].shape[1] == rp_ and WSK_PACK and _wsk_is_frozen(W)))      # rank pads 32 / 64: packed weights only
-            and wsk_shape(X.shape[0], W.shape[0], W.shape[1], lora is not None)):
-        # 1280-wide product at batch 1 with exactly one 64 x 80 tile per CU: K split over the waves, rank-16 adapter fused (sdlt_wsk_gemm)
-        _chk2(X), _chk2(W), _chk2(out)
-        M_, N_, K_ = X.shape[0], W.shape[0], W.shape[1]
-        assert X.shape[1] == K_ and tuple(out.shape) == (M_, N_)
-        if bias is not None:
-            _chk2(bias, F32)
-        if residual is not None:
-            _chk2(residual)
-        A_ = B_ = T_ = None
-        scale_ = 0.0
-        if lora is not None:
-            A_, B_, scale_, T_ = lora
-            _chk2(A_), _chk2(B_)
-            G_ = K_ // lora_group_k if lora_group_k else 1
-            assert tuple(A_.shape) == (rp_, K_) and tuple(B_.shape) == (N_, rp_ * G_)
-            if T_ is not None:
-                _chk2(T_)
-                assert tuple(T_.shape) == (M_, rp_ * G_)
-        Wptr, Wld = _wsk_operand(W)
-        hint = _pf_hint(Wptr, Wld, N_, K_)
-        if rp_ > 16 or col_scale is not None or out0 is not None or hint is not None:
-            # the parameter-block entry point: rank pads 32 / 64 (packed weights) and DoRA's column factor exist only there
-            q = _lib.WskGemmParams()
-            q.X, q.ldx, q.W, q.ldw, q.M, q.N, q.K = _p(X), _ld(X), Wptr, Wld, M_, N_, K_
-            q.bias, q.Y, q.ldy = _p(bias), _p(out), _ld(out)
-            if hint is not None:
-                q.pf_next_w, q.pf_next_n, q.pf_next_k, q.pf_steps = hint[0], hint[1], hint[2], min(hint[2] // 64, WSK_PREFETCH_STEPS)
-            if lora is not None:
-                q.Adown, q.ld_adown, q.Bup, q.ld_bup, q.lora_scale, q.lora_rp = _p(A_), _ld(A_), _p(B_), _ld(B_), float(scale_), rp_
-            if T_ is not None:
-                q.T_out, q.ld_t = _p(T_), _ld(T_)
-            q.lora_group_k = int(lora_group_k)
-            if col_scale is not None:
-                _chk2(col_scale, F32)
-                assert col_scale.numel() == N_
-                q.col_scale = _p(col_scale)
-            if residual is not None:
-                q.R, q.ldr = _p(residual), _ld(residual)
-            if out0 is not None:
-                _chk2(out0)
-                q.Y0, q.ldy0 = _p(out0), _ld(out0)
-            if ln is not None:
-                c1, stats_, eps_, lnad = ln[:4]
-                _chk2(c1, F32)
-                assert c1.numel() == N_ and (stats_ is None or (stats_.dtype == F32 and stats_.numel() >= 2 * M_)) and (lora is None or (lnad is not None and lnad.numel() >= 2 * rp_))
-                q.ln_c1, q.ln_stats, q.ln_eps, q.ln_adapter = _p(c1), _p(stats_), float(eps_), _p(lnad)
-            elif ln_parts_out is not None:
-                assert ln_parts_out.dtype == F32 and ln_parts_out.is_contiguous() and ln_parts_out.numel() >= M_ * (N_ // 80) * 2
-                q.ln_parts = _p(ln_parts_out)
-            elif rowdot is not None and ROWDOT and residual is None and N_ % 64 == 0 and M_ % rowdot["Nq"] == 0:
-                O_, D_ = rowdot["O"], rowdot["D"]
-                _chk2(O_), _chk2(D_, F32)
-                assert tuple(O_.shape) == (M_, N_) and D_.is_contiguous() and D_.numel() >= M_ * (N_ // 64)
-                q.R, q.ldr, q.dotD, q.dot_nq = _p(O_), _ld(O_), _p(D_), int(rowdot["Nq"])
-                rowdot["done"] = True
-            assert rp_ <= 16 or Wld == 0, "rank pad 32 runs on the packed copy of a frozen weight"
-            _lib.check(lib.sdlt_wsk_gemm_p(C.byref(q), _stream()), "sdlt_wsk_gemm_p")
-            return out
-        if ln is not None:
-            c1, stats_, eps_, lnad = ln[:4]
-            _chk2(c1, F32)
-            assert c1.numel() == N_ and (stats_ is None or (stats_.dtype == F32 and stats_.numel() >= 2 * M_)) and (lora is None or lnad is not None)
-            _lib.check(lib.sdlt_wsk_gemm_ln(_p(X), _ld(X), Wptr, Wld, M_, N_, K_, _p(bias), _p(residual), _ld(residual) if residual is not None else 0,
-                                            _p(out), _ld(out), _p(A_), _ld(A_) if A_ is not None else 0, _p(B_), _ld(B_) if B_ is not None else 0, float(scale_),
-                                            _p(T_), _ld(T_) if T_ is not None else 0, _p(c1), _p(stats_), float(eps_), _p(lnad), _stream()), "sdlt_wsk_gemm_ln")
-            return out
-        if ln_parts_out is not None:
-            assert ln_parts_out.dtype == F32 and ln_parts_out.is_contiguous() and ln_parts_out.numel() >= M_ * (N_ // 80) * 2
-            _lib.check(lib.sdlt_wsk_gemm_parts(_p(X), _ld(X), Wptr, Wld, M_, N_, K_, _p(bias), _p(residual), _ld(residual) if residual is not None else 0,
-                                               _p(out), _ld(out), _p(A_), _ld(A_) if A_ is not None else 0, _p(B_), _ld(B_) if B_ is not None else 0, float(scale_),
-                                               _p(T_), _ld(T_) if T_ is not None else 0, int(lora_group_k) if lora is not None else 0, _p(ln_parts_out), _stream()),
-                       "sdlt_wsk_gemm_parts")
-            return out
-        if rowdot is not None and ROWDOT and residual is None and N_ % 64 == 0 and M_ % rowdot["Nq"] == 0:
-            O_, D_ = rowdot["O"], rowdot["D"]
-            _chk2(O_), _chk2(D_, F32)
-            assert tuple(O_.shape) == (M_, N_) and D_.is_contiguous() and D_.numel() >= M_ * (N_ // 64)
-            _lib.check(lib.sdlt_wsk_gemm_rowdot(_p(X), _ld(X), Wptr, Wld, M_, N_, K_, _p(bias), _p(O_), _ld(O_), _p(out), _ld(out), _p(A_),
-                                                _ld(A_) if A_ is not None else 0, _p(B_), _ld(B_) if B_ is not None else 0, float(scale_), _p(T_),
-                                                _ld(T_) if T_ is not None else 0, int(lora_group_k) if lora is not None else 0, _p(D_), int(rowdot["Nq"]), _stream()),
-                       "sdlt_wsk_gemm_rowdot")
-            rowdot["done"] = True
-            return out
-        _lib.check(lib.sdlt_wsk_gemm(_p(X), _ld(X), Wptr, Wld, M_, N_, K_, _p(bias), _p(residual), _ld(residual) if residual is not None else 0,
-                                     _p(out), _ld(out), _p(A_), _ld(A_) if A_ is not None else 0, _p(B_), _ld(B_) if B_ is not None else 0, float(scale_),
-                                     _p(T_), _ld(T_) if T_ is not None else 0, int(lora_group_k) if lora is not None else 0, _stream()), "sdlt_wsk_gemm")
-        return out
-    assert ln_parts_out is None, "ln_parts_out: this product does not run on the wave-split-K kernel (ops.gemm_emits_parts)"
-    if out0 is not None:          # (no wave-split-K shape: the product without the residual, then the add as its own launch)
-        gemm(X, W, out0, lora=lora, bias=bias, col_scale=col_scale, tile=tile, splitk=splitk, stages=stages, lora_group_n=lora_group_n, lora_group_k=lora_group_k)
-        return add2d(out0, residual, out)
-    if (conv is not None and X2 is None and alpha == 1.0 and Ct is None and batch is None and geglu_out is None and geglu_bwd is None and act_out is None
-            and dact_in is None and col_scale is None and not accumulate and tile == 0 and splitk == 0 and not lora_group_n and not lora_group_k and ln is None
-            and out is not None and out.dtype == BF16 and not THROUGHPUT_HINT and (lora is None or (lora[0].shape[0] == 16 and lora[1].shape[1] == 16))
-            and wsk_conv_shape(conv, W.shape[0], 16 if lora is not None else 0)):
-        # 3 x 3 convolution of the 32 x 32 level: one 64 x 80 tile per CU, K = 9 Cin split over the waves, no split-K partials through HBM (sdlt_wsk_conv)
-        _chk2(X), _chk2(W), _chk2(out)
-        M_, N_ = conv.B * conv.Hout * conv.Wout, W.shape[0]
-        assert W.shape[1] == 9 * conv.Cin and X.shape[1] == conv.Cin and X.shape[0] == M_ and tuple(out.shape) == (M_, N_)
-        A_ = B_ = T_ = None
-        scale_ = 0.0
-        if lora is not None:
-            A_, B_, scale_, T_ = lora
-            _chk2(A_), _chk2(B_)
-            assert tuple(A_.shape) == (16, 9 * conv.Cin) and tuple(B_.shape) == (N_, 16) and (T_ is None or tuple(T_.shape) == (M_, 16))
-        if bias is not None:
-            _chk2(bias, F32)
-        if rowbias is not None:
-            _chk2(rowbias)
-            assert rowbias.shape[1] == N_ and rows_per_batch == conv.Hout * conv.Wout and rowbias.shape[0] >= conv.B
-        if residual is not None:
-            _chk2(residual)
-            assert tuple(residual.shape) == (M_, N_)
-        Wptr, Wld = _wsk_operand(W)
-        _lib.check(lib.sdlt_wsk_conv(_p(X), _ld(X), Wptr, Wld, conv.B, conv.Hout, conv.Wout, conv.Cin, N_, int(conv.flip), _p(bias), _p(rowbias),
-                                     _ld(rowbias) if rowbias is not None else 0, _p(residual), _ld(residual) if residual is not None else 0, _p(out), _ld(out),
-                                     _p(A_), _ld(A_) if A_ is not None else 0, _p(B_), _ld(B_) if B_ is not None else 0, float(scale_), _p(T_),
-                                     _ld(T_) if T_ is not None else 0, _p(zero_page(X.device)), _stream()), "sdlt_wsk_conv")
-        return out
+                 or (rp_ in WSK_RANKS and rp_ > 16 and not lora_group_k and ln is None and lora[1].shape[1] == rp_ and WSK_PACK and _wsk_is_frozen(W)))
+            and wsk_shape(X.shape[0], W.shape[0], W.shape[1], lora is not None))
+
+
+def _wsk_conv_route(W, lora, *, conv, col_scale, lora_group_k, ln):
+    """Does a convolution whose epilogue is plain (gemm() checks that) run on the wave-split-K kernel?"""
+    return (conv is not None and col_scale is None and not lora_group_k and ln is None and (lora is None or (lora[0].shape[0] == 16 and lora[1].shape[1] == 16))
+            and wsk_conv_shape(conv, W.shape[0], 16 if lora is not None else 0))
+
+
+def _gemm_wsk(X, W, out, *, lora, bias, residual, lora_group_k, col_scale, ln, ln_parts_out, rowdot, out0):
+    """gemm() on the wave-split-K kernel: 1280-wide product at batch 1 with exactly one 64 x 80 tile per CU, K split over the waves, adapter fused (sdlt_wsk_gemm_p).
+    Side outputs, in this order of precedence: the folded LayerNorm, the row partials, the row dots."""
+    _chk2(X), _chk2(W), _chk2(out)
+    M_, N_, K_ = X.shape[0], W.shape[0], W.shape[1]
+    assert X.shape[1] == K_ and tuple(out.shape) == (M_, N_)
+    q = _lib.WskGemmParams()
+    Wptr, Wld = _wsk_operand(W)
+    q.X, q.ldx, q.W, q.ldw, q.M, q.N, q.K = _p(X), _ld(X), Wptr, Wld, M_, N_, K_
+    q.Y, q.ldy = _p(out), _ld(out)
+    hint = _pf_hint(Wptr, Wld, N_, K_)
+    if hint is not None:
+        q.pf_next_w, q.pf_next_n, q.pf_next_k, q.pf_steps = hint[0], hint[1], hint[2], min(hint[2] // 64, WSK_PREFETCH_STEPS)
+    if bias is not None:
+        _chk2(bias, F32)
+        q.bias = _p(bias)
+    if residual is not None:
+        _chk2(residual)
+        q.R, q.ldr = _p(residual), _ld(residual)
+    rp_ = 0
+    if lora is not None:
+        A_, B_, scale_, T_ = lora
+        _chk2(A_), _chk2(B_)
+        rp_, G_ = A_.shape[0], K_ // lora_group_k if lora_group_k else 1
+        assert tuple(A_.shape) == (rp_, K_) and tuple(B_.shape) == (N_, rp_ * G_)
+        assert rp_ <= 16 or Wld == 0, "rank pad 32 runs on the packed copy of a frozen weight"
+        q.Adown, q.ld_adown, q.Bup, q.ld_bup, q.lora_scale, q.lora_rp, q.lora_group_k = _p(A_), _ld(A_), _p(B_), _ld(B_), float(scale_), rp_, int(lora_group_k)
+        if T_ is not None:
+            _chk2(T_)
+            assert tuple(T_.shape) == (M_, rp_ * G_)
+            q.T_out, q.ld_t = _p(T_), _ld(T_)
+    if col_scale is not None:
+        _chk2(col_scale, F32)
+        assert col_scale.numel() == N_
+        q.col_scale = _p(col_scale)
+    if out0 is not None:
+        _chk2(out0)
+        q.Y0, q.ldy0 = _p(out0), _ld(out0)
+    if ln is not None:
+        c1, stats_, eps_, lnad = ln[:4]
+        _chk2(c1, F32)
+        assert c1.numel() == N_ and (stats_ is None or (stats_.dtype == F32 and stats_.numel() >= 2 * M_)) and (lora is None or (lnad is not None and lnad.numel() >= 2 * rp_))
+        q.ln_c1, q.ln_stats, q.ln_eps, q.ln_adapter = _p(c1), _p(stats_), float(eps_), _p(lnad)
+    elif ln_parts_out is not None:
+        assert ln_parts_out.dtype == F32 and ln_parts_out.is_contiguous() and ln_parts_out.numel() >= M_ * (N_ // 80) * 2
+        q.ln_parts = _p(ln_parts_out)
+    elif rowdot is not None and ROWDOT and residual is None and N_ % 64 == 0 and M_ % rowdot["Nq"] == 0:
+        O_, D_ = rowdot["O"], rowdot["D"]
+        _chk2(O_), _chk2(D_, F32)
+        assert tuple(O_.shape) == (M_, N_) and D_.is_contiguous() and D_.numel() >= M_ * (N_ // 64)
+        q.R, q.ldr, q.dotD, q.dot_nq = _p(O_), _ld(O_), _p(D_), int(rowdot["Nq"])
+        rowdot["done"] = True
+    _lib.check(_lib.load().sdlt_wsk_gemm_p(C.byref(q), _stream()), "sdlt_wsk_gemm_p")
+    return out
+
+
+def _gemm_wsk_conv(X, W, out, *, conv, lora, bias, rowbias, rows_per_batch, residual):
+    """gemm() on the wave-split-K kernel, 3 x 3 convolution of the 32 x 32 level: one 64 x 80 tile per CU, K = 9 Cin split over the waves, no split-K partials through HBM (sdlt_wsk_conv)."""
+    _chk2(X), _chk2(W), _chk2(out)
+    M_, N_ = conv.B * conv.Hout * conv.Wout, W.shape[0]
+    assert W.shape[1] == 9 * conv.Cin and X.shape[1] == conv.Cin and X.shape[0] == M_ and tuple(out.shape) == (M_, N_)
+    A_ = B_ = T_ = None
+    scale_ = 0.0
+    if lora is not None:
+        A_, B_, scale_, T_ = lora
+        _chk2(A_), _chk2(B_)
+        assert tuple(A_.shape) == (16, 9 * conv.Cin) and tuple(B_.shape) == (N_, 16) and (T_ is None or tuple(T_.shape) == (M_, 16))
+    if bias is not None:
+        _chk2(bias, F32)
+    if rowbias is not None:
+        _chk2(rowbias)
+        assert rowbias.shape[1] == N_ and rows_per_batch == conv.Hout * conv.Wout and rowbias.shape[0] >= conv.B
+    if residual is not None:
+        _chk2(residual)
+        assert tuple(residual.shape) == (M_, N_)
+    Wptr, Wld = _wsk_operand(W)
+    _lib.check(_lib.load().sdlt_wsk_conv(_p(X), _ld(X), Wptr, Wld, conv.B, conv.Hout, conv.Wout, conv.Cin, N_, int(conv.flip), _p(bias), _p(rowbias),
+                                         _ld(rowbias) if rowbias is not None else 0, _p(residual), _ld(residual) if residual is not None else 0, _p(out), _ld(out),
+                                         _p(A_), _ld(A_) if A_ is not None else 0, _p(B_), _ld(B_) if B_ is not None else 0, float(scale_), _p(T_),
+                                         _ld(T_) if T_ is not None else 0, _p(zero_page(X.device)), _stream()), "sdlt_wsk_conv")
+    return out
+
+
+def _gemm_tiled(X, W, out, *, X2, W2, conv, lora, bias, rowbias, rows_per_batch, residual, alpha, Ct, tile, splitk, stages, accumulate, lora_group_n, lora_group_k, batch,
+                geglu_out, geglu_bwd, act_out, dact_in, col_scale, ln, x2_group_n):
+    """gemm() on the tiled kernel (sdlt_gemm_bf16): every option."""
+    lib = _lib.load()
     p = _lib.GemmParams()
     _chk2(X), _chk2(W)
     p.X, p.ldx, p.W, p.ldw = _p(X), _ld(X), _p(W), _ld(W)
@@ -558,6 +500,57 @@ def gemm(X, W, out, *, X2=None, W2=None, conv=None, lora=None, bias=None, rowbia
     p.ws_slab, p.ws_slab_bytes, p.ws_cnt, p.ws_cnt_len = _p(slab), slab.numel(), _p(cnt), cnt.numel()
     _lib.check(lib.sdlt_gemm_bf16(C.byref(p), _stream()), "sdlt_gemm_bf16")
     return out if geglu_bwd is None else geglu_bwd[1]
+
+
+def gemm(X, W, out, *, X2=None, W2=None, conv=None, lora=None, bias=None, rowbias=None, rows_per_batch=0,
+         residual=None, alpha=1.0, Ct=None, tile=0, splitk=0, stages=0, accumulate=False, lora_group_n=0, lora_group_k=0, batch=None,
+         geglu_out=None, geglu_bwd=None, act_out=None, dact_in=None, col_scale=None, ln=None, ln_parts_out=None, rowdot=None, out0=None,
+         x2_group_n=0):
+    """out[M,N] = alpha*col_scale[n]*(X.W^T [+ X2.W2^T] [+ s*(X.Adown^T).Bup^T]) + bias + rowbias[m//rows_per_batch] + residual.
+    X2 [M, K2] / W2 [N, K2]: second K segment (also behind a convolution, `conv`; no adapter with it).  x2_group_n > 0: grouped second
+    segment - W is a stack of G = N / x2_group_n projections, X2 [M, G*K2], output column n reads X2 columns of group n // x2_group_n.
+    out0 [M,N] (with residual, adapter launches): ALSO the value before the residual (DoRA: the magnitude gradient reads the layer's own output) - one launch where the
+    product runs on the wave-split-K kernel (sdlt_wsk_gemm_params.Y0), otherwise the product into out0 and an add2d launch.
+    col_scale fp32 [N]: DoRA's magnitude / norm factor (adapter launches only; DoraPlan keeps it up to date).
+    act_out = (kind, A [M,N]): also writes A = act(out), kind "gelu" | "quick_gelu" (the CLIP MLP's fc1).
+    dact_in = (kind, P [M,N]): out = (...) * act'(P), P = the forward pre-activation (the dX of the CLIP MLP's fc2).
+    geglu_out [M, N/2]: this GEMM is ff.net.0.proj in the interleaved-16 layout (geglu_perm) - also writes hidden * gelu(gate).
+    geglu_bwd = (F1 [M, 2N], dF1 [M, 2N]): this GEMM is the dX of ff.net.2 - writes GEGLU's input gradient instead of `out` (None).
+    lora = (Adown [Rp,K], Bup [N,Rp], scale, T_out [M,Rp] or None).  out dtype bf16 or fp32.  Ct: optional
+    transposed bf16 copy [N, >=M].  conv: ConvGeom -> X is the NHWC activation [B*Hin*Win, Cin].
+    lora_group_n > 0: W is a stack of G = N / lora_group_n projections with one adapter each:
+    Adown [G*Rp, K] (group-major), Bup [N, Rp], T_out [M, G*Rp].
+    lora_group_k > 0: X is a stack of G = K / lora_group_k gradients (the dX of such a stack): Adown [Rp, K], Bup [N, G*Rp],
+    T_out [M, G*Rp].
+    ln = (c1 fp32 [N], stats fp32 [M, 2] or None, eps, adapter constants fp32 [G*32] or None): the LayerNorm in front of this product is
+    folded in (fold_layernorm: X = the raw rows, W = W o gamma, bias = c2; with an adapter Adown = A o gamma, LnFoldPlan) - sdlt_gemm_params.ln_c1.
+    ... optionally followed by (parts fp32 [M, P, 2], P): the row partials the PRODUCER of X left (ln_parts_out of that call).
+    ln_parts_out fp32 [M, N / 80, 2]: also leave the row partials (sum, centred sum of squares of the rounded output row per 80-column tile) for the
+    LayerNorm that reads `out` next - only where this call runs on the wave-split-K kernel (gemm_emits_parts says so; asserted).
+    rowdot = dict(O bf16 [M, N], D fp32 [B * N / 64 * Nq], Nq): `out` is the gradient dO of a self-attention with 64-wide heads; where this call runs on the wave-split-K
+    kernel it also accumulates D[b, h, q] += sum_n rounded(out[m, n]) O[m, n] over each head's columns and sets rowdot["done"] = True (attn_bwd(d_ready=True) then skips its
+    D pre-pass); otherwise the dict is left alone and the caller keeps the pre-pass.  D must be zero on entry (attn_fwd(zero_D=)).
+    batch: a GemmBatch - the launch runs len(batch) problems of identical shape / leading dimensions; the tensor arguments
+    describe problem 0 (shapes, strides, options), every problem's operand pointers come from the batch."""
+    # wide adapters (padded rank > 64) never reach the fused forms: unet.LoraArena.wide decomposes them into plain / second-segment products
+    assert lora is None or (lora[0].shape[0] if lora_group_k else lora[1].shape[1]) <= 64, "fused adapter products exist for rank pads 16 / 32 / 64"
+    assert X2 is None or lora is None, "a second K segment excludes the fused adapter"
+    if out0 is not None:
+        assert residual is not None and lora is not None and Ct is None and ln is None and geglu_out is None and act_out is None and tuple(out0.shape) == tuple(out.shape)
+    # what neither wave-split-K route has: a second K segment, scaling, side outputs of the tiled epilogue, batches, forced tiles, fp32 output
+    plain = (X2 is None and alpha == 1.0 and Ct is None and batch is None and geglu_out is None and geglu_bwd is None and act_out is None and dact_in is None and not accumulate
+             and tile == 0 and splitk == 0 and not lora_group_n and out is not None and out.dtype == BF16 and not THROUGHPUT_HINT)
+    if plain and _wsk_gemm_route(X, W, lora, conv=conv, rowbias=rowbias, col_scale=col_scale, lora_group_k=lora_group_k, ln=ln):
+        return _gemm_wsk(X, W, out, lora=lora, bias=bias, residual=residual, lora_group_k=lora_group_k, col_scale=col_scale, ln=ln, ln_parts_out=ln_parts_out, rowdot=rowdot, out0=out0)
+    assert ln_parts_out is None, "ln_parts_out: this product does not run on the wave-split-K kernel (ops.gemm_emits_parts)"
+    if out0 is not None:          # (no wave-split-K shape: the product without the residual, then the add as its own launch)
+        gemm(X, W, out0, lora=lora, bias=bias, col_scale=col_scale, tile=tile, splitk=splitk, stages=stages, lora_group_n=lora_group_n, lora_group_k=lora_group_k)
+        return add2d(out0, residual, out)
+    if plain and _wsk_conv_route(W, lora, conv=conv, col_scale=col_scale, lora_group_k=lora_group_k, ln=ln):
+        return _gemm_wsk_conv(X, W, out, conv=conv, lora=lora, bias=bias, rowbias=rowbias, rows_per_batch=rows_per_batch, residual=residual)
+    return _gemm_tiled(X, W, out, X2=X2, W2=W2, conv=conv, lora=lora, bias=bias, rowbias=rowbias, rows_per_batch=rows_per_batch, residual=residual, alpha=alpha, Ct=Ct, tile=tile,
+                       splitk=splitk, stages=stages, accumulate=accumulate, lora_group_n=lora_group_n, lora_group_k=lora_group_k, batch=batch, geglu_out=geglu_out,
+                       geglu_bwd=geglu_bwd, act_out=act_out, dact_in=dact_in, col_scale=col_scale, ln=ln, x2_group_n=x2_group_n)
 
 
 STRIP_SPLITK = int(os.environ.get("SDLT_STRIP_SPLITK", "1"))      # in-kernel K split of strip_gemm: 1 = off (default), n = force where K allows

@@ -1612,6 +1612,106 @@ def test_wsk_gemm_rowdot(ops, B, Nq, N, K, lora, packed):
         assert not rd["done"] and float(rd["D"].abs().max()) == 0.0
 
 
+@pytest.mark.parametrize("packed", [False, True])
+@pytest.mark.parametrize("M", [64, 128, 1024])
+def test_wsk_entry_points_agree(ops, M, packed):
+    """The flat entry points sdlt_wsk_gemm / _ln / _parts / _rowdot, the parameter block sdlt_wsk_gemm_p and ops.gemm are three ways to hand the SAME arguments to the same
+    kernel, whose sums are ordered: every output must agree bit for bit (no tolerance).  N = 640, K = 1024: four K steps per wave (more than either ring depth: refills run; a
+    tile rotation of up to 3); M = 64 is one row tile (the 1D XCD map), M = 128 two (the 2D map); row-major and packed weights.  ops.gemm: wsk_shape admits K = 1024 only with an
+    adapter and from 128 tiles on, so that part runs at M = 1024 (the smallest M the predicate accepts for N = 640) on the adapter forms; the plain product has no admitted M."""
+    import ctypes as C
+    N, K, Nq, gk = 640, 1024, 64, 512
+    g = torch.Generator().manual_seed(M + int(packed))
+    x, w = rnd(M, K, g=g).cuda(), rnd(N, K, g=g, scale=K ** -0.5).cuda()
+    b, r, o = torch.randn(N, generator=g).cuda(), rnd(M, N, g=g).cuda(), rnd(M, N, g=g).cuda()
+    A, Bu, Bu2 = rnd(16, K, g=g, scale=1.0 / 16).cuda(), rnd(N, 16, g=g, scale=0.05).cuda(), rnd(N, 32, g=g, scale=0.05).cuda()
+    c1, consts = torch.randn(N, generator=g).cuda(), torch.randn(32, generator=g).cuda()
+    lib = ops._lib.load()
+    st = torch.cuda.current_stream().cuda_stream
+    wptr, ldw = w.data_ptr(), K
+    if packed:
+        wp = torch.empty(N * K, dtype=BF, device="cuda")
+        ops._lib.check(lib.sdlt_wsk_pack_weight(w.data_ptr(), K, N, K, wp.data_ptr(), st), "sdlt_wsk_pack_weight")
+        wptr, ldw = wp.data_ptr(), 0
+    forms = ("plain", "lora", "kgroup", "ln", "parts", "rowdot")        # every form but "plain" carries a rank-16 adapter ("kgroup": one per group of 512 columns)
+
+    def outputs(form):         # (D is zeroed before each call)
+        G = 2 if form == "kgroup" else 1
+        return dict(Y=torch.full((M, N), 7.0, dtype=BF, device="cuda"), T=torch.full((M, 16 * G), 7.0, dtype=BF, device="cuda"), stats=torch.zeros(M, 2, device="cuda"),
+                    parts=torch.zeros(M, N // 80, 2, device="cuda"), D=torch.zeros(M * (N // 64), device="cuda"))
+
+    def flat(form):
+        t = outputs(form)
+        Bu_ = Bu2 if form == "kgroup" else Bu
+        la = (A.data_ptr(), K, Bu_.data_ptr(), Bu_.shape[1], 0.75, t["T"].data_ptr(), t["T"].shape[1]) if form != "plain" else (None, 0, None, 0, 0.0, None, 0)
+        head, y = (x.data_ptr(), K, wptr, ldw, M, N, K, b.data_ptr()), t["Y"].data_ptr()
+        if form == "ln":
+            rc = lib.sdlt_wsk_gemm_ln(*head, r.data_ptr(), N, y, N, *la, c1.data_ptr(), t["stats"].data_ptr(), 1e-5, consts.data_ptr(), st)
+        elif form == "parts":
+            rc = lib.sdlt_wsk_gemm_parts(*head, r.data_ptr(), N, y, N, *la, 0, t["parts"].data_ptr(), st)
+        elif form == "rowdot":
+            rc = lib.sdlt_wsk_gemm_rowdot(*head, o.data_ptr(), N, y, N, *la, 0, t["D"].data_ptr(), Nq, st)
+        else:
+            rc = lib.sdlt_wsk_gemm(*head, r.data_ptr(), N, y, N, *la, gk if form == "kgroup" else 0, st)
+        assert rc == 0, lib.sdlt_last_error()
+        return t
+
+    def block(form):
+        t = outputs(form)
+        q = ops._lib.WskGemmParams()
+        q.X, q.ldx, q.W, q.ldw, q.M, q.N, q.K, q.bias, q.Y, q.ldy = x.data_ptr(), K, wptr, ldw, M, N, K, b.data_ptr(), t["Y"].data_ptr(), N
+        q.R, q.ldr = (o if form == "rowdot" else r).data_ptr(), N
+        if form != "plain":
+            Bu_ = Bu2 if form == "kgroup" else Bu
+            q.Adown, q.ld_adown, q.Bup, q.ld_bup, q.lora_scale, q.lora_rp, q.T_out, q.ld_t = A.data_ptr(), K, Bu_.data_ptr(), Bu_.shape[1], 0.75, 16, t["T"].data_ptr(), t["T"].shape[1]
+        if form == "kgroup":
+            q.lora_group_k = gk
+        if form == "ln":
+            q.ln_c1, q.ln_stats, q.ln_eps, q.ln_adapter = c1.data_ptr(), t["stats"].data_ptr(), 1e-5, consts.data_ptr()
+        if form == "parts":
+            q.ln_parts = t["parts"].data_ptr()
+        if form == "rowdot":
+            q.dotD, q.dot_nq = t["D"].data_ptr(), Nq
+        rc = lib.sdlt_wsk_gemm_p(C.byref(q), st)
+        assert rc == 0, lib.sdlt_last_error()
+        return t
+
+    def via_ops(form, **kw):
+        t = outputs(form)
+        kw = dict(dict(lora=(A, Bu2 if form == "kgroup" else Bu, 0.75, t["T"]), bias=b, residual=r, lora_group_k=gk if form == "kgroup" else 0), **kw)
+        if form == "ln":
+            kw["ln"] = (c1, t["stats"], 1e-5, consts)
+        if form == "parts":
+            kw["ln_parts_out"] = t["parts"]
+        if form == "rowdot":
+            t["rd"] = kw["rowdot"] = dict(O=o, D=t["D"], Nq=Nq, done=False)
+        ops.gemm(x, w, t["Y"], **kw)
+        return t
+
+    def same(got, want, what):
+        torch.cuda.synchronize()
+        for k in ("Y", "T", "stats", "parts", "D"):
+            assert torch.equal(got[k], want[k]), f"{what}: {k} differs, max abs diff {float((got[k].float() - want[k].float()).abs().max())}"
+
+    ref = {form: flat(form) for form in forms}
+    for form in forms:
+        assert float((ref[form]["Y"].float() - 7.0).abs().max()) > 1.0          # (the kernel wrote the output)
+        same(block(form), ref[form], f"sdlt_wsk_gemm_p, {form}")
+    assert float(ref["rowdot"]["D"].abs().max()) > 0.0 and float(ref["parts"]["parts"].abs().max()) > 0.0 and float(ref["ln"]["stats"].abs().max()) > 0.0
+    if not ops.wsk_shape(M, N, K, True):
+        return
+    if packed:
+        ops.wsk_mark_frozen(w)
+    for form in forms[1:]:
+        t = via_ops(form, **(dict(residual=None) if form == "rowdot" else {}))
+        same(t, ref[form], f"ops.gemm, {form}")
+        assert form != "rowdot" or t["rd"]["done"]
+    assert (w.data_ptr() in ops._WSK_PACKED) == packed and (not packed or torch.equal(ops._WSK_PACKED[w.data_ptr()][0], wp))
+    t = via_ops("rowdot")          # with a residual the row-dot form does not apply: the plain adapter product, D untouched, nothing reported
+    same(t, ref["lora"], "ops.gemm, rowdot + residual")
+    assert not t["rd"]["done"]
+
+
 @pytest.mark.parametrize("B,sizes,ratio,has", [(1, [(64, 64, 10), (32, 32, 50)], 1.0, [1]), (2, [(64, 64, 3), (32, 32, 6), (16, 16, 6)], 1.0, [1, 0]),
                                                (2, [(32, 32, 4)], 1.0, [1, 1]), (1, [(32, 64, 2), (16, 32, 5)], 2.0, [1]), (2, [(32, 32, 2), (16, 16, 2)], 1.0, [0, 0])])
 def test_token_attention_loss_fused(ops, B, sizes, ratio, has):
