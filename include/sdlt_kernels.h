@@ -20,7 +20,7 @@ extern "C" {
 
 const char* sdlt_last_error(void);
 int sdlt_abi_version(void);
-int sdlt_struct_size(int which); /* 0 gemm, 1 lora_grad_desc, 2 attn, 3 groupnorm, 4 shadow_desc, 5 gemm_batch_item, 6 dora_desc, 7 dora_wt_desc, 8 dora_grad_desc, 9 splitsum_desc ... 19 merge_desc, 20 sampler_params, 21 delta_desc, 22 sampler_img_params */
+int sdlt_struct_size(int which); /* 0 gemm, 1 lora_grad_desc, 2 attn, 3 groupnorm, 4 shadow_desc, 5 gemm_batch_item, 6 dora_desc, 7 dora_wt_desc, 8 dora_grad_desc, 9 splitsum_desc ... 19 merge_desc, 20 sampler_params, 21 delta_desc, 22 sampler_img_params, 23 sampler_ms_params */
 
 /* ------------------------------------------------------------------------------------------------
  * sdlt_gemm_bf16 : C = alpha*(X.W^T [+ X2.W2^T] [+ s*(X.Adown^T).Bup^T]) + bias + rowbias + R
@@ -561,6 +561,39 @@ typedef struct sdlt_sampler_img_params {
   int32_t n, hw, table_rows, init;
 } sdlt_sampler_img_params;
 int sdlt_sampler_step_img(const sdlt_sampler_img_params* p, void* stream);
+
+/* sdlt_sampler_step_ms : the same launch for DPM-Solver++ (2M) (Lu et al. 2022, second-order multistep; latent unscaled, lambda = -log sigma), for
+ * txt2img, img2img and masked inpainting alike.  With the denoised value D_i:  x_{i+1} = a x + b D_i + c D_{i-1},  a = sigma_{i+1} / sigma_i,
+ * b = (1 - a)(1 + 1 / (2 r)),  c = -(1 - a) / (2 r),  r = h_prev / h,  h = lambda_{i+1} - lambda_i.  The host computes a, b, c (fp64, rounded once):
+ * table fp32 [table_rows, 8], rows 0 and 1 as sdlt_sampler_step_img in columns 0..3 (row 0 column 1 = the FIRST USED sigma), columns 4..7 zero;
+ *     row 2 + i: sigma_i, sigma_{i+1}, 1 / sqrt(sigma_{i+1}^2 + 1), timestep of step i + 1, a_i, b_i, c_i, 0
+ * c_i = 0.0f marks a first-order row (row 0; a step to sigma = 0).  dprev fp32 [n, 4, hw] holds D_{i-1}.  Counter, ticket, repack, timesteps as above.
+ *     init != 0:  x = noise * sigma_0, or x0 + noise * sigma_0 when x0 != NULL ;  xin = bf16(x / sqrt(sigma_0^2 + 1)) ;  first timestep ;  ctr[0] = 0
+ *                 (eps, mask and dprev are not touched)
+ *     init == 0:  1. e = eps_neg + g (eps_pos - eps_neg)
+ *                 2. D = x - sigma e (epsilon) | e * (-sigma / sqrt(sigma^2 + 1)) + x / (sigma^2 + 1) (v prediction)
+ *                 3. xn = a x + b D
+ *                 4. only if c != 0 (uniform over the launch):  xn = xn + c dprev
+ *                 5. with a mask:  k = x0 + noise * sigma_next ;  xn = k + m (xn - k)
+ *                 6. x = xn ;  dprev = D ;  xin, timesteps, ctr
+ * dprev is never read where c == 0: it may hold anything (NaN included) before the first step, and the counter's wrap to 0 after the last step starts
+ * the next trajectory first order again.  m = 0 gives k exactly, and k = x0 exactly after the last step.  Without a mask a step reads neither x0 nor
+ * noise (both may be NULL).  All arithmetic fp32, one rounding per operation, in the order written.  x0 and noise may not alias x; dprev may alias
+ * none of x, x0, noise.  Alignment as sdlt_sampler_step. */
+typedef struct sdlt_sampler_ms_params {
+  const float* eps;                  /* fp32 [2n * hw, 4]: UNet.forward's output (step only) */
+  float* x;                          /* fp32 [n, 4, hw] latent state, in place */
+  const float* x0;                   /* fp32 [n, 4, hw] or NULL: init (img2img), and every step with a mask */
+  const float* noise;                /* fp32 [n, 4, hw]: init, and every step with a mask */
+  const float* mask;                 /* fp32 [n, hw] or NULL */
+  float* dprev;                      /* fp32 [n, 4, hw]: the previous step's denoised value (step only) */
+  void* xin; int64_t ld_xin;         /* bf16 [2n * hw, ld_xin] NHWC model input */
+  float* timesteps;                  /* fp32 [2n] */
+  const float* table;                /* fp32 [table_rows, 8] */
+  int32_t* ctr;
+  int32_t n, hw, table_rows, init;
+} sdlt_sampler_ms_params;
+int sdlt_sampler_step_ms(const sdlt_sampler_ms_params* p, void* stream);
 
 /* out[M,C] = a + b on strided 2-D bf16 views (gradient fan-in of the UNet skip connections). */
 int sdlt_add2d(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int32_t M, int32_t C, void* stream);

@@ -168,6 +168,11 @@ class SamplerImgParams(C.Structure):
                 ("n", i32), ("hw", i32), ("table_rows", i32), ("init", i32)]
 
 
+class SamplerMsParams(C.Structure):
+    _fields_ = [("eps", vp), ("x", vp), ("x0", vp), ("noise", vp), ("mask", vp), ("dprev", vp), ("xin", vp), ("ld_xin", i64), ("timesteps", vp), ("table", vp),
+                ("ctr", vp), ("n", i32), ("hw", i32), ("table_rows", i32), ("init", i32)]
+
+
 class ShadowDesc(C.Structure):
     _fields_ = [("offset", i64), ("src_ld", i64), ("rows", i32), ("cols", i32), ("dst", vp), ("ld", i64), ("dstT", vp), ("ldT", i64)]
 
@@ -220,6 +225,7 @@ SYMBOLS = {
     "sdlt_delta_matmul": (i32, [vp, vp, vp, i32, i32, vp]),
     "sdlt_sampler_step": (i32, [C.POINTER(SamplerParams), vp]),
     "sdlt_sampler_step_img": (i32, [C.POINTER(SamplerImgParams), vp]),
+    "sdlt_sampler_step_ms": (i32, [C.POINTER(SamplerMsParams), vp]),
     "sdlt_strip_gemm": (i32, [C.POINTER(StripParams), vp]),
     "sdlt_strip_gemm_pair": (i32, [C.POINTER(StripParams), C.POINTER(StripParams), vp]),
     "sdlt_attn_pair_ok": (i32, [C.POINTER(AttnParams), C.POINTER(AttnParams)]),
@@ -280,7 +286,8 @@ def struct_sizes():
                 TaParams, LnSlabsParams, TaGroup)
     return [(c.__name__, C.sizeof(c)) for c in mirrored] + [("sdlt_affine_grad_item", 8 * 8), ("sdlt_wgrad_tr_item", 3 * 8), ("LnFoldDesc", C.sizeof(LnFoldDesc)), ("ColsumFinishDesc", C.sizeof(ColsumFinishDesc)),
                                                                ("WskGemmParams", C.sizeof(WskGemmParams)), ("MergeDesc", C.sizeof(MergeDesc)), ("SamplerParams", C.sizeof(SamplerParams)),
-                                                               ("DeltaDesc", C.sizeof(DeltaDesc)), ("SamplerImgParams", C.sizeof(SamplerImgParams))]
+                                                               ("DeltaDesc", C.sizeof(DeltaDesc)), ("SamplerImgParams", C.sizeof(SamplerImgParams)),
+                                                               ("SamplerMsParams", C.sizeof(SamplerMsParams))]
 
 
 def check(rc, what):

@@ -4,7 +4,7 @@ scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-squ
 
     python -m sd_lora_trainer_amd.render --checkpoint DIR --out DIR [--prompt TEXT ...] [--n-validation N] [--lora-scale X ...] [--size W H]
                                          [--steps N] [--guidance G] [--seed S] [--images-per-batch N] [--eager]
-                                         [--init-image PATH [--strength S] [--mask PATH]]
+                                         [--init-image PATH [--strength S] [--mask PATH]] [--sampler euler|dpmpp_2m] [--sigmas trailing|karras]
                                          [--unet F] [--text-encoder F] [--text-encoder-2 F] [--vae F] [--tokenizer DIR]
 
 DIR is a checkpoint directory of train(): training_args.json (the job's TrainingConfig), adapter_config.json + the kohya adapter file
@@ -17,6 +17,10 @@ as one replayed hipGraph (sampler.LatentSampler.sample(graph=True)); --eager iss
 of the loaded stack (the posterior's mean times the scaling factor: deterministic) and noised to the point of the schedule that --strength
 selects (default 0.6; the last int(steps * strength) steps run).  --mask (white: regenerate, black: keep; nearest-resized to the latent grid)
 keeps the black region of the init image: it is put back after every step, and comes out as the encoded image exactly.
+
+--sampler dpmpp_2m integrates with DPM-Solver++ (2M), the second-order multistep solver (sampler.DpmSolverPP2M; the step launch is then
+sdlt_sampler_step_ms), instead of first-order Euler: the same trajectory error in about half the steps.  --sigmas karras spaces the noise levels as
+Karras et al. 2022 (rho = 7) instead of by trailing timesteps; it combines with either sampler, and both combine with --init-image / --mask.
 """
 import argparse
 import json
@@ -180,12 +184,13 @@ def encode_init(loaded, init_image, mask_image, size, latent_hw):
 
 @torch.no_grad()
 def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, guidance_scale=8.0, seed=None, images_per_batch=1, token_scale=None,
-           graph=True, n_validation=4, init_image=None, strength=None, mask_image=None):
+           graph=True, n_validation=4, init_image=None, strength=None, mask_image=None, sampler="euler", sigmas="trailing"):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
     seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
     graph=False is the eager loop with the same fused kernel.  init_image (path or PIL image): every image starts from it (encode_init) at
-    `strength` (default 0.6) instead of from pure noise, each with its own noise; mask_image: white regenerate, black keep.  -> {scale: [paths]}."""
+    `strength` (default 0.6) instead of from pure noise, each with its own noise; mask_image: white regenerate, black keep.  sampler "euler" |
+    "dpmpp_2m", sigmas "trailing" | "karras": LatentSampler.sample's.  -> {scale: [paths]}."""
     from . import train as T
     from . import vae as _vae
     from PIL import Image
@@ -205,20 +210,26 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     f = 2 ** (len(stack.decoder.ups) - 1) if hasattr(stack.decoder, "ups") else 8      # 8 for the SD / SDXL VAE
     w, h = size[0] // f, size[1] // f
     n = images_per_batch
+    from . import sampler as SM
+    if sampler not in SM.SAMPLERS:
+        raise ValueError(f"sampler must be one of {SM.SAMPLERS}, got {sampler!r}")
+    if sigmas not in SM.SIGMAS:
+        raise ValueError(f"sigmas must be one of {SM.SIGMAS}, got {sigmas!r}")
     img_kw = {}
+    if (sampler, sigmas) != ("euler", "trailing"):
+        img_kw.update(sampler=sampler, sigmas=sigmas)
     if init_image is None:
         if mask_image is not None:
             raise ValueError("mask_image needs init_image: the region to keep is taken from it")
         if strength is not None:
             raise ValueError("strength needs init_image")
     else:
-        from . import sampler as SM
         strength = 0.6 if strength is None else strength
         SM.img2img_steps(steps, strength)               # (raises before anything is built)
         x0, mask = encode_init(loaded, init_image, mask_image, size, (h, w))
-        img_kw = dict(init_latents=x0, strength=strength, mask=mask)
+        img_kw.update(init_latents=x0, strength=strength, mask=mask)
     loaded.prepare(n, h, w)
-    smp, fused = stack.sampler, hasattr(stack.rt.ops, "sampler_step")
+    smp, fused = stack.sampler, hasattr(stack.rt.ops, "sampler_step_ms" if sampler == "dpmpp_2m" else "sampler_step")
     graph = graph and dev.type == "cuda"
     os.makedirs(out_dir, exist_ok=True)
     result = {}
@@ -249,6 +260,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         meta = dict(prompts=prompts, lora_scales=list(lora_scales), size=list(size), steps=steps, guidance_scale=guidance_scale, seed=seed)
         if init_image is not None:
             meta.update(strength=strength, masked=mask_image is not None)
+        if (sampler, sigmas) != ("euler", "trailing"):
+            meta.update(sampler=sampler, sigmas=sigmas)
         json.dump(meta, fh, indent=2)
     return result
 
@@ -269,6 +282,8 @@ def main(argv=None, runtime=None):
     ap.add_argument("--init-image", default=None, help="start from this picture instead of pure noise (img2img); resized to --size")
     ap.add_argument("--strength", type=float, default=None, help="how much of the schedule runs on the init image, in (0, 1]; default 0.6 with --init-image")
     ap.add_argument("--mask", default=None, help="inpainting mask for --init-image: white is regenerated, black is kept")
+    ap.add_argument("--sampler", choices=("euler", "dpmpp_2m"), default="euler", help="integrator: first-order Euler, or DPM-Solver++ (2M) (second order: about half the steps)")
+    ap.add_argument("--sigmas", choices=("trailing", "karras"), default="trailing", help="noise levels: those of trailing timesteps, or Karras et al. (rho = 7)")
     ap.add_argument("--device", default="cuda:0")
     for flag, key, what in (("--unet", "path", "base UNet weights or synthetic:<version>"), ("--text-encoder", "text_encoder_path", "text encoder state dict"),
                             ("--text-encoder-2", "text_encoder_2_path", "SDXL's second text encoder"), ("--vae", "vae_path", "AutoencoderKL state dict"),
@@ -287,7 +302,7 @@ def main(argv=None, runtime=None):
     loaded = load_for_inference(a.checkpoint, pm, device=a.device, runtime=runtime)
     res = render(loaded, a.prompt, a.out, lora_scales=a.lora_scale, size=a.size, steps=a.steps, guidance_scale=a.guidance, seed=a.seed,
                  images_per_batch=a.images_per_batch, graph=not a.eager, n_validation=a.n_validation, init_image=a.init_image, strength=a.strength,
-                 mask_image=a.mask)
+                 mask_image=a.mask, sampler=a.sampler, sigmas=a.sigmas)
     for scale, paths in res.items():
         print(f"lora_scale {scale}: {len(paths)} image(s), {os.path.join(a.out, 'grid_scale' + _scale_tag(scale) + '.jpg')}")
     return res

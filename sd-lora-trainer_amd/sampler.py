@@ -39,17 +39,38 @@ class EulerDiscrete:
         self.sigmas_all = np.sqrt((1 - acp) / acp)
         self.T, self.prediction_type = num_train_timesteps, prediction_type
 
-    def set_timesteps(self, n, start=0):
-        """start: skip the first `start` entries of the schedule (img2img: the trajectory begins at timesteps[start] of the n-step schedule)."""
+    def set_timesteps(self, n, start=0, sigmas="trailing"):
+        """start: skip the first `start` entries of the schedule (img2img: the trajectory begins at timesteps[start] of the n-step schedule).
+        sigmas: "trailing" (diffusers' trailing timestep spacing, the sigmas of those timesteps) | "karras" (KARRAS_RHO-spaced noise levels)."""
         assert 0 <= start < n
-        ts = np.round(np.arange(self.T, 0, -self.T / n))[start:] - 1               # "trailing"
-        sig = np.interp(ts, np.arange(self.T), self.sigmas_all)
+        if sigmas == "trailing":
+            ts = np.round(np.arange(self.T, 0, -self.T / n))[start:] - 1               # "trailing"
+            sig = np.interp(ts, np.arange(self.T), self.sigmas_all)
+        elif sigmas == "karras":
+            sig = karras_sigmas(n, float(self.sigmas_all[0]), float(self.sigmas_all[-1]))[start:]
+            ts = np.interp(np.log(sig), np.log(self.sigmas_all), np.arange(self.T))    # sigmas_all rises with t: the fractional training timestep of each level
+        else:
+            raise ValueError(f"sigmas must be 'trailing' or 'karras', got {sigmas!r}")
         self.timesteps = ts.astype(np.float32)
         self.sigmas = np.concatenate([sig, [0.0]]).astype(np.float32)
         # diffusers 0.29.2 EulerDiscreteScheduler.init_noise_sigma: max(sigmas) for timestep_spacing in ("linspace", "trailing") -
         # the reference's configuration (inference.py:358-360); sqrt(sigma_max^2 + 1) only for "leading"
         self.init_noise_sigma = float(self.sigmas.max())
+        self._begin()
         return self
+
+    def set_sigmas(self, sigmas, timesteps=None):
+        """A noise-level grid of the caller's own (decreasing; a final 0 is optional and NOT appended), kept in the dtype given: fp64 for order studies."""
+        self.sigmas = np.asarray(sigmas)
+        n = len(self.sigmas) - 1
+        self.timesteps = np.zeros(n, dtype=np.float32) if timesteps is None else np.asarray(timesteps, dtype=np.float32)
+        assert n >= 1 and len(self.timesteps) == n and bool((np.diff(self.sigmas) < 0).all())
+        self.init_noise_sigma = float(self.sigmas.max())
+        self._begin()
+        return self
+
+    def _begin(self):
+        """A trajectory starts: nothing to prepare for a one-step method."""
 
     def scale_model_input(self, x, i):
         return x / float(np.sqrt(self.sigmas[i] ** 2 + 1))
@@ -63,6 +84,70 @@ class EulerDiscrete:
             d = (x - x0) / s
         return x + d * (sn - s)
 
+
+KARRAS_RHO = 7.0
+
+
+def karras_sigmas(n, sigma_min, sigma_max, rho=KARRAS_RHO):
+    """Karras et al. 2022, eq. 5: sigma_i = (sigma_max^(1/rho) + i / (n - 1) (sigma_min^(1/rho) - sigma_max^(1/rho)))^rho, i = 0 .. n - 1 (fp64; without the final 0)."""
+    ramp = np.arange(n, dtype=np.float64) / max(n - 1, 1)
+    lo, hi = sigma_min ** (1.0 / rho), sigma_max ** (1.0 / rho)
+    sig = (hi + ramp * (lo - hi)) ** rho
+    sig[0] = sigma_max                                      # exactly, not to a rounding of the power
+    if n > 1:
+        sig[-1] = sigma_min
+    return sig
+
+
+def ms_coefficients(sigmas):
+    """DPM-Solver++ (2M) on the grid `sigmas` [k + 1] -> fp64 [k, 3]: (a_i, b_i, c_i) of x_{i+1} = a x + b D_i + c D_{i-1} (module docstring).
+    Row 0 (no history yet) and a step to sigma = 0 (h is infinite there) are first order: c = 0 exactly."""
+    sig = np.asarray(sigmas, dtype=np.float64)
+    k = len(sig) - 1
+    out = np.zeros((k, 3), dtype=np.float64)
+    h_prev = None
+    for i in range(k):
+        s, sn = sig[i], sig[i + 1]
+        a = sn / s
+        if sn == 0.0 or h_prev is None:
+            b, c = 1.0 - a, 0.0
+        else:
+            h = np.log(s) - np.log(sn)                      # lambda_{i+1} - lambda_i, lambda = -log sigma
+            r = h_prev / h
+            b, c = (1.0 - a) * (1.0 + 1.0 / (2.0 * r)), -(1.0 - a) / (2.0 * r)
+        out[i] = (a, b, c)
+        h_prev = None if sn == 0.0 else np.log(s) - np.log(sn)
+    return out
+
+
+class DpmSolverPP2M(EulerDiscrete):
+    """DPM-Solver++ (2M) (module docstring) on EulerDiscrete's schedules: same sigmas, timesteps, model input and init noise; `step` keeps the previous
+    denoised value, so steps are taken in order, i = 0 first (set_timesteps / set_sigmas start a trajectory)."""
+
+    def _begin(self):
+        self.coeffs = ms_coefficients(self.sigmas)          # fp64, from the sigmas as stored (fp32 from set_timesteps)
+        self._dprev = None
+
+    def denoised(self, model_out, i, x):
+        s = float(self.sigmas[i])
+        if self.prediction_type == "epsilon":
+            return x - model_out * s
+        return model_out * (-s / (s * s + 1) ** 0.5) + x / (s * s + 1)
+
+    def step(self, model_out, i, x):
+        if i == 0:
+            self._dprev = None
+        a, b, c = (float(v) for v in self.coeffs[i])
+        D = self.denoised(model_out, i, x)
+        xn = x * a + D * b
+        if c != 0.0:
+            xn = xn + self._dprev * c
+        self._dprev = D
+        return xn
+
+
+SAMPLERS = ("euler", "dpmpp_2m")
+SIGMAS = ("trailing", "karras")
 
 TABLE_ROWS = 2 + 1000      # rows of the device step table: two header rows + at most one step per training timestep
 MAX_GRAPHS = 4             # captured iterations kept per sampler (one per shape and adapter scale)
@@ -102,6 +187,17 @@ def step_table_img(sched, guidance_scale):
     return tab
 
 
+def step_table_ms(sched, guidance_scale):
+    """The device table of ops.sampler_step_ms for a DpmSolverPP2M whose set_timesteps(n[, start]) has run: fp32 [2 + k, 8].  Columns 0..3 are
+    step_table_img's (row 0 column 1 = the first USED sigma, which is init_noise_sigma when nothing is skipped); a step row continues with
+    a_i, b_i, c_i, 0 - ms_coefficients in fp64 from the fp32 sigmas, rounded once.  c = 0.0f exactly on first-order rows."""
+    base = step_table_img(sched, guidance_scale)
+    tab = torch.zeros(base.shape[0], 8, dtype=torch.float32)
+    tab[:, :4] = base
+    tab[2:, 4:7] = torch.from_numpy(ms_coefficients(sched.sigmas).astype(np.float32))
+    return tab
+
+
 class LatentSampler:
     """`pipe(prompt_embeds=c, negative_prompt_embeds=uc, ..., num_inference_steps, guidance_scale, generator)` of the
     reference's render loop, up to the latents.  `unet` is an inference instance built for batch 2 (negative | positive, the
@@ -112,12 +208,14 @@ class LatentSampler:
         self.rt, self.unet = rt, unet
         self.n = rt.B // 2                 # images sampled together (fused / graph path); image j = rows 2j (negative), 2j + 1 (positive)
         self.sched = EulerDiscrete(prediction_type=prediction_type)
+        self.sched_ms = DpmSolverPP2M(prediction_type=prediction_type)
         cfg = unet.cfg
         self.ctx = rt.zeros(rt.B * CTX_PAD, cfg["cross_dim"])
         self.pooled = rt.zeros(rt.B, cfg["proj_class_in"] - 6 * cfg["addition_time_embed_dim"]) if cfg["addition"] else None
         self._fused = None                 # persistent device state of the fused / graph path, built on first use
         self._graphs = {}                  # (h, w, n, adapter scale in effect, DoRA) -> hipGraph of one denoising iteration
         self._img_graphs = {}              # the same key + (masked,) -> hipGraph of one iteration whose step launch is ops.sampler_step_img
+        self._ms_graphs = {}               # the same key + (masked, "multistep") -> hipGraph of one iteration whose step launch is ops.sampler_step_ms
 
     def set_lora_scale(self, lora_scale, train_scale=None):
         """set_adapter_scales (checkpoint.py:31-55): every adapter's contribution is multiplied by lora_scale."""
@@ -129,7 +227,7 @@ class LatentSampler:
 
     @torch.no_grad()
     def sample(self, embeds, h, w, *, steps=25, guidance_scale=8.0, generator=None, size=None, latents=None, graph=False, fused=False, n_images=1,
-               init_latents=None, strength=1.0, mask=None):
+               init_latents=None, strength=1.0, mask=None, sampler="euler", sigmas="trailing"):
         """embeds = (c [1,77,D], uc [1,77,D], pc [1,P] | None, puc | None); h, w latent size.  Returns latents [1,4,h,w] fp32
         (still multiplied by the VAE scaling factor, as the pipeline holds them before `vae.decode(latents / scaling_factor)`).
         fused: guidance, the Euler update and the next model input are ONE kernel between two forwards (ops.sampler_step) instead of torch
@@ -138,10 +236,16 @@ class LatentSampler:
         init_latents [n_images | 1, 4, h, w] (the encoded image times the scaling factor): img2img - the last min(int(steps * strength), steps) steps of
         the schedule, from init_latents noised to the first of them (`latents` / `generator` give the noise, as above).  mask [n_images | 1, 1, h, w] in
         [0, 1]: 1 regenerate, 0 keep - the kept region is re-injected after every step and equals init_latents exactly at the end.  strength 1 without a
-        mask is txt2img from the noise; a mask of ones is no mask."""
+        mask is txt2img from the noise; a mask of ones is no mask.
+        sampler: "euler" | "dpmpp_2m" (DpmSolverPP2M: second-order multistep; fused / graph: the step launch is ops.sampler_step_ms); sigmas: "trailing" |
+        "karras" (EulerDiscrete.set_timesteps), with either sampler."""
+        if sampler not in SAMPLERS:
+            raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
+        if sigmas not in SIGMAS:
+            raise ValueError(f"sigmas must be one of {SIGMAS}, got {sigmas!r}")
         img = self._img_args(init_latents, strength, mask, steps, h, w, n_images)
         if graph or fused:
-            return self._sample_fused(embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img)
+            return self._sample_fused(embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img, sampler, sigmas)
         assert n_images == 1 and self.rt.B == 2, "the torch loop samples one image on a batch-2 runtime; several images together: fused=True or graph=True"
         rt, u, cfg = self.rt, self.unet, self.unet.cfg
         dev = rt.device
@@ -156,7 +260,10 @@ class LatentSampler:
             H, W = size if size is not None else (8 * h, 8 * w)
             tid = torch.tensor([float(H), float(W), 0.0, 0.0, float(H), float(W)] * 2, device=dev)   # original_size, crop, target_size
         x0, m, start = img if img is not None else (None, None, 0)
-        s = self.sched.set_timesteps(steps, start) if img is not None else self.sched.set_timesteps(steps)
+        if sampler == "euler" and sigmas == "trailing":
+            s = self.sched.set_timesteps(steps, start) if img is not None else self.sched.set_timesteps(steps)
+        else:
+            s = (self.sched_ms if sampler == "dpmpp_2m" else self.sched).set_timesteps(steps, start, sigmas)
         x = latents if latents is not None else torch.randn(1, 4, h, w, generator=generator, device=dev, dtype=F32)
         if img is None:
             x = x.to(dev, F32) * s.init_noise_sigma
@@ -228,26 +335,34 @@ class LatentSampler:
             sh["img"] = dict(x0=rt.zeros(n, 4, h, w, dtype=F32), noise=rt.zeros(n, 4, h, w, dtype=F32), mask=rt.zeros(n, 1, h, w, dtype=F32))
         return sh["img"]
 
-    def _iteration(self, st, sh, h, w, masked=None):
-        """masked None: txt2img; False / True: from init latents, without / with the mask (sh["img"] holds them)."""
+    def _iteration(self, st, sh, h, w, masked=None, ms=False):
+        """masked None: txt2img; False / True: from init latents, without / with the mask (sh["img"] holds them).  ms: the DPM-Solver++ (2M) launch;
+        without a mask it reads neither the init latents nor the noise, whatever the trajectory started from."""
         u = self.unet
         eps = u.forward(sh["x64"], st["tf"], self.ctx, self.pooled, st["tid"] if u.cfg["addition"] else None, B=2 * self.n, H=h, W=w)
-        if masked is None:
+        if ms:
+            im = sh["img"] if masked else dict(x0=None, noise=None, mask=None)
+            self.rt.ops.sampler_step_ms(eps, sh["x"], sh["x64"], st["tf"], st["table_ms"], st["ctr"], dprev=sh["dprev"], x0=im["x0"], noise=im["noise"], mask=im["mask"])
+        elif masked is None:
             self.rt.ops.sampler_step(eps, sh["x"], sh["x64"], st["tf"], st["table"], st["ctr"])
         else:
             im = sh["img"]
             self.rt.ops.sampler_step_img(eps, sh["x"], sh["x64"], st["tf"], st["table"], st["ctr"], x0=im["x0"], noise=im["noise"],
                                          mask=im["mask"] if masked else None)
 
-    def _graph(self, st, sh, h, w, masked=None):
+    def _graph(self, st, sh, h, w, masked=None, ms=False):
         """The hipGraph of one iteration for this shape and the adapter scale in effect.  The scale is a launch argument of every adapted GEMM
         (baked by capture), hence part of the key; adapters, DoRA factors, token rows, conditioning, table and counter are device memory.
         From init latents (masked False / True) the step launch is another kernel: those captures live in a dict of their own, keyed by the mask
-        pointer's presence as well; strength and step count are in the table, init latents, noise and mask in persistent buffers."""
+        pointer's presence as well; strength and step count are in the table, init latents, noise and mask in persistent buffers.
+        ms: the captures of the multistep launch, in a third dict, keyed by the mask's presence too (without one, txt2img and img2img issue the same
+        launch and share a capture); step count, strength, schedule kind and coefficients are in its table, the previous denoised value in sh["dprev"]."""
         a = self.unet.arena
         key = (h, w, self.n, None if a is None else float(a.scale), bool(a is not None and a.dora))
         graphs = self._graphs
-        if masked is not None:
+        if ms:
+            key, graphs = key + (bool(masked), "multistep"), self._ms_graphs
+        elif masked is not None:
             key, graphs = key + (bool(masked),), self._img_graphs
         g = graphs.get(key)
         if g is not None:
@@ -260,11 +375,11 @@ class LatentSampler:
         side.wait_stream(torch.cuda.current_stream())
         seq = None
         with torch.cuda.stream(side):
-            self._iteration(st, sh, h, w, masked)         # eager warm-up: every persistent buffer and packed-weight copy exists before the capture
+            self._iteration(st, sh, h, w, masked, ms)     # eager warm-up: every persistent buffer and packed-weight copy exists before the capture
             if prefetch:                                  # next-weight hints of the wave-split-K products, recorded from one eager pass (step.TrainStep.capture)
                 ops.pf_record_begin()
                 try:
-                    self._iteration(st, sh, h, w, masked)
+                    self._iteration(st, sh, h, w, masked, ms)
                 finally:
                     seq = ops.pf_record_end()
         torch.cuda.current_stream().wait_stream(side)
@@ -273,15 +388,18 @@ class LatentSampler:
             if seq:
                 ops.pf_replay_begin(seq)
             try:
-                self._iteration(st, sh, h, w, masked)
+                self._iteration(st, sh, h, w, masked, ms)
             finally:
                 if seq:
                     ops.pf_replay_end()
         graphs[key] = g
         return g
 
-    def _sample_fused(self, embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img=None):
+    def _sample_fused(self, embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img=None, sampler="euler", sigmas="trailing"):
         rt, cfg, n = self.rt, self.unet.cfg, self.n
+        ms = sampler == "dpmpp_2m"
+        if ms and not hasattr(rt.ops, "sampler_step_ms"):
+            raise NotImplementedError("this op table has no sampler_step_ms kernel: sample(sampler='dpmpp_2m', graph=False, fused=False) is the torch loop")
         if not hasattr(rt.ops, "sampler_step"):
             raise NotImplementedError("this op table has no sampler_step kernel: sample(graph=False, fused=False) is the torch loop")
         if img is not None and not hasattr(rt.ops, "sampler_step_img"):
@@ -303,20 +421,40 @@ class LatentSampler:
         if cfg["addition"]:
             H, W = size if size is not None else (8 * h, 8 * w)
             st["tid"].copy_(torch.tensor([float(H), float(W), 0.0, 0.0, float(H), float(W)] * (2 * n)))
-        if img is None:
-            s = self.sched.set_timesteps(steps)
-            tab = step_table(s, guidance_scale)
+        if ms:
+            if "table_ms" not in st:
+                st["table_ms"] = rt.zeros(TABLE_ROWS, 8, dtype=F32)
+            if "dprev" not in sh:
+                sh["dprev"] = rt.zeros(n, 4, h, w, dtype=F32)
+            start = 0 if img is None else img[2]
+            tab = step_table_ms(self.sched_ms.set_timesteps(steps, start, sigmas), guidance_scale)
+            steps -= start
+            st["table_ms"][: tab.shape[0]].copy_(tab)
         else:
-            s = self.sched.set_timesteps(steps, img[2])
-            tab = step_table_img(s, guidance_scale)
-            steps -= img[2]                                 # the steps that run: the table holds their rows only
-        st["table"][: tab.shape[0]].copy_(tab)
+            if img is None:
+                s = self.sched.set_timesteps(steps) if sigmas == "trailing" else self.sched.set_timesteps(steps, 0, sigmas)
+                tab = step_table(s, guidance_scale)
+            else:
+                s = self.sched.set_timesteps(steps, img[2]) if sigmas == "trailing" else self.sched.set_timesteps(steps, img[2], sigmas)
+                tab = step_table_img(s, guidance_scale)
+                steps -= img[2]                             # the steps that run: the table holds their rows only
+            st["table"][: tab.shape[0]].copy_(tab)
         noise = latents if latents is not None else torch.randn(n, 4, h, w, generator=generator, device=dev, dtype=F32)
         noise = noise.to(dev, F32).contiguous()
         assert tuple(noise.shape) == (n, 4, h, w)
         x, x64 = sh["x"], sh["x64"]
         masked = None
-        if img is None:
+        if ms:
+            x0 = None
+            if img is not None:
+                im, masked = self._img_state(sh, h, w), img[1] is not None
+                im["x0"].copy_(img[0])
+                im["noise"].copy_(noise)
+                if masked:
+                    im["mask"].copy_(img[1])
+                x0, noise = im["x0"], im["noise"]
+            init = lambda: rt.ops.sampler_step_ms(None, x, x64, st["tf"], st["table_ms"], st["ctr"], dprev=sh["dprev"], x0=x0, noise=noise, init=True)  # noqa: E731
+        elif img is None:
             init = lambda: rt.ops.sampler_step(None, x, x64, st["tf"], st["table"], st["ctr"], noise=noise)  # noqa: E731
         else:
             im, masked = self._img_state(sh, h, w), img[1] is not None
@@ -329,13 +467,13 @@ class LatentSampler:
             g = None
             if graph:
                 init()                                    # (a defined state for the warm-up passes)
-                g = self._graph(st, sh, h, w, masked)
+                g = self._graph(st, sh, h, w, masked, ms)
             init()
             for _ in range(steps):                        # no host read in here: the step index lives in ctr, its scalars in the table
                 if g is not None:
                     g.replay()
                 else:
-                    self._iteration(st, sh, h, w, masked)
+                    self._iteration(st, sh, h, w, masked, ms)
         return x.clone()
 
 

@@ -3,9 +3,11 @@ them alike): (a) LatentSampler.sample as train() uses it (torch element-wise lau
 sdlt_sampler_step kernel, (c) one replayed hipGraph per iteration.  SDXL topology (random weights), 128 x 128 latent, rank-16 adapters, 25 steps,
 n = 1 and n = 2 images per batch ((a) samples the n images one after the other on its batch-2 instance).  --img2img adds the replayed graph
 whose step launch is sdlt_sampler_step_img: (d) from init latents at strength 0.6 (15 of the 25 iterations run, no mask) and (e) masked inpainting at
-strength 1 (all 25, the mask blend in every one); their time is divided by the iterations that ran.
+strength 1 (all 25, the mask blend in every one); their time is divided by the iterations that ran.  --sampler / --sigmas add the replayed graph of
+each named combination other than the default one - e.g. `--sampler dpmpp_2m` times (f) the iteration whose step launch is sdlt_sampler_step_ms
+against (c) - and, with --img2img, its masked variant (`inp`).
 
-    python tools/render_bench.py [--out FILE] [--rounds 5] [--version sdxl] [--latent 128] [--n 1 2] [--img2img]
+    python tools/render_bench.py [--out FILE] [--rounds 5] [--version sdxl] [--latent 128] [--n 1 2] [--img2img] [--sampler dpmpp_2m] [--sigmas karras]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/render_bench.py --trace-iteration --n 1      # kernel time of one iteration: sum the stats
 
 Prints one table: wall milliseconds per iteration (median over the rounds, min .. max) per variant and n, per image in brackets.
@@ -67,6 +69,8 @@ def main():
     ap.add_argument("--trace-iteration", action="store_true", help="run the eager fused loop once and exit (under rocprofv3 --kernel-trace --stats: kernel time per iteration = total / steps, without the one-off pack kernels)")
     ap.add_argument("--img2img", action="store_true", help="also time the graph sampler from init latents: strength 0.6 without a mask, strength 1 with a mask "
                     "(with --trace-iteration: run the masked eager loop instead of the txt2img one)")
+    ap.add_argument("--sampler", nargs="+", choices=("euler", "dpmpp_2m"), default=["euler"], help="also time the graph sampler with these integrators")
+    ap.add_argument("--sigmas", nargs="+", choices=("trailing", "karras"), default=["trailing"], help="... on these noise levels")
     a = ap.parse_args()
     h = a.latent
     lines = [f"# {a.version} topology, {h} x {h} latent, rank {a.rank}, {a.steps} steps, guidance 8; wall ms per denoising iteration: median (min .. max) of {a.rounds} rounds, alternated",
@@ -92,8 +96,14 @@ def main():
             variants["d graph, init latents 0.6"] = lambda: one(graph=True, init_latents=x0, strength=0.6)
             variants["e graph, inpaint 1.0"] = lambda: one(graph=True, init_latents=x0, strength=1.0, mask=mask)
             ran["d graph, init latents 0.6"], ran["e graph, inpaint 1.0"] = min(int(a.steps * 0.6), a.steps), a.steps
+        extra = [(s, k) for s in a.sampler for k in a.sigmas if (s, k) != ("euler", "trailing")]
+        for tag, (s, k) in zip("fghij", extra):
+            name = f"{tag} graph, {s} {k}"
+            variants[name], ran[name] = (lambda s=s, k=k: one(graph=True, sampler=s, sigmas=k)), a.steps
+            if a.img2img:
+                variants[name + " inp"], ran[name + " inp"] = (lambda s=s, k=k: one(graph=True, sampler=s, sigmas=k, init_latents=x0, strength=1.0, mask=mask)), a.steps
         if a.trace_iteration:                               # the kernels of `steps` eager iterations (+ the one-off weight packing of the first)
-            one(fused=True, **(dict(init_latents=x0, strength=1.0, mask=mask) if a.img2img else {}))
+            one(fused=True, **(dict(init_latents=x0, strength=1.0, mask=mask) if a.img2img else {}), **(dict(sampler=extra[0][0], sigmas=extra[0][1]) if extra else {}))
             torch.cuda.synchronize()
             return
         for fn in variants.values():                        # warm-up: buffers, packed weights, the capture
