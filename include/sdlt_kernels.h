@@ -20,7 +20,7 @@ extern "C" {
 
 const char* sdlt_last_error(void);
 int sdlt_abi_version(void);
-int sdlt_struct_size(int which); /* 0 gemm, 1 lora_grad_desc, 2 attn, 3 groupnorm, 4 shadow_desc, 5 gemm_batch_item, 6 dora_desc, 7 dora_wt_desc, 8 dora_grad_desc, 9 splitsum_desc ... 19 merge_desc, 20 sampler_params, 21 delta_desc, 22 sampler_img_params, 23 sampler_ms_params */
+int sdlt_struct_size(int which); /* 0 gemm, 1 lora_grad_desc, 2 attn, 3 groupnorm, 4 shadow_desc, 5 gemm_batch_item, 6 dora_desc, 7 dora_wt_desc, 8 dora_grad_desc, 9 splitsum_desc ... 19 merge_desc, 20 sampler_params, 21 delta_desc, 22 sampler_img_params, 23 sampler_ms_params, 24 sampler_sde_params */
 
 /* ------------------------------------------------------------------------------------------------
  * sdlt_gemm_bf16 : C = alpha*(X.W^T [+ X2.W2^T] [+ s*(X.Adown^T).Bup^T]) + bias + rowbias + R
@@ -594,6 +594,38 @@ typedef struct sdlt_sampler_ms_params {
   int32_t n, hw, table_rows, init;
 } sdlt_sampler_ms_params;
 int sdlt_sampler_step_ms(const sdlt_sampler_ms_params* p, void* stream);
+
+/* sdlt_sampler_step_sde : the same launch for the stochastic samplers - Euler ancestral and DPM-Solver++ (2M) SDE (k-diffusion's
+ * sample_euler_ancestral / sample_dpmpp_2m_sde, midpoint, s_noise = 1) - which add fresh Gaussian noise after every step:
+ *     x_{i+1} = a x + b D_i + c D_{i-1} + d z_i,   z_i ~ N(0, I)
+ * Table, counter, ticket, repack, timesteps, init and the step are sdlt_sampler_step_ms's, with column 7 of a step row = d_i
+ * (sampler.sde_coefficients / step_table_sde), and between steps 4 and 5 of that contract
+ *     4b. only if d != 0 (uniform over the launch):  xn = xn + d z
+ * - before the mask blend, so a kept pixel (m = 0) is still k exactly.  z is made in the launch (a replayed graph has no host work between two
+ * launches): one Philox4x32-10 call per pixel of an image gives its four channel normals,
+ *     key = (seeds[2 j], seeds[2 j + 1]) of image j ;  counter = (pixel index within the image, step row index i, 0, 0x53444531)
+ *     u_k = ((word_k >> 9) + 0.5) 2^-23   (exact in fp32, strictly inside (0, 1))
+ *     z_0 = r cos(2 pi u_1), z_1 = r sin(2 pi u_1), r = sqrt(-2 ln u_0) ;  z_2, z_3 likewise from (u_2, u_3)      (fp32: logf, sqrtf, sincospif(2 u))
+ * so image j's noise depends on its seed, the step and the pixel only.  seeds is read only where d != 0 (never by init, never by the step to
+ * sigma = 0); with d = 0 in every row the launch gives sdlt_sampler_step_ms's bits. */
+typedef struct sdlt_sampler_sde_params {
+  const float* eps;                  /* fp32 [2n * hw, 4]: UNet.forward's output (step only) */
+  float* x;                          /* fp32 [n, 4, hw] latent state, in place */
+  const float* x0;                   /* fp32 [n, 4, hw] or NULL: init (img2img), and every step with a mask */
+  const float* noise;                /* fp32 [n, 4, hw]: init, and every step with a mask */
+  const float* mask;                 /* fp32 [n, hw] or NULL */
+  float* dprev;                      /* fp32 [n, 4, hw]: the previous step's denoised value (step only) */
+  void* xin; int64_t ld_xin;         /* bf16 [2n * hw, ld_xin] NHWC model input */
+  float* timesteps;                  /* fp32 [2n] */
+  const float* table;                /* fp32 [table_rows, 8] */
+  int32_t* ctr;
+  int32_t n, hw, table_rows, init;
+  const uint32_t* seeds;             /* uint32 [n, 2]: (lo, hi) of each image's 64-bit seed (step only; 4-byte aligned) */
+} sdlt_sampler_sde_params;
+int sdlt_sampler_step_sde(const sdlt_sampler_sde_params* p, void* stream);
+
+/* sdlt_sampler_noise : out fp32 [n, 4, hw] = the z that sdlt_sampler_step_sde adds at step row `step` for these seeds (the same device function). */
+int sdlt_sampler_noise(const uint32_t* seeds, int32_t step, int32_t n, int32_t hw, float* out, void* stream);
 
 /* out[M,C] = a + b on strided 2-D bf16 views (gradient fan-in of the UNet skip connections). */
 int sdlt_add2d(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int32_t M, int32_t C, void* stream);

@@ -173,6 +173,10 @@ class SamplerMsParams(C.Structure):
                 ("ctr", vp), ("n", i32), ("hw", i32), ("table_rows", i32), ("init", i32)]
 
 
+class SamplerSdeParams(C.Structure):
+    _fields_ = SamplerMsParams._fields_ + [("seeds", vp)]
+
+
 class ShadowDesc(C.Structure):
     _fields_ = [("offset", i64), ("src_ld", i64), ("rows", i32), ("cols", i32), ("dst", vp), ("ld", i64), ("dstT", vp), ("ldT", i64)]
 
@@ -226,6 +230,8 @@ SYMBOLS = {
     "sdlt_sampler_step": (i32, [C.POINTER(SamplerParams), vp]),
     "sdlt_sampler_step_img": (i32, [C.POINTER(SamplerImgParams), vp]),
     "sdlt_sampler_step_ms": (i32, [C.POINTER(SamplerMsParams), vp]),
+    "sdlt_sampler_step_sde": (i32, [C.POINTER(SamplerSdeParams), vp]),
+    "sdlt_sampler_noise": (i32, [vp, i32, i32, i32, vp, vp]),
     "sdlt_strip_gemm": (i32, [C.POINTER(StripParams), vp]),
     "sdlt_strip_gemm_pair": (i32, [C.POINTER(StripParams), C.POINTER(StripParams), vp]),
     "sdlt_attn_pair_ok": (i32, [C.POINTER(AttnParams), C.POINTER(AttnParams)]),
@@ -287,7 +293,7 @@ def struct_sizes():
     return [(c.__name__, C.sizeof(c)) for c in mirrored] + [("sdlt_affine_grad_item", 8 * 8), ("sdlt_wgrad_tr_item", 3 * 8), ("LnFoldDesc", C.sizeof(LnFoldDesc)), ("ColsumFinishDesc", C.sizeof(ColsumFinishDesc)),
                                                                ("WskGemmParams", C.sizeof(WskGemmParams)), ("MergeDesc", C.sizeof(MergeDesc)), ("SamplerParams", C.sizeof(SamplerParams)),
                                                                ("DeltaDesc", C.sizeof(DeltaDesc)), ("SamplerImgParams", C.sizeof(SamplerImgParams)),
-                                                               ("SamplerMsParams", C.sizeof(SamplerMsParams))]
+                                                               ("SamplerMsParams", C.sizeof(SamplerMsParams)), ("SamplerSdeParams", C.sizeof(SamplerSdeParams))]
 
 
 def check(rc, what):

@@ -1289,6 +1289,49 @@ def sampler_step_ms(eps, x, xin, timesteps, table, ctr, *, dprev, x0=None, noise
     return x
 
 
+def sampler_step_sde(eps, x, xin, timesteps, table, ctr, *, dprev, seeds, x0=None, noise=None, mask=None, init=False):
+    """sdlt_sampler_step_sde: the step launch of the stochastic samplers (Euler ancestral, DPM-Solver++ (2M) SDE), x_next = a x + b D + c D_prev + d z
+    with a, b, c, d from the table row (fp32 [rows, 8], sampler.step_table_sde) and z ~ N(0, I) made in the launch from seeds (int32 [n, 2]: the
+    (lo, hi) words of each image's 64-bit seed), the step index and the pixel - ops.sampler_noise returns the same z.  seeds is read only where
+    d != 0.  The other operands as sampler_step_ms."""
+    lib = _lib.load()
+    n, c4, h, w = x.shape
+    _chk2(x, F32), _chk2(xin), _chk2(timesteps, F32), _chk2(table, F32), _chk2(ctr, torch.int32), _chk2(dprev, F32), _chk2(seeds, torch.int32)
+    assert c4 == 4 and x.is_contiguous() and table.is_contiguous() and table.dim() == 2 and table.shape[1] == 8 and ctr.numel() >= 2
+    assert xin.shape[0] == 2 * n * h * w and timesteps.numel() >= 2 * n and timesteps.is_contiguous()
+    assert dprev.shape == x.shape and dprev.is_contiguous() and dprev.data_ptr() != x.data_ptr()
+    assert tuple(seeds.shape) == (n, 2) and seeds.is_contiguous()
+    masked = mask is not None and not init
+    assert noise is not None or not (init or masked), "the init entry and a masked step read the noise"
+    assert x0 is not None or not masked, "a masked step reads x0"
+    for t in (x0, noise):
+        if t is not None:
+            _chk2(t, F32)
+            assert t.shape == x.shape and t.is_contiguous() and t.data_ptr() not in (x.data_ptr(), dprev.data_ptr()), "x0 and noise may alias neither x nor dprev"
+    if mask is not None:
+        _chk2(mask, F32)
+        assert tuple(mask.shape) == (n, 1, h, w) and mask.is_contiguous()
+    if not init:
+        _chk2(eps, F32)
+        assert eps.is_contiguous() and tuple(eps.shape) == (2 * n * h * w, 4)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    p = _lib.SamplerSdeParams(eps=None if init else eps.data_ptr(), x=x.data_ptr(), x0=ptr(x0), noise=ptr(noise), mask=None if init else ptr(mask),
+                              dprev=dprev.data_ptr(), xin=xin.data_ptr(), ld_xin=_ld(xin), timesteps=timesteps.data_ptr(), table=table.data_ptr(),
+                              ctr=ctr.data_ptr(), n=n, hw=h * w, table_rows=table.shape[0], init=int(init), seeds=seeds.data_ptr())
+    _lib.check(lib.sdlt_sampler_step_sde(C.byref(p), _stream()), "sdlt_sampler_step_sde")
+    return x
+
+
+def sampler_noise(seeds, step, out):
+    """sdlt_sampler_noise: out fp32 [n, 4, h, w] = the noise sdlt_sampler_step_sde adds at step row `step` for seeds int32 [n, 2]."""
+    lib = _lib.load()
+    n, c4, h, w = out.shape
+    _chk2(out, F32), _chk2(seeds, torch.int32)
+    assert c4 == 4 and out.is_contiguous() and tuple(seeds.shape) == (n, 2) and seeds.is_contiguous() and step >= 0
+    _lib.check(lib.sdlt_sampler_noise(seeds.data_ptr(), int(step), n, h * w, out.data_ptr(), _stream()), "sdlt_sampler_noise")
+    return out
+
+
 def masked_mse_fwd_bwd(pred, noise, noisy, mask, timesteps, alphas_cumprod, sums, loss_out, dpred, *, snr_gamma, v_prediction=False,
                        loss_scale=1.0):
     lib = _lib.load()

@@ -4,7 +4,8 @@ scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-squ
 
     python -m sd_lora_trainer_amd.render --checkpoint DIR --out DIR [--prompt TEXT ...] [--n-validation N] [--lora-scale X ...] [--size W H]
                                          [--steps N] [--guidance G] [--seed S] [--images-per-batch N] [--eager]
-                                         [--init-image PATH [--strength S] [--mask PATH]] [--sampler euler|dpmpp_2m] [--sigmas trailing|karras]
+                                         [--init-image PATH [--strength S] [--mask PATH]] [--sampler euler|dpmpp_2m|euler_a|dpmpp_2m_sde] [--eta F]
+                                         [--sigmas trailing|karras]
                                          [--unet F] [--text-encoder F] [--text-encoder-2 F] [--vae F] [--tokenizer DIR]
 
 DIR is a checkpoint directory of train(): training_args.json (the job's TrainingConfig), adapter_config.json + the kohya adapter file
@@ -21,6 +22,10 @@ keeps the black region of the init image: it is put back after every step, and c
 --sampler dpmpp_2m integrates with DPM-Solver++ (2M), the second-order multistep solver (sampler.DpmSolverPP2M; the step launch is then
 sdlt_sampler_step_ms), instead of first-order Euler: the same trajectory error in about half the steps.  --sigmas karras spaces the noise levels as
 Karras et al. 2022 (rho = 7) instead of by trailing timesteps; it combines with either sampler, and both combine with --init-image / --mask.
+
+--sampler euler_a / dpmpp_2m_sde are the stochastic samplers (Euler ancestral; the SDE form of DPM-Solver++ (2M)): fresh Gaussian noise after every
+step, made inside the step launch (sdlt_sampler_step_sde) from the image's seed, the step and the pixel, so the replayed graph needs no host work and
+the same --seed gives the same files.  --eta (default 1; 0 is the deterministic limit) scales that noise; it is an error with the other samplers.
 """
 import argparse
 import json
@@ -184,13 +189,14 @@ def encode_init(loaded, init_image, mask_image, size, latent_hw):
 
 @torch.no_grad()
 def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, guidance_scale=8.0, seed=None, images_per_batch=1, token_scale=None,
-           graph=True, n_validation=4, init_image=None, strength=None, mask_image=None, sampler="euler", sigmas="trailing"):
+           graph=True, n_validation=4, init_image=None, strength=None, mask_image=None, sampler="euler", sigmas="trailing", eta=None):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
     seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
     graph=False is the eager loop with the same fused kernel.  init_image (path or PIL image): every image starts from it (encode_init) at
     `strength` (default 0.6) instead of from pure noise, each with its own noise; mask_image: white regenerate, black keep.  sampler "euler" |
-    "dpmpp_2m", sigmas "trailing" | "karras": LatentSampler.sample's.  -> {scale: [paths]}."""
+    "dpmpp_2m" | "euler_a" | "dpmpp_2m_sde", sigmas "trailing" | "karras", eta (stochastic samplers only; default 1): LatentSampler.sample's; the
+    per-step noise of image i is keyed by seed + i, like its initial latents.  -> {scale: [paths]}."""
     from . import train as T
     from . import vae as _vae
     from PIL import Image
@@ -215,9 +221,18 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         raise ValueError(f"sampler must be one of {SM.SAMPLERS}, got {sampler!r}")
     if sigmas not in SM.SIGMAS:
         raise ValueError(f"sigmas must be one of {SM.SIGMAS}, got {sigmas!r}")
+    sde = sampler in SM.SDE_KINDS
+    if eta is not None and not sde:
+        raise ValueError(f"eta scales the per-step noise of {SM.SDE_KINDS}; sampler {sampler!r} adds none")
+    if sde:
+        eta = 1.0 if eta is None else eta
+        if not eta >= 0.0:
+            raise ValueError(f"eta must be >= 0, got {eta!r}")
     img_kw = {}
     if (sampler, sigmas) != ("euler", "trailing"):
         img_kw.update(sampler=sampler, sigmas=sigmas)
+    if sde:
+        img_kw.update(eta=eta)
     if init_image is None:
         if mask_image is not None:
             raise ValueError("mask_image needs init_image: the region to keep is taken from it")
@@ -229,7 +244,7 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         x0, mask = encode_init(loaded, init_image, mask_image, size, (h, w))
         img_kw.update(init_latents=x0, strength=strength, mask=mask)
     loaded.prepare(n, h, w)
-    smp, fused = stack.sampler, hasattr(stack.rt.ops, "sampler_step_ms" if sampler == "dpmpp_2m" else "sampler_step")
+    smp, fused = stack.sampler, hasattr(stack.rt.ops, "sampler_step_sde" if sde else "sampler_step_ms" if sampler == "dpmpp_2m" else "sampler_step")
     graph = graph and dev.type == "cuda"
     os.makedirs(out_dir, exist_ok=True)
     result = {}
@@ -241,12 +256,13 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             for s0 in range(0, len(prompts), n):
                 idx = [min(s0 + j, len(prompts) - 1) for j in range(n)]          # a short last batch repeats its last prompt
                 noise = torch.cat([torch.randn(1, 4, h, w, generator=torch.Generator(device=dev).manual_seed(seed + i), device=dev) for i in idx])
+                sd = (lambda js: dict(seeds=[seed + idx[j] for j in js])) if sde else (lambda js: {})
                 if fused:
                     lat = smp.sample([embeds[i] for i in idx] if n > 1 else embeds[idx[0]], h, w, steps=steps, guidance_scale=guidance_scale,
-                                     size=(size[1], size[0]), latents=noise, graph=graph, fused=True, n_images=n, **img_kw)
+                                     size=(size[1], size[0]), latents=noise, graph=graph, fused=True, n_images=n, **img_kw, **sd(range(n)))
                 else:                                                            # an op table without the fused kernel: the torch loop, image by image
                     lat = torch.cat([smp.sample(embeds[i], h, w, steps=steps, guidance_scale=guidance_scale, size=(size[1], size[0]),
-                                                latents=noise[j:j + 1], **img_kw) for j, i in enumerate(idx)])
+                                                latents=noise[j:j + 1], **img_kw, **sd([j])) for j, i in enumerate(idx)])
                 for j, i in enumerate(idx[: len(prompts) - s0]):
                     img = _vae.postprocess(stack.decoder.decode(lat[j:j + 1] / cfg["scaling_factor"]))[0].permute(1, 2, 0)
                     arr = (img.float().cpu().numpy() * 255).round().astype("uint8")
@@ -262,6 +278,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             meta.update(strength=strength, masked=mask_image is not None)
         if (sampler, sigmas) != ("euler", "trailing"):
             meta.update(sampler=sampler, sigmas=sigmas)
+        if sde:
+            meta.update(eta=eta)
         json.dump(meta, fh, indent=2)
     return result
 
@@ -282,7 +300,10 @@ def main(argv=None, runtime=None):
     ap.add_argument("--init-image", default=None, help="start from this picture instead of pure noise (img2img); resized to --size")
     ap.add_argument("--strength", type=float, default=None, help="how much of the schedule runs on the init image, in (0, 1]; default 0.6 with --init-image")
     ap.add_argument("--mask", default=None, help="inpainting mask for --init-image: white is regenerated, black is kept")
-    ap.add_argument("--sampler", choices=("euler", "dpmpp_2m"), default="euler", help="integrator: first-order Euler, or DPM-Solver++ (2M) (second order: about half the steps)")
+    ap.add_argument("--sampler", choices=("euler", "dpmpp_2m", "euler_a", "dpmpp_2m_sde"), default="euler",
+                    help="integrator: first-order Euler, DPM-Solver++ (2M) (second order: about half the steps), or their stochastic forms - Euler ancestral, "
+                    "DPM-Solver++ (2M) SDE - which add fresh noise after every step")
+    ap.add_argument("--eta", type=float, default=None, help="amount of per-step noise of --sampler euler_a / dpmpp_2m_sde, >= 0 (default 1; 0: none)")
     ap.add_argument("--sigmas", choices=("trailing", "karras"), default="trailing", help="noise levels: those of trailing timesteps, or Karras et al. (rho = 7)")
     ap.add_argument("--device", default="cuda:0")
     for flag, key, what in (("--unet", "path", "base UNet weights or synthetic:<version>"), ("--text-encoder", "text_encoder_path", "text encoder state dict"),
@@ -292,6 +313,10 @@ def main(argv=None, runtime=None):
     a = ap.parse_args(argv)
     if a.init_image is None and (a.mask is not None or a.strength is not None):
         ap.error("--mask and --strength need --init-image")
+    if a.eta is not None and a.sampler not in ("euler_a", "dpmpp_2m_sde"):
+        ap.error(f"--eta needs --sampler euler_a or dpmpp_2m_sde: --sampler {a.sampler} adds no noise")
+    if a.eta is not None and not a.eta >= 0.0:
+        ap.error(f"--eta must be >= 0, got {a.eta}")
     if a.strength is not None and not 0.0 < a.strength <= 1.0:
         ap.error(f"--strength must be in (0, 1], got {a.strength}")
     over = {k: getattr(a, k) for k in ("path", "text_encoder_path", "text_encoder_2_path", "vae_path", "tokenizer_path") if getattr(a, k)}
@@ -302,7 +327,7 @@ def main(argv=None, runtime=None):
     loaded = load_for_inference(a.checkpoint, pm, device=a.device, runtime=runtime)
     res = render(loaded, a.prompt, a.out, lora_scales=a.lora_scale, size=a.size, steps=a.steps, guidance_scale=a.guidance, seed=a.seed,
                  images_per_batch=a.images_per_batch, graph=not a.eager, n_validation=a.n_validation, init_image=a.init_image, strength=a.strength,
-                 mask_image=a.mask, sampler=a.sampler, sigmas=a.sigmas)
+                 mask_image=a.mask, sampler=a.sampler, sigmas=a.sigmas, eta=a.eta)
     for scale, paths in res.items():
         print(f"lora_scale {scale}: {len(paths)} image(s), {os.path.join(a.out, 'grid_scale' + _scale_tag(scale) + '.jpg')}")
     return res

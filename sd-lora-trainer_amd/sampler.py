@@ -146,7 +146,105 @@ class DpmSolverPP2M(EulerDiscrete):
         return xn
 
 
-SAMPLERS = ("euler", "dpmpp_2m")
+SDE_KINDS = ("euler_a", "dpmpp_2m_sde")
+
+
+def sde_coefficients(sigmas, kind, eta=1.0):
+    """The stochastic samplers on the grid `sigmas` [k + 1] -> fp64 [k, 4]: (a_i, b_i, c_i, d_i) of x_{i+1} = a x + b D_i + c D_{i-1} + d z_i with
+    z_i ~ N(0, I) fresh per step.  With s = sigma_i, sn = sigma_{i+1}:
+      "euler_a"       k-diffusion's sample_euler_ancestral: sigma_up = min(sn, eta sqrt(sn^2 (s^2 - sn^2) / s^2)), sigma_down = sqrt(sn^2 - sigma_up^2),
+                      a = sigma_down / s, b = 1 - a, c = 0, d = sigma_up
+      "dpmpp_2m_sde"  k-diffusion's sample_dpmpp_2m_sde (midpoint, s_noise = 1): h = ln s - ln sn, E = -expm1(-(1 + eta) h), a = (sn / s) e^(-eta h),
+                      b = E (1 + 1 / (2 r)), c = -E / (2 r), r = h_prev / h, d = sn sqrt(-expm1(-2 eta h)); row 0 and a step to sn = 0 are first
+                      order (b = E, c = 0 exactly)
+    A row with sn = 0 is (0, 1, 0, 0): x = D, no noise.  eta = 0 is a branch of its own, not a rounding: ms_coefficients' rows with d = 0, and Euler's
+    rows (sn / s, 1 - sn / s, 0, 0)."""
+    if kind not in SDE_KINDS:
+        raise ValueError(f"kind must be one of {SDE_KINDS}, got {kind!r}")
+    if not eta >= 0.0:
+        raise ValueError(f"eta must be >= 0, got {eta!r}")
+    sig = np.asarray(sigmas, dtype=np.float64)
+    k = len(sig) - 1
+    out = np.zeros((k, 4), dtype=np.float64)
+    if eta == 0.0:
+        if kind == "dpmpp_2m_sde":
+            out[:, :3] = ms_coefficients(sig)
+        else:
+            out[:, 0] = sig[1:] / sig[:-1]
+            out[:, 1] = 1.0 - out[:, 0]
+        return out
+    h_prev = None
+    for i in range(k):
+        s, sn = sig[i], sig[i + 1]
+        if sn == 0.0:
+            out[i] = (0.0, 1.0, 0.0, 0.0)
+            h_prev = None
+        elif kind == "euler_a":
+            up = min(sn, eta * np.sqrt(sn * sn * (s * s - sn * sn) / (s * s)))
+            a = np.sqrt(sn * sn - up * up) / s
+            out[i] = (a, 1.0 - a, 0.0, up)
+        else:
+            h = np.log(s) - np.log(sn)
+            E = -np.expm1(-(1.0 + eta) * h)
+            b, c = E, 0.0
+            if h_prev is not None:
+                r = h_prev / h
+                b, c = E * (1.0 + 1.0 / (2.0 * r)), -E / (2.0 * r)
+            out[i] = ((sn / s) * np.exp(-eta * h), b, c, sn * np.sqrt(-np.expm1(-2.0 * eta * h)))
+            h_prev = h
+    return out
+
+
+class _Stochastic(DpmSolverPP2M):
+    """A stochastic sampler on EulerDiscrete's schedules, in DpmSolverPP2M's shape: `step(model_out, i, x, z)` takes the step's noise z ~ N(0, I)
+    (ignored on a row with d = 0).  On fp32 tensors model input, denoised value and update are the step kernel's contract (sdlt_sampler_step_sde:
+    the table's fp32 factors, one rounding per operation, in its order), so the torch loop and the fused path agree bit for bit."""
+    KIND = None
+
+    def __init__(self, *args, eta=1.0, **kw):
+        super().__init__(*args, **kw)
+        self.eta = eta
+
+    def _begin(self):
+        self.coeffs = sde_coefficients(self.sigmas, self.KIND, self.eta)
+        self._dprev = None
+
+    def scale_model_input(self, x, i):
+        return x * float(1.0 / np.sqrt(np.float64(self.sigmas[i]) ** 2 + 1.0))
+
+    def denoised(self, model_out, i, x):
+        if self.prediction_type == "epsilon":
+            return x - model_out * float(self.sigmas[i])
+        f = np.float32 if x.dtype == torch.float32 else np.float64      # the scalars in the tensors' precision; a full-tensor divisor: IEEE division
+        s = f(self.sigmas[i])
+        q = s * s + f(1.0)
+        return model_out * float(-s / np.sqrt(q)) + x / torch.full_like(x, float(q))
+
+    def step(self, model_out, i, x, z=None):
+        if i == 0:
+            self._dprev = None
+        a, b, c, d = (float(v) for v in self.coeffs[i])
+        D = self.denoised(model_out, i, x)
+        xn = x * a + D * b
+        if c != 0.0:
+            xn = xn + self._dprev * c
+        if d != 0.0:
+            xn = xn + z * d
+        self._dprev = D
+        return xn
+
+
+class EulerAncestral(_Stochastic):
+    """k-diffusion's sample_euler_ancestral (sde_coefficients)."""
+    KIND = "euler_a"
+
+
+class DpmSolverPP2MSDE(_Stochastic):
+    """k-diffusion's sample_dpmpp_2m_sde, midpoint solver, s_noise = 1 (sde_coefficients)."""
+    KIND = "dpmpp_2m_sde"
+
+
+SAMPLERS = ("euler", "dpmpp_2m", "euler_a", "dpmpp_2m_sde")
 SIGMAS = ("trailing", "karras")
 
 TABLE_ROWS = 2 + 1000      # rows of the device step table: two header rows + at most one step per training timestep
@@ -198,6 +296,28 @@ def step_table_ms(sched, guidance_scale):
     return tab
 
 
+def step_table_sde(sched, guidance_scale):
+    """The device table of ops.sampler_step_sde for an EulerAncestral / DpmSolverPP2MSDE whose set_timesteps(n[, start]) has run: step_table_ms with
+    sde_coefficients in columns 4..7 (column 7 = d, zero in step_table_ms: the 8-float row is unchanged), rounded once."""
+    base = step_table_img(sched, guidance_scale)
+    tab = torch.zeros(base.shape[0], 8, dtype=torch.float32)
+    tab[:, :4] = base
+    tab[2:, 4:8] = torch.from_numpy(sched.coeffs.astype(np.float32))
+    return tab
+
+
+def seed_words(seeds, n, generator=None, device="cpu"):
+    """-> int32 [n, 2] on `device`: (lo, hi) 32-bit words of each image's 64-bit seed (ops.sampler_step_sde reads them as unsigned).  seeds: n Python
+    ints, or None: drawn from `generator`."""
+    if seeds is None:
+        return torch.randint(-2 ** 31, 2 ** 31, (n, 2), generator=generator, device=device, dtype=torch.int64).to(torch.int32)
+    seeds = list(seeds)
+    if len(seeds) != n or not all(isinstance(v, int) and not isinstance(v, bool) for v in seeds):
+        raise ValueError(f"seeds must be {n} int(s), one per image, got {seeds!r}")
+    words = np.array([[v & 0xFFFFFFFF, (v >> 32) & 0xFFFFFFFF] for v in seeds], dtype=np.uint32)
+    return torch.from_numpy(words.view(np.int32)).to(device)
+
+
 class LatentSampler:
     """`pipe(prompt_embeds=c, negative_prompt_embeds=uc, ..., num_inference_steps, guidance_scale, generator)` of the
     reference's render loop, up to the latents.  `unet` is an inference instance built for batch 2 (negative | positive, the
@@ -209,6 +329,7 @@ class LatentSampler:
         self.n = rt.B // 2                 # images sampled together (fused / graph path); image j = rows 2j (negative), 2j + 1 (positive)
         self.sched = EulerDiscrete(prediction_type=prediction_type)
         self.sched_ms = DpmSolverPP2M(prediction_type=prediction_type)
+        self.sched_sde = dict(euler_a=EulerAncestral(prediction_type=prediction_type), dpmpp_2m_sde=DpmSolverPP2MSDE(prediction_type=prediction_type))
         cfg = unet.cfg
         self.ctx = rt.zeros(rt.B * CTX_PAD, cfg["cross_dim"])
         self.pooled = rt.zeros(rt.B, cfg["proj_class_in"] - 6 * cfg["addition_time_embed_dim"]) if cfg["addition"] else None
@@ -216,6 +337,7 @@ class LatentSampler:
         self._graphs = {}                  # (h, w, n, adapter scale in effect, DoRA) -> hipGraph of one denoising iteration
         self._img_graphs = {}              # the same key + (masked,) -> hipGraph of one iteration whose step launch is ops.sampler_step_img
         self._ms_graphs = {}               # the same key + (masked, "multistep") -> hipGraph of one iteration whose step launch is ops.sampler_step_ms
+        self._sde_graphs = {}              # the same key + (masked, "sde") -> hipGraph of one iteration whose step launch is ops.sampler_step_sde
 
     def set_lora_scale(self, lora_scale, train_scale=None):
         """set_adapter_scales (checkpoint.py:31-55): every adapter's contribution is multiplied by lora_scale."""
@@ -227,7 +349,7 @@ class LatentSampler:
 
     @torch.no_grad()
     def sample(self, embeds, h, w, *, steps=25, guidance_scale=8.0, generator=None, size=None, latents=None, graph=False, fused=False, n_images=1,
-               init_latents=None, strength=1.0, mask=None, sampler="euler", sigmas="trailing"):
+               init_latents=None, strength=1.0, mask=None, sampler="euler", sigmas="trailing", eta=1.0, seeds=None):
         """embeds = (c [1,77,D], uc [1,77,D], pc [1,P] | None, puc | None); h, w latent size.  Returns latents [1,4,h,w] fp32
         (still multiplied by the VAE scaling factor, as the pipeline holds them before `vae.decode(latents / scaling_factor)`).
         fused: guidance, the Euler update and the next model input are ONE kernel between two forwards (ops.sampler_step) instead of torch
@@ -238,17 +360,27 @@ class LatentSampler:
         [0, 1]: 1 regenerate, 0 keep - the kept region is re-injected after every step and equals init_latents exactly at the end.  strength 1 without a
         mask is txt2img from the noise; a mask of ones is no mask.
         sampler: "euler" | "dpmpp_2m" (DpmSolverPP2M: second-order multistep; fused / graph: the step launch is ops.sampler_step_ms); sigmas: "trailing" |
-        "karras" (EulerDiscrete.set_timesteps), with either sampler."""
+        "karras" (EulerDiscrete.set_timesteps), with either sampler.
+        sampler "euler_a" | "dpmpp_2m_sde" (EulerAncestral, DpmSolverPP2MSDE): fresh noise after every step, its amount set by eta >= 0 (0: the
+        deterministic limit), drawn on the device from one 64-bit seed per image - seeds: n_images ints, None: drawn from `generator` after the initial
+        latents - the step index and the pixel, so an image's noise does not depend on the batch it is sampled in.  The torch loop takes it from
+        ops.sampler_noise, fused / graph make it inside ops.sampler_step_sde: the three paths give the same bits."""
         if sampler not in SAMPLERS:
             raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
+        if sampler in SDE_KINDS and not eta >= 0.0:       # (the deterministic samplers do not read eta)
+            raise ValueError(f"eta must be >= 0, got {eta!r}")
         if sigmas not in SIGMAS:
             raise ValueError(f"sigmas must be one of {SIGMAS}, got {sigmas!r}")
         img = self._img_args(init_latents, strength, mask, steps, h, w, n_images)
         if graph or fused:
-            return self._sample_fused(embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img, sampler, sigmas)
+            return self._sample_fused(embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img, sampler, sigmas, eta, seeds)
         assert n_images == 1 and self.rt.B == 2, "the torch loop samples one image on a batch-2 runtime; several images together: fused=True or graph=True"
         rt, u, cfg = self.rt, self.unet, self.unet.cfg
         dev = rt.device
+        sde = sampler in SDE_KINDS
+        if sde and not hasattr(rt.ops, "sampler_noise"):
+            raise NotImplementedError(f"this op table has no sampler_step_sde kernel: sample(sampler={sampler!r}) takes its per-step noise from that kernel's "
+                                      "generator (ops.sampler_noise), in the torch loop too")
         c, uc, pc, puc = (tuple(embeds) + (None, None))[:4]
         cv = self.ctx.view(2, CTX_PAD, -1)
         cv[0, :77].copy_(uc[0])
@@ -262,6 +394,10 @@ class LatentSampler:
         x0, m, start = img if img is not None else (None, None, 0)
         if sampler == "euler" and sigmas == "trailing":
             s = self.sched.set_timesteps(steps, start) if img is not None else self.sched.set_timesteps(steps)
+        elif sde:
+            s = self.sched_sde[sampler]
+            s.eta = eta
+            s.set_timesteps(steps, start, sigmas)
         else:
             s = (self.sched_ms if sampler == "dpmpp_2m" else self.sched).set_timesteps(steps, start, sigmas)
         x = latents if latents is not None else torch.randn(1, 4, h, w, generator=generator, device=dev, dtype=F32)
@@ -270,6 +406,8 @@ class LatentSampler:
         else:
             noise = x.to(dev, F32)
             x = x0 + noise * float(s.sigmas[0])
+        if sde:
+            words, z = seed_words(seeds, 1, generator, dev), rt.zeros(1, 4, h, w, dtype=F32)
         x64 = rt.zeros(2 * h * w, 64)
         for i, t in enumerate(s.timesteps):
             xin = s.scale_model_input(x, i)
@@ -277,7 +415,10 @@ class LatentSampler:
             tf = torch.full((2,), float(t), device=dev, dtype=F32)
             eps = u.forward(x64, tf, self.ctx, self.pooled, tid, B=2, H=h, W=w).view(2, h, w, 4).permute(0, 3, 1, 2)
             e = eps[0:1] + guidance_scale * (eps[1:2] - eps[0:1])
-            x = s.step(e, i, x)
+            if sde:                                # the kernel's own noise of step i (not drawn where the row adds none)
+                x = s.step(e, i, x, rt.ops.sampler_noise(words, i, z) if s.coeffs[i, 3] != 0.0 else None)
+            else:
+                x = s.step(e, i, x)
             if m is not None:                      # the known region, noised to the sigma this step arrived at (0 after the last: init_latents itself)
                 k = x0 + noise * float(s.sigmas[i + 1])
                 x = k + m * (x - k)
@@ -335,12 +476,17 @@ class LatentSampler:
             sh["img"] = dict(x0=rt.zeros(n, 4, h, w, dtype=F32), noise=rt.zeros(n, 4, h, w, dtype=F32), mask=rt.zeros(n, 1, h, w, dtype=F32))
         return sh["img"]
 
-    def _iteration(self, st, sh, h, w, masked=None, ms=False):
+    def _iteration(self, st, sh, h, w, masked=None, ms=False, sde=False):
         """masked None: txt2img; False / True: from init latents, without / with the mask (sh["img"] holds them).  ms: the DPM-Solver++ (2M) launch;
-        without a mask it reads neither the init latents nor the noise, whatever the trajectory started from."""
+        without a mask it reads neither the init latents nor the noise, whatever the trajectory started from.  sde: the stochastic samplers' launch,
+        the same operands plus the seeds."""
         u = self.unet
         eps = u.forward(sh["x64"], st["tf"], self.ctx, self.pooled, st["tid"] if u.cfg["addition"] else None, B=2 * self.n, H=h, W=w)
-        if ms:
+        if sde:
+            im = sh["img"] if masked else dict(x0=None, noise=None, mask=None)
+            self.rt.ops.sampler_step_sde(eps, sh["x"], sh["x64"], st["tf"], st["table_ms"], st["ctr"], dprev=sh["dprev"], seeds=st["seeds"], x0=im["x0"],
+                                         noise=im["noise"], mask=im["mask"])
+        elif ms:
             im = sh["img"] if masked else dict(x0=None, noise=None, mask=None)
             self.rt.ops.sampler_step_ms(eps, sh["x"], sh["x64"], st["tf"], st["table_ms"], st["ctr"], dprev=sh["dprev"], x0=im["x0"], noise=im["noise"], mask=im["mask"])
         elif masked is None:
@@ -350,17 +496,21 @@ class LatentSampler:
             self.rt.ops.sampler_step_img(eps, sh["x"], sh["x64"], st["tf"], st["table"], st["ctr"], x0=im["x0"], noise=im["noise"],
                                          mask=im["mask"] if masked else None)
 
-    def _graph(self, st, sh, h, w, masked=None, ms=False):
+    def _graph(self, st, sh, h, w, masked=None, ms=False, sde=False):
         """The hipGraph of one iteration for this shape and the adapter scale in effect.  The scale is a launch argument of every adapted GEMM
         (baked by capture), hence part of the key; adapters, DoRA factors, token rows, conditioning, table and counter are device memory.
         From init latents (masked False / True) the step launch is another kernel: those captures live in a dict of their own, keyed by the mask
         pointer's presence as well; strength and step count are in the table, init latents, noise and mask in persistent buffers.
         ms: the captures of the multistep launch, in a third dict, keyed by the mask's presence too (without one, txt2img and img2img issue the same
-        launch and share a capture); step count, strength, schedule kind and coefficients are in its table, the previous denoised value in sh["dprev"]."""
+        launch and share a capture); step count, strength, schedule kind and coefficients are in its table, the previous denoised value in sh["dprev"].
+        sde: the captures of the stochastic samplers' launch, in a fourth dict, keyed like the third; which of the two samplers, eta, step count and
+        strength are in the table and the seeds in a persistent buffer, so one capture serves all of them."""
         a = self.unet.arena
         key = (h, w, self.n, None if a is None else float(a.scale), bool(a is not None and a.dora))
         graphs = self._graphs
-        if ms:
+        if sde:
+            key, graphs = key + (bool(masked), "sde"), self._sde_graphs
+        elif ms:
             key, graphs = key + (bool(masked), "multistep"), self._ms_graphs
         elif masked is not None:
             key, graphs = key + (bool(masked),), self._img_graphs
@@ -375,11 +525,11 @@ class LatentSampler:
         side.wait_stream(torch.cuda.current_stream())
         seq = None
         with torch.cuda.stream(side):
-            self._iteration(st, sh, h, w, masked, ms)     # eager warm-up: every persistent buffer and packed-weight copy exists before the capture
+            self._iteration(st, sh, h, w, masked, ms, sde)     # eager warm-up: every persistent buffer and packed-weight copy exists before the capture
             if prefetch:                                  # next-weight hints of the wave-split-K products, recorded from one eager pass (step.TrainStep.capture)
                 ops.pf_record_begin()
                 try:
-                    self._iteration(st, sh, h, w, masked, ms)
+                    self._iteration(st, sh, h, w, masked, ms, sde)
                 finally:
                     seq = ops.pf_record_end()
         torch.cuda.current_stream().wait_stream(side)
@@ -388,16 +538,19 @@ class LatentSampler:
             if seq:
                 ops.pf_replay_begin(seq)
             try:
-                self._iteration(st, sh, h, w, masked, ms)
+                self._iteration(st, sh, h, w, masked, ms, sde)
             finally:
                 if seq:
                     ops.pf_replay_end()
         graphs[key] = g
         return g
 
-    def _sample_fused(self, embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img=None, sampler="euler", sigmas="trailing"):
+    def _sample_fused(self, embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img=None, sampler="euler", sigmas="trailing",
+                      eta=1.0, seeds=None):
         rt, cfg, n = self.rt, self.unet.cfg, self.n
-        ms = sampler == "dpmpp_2m"
+        ms, sde = sampler == "dpmpp_2m", sampler in SDE_KINDS
+        if sde and not hasattr(rt.ops, "sampler_step_sde"):
+            raise NotImplementedError(f"this op table has no sampler_step_sde kernel: sample(sampler={sampler!r}) draws its per-step noise inside that launch")
         if ms and not hasattr(rt.ops, "sampler_step_ms"):
             raise NotImplementedError("this op table has no sampler_step_ms kernel: sample(sampler='dpmpp_2m', graph=False, fused=False) is the torch loop")
         if not hasattr(rt.ops, "sampler_step"):
@@ -421,13 +574,20 @@ class LatentSampler:
         if cfg["addition"]:
             H, W = size if size is not None else (8 * h, 8 * w)
             st["tid"].copy_(torch.tensor([float(H), float(W), 0.0, 0.0, float(H), float(W)] * (2 * n)))
-        if ms:
+        if ms or sde:                                     # (the two share the 8-column table and the history buffer: both are rewritten per trajectory)
             if "table_ms" not in st:
                 st["table_ms"] = rt.zeros(TABLE_ROWS, 8, dtype=F32)
             if "dprev" not in sh:
                 sh["dprev"] = rt.zeros(n, 4, h, w, dtype=F32)
             start = 0 if img is None else img[2]
-            tab = step_table_ms(self.sched_ms.set_timesteps(steps, start, sigmas), guidance_scale)
+            if sde:
+                if "seeds" not in st:
+                    st["seeds"] = torch.zeros(n, 2, dtype=torch.int32, device=rt.device)
+                sch = self.sched_sde[sampler]
+                sch.eta = eta
+                tab = step_table_sde(sch.set_timesteps(steps, start, sigmas), guidance_scale)
+            else:
+                tab = step_table_ms(self.sched_ms.set_timesteps(steps, start, sigmas), guidance_scale)
             steps -= start
             st["table_ms"][: tab.shape[0]].copy_(tab)
         else:
@@ -442,9 +602,11 @@ class LatentSampler:
         noise = latents if latents is not None else torch.randn(n, 4, h, w, generator=generator, device=dev, dtype=F32)
         noise = noise.to(dev, F32).contiguous()
         assert tuple(noise.shape) == (n, 4, h, w)
+        if sde:                                           # after the initial latents, as in the torch loop; a captured launch holds the buffer
+            st["seeds"].copy_(seed_words(seeds, n, generator, dev))
         x, x64 = sh["x"], sh["x64"]
         masked = None
-        if ms:
+        if ms or sde:
             x0 = None
             if img is not None:
                 im, masked = self._img_state(sh, h, w), img[1] is not None
@@ -453,7 +615,10 @@ class LatentSampler:
                 if masked:
                     im["mask"].copy_(img[1])
                 x0, noise = im["x0"], im["noise"]
-            init = lambda: rt.ops.sampler_step_ms(None, x, x64, st["tf"], st["table_ms"], st["ctr"], dprev=sh["dprev"], x0=x0, noise=noise, init=True)  # noqa: E731
+            if sde:
+                init = lambda: rt.ops.sampler_step_sde(None, x, x64, st["tf"], st["table_ms"], st["ctr"], dprev=sh["dprev"], seeds=st["seeds"], x0=x0, noise=noise, init=True)  # noqa: E731
+            else:
+                init = lambda: rt.ops.sampler_step_ms(None, x, x64, st["tf"], st["table_ms"], st["ctr"], dprev=sh["dprev"], x0=x0, noise=noise, init=True)  # noqa: E731
         elif img is None:
             init = lambda: rt.ops.sampler_step(None, x, x64, st["tf"], st["table"], st["ctr"], noise=noise)  # noqa: E731
         else:
@@ -467,13 +632,13 @@ class LatentSampler:
             g = None
             if graph:
                 init()                                    # (a defined state for the warm-up passes)
-                g = self._graph(st, sh, h, w, masked, ms)
+                g = self._graph(st, sh, h, w, masked, ms, sde)
             init()
             for _ in range(steps):                        # no host read in here: the step index lives in ctr, its scalars in the table
                 if g is not None:
                     g.replay()
                 else:
-                    self._iteration(st, sh, h, w, masked, ms)
+                    self._iteration(st, sh, h, w, masked, ms, sde)
         return x.clone()
 
 

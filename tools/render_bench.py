@@ -5,7 +5,8 @@ n = 1 and n = 2 images per batch ((a) samples the n images one after the other o
 whose step launch is sdlt_sampler_step_img: (d) from init latents at strength 0.6 (15 of the 25 iterations run, no mask) and (e) masked inpainting at
 strength 1 (all 25, the mask blend in every one); their time is divided by the iterations that ran.  --sampler / --sigmas add the replayed graph of
 each named combination other than the default one - e.g. `--sampler dpmpp_2m` times (f) the iteration whose step launch is sdlt_sampler_step_ms
-against (c) - and, with --img2img, its masked variant (`inp`).
+against (c) - and, with --img2img, its masked variant (`inp`).  The stochastic samplers (`euler_a`, `dpmpp_2m_sde`: step launch sdlt_sampler_step_sde)
+are timed at eta = 1 with fixed seeds.
 
     python tools/render_bench.py [--out FILE] [--rounds 5] [--version sdxl] [--latent 128] [--n 1 2] [--img2img] [--sampler dpmpp_2m] [--sigmas karras]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/render_bench.py --trace-iteration --n 1      # kernel time of one iteration: sum the stats
@@ -69,7 +70,7 @@ def main():
     ap.add_argument("--trace-iteration", action="store_true", help="run the eager fused loop once and exit (under rocprofv3 --kernel-trace --stats: kernel time per iteration = total / steps, without the one-off pack kernels)")
     ap.add_argument("--img2img", action="store_true", help="also time the graph sampler from init latents: strength 0.6 without a mask, strength 1 with a mask "
                     "(with --trace-iteration: run the masked eager loop instead of the txt2img one)")
-    ap.add_argument("--sampler", nargs="+", choices=("euler", "dpmpp_2m"), default=["euler"], help="also time the graph sampler with these integrators")
+    ap.add_argument("--sampler", nargs="+", choices=("euler", "dpmpp_2m", "euler_a", "dpmpp_2m_sde"), default=["euler"], help="also time the graph sampler with these integrators")
     ap.add_argument("--sigmas", nargs="+", choices=("trailing", "karras"), default=["trailing"], help="... on these noise levels")
     a = ap.parse_args()
     h = a.latent
@@ -97,13 +98,14 @@ def main():
             variants["e graph, inpaint 1.0"] = lambda: one(graph=True, init_latents=x0, strength=1.0, mask=mask)
             ran["d graph, init latents 0.6"], ran["e graph, inpaint 1.0"] = min(int(a.steps * 0.6), a.steps), a.steps
         extra = [(s, k) for s in a.sampler for k in a.sigmas if (s, k) != ("euler", "trailing")]
+        sd = lambda s: dict(seeds=list(range(n))) if s in ("euler_a", "dpmpp_2m_sde") else {}  # noqa: E731
         for tag, (s, k) in zip("fghij", extra):
             name = f"{tag} graph, {s} {k}"
-            variants[name], ran[name] = (lambda s=s, k=k: one(graph=True, sampler=s, sigmas=k)), a.steps
+            variants[name], ran[name] = (lambda s=s, k=k: one(graph=True, sampler=s, sigmas=k, **sd(s))), a.steps
             if a.img2img:
-                variants[name + " inp"], ran[name + " inp"] = (lambda s=s, k=k: one(graph=True, sampler=s, sigmas=k, init_latents=x0, strength=1.0, mask=mask)), a.steps
+                variants[name + " inp"], ran[name + " inp"] = (lambda s=s, k=k: one(graph=True, sampler=s, sigmas=k, init_latents=x0, strength=1.0, mask=mask, **sd(s))), a.steps
         if a.trace_iteration:                               # the kernels of `steps` eager iterations (+ the one-off weight packing of the first)
-            one(fused=True, **(dict(init_latents=x0, strength=1.0, mask=mask) if a.img2img else {}), **(dict(sampler=extra[0][0], sigmas=extra[0][1]) if extra else {}))
+            one(fused=True, **(dict(init_latents=x0, strength=1.0, mask=mask) if a.img2img else {}), **(dict(sampler=extra[0][0], sigmas=extra[0][1], **sd(extra[0][0])) if extra else {}))
             torch.cuda.synchronize()
             return
         for fn in variants.values():                        # warm-up: buffers, packed weights, the capture
