@@ -20,7 +20,7 @@ extern "C" {
 
 const char* sdlt_last_error(void);
 int sdlt_abi_version(void);
-int sdlt_struct_size(int which); /* 0 gemm, 1 lora_grad_desc, 2 attn, 3 groupnorm, 4 shadow_desc, 5 gemm_batch_item, 6 dora_desc, 7 dora_wt_desc, 8 dora_grad_desc, 9 splitsum_desc ... 19 merge_desc, 20 sampler_params, 21 delta_desc, 22 sampler_img_params, 23 sampler_ms_params, 24 sampler_sde_params */
+int sdlt_struct_size(int which); /* 0 gemm, 1 lora_grad_desc, 2 attn, 3 groupnorm, 4 shadow_desc, 5 gemm_batch_item, 6 dora_desc, 7 dora_wt_desc, 8 dora_grad_desc, 9 splitsum_desc ... 19 merge_desc, 20 sampler_params, 21 delta_desc, 22 sampler_img_params, 23 sampler_ms_params, 24 sampler_sde_params, 25 guidance_params */
 
 /* ------------------------------------------------------------------------------------------------
  * sdlt_gemm_bf16 : C = alpha*(X.W^T [+ X2.W2^T] [+ s*(X.Adown^T).Bup^T]) + bias + rowbias + R
@@ -626,6 +626,28 @@ int sdlt_sampler_step_sde(const sdlt_sampler_sde_params* p, void* stream);
 
 /* sdlt_sampler_noise : out fp32 [n, 4, hw] = the z that sdlt_sampler_step_sde adds at step row `step` for these seeds (the same device function). */
 int sdlt_sampler_noise(const uint32_t* seeds, int32_t step, int32_t n, int32_t hw, float* out, void* stream);
+
+/* sdlt_guidance : the guidance pre-pass, issued between the UNet forward and whichever of the four step launches follows.  It rewrites eps in
+ * place so that both row blocks of image j (rows 2j negative, 2j + 1 positive) hold the final prediction e; the step launch then forms
+ * e + g (e - e) = e (exact for finite values, the sign of a zero apart) whatever guidance scale its own table holds.
+ * gtab fp32 [gtab_rows, 4]: row 0 = (k, 0, 0, 0), row 1 + i = (g_i, phi_i, 0, 0), k <= gtab_rows - 1.  ctr: the sampler's counter; ctr[0] is READ
+ * as the step row i (clamped to 0 .. k - 1) and never written - the step launch advances and wraps it.  Per image, fp32, one rounding per
+ * operation, in the order written:
+ *     g_i == 1 and phi_i == 0:   e = e_pos                                 (guidance off)
+ *     otherwise                  e_c = e_neg + g_i (e_pos - e_neg)
+ *     phi_i == 0:                e = e_c                                   (no reduction is run)
+ *     otherwise                  s_pos, s_c = unbiased standard deviations (divisor 4 hw - 1, about the mean) of e_pos and e_c over the 4 hw values
+ *                                r = s_pos / s_c, and r = 1 where s_c == 0 (this library's choice: the published function divides by zero there)
+ *                                e = phi_i (e_c r) + (1 - phi_i) e_c       (rescale_noise_cfg of Lin et al. 2024, section 3.4)
+ * One workgroup per image and a fixed summation order: image j's result depends on neither n nor j and repeats bit for bit.  eps 16-byte
+ * aligned.  Null pointers, n < 1, hw < 1 or gtab_rows < 2 return -1 (shape error) and launch nothing. */
+typedef struct sdlt_guidance_params {
+  float* eps;                        /* fp32 [2n * hw, 4]: UNet.forward's output, rewritten in place */
+  const float* gtab;                 /* fp32 [gtab_rows, 4] */
+  const int32_t* ctr;                /* int32 [>= 1]: ctr[0] = step row, read only */
+  int32_t n, hw, gtab_rows, pad_;
+} sdlt_guidance_params;
+int sdlt_guidance(const sdlt_guidance_params* p, void* stream);
 
 /* out[M,C] = a + b on strided 2-D bf16 views (gradient fan-in of the UNet skip connections). */
 int sdlt_add2d(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int32_t M, int32_t C, void* stream);

@@ -177,6 +177,10 @@ class SamplerSdeParams(C.Structure):
     _fields_ = SamplerMsParams._fields_ + [("seeds", vp)]
 
 
+class GuidanceParams(C.Structure):
+    _fields_ = [("eps", vp), ("gtab", vp), ("ctr", vp), ("n", i32), ("hw", i32), ("gtab_rows", i32), ("pad_", i32)]
+
+
 class ShadowDesc(C.Structure):
     _fields_ = [("offset", i64), ("src_ld", i64), ("rows", i32), ("cols", i32), ("dst", vp), ("ld", i64), ("dstT", vp), ("ldT", i64)]
 
@@ -232,6 +236,7 @@ SYMBOLS = {
     "sdlt_sampler_step_ms": (i32, [C.POINTER(SamplerMsParams), vp]),
     "sdlt_sampler_step_sde": (i32, [C.POINTER(SamplerSdeParams), vp]),
     "sdlt_sampler_noise": (i32, [vp, i32, i32, i32, vp, vp]),
+    "sdlt_guidance": (i32, [C.POINTER(GuidanceParams), vp]),
     "sdlt_strip_gemm": (i32, [C.POINTER(StripParams), vp]),
     "sdlt_strip_gemm_pair": (i32, [C.POINTER(StripParams), C.POINTER(StripParams), vp]),
     "sdlt_attn_pair_ok": (i32, [C.POINTER(AttnParams), C.POINTER(AttnParams)]),
@@ -293,7 +298,8 @@ def struct_sizes():
     return [(c.__name__, C.sizeof(c)) for c in mirrored] + [("sdlt_affine_grad_item", 8 * 8), ("sdlt_wgrad_tr_item", 3 * 8), ("LnFoldDesc", C.sizeof(LnFoldDesc)), ("ColsumFinishDesc", C.sizeof(ColsumFinishDesc)),
                                                                ("WskGemmParams", C.sizeof(WskGemmParams)), ("MergeDesc", C.sizeof(MergeDesc)), ("SamplerParams", C.sizeof(SamplerParams)),
                                                                ("DeltaDesc", C.sizeof(DeltaDesc)), ("SamplerImgParams", C.sizeof(SamplerImgParams)),
-                                                               ("SamplerMsParams", C.sizeof(SamplerMsParams)), ("SamplerSdeParams", C.sizeof(SamplerSdeParams))]
+                                                               ("SamplerMsParams", C.sizeof(SamplerMsParams)), ("SamplerSdeParams", C.sizeof(SamplerSdeParams)),
+                                                               ("GuidanceParams", C.sizeof(GuidanceParams))]
 
 
 def check(rc, what):

@@ -45,6 +45,7 @@ extern "C" int sdlt_struct_size(int which) {
     case 22: return (int)sizeof(sdlt_sampler_img_params);
     case 23: return (int)sizeof(sdlt_sampler_ms_params);
     case 24: return (int)sizeof(sdlt_sampler_sde_params);
+    case 25: return (int)sizeof(sdlt_guidance_params);
   }
   return -1;
 }

@@ -1332,6 +1332,20 @@ def sampler_noise(seeds, step, out):
     return out
 
 
+def guidance(eps, gtab, ctr, n):
+    """sdlt_guidance: the guidance pre-pass between UNet.forward and a step launch.  eps fp32 [2n hw, 4] is rewritten in place: both row blocks of
+    image j (rows 2j negative, 2j + 1 positive) then hold e = the guided prediction of step row ctr[0] - per-step scale g_i and rescale phi_i from
+    gtab fp32 [1 + k or more, 4] (sampler.guidance_table: row 0 = (k, 0, 0, 0), row 1 + i = (g_i, phi_i, 0, 0)) - so that the step launch's own
+    e + g (e - e) returns it.  ctr int32 [>= 1] is read, never written."""
+    lib = _lib.load()
+    _chk2(eps, F32), _chk2(gtab, F32), _chk2(ctr, torch.int32)
+    assert eps.dim() == 2 and eps.shape[1] == 4 and eps.is_contiguous() and n >= 1 and eps.shape[0] % (2 * n) == 0 and eps.shape[0] >= 2 * n
+    assert gtab.dim() == 2 and gtab.shape[1] == 4 and gtab.shape[0] >= 2 and gtab.is_contiguous() and ctr.numel() >= 1
+    p = _lib.GuidanceParams(eps=eps.data_ptr(), gtab=gtab.data_ptr(), ctr=ctr.data_ptr(), n=n, hw=eps.shape[0] // (2 * n), gtab_rows=gtab.shape[0])
+    _lib.check(lib.sdlt_guidance(C.byref(p), _stream()), "sdlt_guidance")
+    return eps
+
+
 def masked_mse_fwd_bwd(pred, noise, noisy, mask, timesteps, alphas_cumprod, sums, loss_out, dpred, *, snr_gamma, v_prediction=False,
                        loss_scale=1.0):
     lib = _lib.load()

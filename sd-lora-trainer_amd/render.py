@@ -5,7 +5,8 @@ scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-squ
     python -m sd_lora_trainer_amd.render --checkpoint DIR --out DIR [--prompt TEXT ...] [--n-validation N] [--lora-scale X ...] [--size W H]
                                          [--steps N] [--guidance G] [--seed S] [--images-per-batch N] [--eager]
                                          [--init-image PATH [--strength S] [--mask PATH]] [--sampler euler|dpmpp_2m|euler_a|dpmpp_2m_sde] [--eta F]
-                                         [--sigmas trailing|karras]
+                                         [--sigmas trailing|karras] [--guidance-rescale F] [--guidance-interval SIGMA_LO SIGMA_HI]
+                                         [--negative-prompt TEXT]
                                          [--unet F] [--text-encoder F] [--text-encoder-2 F] [--vae F] [--tokenizer DIR]
 
 DIR is a checkpoint directory of train(): training_args.json (the job's TrainingConfig), adapter_config.json + the kohya adapter file
@@ -26,6 +27,12 @@ Karras et al. 2022 (rho = 7) instead of by trailing timesteps; it combines with 
 --sampler euler_a / dpmpp_2m_sde are the stochastic samplers (Euler ancestral; the SDE form of DPM-Solver++ (2M)): fresh Gaussian noise after every
 step, made inside the step launch (sdlt_sampler_step_sde) from the image's seed, the step and the pixel, so the replayed graph needs no host work and
 the same --seed gives the same files.  --eta (default 1; 0 is the deterministic limit) scales that noise; it is an error with the other samplers.
+
+--guidance-rescale F (0 .. 1) rescales the guided prediction of every step to the standard deviation of the positive one and blends it in with weight
+F (Lin et al. 2024, section 3.4; diffusers' guidance_rescale): it takes the over-exposure out of a strong --guidance, and a v-prediction base needs
+it.  --guidance-interval SIGMA_LO SIGMA_HI applies guidance only at the steps whose noise level lies in (SIGMA_LO, SIGMA_HI] (Kynkaanniemi et al.
+2024).  Both are evaluated by one more launch per iteration (sdlt_guidance) inside the replayed graph; without them nothing changes.
+--negative-prompt TEXT replaces the fixed negative prompt of the training-time renders.
 """
 import argparse
 import json
@@ -189,14 +196,16 @@ def encode_init(loaded, init_image, mask_image, size, latent_hw):
 
 @torch.no_grad()
 def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, guidance_scale=8.0, seed=None, images_per_batch=1, token_scale=None,
-           graph=True, n_validation=4, init_image=None, strength=None, mask_image=None, sampler="euler", sigmas="trailing", eta=None):
+           graph=True, n_validation=4, init_image=None, strength=None, mask_image=None, sampler="euler", sigmas="trailing", eta=None,
+           guidance_rescale=0.0, guidance_interval=None, negative_prompt=None):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
     seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
     graph=False is the eager loop with the same fused kernel.  init_image (path or PIL image): every image starts from it (encode_init) at
     `strength` (default 0.6) instead of from pure noise, each with its own noise; mask_image: white regenerate, black keep.  sampler "euler" |
     "dpmpp_2m" | "euler_a" | "dpmpp_2m_sde", sigmas "trailing" | "karras", eta (stochastic samplers only; default 1): LatentSampler.sample's; the
-    per-step noise of image i is keyed by seed + i, like its initial latents.  -> {scale: [paths]}."""
+    per-step noise of image i is keyed by seed + i, like its initial latents.  guidance_rescale in [0, 1], guidance_interval (sigma_lo, sigma_hi):
+    LatentSampler.sample's; negative_prompt: the negative row's text (None: prompts.NEGATIVE_PROMPT).  -> {scale: [paths]}."""
     from . import train as T
     from . import vae as _vae
     from PIL import Image
@@ -228,7 +237,17 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         eta = 1.0 if eta is None else eta
         if not eta >= 0.0:
             raise ValueError(f"eta must be >= 0, got {eta!r}")
+    if not 0.0 <= guidance_rescale <= 1.0:
+        raise ValueError(f"guidance_rescale must be in [0, 1], got {guidance_rescale!r}")
+    if guidance_interval is not None:
+        guidance_interval = tuple(float(v) for v in guidance_interval)
+        if len(guidance_interval) != 2 or not guidance_interval[0] < guidance_interval[1]:
+            raise ValueError(f"guidance_interval must be (sigma_lo, sigma_hi) with sigma_lo < sigma_hi, got {guidance_interval!r}")
     img_kw = {}
+    if guidance_rescale != 0.0:
+        img_kw.update(guidance_rescale=guidance_rescale)
+    if guidance_interval is not None:
+        img_kw.update(guidance_interval=guidance_interval)
     if (sampler, sigmas) != ("euler", "trailing"):
         img_kw.update(sampler=sampler, sigmas=sigmas)
     if sde:
@@ -251,7 +270,7 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     try:
         for scale in lora_scales:
             smp.set_lora_scale(scale)
-            embeds = [stack.conditioning(p, scale, token_scale)[0] for p in prompts]
+            embeds = [stack.conditioning(p, scale, token_scale, negative_prompt)[0] for p in prompts]
             paths = []
             for s0 in range(0, len(prompts), n):
                 idx = [min(s0 + j, len(prompts) - 1) for j in range(n)]          # a short last batch repeats its last prompt
@@ -280,6 +299,12 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             meta.update(sampler=sampler, sigmas=sigmas)
         if sde:
             meta.update(eta=eta)
+        if guidance_rescale != 0.0:
+            meta.update(guidance_rescale=guidance_rescale)
+        if guidance_interval is not None:
+            meta.update(guidance_interval=list(guidance_interval))
+        if negative_prompt is not None:
+            meta.update(negative_prompt=negative_prompt)
         json.dump(meta, fh, indent=2)
     return result
 
@@ -305,6 +330,10 @@ def main(argv=None, runtime=None):
                     "DPM-Solver++ (2M) SDE - which add fresh noise after every step")
     ap.add_argument("--eta", type=float, default=None, help="amount of per-step noise of --sampler euler_a / dpmpp_2m_sde, >= 0 (default 1; 0: none)")
     ap.add_argument("--sigmas", choices=("trailing", "karras"), default="trailing", help="noise levels: those of trailing timesteps, or Karras et al. (rho = 7)")
+    ap.add_argument("--guidance-rescale", type=float, default=0.0, help="rescale the guided prediction to the positive one's standard deviation, blended with this weight in [0, 1] (default 0: off)")
+    ap.add_argument("--guidance-interval", type=float, nargs=2, metavar=("SIGMA_LO", "SIGMA_HI"), default=None,
+                    help="apply guidance only at the steps whose noise level lies in (SIGMA_LO, SIGMA_HI]")
+    ap.add_argument("--negative-prompt", default=None, help="the negative prompt; default: the fixed one of the training-time renders")
     ap.add_argument("--device", default="cuda:0")
     for flag, key, what in (("--unet", "path", "base UNet weights or synthetic:<version>"), ("--text-encoder", "text_encoder_path", "text encoder state dict"),
                             ("--text-encoder-2", "text_encoder_2_path", "SDXL's second text encoder"), ("--vae", "vae_path", "AutoencoderKL state dict"),
@@ -317,6 +346,10 @@ def main(argv=None, runtime=None):
         ap.error(f"--eta needs --sampler euler_a or dpmpp_2m_sde: --sampler {a.sampler} adds no noise")
     if a.eta is not None and not a.eta >= 0.0:
         ap.error(f"--eta must be >= 0, got {a.eta}")
+    if not 0.0 <= a.guidance_rescale <= 1.0:
+        ap.error(f"--guidance-rescale must be in [0, 1], got {a.guidance_rescale}")
+    if a.guidance_interval is not None and not a.guidance_interval[0] < a.guidance_interval[1]:
+        ap.error(f"--guidance-interval needs SIGMA_LO < SIGMA_HI, got {a.guidance_interval[0]} {a.guidance_interval[1]}")
     if a.strength is not None and not 0.0 < a.strength <= 1.0:
         ap.error(f"--strength must be in (0, 1], got {a.strength}")
     over = {k: getattr(a, k) for k in ("path", "text_encoder_path", "text_encoder_2_path", "vae_path", "tokenizer_path") if getattr(a, k)}
@@ -327,7 +360,8 @@ def main(argv=None, runtime=None):
     loaded = load_for_inference(a.checkpoint, pm, device=a.device, runtime=runtime)
     res = render(loaded, a.prompt, a.out, lora_scales=a.lora_scale, size=a.size, steps=a.steps, guidance_scale=a.guidance, seed=a.seed,
                  images_per_batch=a.images_per_batch, graph=not a.eager, n_validation=a.n_validation, init_image=a.init_image, strength=a.strength,
-                 mask_image=a.mask, sampler=a.sampler, sigmas=a.sigmas, eta=a.eta)
+                 mask_image=a.mask, sampler=a.sampler, sigmas=a.sigmas, eta=a.eta, guidance_rescale=a.guidance_rescale,
+                 guidance_interval=a.guidance_interval, negative_prompt=a.negative_prompt)
     for scale, paths in res.items():
         print(f"lora_scale {scale}: {len(paths)} image(s), {os.path.join(a.out, 'grid_scale' + _scale_tag(scale) + '.jpg')}")
     return res

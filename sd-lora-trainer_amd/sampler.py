@@ -15,7 +15,15 @@ From an init image (`sample(init_latents=, strength=, mask=)`): diffusers' img2i
 entries of the trailing schedule (StableDiffusionImg2ImgPipeline.get_timesteps) and starts from x0 + noise * sigma of the first kept entry
 (EulerDiscreteScheduler.add_noise); with a mask (1 regenerate, 0 keep) the known region is put back after every step, noised to the sigma the
 step arrived at, from the same noise draw (the legacy inpainting loop of diffusers: latents = init_latents_proper * (1 - mask) + latents * mask).
+
+Guidance controls (`sample(guidance_scale=[...], guidance_rescale=, guidance_interval=)`): a guidance scale per step, guidance applied only where
+sigma_i lies in (sigma_lo, sigma_hi] (Kynkaanniemi et al. 2024, "Applying Guidance in a Limited Interval"; g_i = 1 elsewhere) and the rescale of Lin et
+al. 2024, section 3.4 (diffusers' rescale_noise_cfg: the guided prediction is scaled to the standard deviation of the positive one, per image, and
+blended with weight phi).  `guidance_table` holds (g_i, phi_i) per step; ops.guidance evaluates it on the device between the forward and the step
+launch, on all three paths.
 """
+import numbers
+
 import numpy as np
 import torch
 
@@ -244,6 +252,57 @@ class DpmSolverPP2MSDE(_Stochastic):
     KIND = "dpmpp_2m_sde"
 
 
+class EulerStepOrder(EulerDiscrete):
+    """EulerDiscrete with model input and update in sdlt_sampler_step's contract on fp32 tensors (the table's fp32 factors, one rounding per
+    operation, in its order), as _Stochastic restates sdlt_sampler_step_sde: the torch loop and the fused path then agree bit for bit.  The torch loop
+    uses it where the guidance pre-pass runs."""
+
+    def scale_model_input(self, x, i):
+        return x * float(1.0 / np.sqrt(np.float64(self.sigmas[i]) ** 2 + 1.0))
+
+    def step(self, model_out, i, x):
+        f = np.float32
+        s, sn = f(self.sigmas[i]), f(self.sigmas[i + 1])
+        d = model_out
+        if self.prediction_type != "epsilon":                # (the scalars in fp32; full-tensor divisors: IEEE division)
+            q = s * s + f(1.0)
+            c1 = -s / np.sqrt(q)
+            d = (x - (model_out * float(c1) + x / torch.full_like(x, float(q)))) / torch.full_like(x, float(s))
+        return x + d * float(sn - s)
+
+
+def guidance_in_use(guidance_scale, guidance_rescale=0.0, guidance_interval=None):
+    """Whether sample() launches the guidance pre-pass: not for a scalar guidance scale without rescale and interval (today's tables and captures)."""
+    return not isinstance(guidance_scale, numbers.Real) or guidance_rescale != 0.0 or guidance_interval is not None
+
+
+def guidance_table(sched, guidance_scale, guidance_rescale=0.0, guidance_interval=None):
+    """The device table of ops.guidance for a scheduler whose set_timesteps(n[, start]) has run: fp32 [1 + k, 4] for the k steps that run, row 0
+    (k, 0, 0, 0), row 1 + i (g_i, phi_i, 0, 0).  guidance_scale: a number, or one per step that runs; guidance_interval (sigma_lo, sigma_hi): g_i = 1
+    where sigma_i lies outside (sigma_lo, sigma_hi]; guidance_rescale in [0, 1] is phi, on the rows whose (fp32) g_i is not 1."""
+    k = len(sched.timesteps)
+    phi = float(guidance_rescale)
+    if not 0.0 <= phi <= 1.0:
+        raise ValueError(f"guidance_rescale must be in [0, 1], got {guidance_rescale!r}")
+    if isinstance(guidance_scale, numbers.Real):
+        g = np.full(k, float(guidance_scale), dtype=np.float64)
+    else:
+        g = np.array([float(v) for v in guidance_scale], dtype=np.float64)
+        if g.shape != (k,):
+            raise ValueError(f"guidance_scale: {len(g)} value(s) for the {k} step(s) that run (one each, or a number)")
+    if guidance_interval is not None:
+        lo, hi = (float(v) for v in guidance_interval)
+        if not lo < hi:
+            raise ValueError(f"guidance_interval must be (sigma_lo, sigma_hi) with sigma_lo < sigma_hi, got {guidance_interval!r}")
+        sig = np.asarray(sched.sigmas[:k], dtype=np.float64)
+        g[~((sig > lo) & (sig <= hi))] = 1.0
+    tab = np.zeros((1 + k, 4), dtype=np.float32)
+    tab[0, 0] = k
+    tab[1:, 0] = g
+    tab[1:, 1] = np.where(tab[1:, 0] != 1.0, np.float32(phi), np.float32(0.0))
+    return torch.from_numpy(tab)
+
+
 SAMPLERS = ("euler", "dpmpp_2m", "euler_a", "dpmpp_2m_sde")
 SIGMAS = ("trailing", "karras")
 
@@ -338,6 +397,10 @@ class LatentSampler:
         self._img_graphs = {}              # the same key + (masked,) -> hipGraph of one iteration whose step launch is ops.sampler_step_img
         self._ms_graphs = {}               # the same key + (masked, "multistep") -> hipGraph of one iteration whose step launch is ops.sampler_step_ms
         self._sde_graphs = {}              # the same key + (masked, "sde") -> hipGraph of one iteration whose step launch is ops.sampler_step_sde
+        self._guided_graphs = {}           # any of the four keys above + (its family,) -> hipGraph of that iteration with ops.guidance before the step launch
+        # the torch loop where the pre-pass runs: the deterministic samplers in their step kernels' order (dpmpp_2m: the SDE form's eta = 0 rows are
+        # ms_coefficients with d = 0)
+        self.sched_exact = dict(euler=EulerStepOrder(prediction_type=prediction_type), dpmpp_2m=DpmSolverPP2MSDE(prediction_type=prediction_type, eta=0.0))
 
     def set_lora_scale(self, lora_scale, train_scale=None):
         """set_adapter_scales (checkpoint.py:31-55): every adapter's contribution is multiplied by lora_scale."""
@@ -349,7 +412,8 @@ class LatentSampler:
 
     @torch.no_grad()
     def sample(self, embeds, h, w, *, steps=25, guidance_scale=8.0, generator=None, size=None, latents=None, graph=False, fused=False, n_images=1,
-               init_latents=None, strength=1.0, mask=None, sampler="euler", sigmas="trailing", eta=1.0, seeds=None):
+               init_latents=None, strength=1.0, mask=None, sampler="euler", sigmas="trailing", eta=1.0, seeds=None, guidance_rescale=0.0,
+               guidance_interval=None):
         """embeds = (c [1,77,D], uc [1,77,D], pc [1,P] | None, puc | None); h, w latent size.  Returns latents [1,4,h,w] fp32
         (still multiplied by the VAE scaling factor, as the pipeline holds them before `vae.decode(latents / scaling_factor)`).
         fused: guidance, the Euler update and the next model input are ONE kernel between two forwards (ops.sampler_step) instead of torch
@@ -364,7 +428,13 @@ class LatentSampler:
         sampler "euler_a" | "dpmpp_2m_sde" (EulerAncestral, DpmSolverPP2MSDE): fresh noise after every step, its amount set by eta >= 0 (0: the
         deterministic limit), drawn on the device from one 64-bit seed per image - seeds: n_images ints, None: drawn from `generator` after the initial
         latents - the step index and the pixel, so an image's noise does not depend on the batch it is sampled in.  The torch loop takes it from
-        ops.sampler_noise, fused / graph make it inside ops.sampler_step_sde: the three paths give the same bits."""
+        ops.sampler_noise, fused / graph make it inside ops.sampler_step_sde: the three paths give the same bits.
+        guidance_scale: a number, or one per step that runs; guidance_interval (sigma_lo, sigma_hi): guidance only at the steps whose sigma_i lies
+        in (sigma_lo, sigma_hi] (g_i = 1 elsewhere - both rows of a pair still go through the UNet there: the picture changes, the time does not);
+        guidance_rescale phi in [0, 1]: the guided prediction rescaled to the positive one's standard deviation and blended with weight phi, on the
+        steps with g_i != 1 (guidance_table).  With any of the three in use, ops.guidance forms the prediction on the device between the forward and
+        the step launch - in the torch loop too, whose update is then taken in the step kernel's order: the three paths give the same bits.  A
+        scalar guidance_scale without the other two launches nothing new."""
         if sampler not in SAMPLERS:
             raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
         if sampler in SDE_KINDS and not eta >= 0.0:       # (the deterministic samplers do not read eta)
@@ -372,8 +442,12 @@ class LatentSampler:
         if sigmas not in SIGMAS:
             raise ValueError(f"sigmas must be one of {SIGMAS}, got {sigmas!r}")
         img = self._img_args(init_latents, strength, mask, steps, h, w, n_images)
+        guide = (guidance_scale, guidance_rescale, guidance_interval) if guidance_in_use(guidance_scale, guidance_rescale, guidance_interval) else None
+        if guide is not None and not hasattr(self.rt.ops, "guidance"):
+            raise NotImplementedError("this op table has no guidance kernel: a per-step guidance_scale, guidance_rescale and guidance_interval are evaluated "
+                                      "by that launch (ops.guidance), in the torch loop too")
         if graph or fused:
-            return self._sample_fused(embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img, sampler, sigmas, eta, seeds)
+            return self._sample_fused(embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img, sampler, sigmas, eta, seeds, guide)
         assert n_images == 1 and self.rt.B == 2, "the torch loop samples one image on a batch-2 runtime; several images together: fused=True or graph=True"
         rt, u, cfg = self.rt, self.unet, self.unet.cfg
         dev = rt.device
@@ -392,7 +466,9 @@ class LatentSampler:
             H, W = size if size is not None else (8 * h, 8 * w)
             tid = torch.tensor([float(H), float(W), 0.0, 0.0, float(H), float(W)] * 2, device=dev)   # original_size, crop, target_size
         x0, m, start = img if img is not None else (None, None, 0)
-        if sampler == "euler" and sigmas == "trailing":
+        if guide is not None and not sde:
+            s = self.sched_exact[sampler].set_timesteps(steps, start, sigmas)
+        elif sampler == "euler" and sigmas == "trailing":
             s = self.sched.set_timesteps(steps, start) if img is not None else self.sched.set_timesteps(steps)
         elif sde:
             s = self.sched_sde[sampler]
@@ -408,13 +484,20 @@ class LatentSampler:
             x = x0 + noise * float(s.sigmas[0])
         if sde:
             words, z = seed_words(seeds, 1, generator, dev), rt.zeros(1, 4, h, w, dtype=F32)
+        if guide is not None:                      # the pre-pass reads its row index from a device counter, as in the fused path
+            gtab, gctr = guidance_table(s, *guide).to(dev), torch.zeros(2, dtype=torch.int32, device=dev)
         x64 = rt.zeros(2 * h * w, 64)
         for i, t in enumerate(s.timesteps):
             xin = s.scale_model_input(x, i)
             x64[:, :4] = xin.permute(0, 2, 3, 1).reshape(h * w, 4).repeat(2, 1).to(x64.dtype)
             tf = torch.full((2,), float(t), device=dev, dtype=F32)
-            eps = u.forward(x64, tf, self.ctx, self.pooled, tid, B=2, H=h, W=w).view(2, h, w, 4).permute(0, 3, 1, 2)
-            e = eps[0:1] + guidance_scale * (eps[1:2] - eps[0:1])
+            eps = u.forward(x64, tf, self.ctx, self.pooled, tid, B=2, H=h, W=w)
+            if guide is not None:
+                gctr[0] = i
+                e = rt.ops.guidance(eps, gtab, gctr, 1).view(2, h, w, 4).permute(0, 3, 1, 2)[1:2]      # (both rows hold the prediction)
+            else:
+                eps = eps.view(2, h, w, 4).permute(0, 3, 1, 2)
+                e = eps[0:1] + guidance_scale * (eps[1:2] - eps[0:1])
             if sde:                                # the kernel's own noise of step i (not drawn where the row adds none)
                 x = s.step(e, i, x, rt.ops.sampler_noise(words, i, z) if s.coeffs[i, 3] != 0.0 else None)
             else:
@@ -476,12 +559,14 @@ class LatentSampler:
             sh["img"] = dict(x0=rt.zeros(n, 4, h, w, dtype=F32), noise=rt.zeros(n, 4, h, w, dtype=F32), mask=rt.zeros(n, 1, h, w, dtype=F32))
         return sh["img"]
 
-    def _iteration(self, st, sh, h, w, masked=None, ms=False, sde=False):
+    def _iteration(self, st, sh, h, w, masked=None, ms=False, sde=False, guided=False):
         """masked None: txt2img; False / True: from init latents, without / with the mask (sh["img"] holds them).  ms: the DPM-Solver++ (2M) launch;
         without a mask it reads neither the init latents nor the noise, whatever the trajectory started from.  sde: the stochastic samplers' launch,
-        the same operands plus the seeds."""
+        the same operands plus the seeds.  guided: ops.guidance rewrites eps first (row ctr[0] of st["gtab"]); the step launch is the same."""
         u = self.unet
         eps = u.forward(sh["x64"], st["tf"], self.ctx, self.pooled, st["tid"] if u.cfg["addition"] else None, B=2 * self.n, H=h, W=w)
+        if guided:
+            self.rt.ops.guidance(eps, st["gtab"], st["ctr"], self.n)
         if sde:
             im = sh["img"] if masked else dict(x0=None, noise=None, mask=None)
             self.rt.ops.sampler_step_sde(eps, sh["x"], sh["x64"], st["tf"], st["table_ms"], st["ctr"], dprev=sh["dprev"], seeds=st["seeds"], x0=im["x0"],
@@ -496,7 +581,7 @@ class LatentSampler:
             self.rt.ops.sampler_step_img(eps, sh["x"], sh["x64"], st["tf"], st["table"], st["ctr"], x0=im["x0"], noise=im["noise"],
                                          mask=im["mask"] if masked else None)
 
-    def _graph(self, st, sh, h, w, masked=None, ms=False, sde=False):
+    def _graph(self, st, sh, h, w, masked=None, ms=False, sde=False, guided=False):
         """The hipGraph of one iteration for this shape and the adapter scale in effect.  The scale is a launch argument of every adapted GEMM
         (baked by capture), hence part of the key; adapters, DoRA factors, token rows, conditioning, table and counter are device memory.
         From init latents (masked False / True) the step launch is another kernel: those captures live in a dict of their own, keyed by the mask
@@ -504,7 +589,9 @@ class LatentSampler:
         ms: the captures of the multistep launch, in a third dict, keyed by the mask's presence too (without one, txt2img and img2img issue the same
         launch and share a capture); step count, strength, schedule kind and coefficients are in its table, the previous denoised value in sh["dprev"].
         sde: the captures of the stochastic samplers' launch, in a fourth dict, keyed like the third; which of the two samplers, eta, step count and
-        strength are in the table and the seeds in a persistent buffer, so one capture serves all of them."""
+        strength are in the table and the seeds in a persistent buffer, so one capture serves all of them.
+        guided: the captures with the guidance pre-pass in them, in a fifth dict, keyed by the key the iteration has above plus its family, so they
+        neither collide with those captures nor evict them; the scales, phi and the interval are in st["gtab"]: one capture per family serves all."""
         a = self.unet.arena
         key = (h, w, self.n, None if a is None else float(a.scale), bool(a is not None and a.dora))
         graphs = self._graphs
@@ -514,6 +601,8 @@ class LatentSampler:
             key, graphs = key + (bool(masked), "multistep"), self._ms_graphs
         elif masked is not None:
             key, graphs = key + (bool(masked),), self._img_graphs
+        if guided:
+            key, graphs = key + ("sde" if sde else "multistep" if ms else "euler" if masked is None else "img",), self._guided_graphs
         g = graphs.get(key)
         if g is not None:
             return g
@@ -525,11 +614,11 @@ class LatentSampler:
         side.wait_stream(torch.cuda.current_stream())
         seq = None
         with torch.cuda.stream(side):
-            self._iteration(st, sh, h, w, masked, ms, sde)     # eager warm-up: every persistent buffer and packed-weight copy exists before the capture
+            self._iteration(st, sh, h, w, masked, ms, sde, guided)     # eager warm-up: every persistent buffer and packed-weight copy exists before the capture
             if prefetch:                                  # next-weight hints of the wave-split-K products, recorded from one eager pass (step.TrainStep.capture)
                 ops.pf_record_begin()
                 try:
-                    self._iteration(st, sh, h, w, masked, ms, sde)
+                    self._iteration(st, sh, h, w, masked, ms, sde, guided)
                 finally:
                     seq = ops.pf_record_end()
         torch.cuda.current_stream().wait_stream(side)
@@ -538,7 +627,7 @@ class LatentSampler:
             if seq:
                 ops.pf_replay_begin(seq)
             try:
-                self._iteration(st, sh, h, w, masked, ms, sde)
+                self._iteration(st, sh, h, w, masked, ms, sde, guided)
             finally:
                 if seq:
                     ops.pf_replay_end()
@@ -546,8 +635,11 @@ class LatentSampler:
         return g
 
     def _sample_fused(self, embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img=None, sampler="euler", sigmas="trailing",
-                      eta=1.0, seeds=None):
+                      eta=1.0, seeds=None, guide=None):
         rt, cfg, n = self.rt, self.unet.cfg, self.n
+        guided = guide is not None
+        if guided:
+            guidance_scale = 1.0                          # the step launch's own scale multiplies e - e = 0: any value gives the same bits
         ms, sde = sampler == "dpmpp_2m", sampler in SDE_KINDS
         if sde and not hasattr(rt.ops, "sampler_step_sde"):
             raise NotImplementedError(f"this op table has no sampler_step_sde kernel: sample(sampler={sampler!r}) draws its per-step noise inside that launch")
@@ -587,7 +679,8 @@ class LatentSampler:
                 sch.eta = eta
                 tab = step_table_sde(sch.set_timesteps(steps, start, sigmas), guidance_scale)
             else:
-                tab = step_table_ms(self.sched_ms.set_timesteps(steps, start, sigmas), guidance_scale)
+                sch = self.sched_ms.set_timesteps(steps, start, sigmas)
+                tab = step_table_ms(sch, guidance_scale)
             steps -= start
             st["table_ms"][: tab.shape[0]].copy_(tab)
         else:
@@ -598,7 +691,13 @@ class LatentSampler:
                 s = self.sched.set_timesteps(steps, img[2]) if sigmas == "trailing" else self.sched.set_timesteps(steps, img[2], sigmas)
                 tab = step_table_img(s, guidance_scale)
                 steps -= img[2]                             # the steps that run: the table holds their rows only
+            sch = s
             st["table"][: tab.shape[0]].copy_(tab)
+        if guided:                                        # a persistent buffer, rewritten per trajectory: a captured pre-pass holds its pointer
+            gtab = guidance_table(sch, *guide)
+            if "gtab" not in st:
+                st["gtab"] = rt.zeros(TABLE_ROWS - 1, 4, dtype=F32)
+            st["gtab"][: gtab.shape[0]].copy_(gtab)
         noise = latents if latents is not None else torch.randn(n, 4, h, w, generator=generator, device=dev, dtype=F32)
         noise = noise.to(dev, F32).contiguous()
         assert tuple(noise.shape) == (n, 4, h, w)
@@ -632,13 +731,13 @@ class LatentSampler:
             g = None
             if graph:
                 init()                                    # (a defined state for the warm-up passes)
-                g = self._graph(st, sh, h, w, masked, ms, sde)
+                g = self._graph(st, sh, h, w, masked, ms, sde, guided)
             init()
             for _ in range(steps):                        # no host read in here: the step index lives in ctr, its scalars in the table
                 if g is not None:
                     g.replay()
                 else:
-                    self._iteration(st, sh, h, w, masked, ms, sde)
+                    self._iteration(st, sh, h, w, masked, ms, sde, guided)
         return x.clone()
 
 

@@ -325,14 +325,16 @@ class RenderStack:
             out += (pf[1:2], pf[0:1])
         return out
 
-    def conditioning(self, prompt, lora_scale, token_scale=None):
-        """encode_prompt_advanced + blend_conditions for one raw prompt -> (conditioning 4-tuple, the prompt with the learned tokens)."""
+    def conditioning(self, prompt, lora_scale, token_scale=None, negative_prompt=None):
+        """encode_prompt_advanced + blend_conditions for one raw prompt -> (conditioning 4-tuple, the prompt with the learned tokens).
+        negative_prompt: the text of the negative row of every pair; None: prompts.NEGATIVE_PROMPT, the one the reference's render entry points fix."""
         from . import sampler as SM
         config = self.config
         trig = (config.training_attributes or {}).get("trigger_text", "TOK")
         lora_p, zero_p = P.prompt_pair(prompt, config.token_dict, trig, config.name, config.concept_mode, use_lora=not config.disable_ti)
         # render_images passes token_scale = 0 with disable_ti (inference.py:289-385): the conditioning is the zero prompt's alone
-        e, _ = SM.blend_conditions(self.encode(zero_p, P.NEGATIVE_PROMPT), self.encode(lora_p, P.NEGATIVE_PROMPT), lora_scale,
+        neg = P.NEGATIVE_PROMPT if negative_prompt is None else negative_prompt
+        e, _ = SM.blend_conditions(self.encode(zero_p, neg), self.encode(lora_p, neg), lora_scale,
                                    token_scale=0.0 if config.disable_ti else token_scale)
         return e, lora_p
 

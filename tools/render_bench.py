@@ -6,9 +6,9 @@ whose step launch is sdlt_sampler_step_img: (d) from init latents at strength 0.
 strength 1 (all 25, the mask blend in every one); their time is divided by the iterations that ran.  --sampler / --sigmas add the replayed graph of
 each named combination other than the default one - e.g. `--sampler dpmpp_2m` times (f) the iteration whose step launch is sdlt_sampler_step_ms
 against (c) - and, with --img2img, its masked variant (`inp`).  The stochastic samplers (`euler_a`, `dpmpp_2m_sde`: step launch sdlt_sampler_step_sde)
-are timed at eta = 1 with fixed seeds.
+are timed at eta = 1 with fixed seeds.  --guidance-rescale F adds (r) the default iteration with the sdlt_guidance pre-pass in it (phi = F) against (c).
 
-    python tools/render_bench.py [--out FILE] [--rounds 5] [--version sdxl] [--latent 128] [--n 1 2] [--img2img] [--sampler dpmpp_2m] [--sigmas karras]
+    python tools/render_bench.py [--out FILE] [--rounds 5] [--version sdxl] [--latent 128] [--n 1 2] [--img2img] [--sampler dpmpp_2m] [--sigmas karras] [--guidance-rescale 0.7]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/render_bench.py --trace-iteration --n 1      # kernel time of one iteration: sum the stats
 
 Prints one table: wall milliseconds per iteration (median over the rounds, min .. max) per variant and n, per image in brackets.
@@ -72,6 +72,7 @@ def main():
                     "(with --trace-iteration: run the masked eager loop instead of the txt2img one)")
     ap.add_argument("--sampler", nargs="+", choices=("euler", "dpmpp_2m", "euler_a", "dpmpp_2m_sde"), default=["euler"], help="also time the graph sampler with these integrators")
     ap.add_argument("--sigmas", nargs="+", choices=("trailing", "karras"), default=["trailing"], help="... on these noise levels")
+    ap.add_argument("--guidance-rescale", type=float, default=0.0, help="also time the default graph sampler with the guidance pre-pass at this rescale weight")
     a = ap.parse_args()
     h = a.latent
     lines = [f"# {a.version} topology, {h} x {h} latent, rank {a.rank}, {a.steps} steps, guidance 8; wall ms per denoising iteration: median (min .. max) of {a.rounds} rounds, alternated",
@@ -97,6 +98,8 @@ def main():
             variants["d graph, init latents 0.6"] = lambda: one(graph=True, init_latents=x0, strength=0.6)
             variants["e graph, inpaint 1.0"] = lambda: one(graph=True, init_latents=x0, strength=1.0, mask=mask)
             ran["d graph, init latents 0.6"], ran["e graph, inpaint 1.0"] = min(int(a.steps * 0.6), a.steps), a.steps
+        if a.guidance_rescale:
+            variants["r graph, guidance rescale"], ran["r graph, guidance rescale"] = (lambda: one(graph=True, guidance_rescale=a.guidance_rescale)), a.steps
         extra = [(s, k) for s in a.sampler for k in a.sigmas if (s, k) != ("euler", "trailing")]
         sd = lambda s: dict(seeds=list(range(n))) if s in ("euler_a", "dpmpp_2m_sde") else {}  # noqa: E731
         for tag, (s, k) in zip("fghij", extra):
