@@ -1,5 +1,5 @@
-// The guidance pre-pass of the latent sampler: one launch between the UNet forward and whichever step launch follows (sampler.hip, sampler_img.hip,
-// sampler_ms.hip, sampler_sde.hip).  It rewrites eps (fp32 [2n hw, 4]; image j = rows 2j negative, 2j + 1 positive) in place so that BOTH row blocks
+// The guidance pre-pass of the latent sampler: one launch between the UNet forward and whichever step launch follows (sampler.hip: any of its
+// four entry points).  It rewrites eps (fp32 [2n hw, 4]; image j = rows 2j negative, 2j + 1 positive) in place so that BOTH row blocks
 // of image j hold the final prediction e; the step launch then forms e + g (e - e) = e whatever its own table holds, and needs no change.
 //   row i = ctr[0] of gtab (fp32 [1 + k, 4]: row 0 = (k, 0, 0, 0), row 1 + i = (g_i, phi_i, 0, 0)); ctr is read, never written
 //   g_i == 1 and phi_i == 0:   e = e_pos                                   guidance off (outside the guidance interval)

@@ -1208,28 +1208,45 @@ def add_noise_nhwc(x0, noise, timesteps, alphas_cumprod, out, noisy_nchw=None):
     return out
 
 
+def _sampler_launch(entry, params, width, eps, x, xin, timesteps, table, ctr, init, **operands):
+    """What the four sampler_step* wrappers share: the checks on the common operands, the entry's parameter block `params` filled from them and from
+    `operands` (the entry's own: x0 / noise / dprev fp32 shaped like x, mask fp32 [n, 1, h, w], seeds int32 [n, 2]; None where absent), and the call."""
+    lib = _lib.load()
+    n, c4, h, w = x.shape
+    _chk2(x, F32), _chk2(xin), _chk2(timesteps, F32), _chk2(table, F32), _chk2(ctr, torch.int32)
+    assert c4 == 4 and x.is_contiguous() and table.is_contiguous() and table.dim() == 2 and table.shape[1] == width and ctr.numel() >= 2
+    assert xin.shape[0] == 2 * n * h * w and timesteps.numel() >= 2 * n and timesteps.is_contiguous()
+    shapes = dict(mask=(n, 1, h, w), seeds=(n, 2))
+    for name, t in operands.items():
+        if t is not None:
+            _chk2(t, torch.int32 if name == "seeds" else F32)
+            assert tuple(t.shape) == shapes.get(name, tuple(x.shape)) and t.is_contiguous(), name
+    if not init:
+        _chk2(eps, F32)
+        assert eps.is_contiguous() and tuple(eps.shape) == (2 * n * h * w, 4)
+    p = params(eps=None if init else eps.data_ptr(), x=x.data_ptr(), xin=xin.data_ptr(), ld_xin=_ld(xin), timesteps=timesteps.data_ptr(),
+               table=table.data_ptr(), ctr=ctr.data_ptr(), n=n, hw=h * w, table_rows=table.shape[0], init=int(init),
+               **{name: None if t is None else t.data_ptr() for name, t in operands.items()})
+    _lib.check(getattr(lib, entry)(C.byref(p), _stream()), entry)
+    return x
+
+
+def _sampler_history_checks(x, dprev, x0, noise, mask, init):
+    """The operand rules of the two entries with a history buffer (sampler_step_ms, sampler_step_sde)."""
+    assert dprev.data_ptr() != x.data_ptr()
+    masked = mask is not None and not init
+    assert noise is not None or not (init or masked), "the init entry and a masked step read the noise"
+    assert x0 is not None or not masked, "a masked step reads x0"
+    for t in (x0, noise):
+        assert t is None or t.data_ptr() not in (x.data_ptr(), dprev.data_ptr()), "x0 and noise may alias neither x nor dprev"
+
+
 def sampler_step(eps, x, xin, timesteps, table, ctr, *, noise=None):
     """sdlt_sampler_step: guidance + Euler update + repack of the next model input for the n = x.shape[0] images of a UNet batch 2n (image j =
     rows 2j negative, 2j + 1 positive).  eps fp32 [2n hw, 4] (None with `noise`: the init entry, x = noise * init_noise_sigma), x fp32
     [n, 4, h, w] in place, xin bf16 [2n hw, >= 4] (columns 0..3 written), timesteps fp32 [2n], table fp32 [rows, 4] (sampler.step_table),
     ctr int32 [2] = {step, ticket}.  Guidance scale, prediction type, step count and the step itself are read from table / ctr on the device."""
-    lib = _lib.load()
-    n, c4, h, w = x.shape
-    init = noise is not None
-    _chk2(x, F32), _chk2(xin), _chk2(timesteps, F32), _chk2(table, F32), _chk2(ctr, torch.int32)
-    assert c4 == 4 and x.is_contiguous() and table.is_contiguous() and table.dim() == 2 and table.shape[1] == 4 and ctr.numel() >= 2
-    assert xin.shape[0] == 2 * n * h * w and timesteps.numel() >= 2 * n and timesteps.is_contiguous()
-    if init:
-        _chk2(noise, F32)
-        assert noise.shape == x.shape and noise.is_contiguous()
-    else:
-        _chk2(eps, F32)
-        assert eps.is_contiguous() and tuple(eps.shape) == (2 * n * h * w, 4)
-    p = _lib.SamplerParams(eps=None if init else eps.data_ptr(), x=x.data_ptr(), noise=noise.data_ptr() if init else None, xin=xin.data_ptr(),
-                           ld_xin=_ld(xin), timesteps=timesteps.data_ptr(), table=table.data_ptr(), ctr=ctr.data_ptr(), n=n, hw=h * w,
-                           table_rows=table.shape[0], init=int(init))
-    _lib.check(lib.sdlt_sampler_step(C.byref(p), _stream()), "sdlt_sampler_step")
-    return x
+    return _sampler_launch("sdlt_sampler_step", _lib.SamplerParams, 4, eps, x, xin, timesteps, table, ctr, noise is not None, noise=noise)
 
 
 def sampler_step_img(eps, x, xin, timesteps, table, ctr, *, x0, noise, mask=None, init=False):
@@ -1237,24 +1254,8 @@ def sampler_step_img(eps, x, xin, timesteps, table, ctr, *, x0, noise, mask=None
     scaling factor; ONE noise draw for all steps), mask fp32 [n, 1, h, w] or None (1 regenerate, 0 keep), table from sampler.step_table_img.
     init: x = x0 + noise * (first used sigma), eps is not read (None); otherwise the Euler step and, with a mask, the blend with x0 noised to the
     next sigma.  The other operands as sampler_step."""
-    lib = _lib.load()
-    n, c4, h, w = x.shape
-    _chk2(x, F32), _chk2(xin), _chk2(timesteps, F32), _chk2(table, F32), _chk2(ctr, torch.int32), _chk2(x0, F32), _chk2(noise, F32)
-    assert c4 == 4 and x.is_contiguous() and table.is_contiguous() and table.dim() == 2 and table.shape[1] == 4 and ctr.numel() >= 2
-    assert xin.shape[0] == 2 * n * h * w and timesteps.numel() >= 2 * n and timesteps.is_contiguous()
-    assert x0.shape == x.shape and x0.is_contiguous() and noise.shape == x.shape and noise.is_contiguous()
     assert x0.data_ptr() != x.data_ptr() and noise.data_ptr() != x.data_ptr(), "x0 and noise are read at every step: they may not alias x"
-    if mask is not None:
-        _chk2(mask, F32)
-        assert tuple(mask.shape) == (n, 1, h, w) and mask.is_contiguous()
-    if not init:
-        _chk2(eps, F32)
-        assert eps.is_contiguous() and tuple(eps.shape) == (2 * n * h * w, 4)
-    p = _lib.SamplerImgParams(eps=None if init else eps.data_ptr(), x=x.data_ptr(), x0=x0.data_ptr(), noise=noise.data_ptr(),
-                              mask=None if mask is None else mask.data_ptr(), xin=xin.data_ptr(), ld_xin=_ld(xin), timesteps=timesteps.data_ptr(),
-                              table=table.data_ptr(), ctr=ctr.data_ptr(), n=n, hw=h * w, table_rows=table.shape[0], init=int(init))
-    _lib.check(lib.sdlt_sampler_step_img(C.byref(p), _stream()), "sdlt_sampler_step_img")
-    return x
+    return _sampler_launch("sdlt_sampler_step_img", _lib.SamplerImgParams, 4, eps, x, xin, timesteps, table, ctr, init, x0=x0, noise=noise, mask=mask)
 
 
 def sampler_step_ms(eps, x, xin, timesteps, table, ctr, *, dprev, x0=None, noise=None, mask=None, init=False):
@@ -1262,31 +1263,9 @@ def sampler_step_ms(eps, x, xin, timesteps, table, ctr, *, dprev, x0=None, noise
     sampler.step_table_ms), for txt2img (x0 None), img2img (x0 at init only) and masked inpainting (x0, noise and mask at every step).  dprev fp32
     [n, 4, h, w]: the previous denoised value, written by every step and read only where c != 0.  init: x = noise * (first used sigma), plus x0 when
     given; eps is not read (None).  The other operands as sampler_step_img."""
-    lib = _lib.load()
-    n, c4, h, w = x.shape
-    _chk2(x, F32), _chk2(xin), _chk2(timesteps, F32), _chk2(table, F32), _chk2(ctr, torch.int32), _chk2(dprev, F32)
-    assert c4 == 4 and x.is_contiguous() and table.is_contiguous() and table.dim() == 2 and table.shape[1] == 8 and ctr.numel() >= 2
-    assert xin.shape[0] == 2 * n * h * w and timesteps.numel() >= 2 * n and timesteps.is_contiguous()
-    assert dprev.shape == x.shape and dprev.is_contiguous() and dprev.data_ptr() != x.data_ptr()
-    masked = mask is not None and not init
-    assert noise is not None or not (init or masked), "the init entry and a masked step read the noise"
-    assert x0 is not None or not masked, "a masked step reads x0"
-    for t in (x0, noise):
-        if t is not None:
-            _chk2(t, F32)
-            assert t.shape == x.shape and t.is_contiguous() and t.data_ptr() not in (x.data_ptr(), dprev.data_ptr()), "x0 and noise may alias neither x nor dprev"
-    if mask is not None:
-        _chk2(mask, F32)
-        assert tuple(mask.shape) == (n, 1, h, w) and mask.is_contiguous()
-    if not init:
-        _chk2(eps, F32)
-        assert eps.is_contiguous() and tuple(eps.shape) == (2 * n * h * w, 4)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    p = _lib.SamplerMsParams(eps=None if init else eps.data_ptr(), x=x.data_ptr(), x0=ptr(x0), noise=ptr(noise), mask=None if init else ptr(mask),
-                             dprev=dprev.data_ptr(), xin=xin.data_ptr(), ld_xin=_ld(xin), timesteps=timesteps.data_ptr(), table=table.data_ptr(),
-                             ctr=ctr.data_ptr(), n=n, hw=h * w, table_rows=table.shape[0], init=int(init))
-    _lib.check(lib.sdlt_sampler_step_ms(C.byref(p), _stream()), "sdlt_sampler_step_ms")
-    return x
+    _sampler_history_checks(x, dprev, x0, noise, mask, init)
+    return _sampler_launch("sdlt_sampler_step_ms", _lib.SamplerMsParams, 8, eps, x, xin, timesteps, table, ctr, init, dprev=dprev, x0=x0, noise=noise,
+                           mask=mask)
 
 
 def sampler_step_sde(eps, x, xin, timesteps, table, ctr, *, dprev, seeds, x0=None, noise=None, mask=None, init=False):
@@ -1294,32 +1273,9 @@ def sampler_step_sde(eps, x, xin, timesteps, table, ctr, *, dprev, seeds, x0=Non
     with a, b, c, d from the table row (fp32 [rows, 8], sampler.step_table_sde) and z ~ N(0, I) made in the launch from seeds (int32 [n, 2]: the
     (lo, hi) words of each image's 64-bit seed), the step index and the pixel - ops.sampler_noise returns the same z.  seeds is read only where
     d != 0.  The other operands as sampler_step_ms."""
-    lib = _lib.load()
-    n, c4, h, w = x.shape
-    _chk2(x, F32), _chk2(xin), _chk2(timesteps, F32), _chk2(table, F32), _chk2(ctr, torch.int32), _chk2(dprev, F32), _chk2(seeds, torch.int32)
-    assert c4 == 4 and x.is_contiguous() and table.is_contiguous() and table.dim() == 2 and table.shape[1] == 8 and ctr.numel() >= 2
-    assert xin.shape[0] == 2 * n * h * w and timesteps.numel() >= 2 * n and timesteps.is_contiguous()
-    assert dprev.shape == x.shape and dprev.is_contiguous() and dprev.data_ptr() != x.data_ptr()
-    assert tuple(seeds.shape) == (n, 2) and seeds.is_contiguous()
-    masked = mask is not None and not init
-    assert noise is not None or not (init or masked), "the init entry and a masked step read the noise"
-    assert x0 is not None or not masked, "a masked step reads x0"
-    for t in (x0, noise):
-        if t is not None:
-            _chk2(t, F32)
-            assert t.shape == x.shape and t.is_contiguous() and t.data_ptr() not in (x.data_ptr(), dprev.data_ptr()), "x0 and noise may alias neither x nor dprev"
-    if mask is not None:
-        _chk2(mask, F32)
-        assert tuple(mask.shape) == (n, 1, h, w) and mask.is_contiguous()
-    if not init:
-        _chk2(eps, F32)
-        assert eps.is_contiguous() and tuple(eps.shape) == (2 * n * h * w, 4)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    p = _lib.SamplerSdeParams(eps=None if init else eps.data_ptr(), x=x.data_ptr(), x0=ptr(x0), noise=ptr(noise), mask=None if init else ptr(mask),
-                              dprev=dprev.data_ptr(), xin=xin.data_ptr(), ld_xin=_ld(xin), timesteps=timesteps.data_ptr(), table=table.data_ptr(),
-                              ctr=ctr.data_ptr(), n=n, hw=h * w, table_rows=table.shape[0], init=int(init), seeds=seeds.data_ptr())
-    _lib.check(lib.sdlt_sampler_step_sde(C.byref(p), _stream()), "sdlt_sampler_step_sde")
-    return x
+    _sampler_history_checks(x, dprev, x0, noise, mask, init)
+    return _sampler_launch("sdlt_sampler_step_sde", _lib.SamplerSdeParams, 8, eps, x, xin, timesteps, table, ctr, init, dprev=dprev, seeds=seeds, x0=x0,
+                           noise=noise, mask=mask)
 
 
 def sampler_noise(seeds, step, out):

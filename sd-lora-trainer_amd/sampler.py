@@ -22,6 +22,7 @@ al. 2024, section 3.4 (diffusers' rescale_noise_cfg: the guided prediction is sc
 blended with weight phi).  `guidance_table` holds (g_i, phi_i) per step; ops.guidance evaluates it on the device between the forward and the step
 launch, on all three paths.
 """
+import collections
 import numbers
 
 import numpy as np
@@ -377,6 +378,23 @@ def seed_words(seeds, n, generator=None, device="cpu"):
     return torch.from_numpy(words.view(np.int32)).to(device)
 
 
+# The four step launches of the fused / graph path, as data: the op (looked up on the op table when it is called), the builder of its device table,
+# that table's key in the persistent state and its row width, whether the launch takes the history buffer and the seeds, the dict of LatentSampler that
+# holds its captures, and what the capture key gains: None: nothing; a tuple: (the mask's presence,) + the tuple.
+Family = collections.namedtuple("Family", "op table tab width dprev seeds graphs suffix")
+FAMILIES = dict(
+    euler=Family("sampler_step", step_table, "table", 4, False, False, "_graphs", None),
+    img=Family("sampler_step_img", step_table_img, "table", 4, False, False, "_img_graphs", ()),
+    multistep=Family("sampler_step_ms", step_table_ms, "table_ms", 8, True, False, "_ms_graphs", ("multistep",)),
+    sde=Family("sampler_step_sde", step_table_sde, "table_ms", 8, True, True, "_sde_graphs", ("sde",)),
+)
+
+
+def step_family(sampler, img):
+    """The family of sample(sampler=...): img None: txt2img."""
+    return "sde" if sampler in SDE_KINDS else "multistep" if sampler == "dpmpp_2m" else "euler" if img is None else "img"
+
+
 class LatentSampler:
     """`pipe(prompt_embeds=c, negative_prompt_embeds=uc, ..., num_inference_steps, guidance_scale, generator)` of the
     reference's render loop, up to the latents.  `unet` is an inference instance built for batch 2 (negative | positive, the
@@ -466,16 +484,7 @@ class LatentSampler:
             H, W = size if size is not None else (8 * h, 8 * w)
             tid = torch.tensor([float(H), float(W), 0.0, 0.0, float(H), float(W)] * 2, device=dev)   # original_size, crop, target_size
         x0, m, start = img if img is not None else (None, None, 0)
-        if guide is not None and not sde:
-            s = self.sched_exact[sampler].set_timesteps(steps, start, sigmas)
-        elif sampler == "euler" and sigmas == "trailing":
-            s = self.sched.set_timesteps(steps, start) if img is not None else self.sched.set_timesteps(steps)
-        elif sde:
-            s = self.sched_sde[sampler]
-            s.eta = eta
-            s.set_timesteps(steps, start, sigmas)
-        else:
-            s = (self.sched_ms if sampler == "dpmpp_2m" else self.sched).set_timesteps(steps, start, sigmas)
+        s = self._scheduler(sampler, steps, start, sigmas, eta, exact=guide is not None)
         x = latents if latents is not None else torch.randn(1, 4, h, w, generator=generator, device=dev, dtype=F32)
         if img is None:
             x = x.to(dev, F32) * s.init_noise_sigma
@@ -506,6 +515,18 @@ class LatentSampler:
                 k = x0 + noise * float(s.sigmas[i + 1])
                 x = k + m * (x - k)
         return x
+
+    def _scheduler(self, sampler, steps, start, sigmas, eta, exact=False):
+        """The scheduler of a trajectory, its timesteps set.  exact (the torch loop where the guidance pre-pass runs): the deterministic samplers in
+        their step kernels' order."""
+        if sampler in SDE_KINDS:
+            s = self.sched_sde[sampler]
+            s.eta = eta
+        elif exact:
+            s = self.sched_exact[sampler]
+        else:
+            s = self.sched_ms if sampler == "dpmpp_2m" else self.sched
+        return s.set_timesteps(steps, start, sigmas)
 
     def _img_args(self, init_latents, strength, mask, steps, h, w, n):
         """-> None (txt2img: no init_latents, or strength 1 without a mask) | (x0 [n, 4, h, w], mask [n, 1, h, w] | None, first step) on the device."""
@@ -552,57 +573,59 @@ class LatentSampler:
             st["shapes"][(h, w)] = dict(x=rt.zeros(n, 4, h, w, dtype=F32), x64=rt.zeros(2 * n * h * w, 64))
         return st, st["shapes"][(h, w)]
 
-    def _img_state(self, sh, h, w):
-        """The persistent init latents, noise and mask of a shape: a captured ops.sampler_step_img launch holds their pointers."""
+    def _load_image_state(self, sh, h, w, img, noise):
+        """-> (x0, noise, masked) of the init launch.  From init latents: x0, the noise and the mask are copied into the persistent buffers of the shape
+        (a captured step launch holds their pointers) and those are returned; txt2img: (None, the noise as given, None)."""
+        if img is None:
+            return None, noise, None
         if "img" not in sh:
             rt, n = self.rt, self.n
             sh["img"] = dict(x0=rt.zeros(n, 4, h, w, dtype=F32), noise=rt.zeros(n, 4, h, w, dtype=F32), mask=rt.zeros(n, 1, h, w, dtype=F32))
-        return sh["img"]
+        im, masked = sh["img"], img[1] is not None
+        im["x0"].copy_(img[0])
+        im["noise"].copy_(noise)
+        if masked:
+            im["mask"].copy_(img[1])
+        return im["x0"], im["noise"], masked
 
-    def _iteration(self, st, sh, h, w, masked=None, ms=False, sde=False, guided=False):
-        """masked None: txt2img; False / True: from init latents, without / with the mask (sh["img"] holds them).  ms: the DPM-Solver++ (2M) launch;
-        without a mask it reads neither the init latents nor the noise, whatever the trajectory started from.  sde: the stochastic samplers' launch,
-        the same operands plus the seeds.  guided: ops.guidance rewrites eps first (row ctr[0] of st["gtab"]); the step launch is the same."""
+    def _step_launch(self, fam, st, sh, eps, x0=None, noise=None, mask=None):
+        """The launch of family `fam` (FAMILIES) on the persistent state; eps None: its init entry."""
+        f, init = FAMILIES[fam], eps is None
+        kw = dict(x0=x0, noise=noise, mask=mask, init=init) if fam != "euler" else dict(noise=noise) if init else {}
+        if f.dprev:
+            kw["dprev"] = sh["dprev"]
+        if f.seeds:
+            kw["seeds"] = st["seeds"]
+        getattr(self.rt.ops, f.op)(eps, sh["x"], sh["x64"], st["tf"], st[f.tab], st["ctr"], **kw)
+
+    def _iteration(self, st, sh, h, w, fam="euler", masked=None, guided=False):
+        """fam: the step launch (FAMILIES).  masked None: txt2img; False / True: from init latents, without / with the mask (sh["img"] holds them).
+        The Euler launch from init latents takes them at every step; the multistep and stochastic launches read neither the init latents nor the
+        noise without a mask, whatever the trajectory started from.  guided: ops.guidance rewrites eps first (row ctr[0] of st["gtab"]); the step
+        launch is the same."""
         u = self.unet
         eps = u.forward(sh["x64"], st["tf"], self.ctx, self.pooled, st["tid"] if u.cfg["addition"] else None, B=2 * self.n, H=h, W=w)
         if guided:
             self.rt.ops.guidance(eps, st["gtab"], st["ctr"], self.n)
-        if sde:
-            im = sh["img"] if masked else dict(x0=None, noise=None, mask=None)
-            self.rt.ops.sampler_step_sde(eps, sh["x"], sh["x64"], st["tf"], st["table_ms"], st["ctr"], dprev=sh["dprev"], seeds=st["seeds"], x0=im["x0"],
-                                         noise=im["noise"], mask=im["mask"])
-        elif ms:
-            im = sh["img"] if masked else dict(x0=None, noise=None, mask=None)
-            self.rt.ops.sampler_step_ms(eps, sh["x"], sh["x64"], st["tf"], st["table_ms"], st["ctr"], dprev=sh["dprev"], x0=im["x0"], noise=im["noise"], mask=im["mask"])
-        elif masked is None:
-            self.rt.ops.sampler_step(eps, sh["x"], sh["x64"], st["tf"], st["table"], st["ctr"])
-        else:
-            im = sh["img"]
-            self.rt.ops.sampler_step_img(eps, sh["x"], sh["x64"], st["tf"], st["table"], st["ctr"], x0=im["x0"], noise=im["noise"],
-                                         mask=im["mask"] if masked else None)
+        im = sh["img"] if masked or fam == "img" else dict(x0=None, noise=None, mask=None)
+        self._step_launch(fam, st, sh, eps, im["x0"], im["noise"], im["mask"] if masked else None)
 
-    def _graph(self, st, sh, h, w, masked=None, ms=False, sde=False, guided=False):
+    def _graph(self, st, sh, h, w, fam="euler", masked=None, guided=False):
         """The hipGraph of one iteration for this shape and the adapter scale in effect.  The scale is a launch argument of every adapted GEMM
         (baked by capture), hence part of the key; adapters, DoRA factors, token rows, conditioning, table and counter are device memory.
-        From init latents (masked False / True) the step launch is another kernel: those captures live in a dict of their own, keyed by the mask
-        pointer's presence as well; strength and step count are in the table, init latents, noise and mask in persistent buffers.
-        ms: the captures of the multistep launch, in a third dict, keyed by the mask's presence too (without one, txt2img and img2img issue the same
-        launch and share a capture); step count, strength, schedule kind and coefficients are in its table, the previous denoised value in sh["dprev"].
-        sde: the captures of the stochastic samplers' launch, in a fourth dict, keyed like the third; which of the two samplers, eta, step count and
-        strength are in the table and the seeds in a persistent buffer, so one capture serves all of them.
+        Each family's step launch is another kernel: its captures live in a dict of their own (FAMILIES), keyed - txt2img Euler apart - by the mask
+        pointer's presence as well (without a mask, the multistep and stochastic launches of txt2img and img2img are the same and share a capture).
+        Step count, strength, schedule kind, coefficients, which stochastic sampler and eta are in the table; init latents, noise, mask, the previous
+        denoised value and the seeds in persistent buffers: one capture serves all of them.
         guided: the captures with the guidance pre-pass in them, in a fifth dict, keyed by the key the iteration has above plus its family, so they
         neither collide with those captures nor evict them; the scales, phi and the interval are in st["gtab"]: one capture per family serves all."""
-        a = self.unet.arena
+        a, f = self.unet.arena, FAMILIES[fam]
         key = (h, w, self.n, None if a is None else float(a.scale), bool(a is not None and a.dora))
-        graphs = self._graphs
-        if sde:
-            key, graphs = key + (bool(masked), "sde"), self._sde_graphs
-        elif ms:
-            key, graphs = key + (bool(masked), "multistep"), self._ms_graphs
-        elif masked is not None:
-            key, graphs = key + (bool(masked),), self._img_graphs
+        if f.suffix is not None:
+            key += (bool(masked),) + f.suffix
+        graphs = getattr(self, f.graphs)
         if guided:
-            key, graphs = key + ("sde" if sde else "multistep" if ms else "euler" if masked is None else "img",), self._guided_graphs
+            key, graphs = key + (fam,), self._guided_graphs
         g = graphs.get(key)
         if g is not None:
             return g
@@ -614,11 +637,11 @@ class LatentSampler:
         side.wait_stream(torch.cuda.current_stream())
         seq = None
         with torch.cuda.stream(side):
-            self._iteration(st, sh, h, w, masked, ms, sde, guided)     # eager warm-up: every persistent buffer and packed-weight copy exists before the capture
+            self._iteration(st, sh, h, w, fam, masked, guided)     # eager warm-up: every persistent buffer and packed-weight copy exists before the capture
             if prefetch:                                  # next-weight hints of the wave-split-K products, recorded from one eager pass (step.TrainStep.capture)
                 ops.pf_record_begin()
                 try:
-                    self._iteration(st, sh, h, w, masked, ms, sde, guided)
+                    self._iteration(st, sh, h, w, fam, masked, guided)
                 finally:
                     seq = ops.pf_record_end()
         torch.cuda.current_stream().wait_stream(side)
@@ -627,7 +650,7 @@ class LatentSampler:
             if seq:
                 ops.pf_replay_begin(seq)
             try:
-                self._iteration(st, sh, h, w, masked, ms, sde, guided)
+                self._iteration(st, sh, h, w, fam, masked, guided)
             finally:
                 if seq:
                     ops.pf_replay_end()
@@ -640,7 +663,8 @@ class LatentSampler:
         guided = guide is not None
         if guided:
             guidance_scale = 1.0                          # the step launch's own scale multiplies e - e = 0: any value gives the same bits
-        ms, sde = sampler == "dpmpp_2m", sampler in SDE_KINDS
+        fam = step_family(sampler, img)
+        ms, sde = fam == "multistep", fam == "sde"
         if sde and not hasattr(rt.ops, "sampler_step_sde"):
             raise NotImplementedError(f"this op table has no sampler_step_sde kernel: sample(sampler={sampler!r}) draws its per-step noise inside that launch")
         if ms and not hasattr(rt.ops, "sampler_step_ms"):
@@ -666,33 +690,17 @@ class LatentSampler:
         if cfg["addition"]:
             H, W = size if size is not None else (8 * h, 8 * w)
             st["tid"].copy_(torch.tensor([float(H), float(W), 0.0, 0.0, float(H), float(W)] * (2 * n)))
-        if ms or sde:                                     # (the two share the 8-column table and the history buffer: both are rewritten per trajectory)
-            if "table_ms" not in st:
-                st["table_ms"] = rt.zeros(TABLE_ROWS, 8, dtype=F32)
-            if "dprev" not in sh:
-                sh["dprev"] = rt.zeros(n, 4, h, w, dtype=F32)
-            start = 0 if img is None else img[2]
-            if sde:
-                if "seeds" not in st:
-                    st["seeds"] = torch.zeros(n, 2, dtype=torch.int32, device=rt.device)
-                sch = self.sched_sde[sampler]
-                sch.eta = eta
-                tab = step_table_sde(sch.set_timesteps(steps, start, sigmas), guidance_scale)
-            else:
-                sch = self.sched_ms.set_timesteps(steps, start, sigmas)
-                tab = step_table_ms(sch, guidance_scale)
-            steps -= start
-            st["table_ms"][: tab.shape[0]].copy_(tab)
-        else:
-            if img is None:
-                s = self.sched.set_timesteps(steps) if sigmas == "trailing" else self.sched.set_timesteps(steps, 0, sigmas)
-                tab = step_table(s, guidance_scale)
-            else:
-                s = self.sched.set_timesteps(steps, img[2]) if sigmas == "trailing" else self.sched.set_timesteps(steps, img[2], sigmas)
-                tab = step_table_img(s, guidance_scale)
-                steps -= img[2]                             # the steps that run: the table holds their rows only
-            sch = s
-            st["table"][: tab.shape[0]].copy_(tab)
+        f, start = FAMILIES[fam], 0 if img is None else img[2]
+        sch = self._scheduler(sampler, steps, start, sigmas, eta)
+        tab = f.table(sch, guidance_scale)
+        steps -= start                                    # the steps that run: the table holds their rows only
+        if f.tab not in st:                               # (the multistep and stochastic launches share the 8-column table and the history buffer: both are rewritten per trajectory)
+            st[f.tab] = rt.zeros(TABLE_ROWS, f.width, dtype=F32)
+        if f.dprev and "dprev" not in sh:
+            sh["dprev"] = rt.zeros(n, 4, h, w, dtype=F32)
+        if f.seeds and "seeds" not in st:
+            st["seeds"] = torch.zeros(n, 2, dtype=torch.int32, device=rt.device)
+        st[f.tab][: tab.shape[0]].copy_(tab)
         if guided:                                        # a persistent buffer, rewritten per trajectory: a captured pre-pass holds its pointer
             gtab = guidance_table(sch, *guide)
             if "gtab" not in st:
@@ -701,44 +709,22 @@ class LatentSampler:
         noise = latents if latents is not None else torch.randn(n, 4, h, w, generator=generator, device=dev, dtype=F32)
         noise = noise.to(dev, F32).contiguous()
         assert tuple(noise.shape) == (n, 4, h, w)
-        if sde:                                           # after the initial latents, as in the torch loop; a captured launch holds the buffer
+        if f.seeds:                                       # after the initial latents, as in the torch loop; a captured launch holds the buffer
             st["seeds"].copy_(seed_words(seeds, n, generator, dev))
-        x, x64 = sh["x"], sh["x64"]
-        masked = None
-        if ms or sde:
-            x0 = None
-            if img is not None:
-                im, masked = self._img_state(sh, h, w), img[1] is not None
-                im["x0"].copy_(img[0])
-                im["noise"].copy_(noise)
-                if masked:
-                    im["mask"].copy_(img[1])
-                x0, noise = im["x0"], im["noise"]
-            if sde:
-                init = lambda: rt.ops.sampler_step_sde(None, x, x64, st["tf"], st["table_ms"], st["ctr"], dprev=sh["dprev"], seeds=st["seeds"], x0=x0, noise=noise, init=True)  # noqa: E731
-            else:
-                init = lambda: rt.ops.sampler_step_ms(None, x, x64, st["tf"], st["table_ms"], st["ctr"], dprev=sh["dprev"], x0=x0, noise=noise, init=True)  # noqa: E731
-        elif img is None:
-            init = lambda: rt.ops.sampler_step(None, x, x64, st["tf"], st["table"], st["ctr"], noise=noise)  # noqa: E731
-        else:
-            im, masked = self._img_state(sh, h, w), img[1] is not None
-            im["x0"].copy_(img[0])
-            im["noise"].copy_(noise)
-            if masked:
-                im["mask"].copy_(img[1])
-            init = lambda: rt.ops.sampler_step_img(None, x, x64, st["tf"], st["table"], st["ctr"], x0=im["x0"], noise=im["noise"], init=True)  # noqa: E731
+        x0, noise, masked = self._load_image_state(sh, h, w, img, noise)
+        init = lambda: self._step_launch(fam, st, sh, None, x0=x0, noise=noise)  # noqa: E731
         with self._scope():
             g = None
             if graph:
                 init()                                    # (a defined state for the warm-up passes)
-                g = self._graph(st, sh, h, w, masked, ms, sde, guided)
+                g = self._graph(st, sh, h, w, fam, masked, guided)
             init()
             for _ in range(steps):                        # no host read in here: the step index lives in ctr, its scalars in the table
                 if g is not None:
                     g.replay()
                 else:
-                    self._iteration(st, sh, h, w, masked, ms, sde, guided)
-        return x.clone()
+                    self._iteration(st, sh, h, w, fam, masked, guided)
+        return sh["x"].clone()
 
 
 def render_images(sampler, decoder, embeds_list, render_size, out_dir, train_step, seed, *, scaling_factor, lora_scale,

@@ -90,6 +90,30 @@ def test_sampler_step_kernel_fp64(n, hw, pred):
         assert ctr.cpu().tolist() == [(i + 1) % steps, 0]           # wraps to 0 after the last step
 
 
+@pytest.mark.parametrize("shape", [(1, 5, 7), (3, 24, 40)])
+def test_sampler_step_init_noise_aliases_x(shape):
+    """sdlt_sampler_step's init entry may be given x itself as `noise` (include/sdlt_kernels.h): every thread reads its pixel before it writes it.
+    x, the model input, the timesteps and the counter equal the call with a buffer of its own, bit for bit."""
+    from sd_lora_trainer_amd import ops
+    n, h, w = shape
+    dev = "cuda"
+    _, tab = _table(6, 7.5, "epsilon")
+    table = tab.to(dev)
+    noise = torch.randn(n, 4, h, w, generator=torch.Generator().manual_seed(h))
+    out = []
+    for aliased in (False, True):
+        x = noise.to(dev) if aliased else torch.zeros(n, 4, h, w, device=dev)
+        xin = torch.full((2 * n * h * w, 64), 3.25, dtype=torch.bfloat16, device=dev)
+        tf = torch.full((2 * n,), -1.0, device=dev)
+        ctr = torch.tensor([5, 0], dtype=torch.int32, device=dev)
+        ops.sampler_step(None, x, xin, tf, table, ctr, noise=x if aliased else noise.to(dev))
+        torch.cuda.synchronize()
+        out.append((x.cpu(), xin[:, :4].cpu(), tf.cpu(), ctr.cpu()))
+    for a, b in zip(*out):
+        assert torch.equal(a, b)
+    assert not torch.equal(out[0][0], noise) and out[0][3].tolist() == [0, 0]
+
+
 def _setup(version, rank=None, dora=False, n=1, h=None):
     from oracle import unet_ref as U
     from sd_lora_trainer_amd import sampler, topology

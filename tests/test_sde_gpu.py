@@ -176,6 +176,46 @@ def test_no_noise_rows_are_the_multistep_kernel(pred):
     assert torch.equal(b["x"], keep)
 
 
+def test_four_entry_points_share_counter_init_and_tail():
+    """ONE counter and ONE timestep buffer, stepped by the four entry points in turn, a whole trajectory each (tables of the same step count, the same
+    noise, eps and init operands): every trajectory leaves the counter at [0, 0] and the table's wrap-around timestep for the next one.  The Euler
+    entry equals sdlt_sampler_step_img without a mask and without skipped steps, the multistep entry equals the stochastic one on a table whose d
+    column is zero, bit for bit: init and the ticket tail serve every form alike."""
+    from sd_lora_trainer_amd import ops
+    from sd_lora_trainer_amd import sampler as SM
+    n, h, w, ld, k, g = 3, 24, 40, 64, 3, 7.5                                   # 2880 pixels: 12 workgroups, both image boundaries inside one
+    dev = "cuda"
+    euler, ms = SM.EulerDiscrete().set_timesteps(k, 0), SM.DpmSolverPP2M().set_timesteps(k, 0, "trailing")
+    tab4, tab4i, tab8 = (t.to(dev) for t in (SM.step_table(euler, g), SM.step_table_img(euler, g), SM.step_table_ms(ms, g)))
+    assert bool((tab8[:, 7] == 0).all()) and float(tab8[3, 6]) != 0.0 and torch.equal(tab4[:, 3], tab8[:, 3])
+    wrap = float(tab4[2 + k - 1, 3])
+    assert wrap == float(tab4[0, 3])
+    gen = torch.Generator().manual_seed(24)
+    noise, zero = torch.randn(n, 4, h, w, generator=gen).to(dev), torch.zeros(n, 4, h, w, device=dev)
+    eps = [torch.randn(2 * n * h * w, 4, generator=gen).to(dev) for _ in range(k)]
+    words = _words(SEEDS3)
+    ctr, tf = torch.tensor([2, 0], dtype=torch.int32, device=dev), torch.full((2 * n,), -1.0, device=dev)
+    runs = dict(euler=(ops.sampler_step, tab4, lambda s, init: dict(noise=noise) if init else {}),
+                img=(ops.sampler_step_img, tab4i, lambda s, init: dict(x0=zero, noise=noise, init=init)),
+                ms=(ops.sampler_step_ms, tab8, lambda s, init: dict(dprev=s["dprev"], x0=zero, noise=noise, init=init)),
+                sde=(ops.sampler_step_sde, tab8, lambda s, init: dict(dprev=s["dprev"], seeds=words, x0=zero, noise=noise, init=init)))
+    out = {}
+    for name, (op, table, kw) in runs.items():
+        s = _trajectory_state(n, h, w, ld, dev)
+        op(None, s["x"], s["xin"], tf, table, ctr, **kw(s, True))
+        for i in range(k):
+            torch.cuda.synchronize()
+            assert ctr.cpu().tolist() == [i, 0], (name, i)
+            op(eps[i], s["x"], s["xin"], tf, table, ctr, **kw(s, False))
+        torch.cuda.synchronize()
+        assert ctr.cpu().tolist() == [0, 0] and torch.equal(tf.cpu(), torch.full((2 * n,), wrap)), name
+        assert bool(torch.isfinite(s["x"]).all()) and bool((s["xin"][:, 4:] == SENT).all()), name
+        out[name] = s
+    for a, b in (("euler", "img"), ("ms", "sde")):
+        assert torch.equal(out[a]["x"], out[b]["x"]) and torch.equal(out[a]["xin"].view(torch.int16), out[b]["xin"].view(torch.int16)), (a, b)
+    assert torch.equal(out["ms"]["dprev"], out["sde"]["dprev"]) and not torch.equal(out["euler"]["x"], out["ms"]["x"])
+
+
 # ---- LatentSampler ---------------------------------------------------------------------------------------------------------------------
 H, W, STEPS = 8, 12, 5
 COMBOS = [(kind, sig, case) for kind in KINDS for sig in ("trailing", "karras") for case in ("txt2img", "masked")]
