@@ -649,6 +649,44 @@ typedef struct sdlt_guidance_params {
 } sdlt_guidance_params;
 int sdlt_guidance(const sdlt_guidance_params* p, void* stream);
 
+/* sdlt_resize_planes : out fp32 [planes, H, W] = in fp32 [planes, h, w] resampled, both contiguous, out not overlapping in.  The step between the two
+ * passes of a hires render (render.py: `hires`): the first pass's latents [n, 4, h, w] (planes = 4 n, planes_per_image = 4) or the decoder's image
+ * [n, 3, 8h, 8w] (planes_per_image = 3) enlarged before the second pass re-noises them.  planes_per_image consecutive planes are one image: its
+ * per-axis indices and weights are computed once per output pixel and reused for each of them (planes must be a multiple).  H == h and / or W == w are legal.
+ * The modes are PyTorch's align_corners=False conventions (F.interpolate's "nearest-exact", "bilinear", "bicubic" without antialiasing).  Per axis,
+ * for output index d, source size `in`, output size `out`, everything fp32 with one rounding per operation, no contraction, in the order written:
+ *     s = (float)in / (float)out                                          one IEEE division (modes 1, 2)
+ *   mode 0  nearest-exact:  index = min(((2 d + 1) in) / (2 out), in - 1)  in integer arithmetic (no float: no ties); weight 1
+ *   mode 1  bilinear:       c = (float)d + 0.5 ; c = c s ; c = c - 0.5 ; c = max(c, 0)
+ *                           i0 = (int)c ; i1 = min(i0 + 1, in - 1) ; t = c - (float)i0 ; weights (1 - t, t) at (i0, i1)
+ *   mode 2  bicubic:        c = (float)d + 0.5 ; c = c s ; c = c - 0.5   (not clamped) ; f = floor(c) ; i = (int)f ; t = c - f ; u = 1 - t
+ *                           taps a_0 .. a_3 at i - 1, i, i + 1, i + 2, each index clamped to [0, in - 1], with the Keys weights for A = -0.75 in their
+ *                           factored forms (no cancellation; the expanded cubics lose ~1e-6 of a weight near distance 2):
+ *                             w_0 = ((-0.75 t) u) u                      = A (x - 1)(x - 2)^2 at x = t + 1
+ *                             w_2 = ((((1 - 1.25 u) u) + 1) t            = (1 - x)(1 + x - 1.25 x^2) at x = u
+ *                             w_3 = ((-0.75 u) t) t                      = A (x - 1)(x - 2)^2 at x = u + 1      (each op rounded, left to right)
+ *                           w_1 = 1 - w_0 - w_2 - w_3 is never formed: the sum is taken about tap i (below)
+ * Per output pixel (oy, ox) and plane, first along x for each source row the pixel reads (rows top to bottom), then along y over those results:
+ *   mode 0:   out = in[iy, ix]                                              (no arithmetic)
+ *   mode 1:   sum(a_0, a_1) = w_0 a_0 + w_1 a_1                              (two products, one addition)
+ *   mode 2:   sum(a_0 .. a_3) = ((a_1 + w_0 (a_0 - a_1)) + w_2 (a_2 - a_1)) + w_3 (a_3 - a_1)
+ *             - the differences first, so a constant image comes out as the constant exactly and t = 0 returns a_1 exactly
+ *   hs_r = sum over x of row iy_r ;  out = sum over y of (hs_0 ..)           (the horizontal sums first, then the vertical sum)
+ * tests/hires_ref.py restates this in NumPy float32 and gives the same bits.  Identity (in == out on an axis) has t = 0: finite data pass through
+ * unchanged (mode 1: weights exactly (1, 0)).  Sums that overflow - mode 2 also differences of opposite values beyond half the fp32 range - and
+ * non-finite inputs propagate as IEEE gives them.  A null pointer, a size < 1 or > 16384, planes not a positive multiple of planes_per_image,
+ * >= 2^31 output pixels per plane set, overlapping buffers (-1), misaligned pointers (-2) or an unknown mode (-4) return the code and launch nothing.
+ * The block is declared without a struct tag and has no index in sdlt_struct_size(): that table ends with guidance_params (25), and a binding's
+ * tests hold it to that; the block is 48 bytes, two pointers and eight int32, with no padding between fields. */
+typedef struct {
+  const float* in;                   /* fp32 [planes, h, w] */
+  float* out;                        /* fp32 [planes, H, W] */
+  int32_t planes, planes_per_image;
+  int32_t h, w, H, W;
+  int32_t mode, pad_;
+} sdlt_resize_params;
+int sdlt_resize_planes(const sdlt_resize_params* p, void* stream);
+
 /* out[M,C] = a + b on strided 2-D bf16 views (gradient fan-in of the UNet skip connections). */
 int sdlt_add2d(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int32_t M, int32_t C, void* stream);
 

@@ -181,6 +181,11 @@ class GuidanceParams(C.Structure):
     _fields_ = [("eps", vp), ("gtab", vp), ("ctr", vp), ("n", i32), ("hw", i32), ("gtab_rows", i32), ("pad_", i32)]
 
 
+class ResizeParams(C.Structure):
+    # sdlt_resize_params: 48 bytes by the header's text (it has no index in sdlt_struct_size, whose table ends with GuidanceParams)
+    _fields_ = [("in_", vp), ("out", vp), ("planes", i32), ("planes_per_image", i32), ("h", i32), ("w", i32), ("H", i32), ("W", i32), ("mode", i32), ("pad_", i32)]
+
+
 class ShadowDesc(C.Structure):
     _fields_ = [("offset", i64), ("src_ld", i64), ("rows", i32), ("cols", i32), ("dst", vp), ("ld", i64), ("dstT", vp), ("ldT", i64)]
 
@@ -237,6 +242,7 @@ SYMBOLS = {
     "sdlt_sampler_step_sde": (i32, [C.POINTER(SamplerSdeParams), vp]),
     "sdlt_sampler_noise": (i32, [vp, i32, i32, i32, vp, vp]),
     "sdlt_guidance": (i32, [C.POINTER(GuidanceParams), vp]),
+    "sdlt_resize_planes": (i32, [C.POINTER(ResizeParams), vp]),
     "sdlt_strip_gemm": (i32, [C.POINTER(StripParams), vp]),
     "sdlt_strip_gemm_pair": (i32, [C.POINTER(StripParams), C.POINTER(StripParams), vp]),
     "sdlt_attn_pair_ok": (i32, [C.POINTER(AttnParams), C.POINTER(AttnParams)]),
@@ -286,6 +292,8 @@ def load():
     for which, (name, size) in enumerate(struct_sizes()):
         if lib.sdlt_struct_size(which) != size:
             raise KernelLibraryError(f"struct layout mismatch for {name}: C {lib.sdlt_struct_size(which)} vs binding {size}")
+    if C.sizeof(ResizeParams) != 48:
+        raise KernelLibraryError(f"struct layout mismatch for ResizeParams: header 48 vs binding {C.sizeof(ResizeParams)}")
     _lib = lib
     return lib
 

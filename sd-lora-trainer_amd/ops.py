@@ -1302,6 +1302,20 @@ def guidance(eps, gtab, ctr, n):
     return eps
 
 
+def resize_planes(src, out, mode):
+    """sdlt_resize_planes: out fp32 [n, c, H, W] = src fp32 [n, c, h, w] resampled with PyTorch's align_corners=False conventions - mode 0 nearest-exact,
+    1 bilinear, 2 bicubic (Keys, A = -0.75), the arithmetic in the order include/sdlt_kernels.h writes down (tests/hires_ref.py gives the same bits).
+    The c planes of an image share one index / weight computation per output pixel.  Both contiguous; out may not overlap src."""
+    lib = _lib.load()
+    _chk2(src, F32), _chk2(out, F32)
+    assert src.dim() == 4 and out.dim() == 4 and src.is_contiguous() and out.is_contiguous(), "resize_planes takes contiguous 4-D tensors [n, c, h, w]"
+    assert tuple(src.shape[:2]) == tuple(out.shape[:2]), f"src {tuple(src.shape)} and out {tuple(out.shape)} must agree in [n, c]"
+    n, c, h, w = src.shape
+    p = _lib.ResizeParams(in_=src.data_ptr(), out=out.data_ptr(), planes=n * c, planes_per_image=c, h=h, w=w, H=out.shape[2], W=out.shape[3], mode=int(mode))
+    _lib.check(lib.sdlt_resize_planes(C.byref(p), _stream()), "sdlt_resize_planes")
+    return out
+
+
 def masked_mse_fwd_bwd(pred, noise, noisy, mask, timesteps, alphas_cumprod, sums, loss_out, dpred, *, snr_gamma, v_prediction=False,
                        loss_scale=1.0):
     lib = _lib.load()

@@ -7,6 +7,8 @@ scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-squ
                                          [--init-image PATH [--strength S] [--mask PATH]] [--sampler euler|dpmpp_2m|euler_a|dpmpp_2m_sde] [--eta F]
                                          [--sigmas trailing|karras] [--guidance-rescale F] [--guidance-interval SIGMA_LO SIGMA_HI]
                                          [--negative-prompt TEXT]
+                                         [--hires-scale F | --hires-size W H] [--hires-strength F] [--hires-steps N] [--hires-upscaler latent|pixel]
+                                         [--hires-resample nearest|bilinear|bicubic]
                                          [--unet F] [--text-encoder F] [--text-encoder-2 F] [--vae F] [--tokenizer DIR]
 
 DIR is a checkpoint directory of train(): training_args.json (the job's TrainingConfig), adapter_config.json + the kohya adapter file
@@ -33,6 +35,13 @@ F (Lin et al. 2024, section 3.4; diffusers' guidance_rescale): it takes the over
 it.  --guidance-interval SIGMA_LO SIGMA_HI applies guidance only at the steps whose noise level lies in (SIGMA_LO, SIGMA_HI] (Kynkaanniemi et al.
 2024).  Both are evaluated by one more launch per iteration (sdlt_guidance) inside the replayed graph; without them nothing changes.
 --negative-prompt TEXT replaces the fixed negative prompt of the training-time renders.
+
+--hires-scale F / --hires-size W H render in two passes (the "hires fix"): a picture much larger than the model was trained for falls apart when it is
+sampled in one go (doubled subjects, tiled compositions), so the first pass samples at --size, the result is enlarged on the device
+(sdlt_resize_planes) - the latents themselves (--hires-upscaler latent, the default; bilinear) or, through the VAE, the decoded picture (pixel;
+bicubic) - noised again to --hires-strength (default 0.6) and the tail of a --hires-steps schedule (default --steps) runs at the large size: an
+ordinary img2img trajectory with the same sampler, noise levels and guidance controls.  All first passes run before the UNet is rebuilt once for the
+large shape.  It combines with --init-image (the first pass is then img2img), not with --mask.
 """
 import argparse
 import json
@@ -172,32 +181,72 @@ def _open(image):
     return Image.open(image) if isinstance(image, (str, os.PathLike)) else image
 
 
+def _vae_encoder(loaded):
+    """A VAE encoder on the loaded stack's device and op table; its buffers belong to the first image size it encodes."""
+    from . import unet as M
+    from . import vae as V
+    rt = loaded.stack.rt
+    return V.VaeEncoder(M.Runtime(rt.device, 1, act_dtype=rt.act, ops=rt.ops), loaded.models.vae_state())
+
+
+@torch.no_grad()
+def encode_image(loaded, img, enc=None):
+    """img [1, 3, H, W] fp32 in about [-1, 1] -> init latents [1, 4, H/f, W/f] fp32: the posterior's mean times the scaling factor (deterministic)."""
+    enc = enc or _vae_encoder(loaded)
+    mom = enc.encode_moments(img)
+    x0 = mom[:, : mom.shape[1] // 2].float() * loaded.models.cfg["scaling_factor"]
+    return x0.contiguous()
+
+
 @torch.no_grad()
 def encode_init(loaded, init_image, mask_image, size, latent_hw):
     """-> (init latents [1, 4, h, w] fp32 = posterior mean of the image, resized to `size` = (width, height), times the scaling factor;
     mask [1, 1, h, w] fp32 | None: dataset.latent_mask's resize, 1 regenerate / 0 keep).  Images are paths or PIL images."""
     from . import dataset as D
-    from . import unet as M
-    from . import vae as V
-    stack, cfg = loaded.stack, loaded.models.cfg
-    rt = stack.rt
-    enc = V.VaeEncoder(M.Runtime(rt.device, 1, act_dtype=rt.act, ops=rt.ops), loaded.models.vae_state())
+    enc = _vae_encoder(loaded)
     f = 2 ** (len(enc.downs) - 1)
     h, w = latent_hw
     if (size[0], size[1]) != (f * w, f * h):
         raise ValueError(f"an init image needs a size that is a multiple of {f}, got {size[0]} x {size[1]}")
-    mom = enc.encode_moments(D.prepare_image(_open(init_image).convert("RGB"), size[0], size[1]))
-    x0 = mom[:, : mom.shape[1] // 2].float() * cfg["scaling_factor"]
+    x0 = encode_image(loaded, D.prepare_image(_open(init_image).convert("RGB"), size[0], size[1]), enc)
     mask = None
     if mask_image is not None:
-        mask = D.latent_mask(_open(mask_image), size, (h, w), channels=1).reshape(1, 1, h, w).to(rt.device)
-    return x0.contiguous(), mask
+        mask = D.latent_mask(_open(mask_image), size, (h, w), channels=1).reshape(1, 1, h, w).to(loaded.stack.rt.device)
+    return x0, mask
+
+
+HIRES_KEYS = ("scale", "size", "strength", "steps", "upscaler", "resample")
+HIRES_UPSCALERS = ("latent", "pixel")
+
+
+def hires_args(hires, size, steps, f=8):
+    """render()'s `hires` dict, checked and completed -> dict(size (W2, H2), base_size, strength, steps, upscaler, resample).  Keys: scale | size
+    (exactly one: sampler.hires_plan), strength (default 0.6: the share of the second schedule that runs), steps (default: the first pass's),
+    upscaler "latent" | "pixel", resample "nearest" | "bilinear" | "bicubic" (default: bilinear for latent, bicubic for pixel)."""
+    from . import sampler as SM
+    unknown = sorted(set(hires) - set(HIRES_KEYS))
+    if unknown:
+        raise ValueError(f"hires: unknown key(s) {unknown}; known: {HIRES_KEYS}")
+    target = SM.hires_plan(size, hires.get("scale"), hires.get("size"), f)
+    strength = hires.get("strength")
+    strength = 0.6 if strength is None else strength
+    if not (isinstance(strength, (int, float)) and 0.0 < strength <= 1.0):
+        raise ValueError(f"hires strength must be in (0, 1], got {strength!r}")
+    steps2 = hires.get("steps") or steps
+    SM.img2img_steps(steps2, strength)
+    upscaler = hires.get("upscaler") or "latent"
+    if upscaler not in HIRES_UPSCALERS:
+        raise ValueError(f"hires upscaler must be one of {HIRES_UPSCALERS}, got {upscaler!r}")
+    resample = hires.get("resample") or ("bilinear" if upscaler == "latent" else "bicubic")
+    if resample not in SM.RESAMPLE:
+        raise ValueError(f"hires resample must be one of {SM.RESAMPLE}, got {resample!r}")
+    return dict(size=target, base_size=(int(size[0]), int(size[1])), strength=strength, steps=int(steps2), upscaler=upscaler, resample=resample)
 
 
 @torch.no_grad()
 def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, guidance_scale=8.0, seed=None, images_per_batch=1, token_scale=None,
            graph=True, n_validation=4, init_image=None, strength=None, mask_image=None, sampler="euler", sigmas="trailing", eta=None,
-           guidance_rescale=0.0, guidance_interval=None, negative_prompt=None):
+           guidance_rescale=0.0, guidance_interval=None, negative_prompt=None, hires=None):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
     seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
@@ -205,7 +254,13 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     `strength` (default 0.6) instead of from pure noise, each with its own noise; mask_image: white regenerate, black keep.  sampler "euler" |
     "dpmpp_2m" | "euler_a" | "dpmpp_2m_sde", sigmas "trailing" | "karras", eta (stochastic samplers only; default 1): LatentSampler.sample's; the
     per-step noise of image i is keyed by seed + i, like its initial latents.  guidance_rescale in [0, 1], guidance_interval (sigma_lo, sigma_hi):
-    LatentSampler.sample's; negative_prompt: the negative row's text (None: prompts.NEGATIVE_PROMPT).  -> {scale: [paths]}."""
+    LatentSampler.sample's; negative_prompt: the negative row's text (None: prompts.NEGATIVE_PROMPT).
+    hires (a dict, hires_args: scale | size, strength, steps, upscaler, resample): two passes - every image is first sampled at `size`, for all adapter
+    scales and prompt batches, its latents staying on the device; they are enlarged (sampler.upscale_latents: the latents, or with upscaler "pixel"
+    the decoded picture, encoded again); then the UNet is rebuilt ONCE for the large shape and every second pass runs: sample(init_latents=the
+    enlarged latents, strength, steps) with the same sampler, sigmas, eta and guidance controls.  Image i's generator (seed + i) gives the first
+    pass's noise with its first draw and the second pass's with its second; the stochastic samplers key the second pass's per-step noise by
+    seed + i + 2^32.  SDXL's size conditioning is the base size in the first pass and the final size in the second.  -> {scale: [paths]}."""
     from . import train as T
     from . import vae as _vae
     from PIL import Image
@@ -243,6 +298,11 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         guidance_interval = tuple(float(v) for v in guidance_interval)
         if len(guidance_interval) != 2 or not guidance_interval[0] < guidance_interval[1]:
             raise ValueError(f"guidance_interval must be (sigma_lo, sigma_hi) with sigma_lo < sigma_hi, got {guidance_interval!r}")
+    hi = None
+    if hires is not None:
+        if mask_image is not None:
+            raise ValueError("hires does not combine with mask_image: the mask would need a resize of its own")
+        hi = hires_args(hires, size, steps, f)                         # (raises before anything is built)
     img_kw = {}
     if guidance_rescale != 0.0:
         img_kw.update(guidance_rescale=guidance_rescale)
@@ -263,34 +323,82 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         x0, mask = encode_init(loaded, init_image, mask_image, size, (h, w))
         img_kw.update(init_latents=x0, strength=strength, mask=mask)
     loaded.prepare(n, h, w)
-    smp, fused = stack.sampler, hasattr(stack.rt.ops, "sampler_step_sde" if sde else "sampler_step_ms" if sampler == "dpmpp_2m" else "sampler_step")
+    fused = hasattr(stack.rt.ops, "sampler_step_sde" if sde else "sampler_step_ms" if sampler == "dpmpp_2m" else "sampler_step")
     graph = graph and dev.type == "cuda"
     os.makedirs(out_dir, exist_ok=True)
     result = {}
+
+    def sample(embeds, idx, lh, lw, px, noise, kw, seed0, steps=steps):
+        """One batch: latents [n, 4, lh, lw].  px = (width, height) of the size conditioning; seed0 + i keys image i's per-step noise."""
+        smp = stack.sampler
+        sd = (lambda js: dict(seeds=[seed0 + idx[j] for j in js])) if sde else (lambda js: {})
+        if fused:
+            return smp.sample([embeds[i] for i in idx] if n > 1 else embeds[idx[0]], lh, lw, steps=steps, guidance_scale=guidance_scale,
+                              size=(px[1], px[0]), latents=noise, graph=graph, fused=True, n_images=n, **kw, **sd(range(n)))
+        # an op table without the fused kernel: the torch loop, image by image
+        one = lambda v, j: v[j:j + 1] if torch.is_tensor(v) and v.shape[0] == n and n > 1 else v  # noqa: E731
+        return torch.cat([smp.sample(embeds[i], lh, lw, steps=steps, guidance_scale=guidance_scale, size=(px[1], px[0]), latents=noise[j:j + 1],
+                                     **{k: one(v, j) for k, v in kw.items()}, **sd([j])) for j, i in enumerate(idx)])
+
+    def save(lat, idx, s0, scale, paths):
+        for j, i in enumerate(idx[: len(prompts) - s0]):
+            img = _vae.postprocess(stack.decoder.decode(lat[j:j + 1] / cfg["scaling_factor"]))[0].permute(1, 2, 0)
+            arr = (img.float().cpu().numpy() * 255).round().astype("uint8")
+            paths.append(os.path.join(out_dir, f"img_{i:02d}_seed{seed + i}_scale{_scale_tag(scale)}.jpg"))
+            Image.fromarray(arr).save(paths[-1], format="JPEG", quality=95)
+
+    def finish(scale, paths):
+        T.make_validation_img_grid(paths, os.path.join(out_dir, f"grid_scale{_scale_tag(scale)}.jpg"))
+        result[scale] = paths
+
+    def enlarge(lat, enc):
+        """The first pass's latents [n, 4, h, w] -> the second pass's init latents [n, 4, h2, w2]."""
+        ops = stack.rt.ops
+        if hi["upscaler"] == "latent":
+            return SM.upscale_latents(ops, lat, h2, w2, hi["resample"])
+        out = []
+        for j in range(n):                      # through the VAE: the decoder's output as it is (not clamped), enlarged, the encoder's posterior mean
+            img = stack.decoder.decode(lat[j:j + 1] / cfg["scaling_factor"])
+            out.append(encode_image(loaded, SM.upscale_latents(ops, img, f * h2, f * w2, hi["resample"]), enc))
+        return torch.cat(out)
+
+    if hi is not None:
+        w2, h2 = hi["size"][0] // f, hi["size"][1] // f
+        if not hasattr(stack.rt.ops, "resize_planes"):
+            SM.upscale_latents(stack.rt.ops, None, h2, w2, hi["resample"])      # (raises: no kernel, no fallback)
+        kw2 = {k: v for k, v in img_kw.items() if k not in ("init_latents", "strength", "mask")}
+        enc = _vae_encoder(loaded) if hi["upscaler"] == "pixel" else None
+        second = []                             # (index of the scale, embeds, first prompt of the batch, idx, enlarged latents, second noise)
     try:
-        for scale in lora_scales:
-            smp.set_lora_scale(scale)
+        for k, scale in enumerate(lora_scales):
+            stack.sampler.set_lora_scale(scale)
             embeds = [stack.conditioning(p, scale, token_scale, negative_prompt)[0] for p in prompts]
             paths = []
             for s0 in range(0, len(prompts), n):
                 idx = [min(s0 + j, len(prompts) - 1) for j in range(n)]          # a short last batch repeats its last prompt
-                noise = torch.cat([torch.randn(1, 4, h, w, generator=torch.Generator(device=dev).manual_seed(seed + i), device=dev) for i in idx])
-                sd = (lambda js: dict(seeds=[seed + idx[j] for j in js])) if sde else (lambda js: {})
-                if fused:
-                    lat = smp.sample([embeds[i] for i in idx] if n > 1 else embeds[idx[0]], h, w, steps=steps, guidance_scale=guidance_scale,
-                                     size=(size[1], size[0]), latents=noise, graph=graph, fused=True, n_images=n, **img_kw, **sd(range(n)))
-                else:                                                            # an op table without the fused kernel: the torch loop, image by image
-                    lat = torch.cat([smp.sample(embeds[i], h, w, steps=steps, guidance_scale=guidance_scale, size=(size[1], size[0]),
-                                                latents=noise[j:j + 1], **img_kw, **sd([j])) for j, i in enumerate(idx)])
-                for j, i in enumerate(idx[: len(prompts) - s0]):
-                    img = _vae.postprocess(stack.decoder.decode(lat[j:j + 1] / cfg["scaling_factor"]))[0].permute(1, 2, 0)
-                    arr = (img.float().cpu().numpy() * 255).round().astype("uint8")
-                    paths.append(os.path.join(out_dir, f"img_{i:02d}_seed{seed + i}_scale{_scale_tag(scale)}.jpg"))
-                    Image.fromarray(arr).save(paths[-1], format="JPEG", quality=95)
-            T.make_validation_img_grid(paths, os.path.join(out_dir, f"grid_scale{_scale_tag(scale)}.jpg"))
-            result[scale] = paths
+                gens = [torch.Generator(device=dev).manual_seed(seed + i) for i in idx]
+                noise = torch.cat([torch.randn(1, 4, h, w, generator=g, device=dev) for g in gens])
+                lat = sample(embeds, idx, h, w, size, noise, img_kw, seed)
+                if hi is None:
+                    save(lat, idx, s0, scale, paths)
+                else:                                                            # each generator's second draw: the second pass's noise
+                    noise2 = torch.cat([torch.randn(1, 4, h2, w2, generator=g, device=dev) for g in gens])
+                    second.append((k, embeds, s0, idx, enlarge(lat, enc), noise2))
+            if hi is None:
+                finish(scale, paths)
+        if hi is not None:
+            del enc
+            loaded.prepare(n, h2, w2)           # the one rebuild: the UNet's (and the decoder's) buffers belong to the first shape they ran
+            for k, scale in enumerate(lora_scales):
+                stack.sampler.set_lora_scale(scale)
+                paths = []
+                for k1, embeds, s0, idx, x0, noise2 in second:
+                    if k1 == k:
+                        lat = sample(embeds, idx, h2, w2, hi["size"], noise2, dict(kw2, init_latents=x0, strength=hi["strength"]), seed + 2 ** 32, hi["steps"])
+                        save(lat, idx, s0, scale, paths)
+                finish(scale, paths)
     finally:
-        smp.set_lora_scale(1.0)
+        stack.sampler.set_lora_scale(1.0)
     with open(os.path.join(out_dir, "prompts.json"), "w") as fh:
         meta = dict(prompts=prompts, lora_scales=list(lora_scales), size=list(size), steps=steps, guidance_scale=guidance_scale, seed=seed)
         if init_image is not None:
@@ -305,6 +413,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             meta.update(guidance_interval=list(guidance_interval))
         if negative_prompt is not None:
             meta.update(negative_prompt=negative_prompt)
+        if hi is not None:
+            meta.update(hires=dict(hi, size=list(hi["size"]), base_size=list(hi["base_size"])))
         json.dump(meta, fh, indent=2)
     return result
 
@@ -334,6 +444,12 @@ def main(argv=None, runtime=None):
     ap.add_argument("--guidance-interval", type=float, nargs=2, metavar=("SIGMA_LO", "SIGMA_HI"), default=None,
                     help="apply guidance only at the steps whose noise level lies in (SIGMA_LO, SIGMA_HI]")
     ap.add_argument("--negative-prompt", default=None, help="the negative prompt; default: the fixed one of the training-time renders")
+    ap.add_argument("--hires-scale", type=float, default=None, help="two passes: sample at --size, enlarge by this factor (each axis rounded to the VAE's multiple), finish at the large size")
+    ap.add_argument("--hires-size", type=int, nargs=2, metavar=("W", "H"), default=None, help="two passes with the final size given in pixels instead of a factor")
+    ap.add_argument("--hires-strength", type=float, default=None, help="how much of the second pass's schedule runs on the enlarged picture, in (0, 1]; default 0.6")
+    ap.add_argument("--hires-steps", type=int, default=None, help="step count of the second pass's schedule; default: --steps")
+    ap.add_argument("--hires-upscaler", choices=HIRES_UPSCALERS, default=None, help="enlarge the latents (default), or the decoded picture through the VAE")
+    ap.add_argument("--hires-resample", choices=("nearest", "bilinear", "bicubic"), default=None, help="resampling filter; default: bilinear for latent, bicubic for pixel")
     ap.add_argument("--device", default="cuda:0")
     for flag, key, what in (("--unet", "path", "base UNet weights or synthetic:<version>"), ("--text-encoder", "text_encoder_path", "text encoder state dict"),
                             ("--text-encoder-2", "text_encoder_2_path", "SDXL's second text encoder"), ("--vae", "vae_path", "AutoencoderKL state dict"),
@@ -352,6 +468,21 @@ def main(argv=None, runtime=None):
         ap.error(f"--guidance-interval needs SIGMA_LO < SIGMA_HI, got {a.guidance_interval[0]} {a.guidance_interval[1]}")
     if a.strength is not None and not 0.0 < a.strength <= 1.0:
         ap.error(f"--strength must be in (0, 1], got {a.strength}")
+    hires = None
+    if a.hires_scale is not None and a.hires_size is not None:
+        ap.error("--hires-scale and --hires-size exclude each other")
+    if a.hires_scale is None and a.hires_size is None:
+        if any(v is not None for v in (a.hires_strength, a.hires_steps, a.hires_upscaler, a.hires_resample)):
+            ap.error("--hires-strength, --hires-steps, --hires-upscaler and --hires-resample need --hires-scale or --hires-size")
+    else:
+        if a.mask is not None:
+            ap.error("--hires-scale / --hires-size do not combine with --mask")
+        if a.hires_strength is not None and not 0.0 < a.hires_strength <= 1.0:
+            ap.error(f"--hires-strength must be in (0, 1], got {a.hires_strength}")
+        if a.hires_steps is not None and a.hires_steps < 1:
+            ap.error(f"--hires-steps must be >= 1, got {a.hires_steps}")
+        hires = {k: v for k, v in dict(scale=a.hires_scale, size=a.hires_size, strength=a.hires_strength, steps=a.hires_steps, upscaler=a.hires_upscaler,
+                                       resample=a.hires_resample).items() if v is not None}
     over = {k: getattr(a, k) for k in ("path", "text_encoder_path", "text_encoder_2_path", "vae_path", "tokenizer_path") if getattr(a, k)}
     pm = None
     if over and os.path.exists(os.path.join(a.checkpoint, "training_args.json")):
@@ -361,7 +492,7 @@ def main(argv=None, runtime=None):
     res = render(loaded, a.prompt, a.out, lora_scales=a.lora_scale, size=a.size, steps=a.steps, guidance_scale=a.guidance, seed=a.seed,
                  images_per_batch=a.images_per_batch, graph=not a.eager, n_validation=a.n_validation, init_image=a.init_image, strength=a.strength,
                  mask_image=a.mask, sampler=a.sampler, sigmas=a.sigmas, eta=a.eta, guidance_rescale=a.guidance_rescale,
-                 guidance_interval=a.guidance_interval, negative_prompt=a.negative_prompt)
+                 guidance_interval=a.guidance_interval, negative_prompt=a.negative_prompt, **({} if hires is None else dict(hires=hires)))
     for scale, paths in res.items():
         print(f"lora_scale {scale}: {len(paths)} image(s), {os.path.join(a.out, 'grid_scale' + _scale_tag(scale) + '.jpg')}")
     return res

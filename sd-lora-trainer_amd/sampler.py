@@ -337,6 +337,41 @@ def img2img_steps(steps, strength):
     return k, steps - k
 
 
+RESAMPLE = ("nearest", "bilinear", "bicubic")      # ops.resize_planes' modes 0, 1, 2 (PyTorch's nearest-exact / bilinear / bicubic, align_corners=False)
+
+
+def hires_plan(size, scale=None, target=None, f=8):
+    """The second-pass size of a hires render -> (W2, H2).  size = (W, H) of the first pass in pixels; exactly one of scale (a factor: each axis becomes
+    round(axis * scale / f) * f) and target = (W2, H2), a multiple of f (the VAE's factor) on both axes.  The result must not be smaller than the base
+    on any axis and must be larger on one."""
+    if (scale is None) == (target is None):
+        raise ValueError("a hires pass takes either a scale or a target size" + (", not both" if scale is not None else ""))
+    W, H = (int(v) for v in size)
+    if scale is not None:
+        if not (isinstance(scale, (int, float)) and not isinstance(scale, bool) and scale > 0):
+            raise ValueError(f"hires scale must be a positive number, got {scale!r}")
+        W2, H2 = (int(round(v * scale / f)) * f for v in (W, H))
+    else:
+        W2, H2 = (int(v) for v in target)
+        if W2 % f or H2 % f:
+            raise ValueError(f"hires size must be a multiple of {f}, got {W2} x {H2}")
+    if W2 < W or H2 < H or (W2, H2) == (W, H):
+        raise ValueError(f"hires size {W2} x {H2} must be at least the base size {W} x {H} on both axes and larger on one")
+    return W2, H2
+
+
+def upscale_latents(ops, lat, H, W, mode="bilinear"):
+    """lat fp32 [n, c, h, w] on the device -> [n, c, H, W], resampled by ops.resize_planes (mode: one of RESAMPLE).  The c planes of an image are the
+    4 latent channels, or the 3 colours of a decoded picture."""
+    if mode not in RESAMPLE:
+        raise ValueError(f"resample must be one of {RESAMPLE}, got {mode!r}")
+    if not hasattr(ops, "resize_planes"):
+        raise NotImplementedError("this op table has no resize_planes kernel: the hires pass resamples on the device by that launch (ops.resize_planes)")
+    lat = lat.to(F32).contiguous()
+    out = torch.empty(lat.shape[0], lat.shape[1], H, W, dtype=F32, device=lat.device)
+    return ops.resize_planes(lat, out, RESAMPLE.index(mode))
+
+
 def step_table_img(sched, guidance_scale):
     """step_table for ops.sampler_step_img, for a scheduler whose set_timesteps(n, start) has run: the rows of the k = n - start steps that run, and
     row 0 column 1 = the FIRST USED sigma (x = x0 + noise * sigma_0) instead of init_noise_sigma."""
