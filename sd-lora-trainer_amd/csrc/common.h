@@ -28,6 +28,20 @@ __device__ __forceinline__ uint32_t pack2bf(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, bf16x2_hw));
 }
 __device__ __forceinline__ bf16_t f2bf(float f) { return (bf16_t)(pack2bf(f, 0.f) & 0xffffu); }
+// eight consecutive bf16 (16-byte aligned) <-> fp32
+__device__ __forceinline__ void load8(const bf16_t* p, float* v) {
+  uint4 u = *(const uint4*)p;
+  v[0] = bf2f(u.x & 0xffff); v[1] = bf2f(u.x >> 16);
+  v[2] = bf2f(u.y & 0xffff); v[3] = bf2f(u.y >> 16);
+  v[4] = bf2f(u.z & 0xffff); v[5] = bf2f(u.z >> 16);
+  v[6] = bf2f(u.w & 0xffff); v[7] = bf2f(u.w >> 16);
+}
+__device__ __forceinline__ void store8(bf16_t* p, const float* v) {
+  uint4 u;
+  u.x = pack2bf(v[0], v[1]); u.y = pack2bf(v[2], v[3]);
+  u.z = pack2bf(v[4], v[5]); u.w = pack2bf(v[6], v[7]);
+  *(uint4*)p = u;
+}
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
 // d/dx silu(x) = s + x*s*(1-s), s = sigmoid(x)
 __device__ __forceinline__ float dsilu_f(float x) {

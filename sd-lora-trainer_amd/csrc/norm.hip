@@ -14,20 +14,6 @@ namespace {
 
 constexpr int G = 32;
 
-__device__ __forceinline__ void load8(const bf16_t* p, float* v) {
-  uint4 u = *(const uint4*)p;
-  v[0] = bf2f(u.x & 0xffff); v[1] = bf2f(u.x >> 16);
-  v[2] = bf2f(u.y & 0xffff); v[3] = bf2f(u.y >> 16);
-  v[4] = bf2f(u.z & 0xffff); v[5] = bf2f(u.z >> 16);
-  v[6] = bf2f(u.w & 0xffff); v[7] = bf2f(u.w >> 16);
-}
-__device__ __forceinline__ void store8(bf16_t* p, const float* v) {
-  uint4 u;
-  u.x = pack2bf(v[0], v[1]); u.y = pack2bf(v[2], v[3]);
-  u.z = pack2bf(v[4], v[5]); u.w = pack2bf(v[6], v[7]);
-  *(uint4*)p = u;
-}
-
 // row pointer for channel c of row r of the (possibly two-tensor, channel-concatenated) input
 struct CatIn {
   const bf16_t* x1; int64_t ld1; int C1;

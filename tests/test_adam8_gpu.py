@@ -157,3 +157,45 @@ def test_adamw8_flat_matches_oracle(n):
             worst = max(worst, float((d > 0).float().mean()))
         assert float(p[n:].abs().max()) == 0.0 and int(m8[n:].max()) == 0 and int(v8[n:].max()) == 0          # nothing behind the range moved
     assert worst <= 2e-3, worst
+
+
+def test_adamw8_forms_agree():
+    """The three forms of the update - the 16-byte tile form, the scalar tile form (full and ragged) and the flat form - share one arithmetic body, so on the same numbers they
+    give the same bits.  96 x 64 fp32 with src_ld 64: the tile-major code layout IS the flat layout (flat block k = half k % 2 of tile k // 2).  (A) arena offset 128: tile 0 takes
+    the 16-byte form, tile 1 the ragged form; (B) offset 129: tile 0 takes the full scalar form; (C) adamw8_flat on the 6144 elements.  Three steps, each form on its own state."""
+    from sd_lora_trainer_amd import ops
+    dev = torch.device("cuda:0")
+    gen = torch.Generator().manual_seed(96 * 64)
+    rows, cols, n = 96, 64, 96 * 64
+    lr, b1, b2, eps, wd = 1e-3, 0.9, 0.999, 1e-8, 0.01
+    p0 = (torch.randn(rows, cols, generator=gen) * 0.05).reshape(-1).to(dev)
+    tables = ops.q8_tables(dev)
+    tiled = []
+    for off in (128, 129):
+        p = torch.zeros(off + n + 63, dtype=F32, device=dev)
+        p[off: off + n] = p0
+        W, Wt = torch.zeros(rows, cols, dtype=BF16, device=dev), torch.zeros(cols, rows, dtype=BF16, device=dev)
+        plan = ops.ShadowPlan([(off, rows, cols, cols, W, Wt)], dev)
+        assert plan.n_blocks == 2
+        tiled.append(dict(off=off, p=p, g=torch.zeros_like(p), plan=plan, m8=torch.zeros(8192, dtype=torch.uint8, device=dev),
+                          v8=torch.zeros(8192, dtype=torch.uint8, device=dev), absmax=torch.zeros(8, dtype=F32, device=dev)))
+    fp, fg = p0.clone(), torch.zeros(n, dtype=F32, device=dev)
+    fm8, fv8, fabsmax = torch.zeros(n, dtype=torch.uint8, device=dev), torch.zeros(n, dtype=torch.uint8, device=dev), torch.zeros(6, dtype=F32, device=dev)
+    for step in range(1, 4):
+        gi = _grad(gen, (rows, cols), 1e-3 * (1 + step % 3), "outliers").reshape(-1).to(dev)
+        hyper = _hyper(dev, lr, b1, b2, eps, wd, step)
+        for t in tiled:
+            t["g"][t["off"]: t["off"] + n] = gi
+            t["plan"].adamw8(t["p"], t["g"], t["m8"], t["v8"], t["absmax"], tables, hyper)
+        fg.copy_(gi)
+        ops.adamw8_flat(fp, fg, fm8, fv8, fabsmax, tables, hyper)
+        torch.cuda.synchronize()
+        fam = fabsmax.view(3, 2)
+        for t in tiled:
+            assert torch.equal(t["p"][t["off"]: t["off"] + n], fp), (step, t["off"], "p")
+            assert torch.equal(t["m8"][:n], fm8) and torch.equal(t["v8"][:n], fv8), (step, t["off"], "codes")
+            am = t["absmax"].view(2, 4)
+            for k in range(3):
+                assert float(am[k // 2][k % 2]) == float(fam[k][0]) and float(am[k // 2][2 + k % 2]) == float(fam[k][1]), (step, t["off"], "absmax", k)
+            # the second half of tile 1 lies outside the tensor: codes untouched, absmax 0
+            assert int(t["m8"][n:].max()) == 0 and int(t["v8"][n:].max()) == 0 and float(am[1][1]) == 0.0 and float(am[1][3]) == 0.0, (step, t["off"])
