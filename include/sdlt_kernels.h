@@ -687,6 +687,34 @@ typedef struct {
 } sdlt_resize_params;
 int sdlt_resize_planes(const sdlt_resize_params* p, void* stream);
 
+/* sdlt_freeu : FreeU (Si et al., CVPR 2024; diffusers' enable_freeu, ComfyUI's FreeU / FreeU_V2) on ONE (backbone, skip) pair, issued just before an
+ * up-block resnet reads them (render.py: `freeu`; inference only).  h bf16 [B H W, C1] (row stride ld_h), skip bf16 [B H W, C2] (ld_s): NHWC rows, image j =
+ * rows j H W .. ; h_out / skip_out the same shapes (ld_ho, ld_so), overlapping neither an input nor each other.  Strided views are fine.
+ * Skip filter.  The published fftn -> fftshift -> mask[crow - 1 : crow + 1, ccol - 1 : ccol + 1] = s -> ifftshift -> ifftn(.).real (threshold 1) scales four
+ * bins of every plane v[y, x] of size H x W - (0, 0), (-1, 0), (0, -1), (-1, -1) - whose inverse transform's real part is, with ty = 2 pi y / H, tx = 2 pi x / W,
+ *     L[y, x] = (S0 + Ay cos ty + By sin ty + Ax cos tx + Bx sin tx + Axy cos(ty + tx) + Bxy sin(ty + tx)) / (H W)
+ *     S0 = sum v ;  A. = sum v cos(.) ;  B. = sum v sin(.)                 (sums over the plane's pixels)
+ *     skip' = skip + (s - 1) L
+ * tab_y fp32 [2, H] = (cos ty | sin ty), tab_x fp32 [2, W] likewise: made by the host in fp64 and rounded once; the (ty + tx) terms by the angle-sum
+ * identities from them.  H, W >= 2 (at size 1 the published slice is empty); odd and non-power-of-two sizes are legal.
+ * Backbone scale, c < C1 / 2 only (the other channels are copied):
+ *     version 1 (diffusers):  h'[p, c] = b h[p, c]
+ *     version 2 (the authors' current code, FreeU_V2):  m[p] = mean over all C1 channels of h[p, :] ;  lo, hi = min, max of m over the image's pixels
+ *                             n = (m - lo) / (hi - lo), and n = 0 where hi == lo (this library's choice: the published code divides by zero there)
+ *                             h'[p, c] = h[p, c] ((b - 1) n + 1)
+ * fp32 arithmetic, one rounding to bf16 at the store.  s == 1 returns the skip's bits and b == 1 the backbone's bits unchanged (copied, not computed: x + 0 L
+ * would turn -0 into +0).  Two launches on the stream, no atomics, a fixed order for every sum: an image's H W rows are cut into <= 16 chunks of
+ * ceil(H W / 16) rounded up to a multiple of 32 rows - a function of H W alone - launch 1 leaves per-chunk partial sums (and version 2's row means and
+ * per-chunk min / max) in ws, launch 2 adds them in ascending chunk order and writes; launch 1 is not issued when nothing reads it (s == 1 and no version-2
+ * scale).  Image j's result depends on neither B nor j and repeats bit for bit.  ws: fp32 scratch of >= sdlt_freeu_ws_floats(B, H, W, C1, C2) floats, live
+ * inside the call only.  A null pointer, B < 1, H or W < 2, C1 or C2 not a positive multiple of 8 (an odd C1 has no half), a leading dimension below its
+ * width, >= 2^31 rows, overlap, a short workspace (-1); pointers not 16-byte aligned (tables, ws: 4) or a leading dimension that is no multiple of 8 (-2);
+ * an unknown version (-4): the code is returned and nothing is launched.  sdlt_freeu_ws_floats returns -1 for sizes sdlt_freeu refuses. */
+int64_t sdlt_freeu_ws_floats(int32_t B, int32_t H, int32_t W, int32_t C1, int32_t C2);
+int sdlt_freeu(const void* h, int64_t ld_h, const void* skip, int64_t ld_s, void* h_out, int64_t ld_ho, void* skip_out, int64_t ld_so,
+               int32_t B, int32_t H, int32_t W, int32_t C1, int32_t C2, float b, float s, int32_t version,
+               const float* tab_y, const float* tab_x, float* ws, int64_t ws_floats, void* stream);
+
 /* out[M,C] = a + b on strided 2-D bf16 views (gradient fan-in of the UNet skip connections). */
 int sdlt_add2d(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int32_t M, int32_t C, void* stream);
 

@@ -243,6 +243,8 @@ SYMBOLS = {
     "sdlt_sampler_noise": (i32, [vp, i32, i32, i32, vp, vp]),
     "sdlt_guidance": (i32, [C.POINTER(GuidanceParams), vp]),
     "sdlt_resize_planes": (i32, [C.POINTER(ResizeParams), vp]),
+    "sdlt_freeu_ws_floats": (i64, [i32, i32, i32, i32, i32]),
+    "sdlt_freeu": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, f32, f32, i32, vp, vp, vp, i64, vp]),
     "sdlt_strip_gemm": (i32, [C.POINTER(StripParams), vp]),
     "sdlt_strip_gemm_pair": (i32, [C.POINTER(StripParams), C.POINTER(StripParams), vp]),
     "sdlt_attn_pair_ok": (i32, [C.POINTER(AttnParams), C.POINTER(AttnParams)]),

@@ -1316,6 +1316,39 @@ def resize_planes(src, out, mode):
     return out
 
 
+def freeu_tables(H, W, device):
+    """The cos / sin tables of sdlt_freeu for an H x W plane: fp32 [2 H + 2 W] = cos(2 pi y / H) | sin(2 pi y / H) | cos(2 pi x / W) | sin(2 pi x / W),
+    evaluated in fp64 and rounded once."""
+    import math
+    y, x = torch.arange(H, dtype=torch.float64) * (2.0 * math.pi / H), torch.arange(W, dtype=torch.float64) * (2.0 * math.pi / W)
+    return torch.cat([torch.cos(y), torch.sin(y), torch.cos(x), torch.sin(x)]).to(F32).to(device)
+
+
+def freeu_ws_floats(B, H, W, C1, C2):
+    """sdlt_freeu_ws_floats: the fp32 workspace of one freeu call."""
+    n = _lib.load().sdlt_freeu_ws_floats(B, H, W, C1, C2)
+    _lib.check(0 if n >= 0 else int(n), "sdlt_freeu_ws_floats")
+    return int(n)
+
+
+def freeu(h, skip, h_out, skip_out, tabs, ws, *, B, H, W, b, s, version=1):
+    """sdlt_freeu: FreeU on one (backbone, skip) pair in front of an up-block resnet.  h bf16 [B H W, C1], skip bf16 [B H W, C2] (row-major views, any
+    leading dimension) -> skip_out = skip + (s - 1) L, L the four lowest-frequency bins' share of every skip plane (the closed form of the published
+    fft -> mask -> ifft with threshold 1), and h_out = h with its first C1 / 2 channels scaled by b (version 1) or by (b - 1) n + 1, n the image's
+    min-max-normalised channel mean (version 2).  tabs: freeu_tables(H, W); ws fp32, >= freeu_ws_floats(B, H, W, C1, C2) floats.  The outputs may overlap
+    neither an input nor each other.  Two launches, fixed summation order: bitwise repeatable, image j independent of B and j.  -> (h_out, skip_out)."""
+    lib = _lib.load()
+    for t in (h, skip, h_out, skip_out):
+        _chk2(t)
+    _chk2(tabs, F32), _chk2(ws, F32)
+    assert h.shape == h_out.shape and skip.shape == skip_out.shape and h.shape[0] == skip.shape[0] == B * H * W, (tuple(h.shape), tuple(skip.shape), B, H, W)
+    assert tabs.is_contiguous() and tabs.numel() == 2 * H + 2 * W and ws.is_contiguous(), "tabs = freeu_tables(H, W, device)"
+    ty = tabs.data_ptr()
+    _lib.check(lib.sdlt_freeu(_p(h), _ld(h), _p(skip), _ld(skip), _p(h_out), _ld(h_out), _p(skip_out), _ld(skip_out), B, H, W, h.shape[1], skip.shape[1],
+                              float(b), float(s), int(version), C.c_void_p(ty), C.c_void_p(ty + 8 * H), _p(ws), ws.numel(), _stream()), "sdlt_freeu")
+    return h_out, skip_out
+
+
 def masked_mse_fwd_bwd(pred, noise, noisy, mask, timesteps, alphas_cumprod, sums, loss_out, dpred, *, snr_gamma, v_prediction=False,
                        loss_scale=1.0):
     lib = _lib.load()

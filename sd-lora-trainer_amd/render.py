@@ -6,7 +6,7 @@ scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-squ
                                          [--steps N] [--guidance G] [--seed S] [--images-per-batch N] [--eager]
                                          [--init-image PATH [--strength S] [--mask PATH]] [--sampler euler|dpmpp_2m|euler_a|dpmpp_2m_sde] [--eta F]
                                          [--sigmas trailing|karras] [--guidance-rescale F] [--guidance-interval SIGMA_LO SIGMA_HI]
-                                         [--negative-prompt TEXT]
+                                         [--negative-prompt TEXT] [--freeu B1 B2 S1 S2 [--freeu-v2]]
                                          [--hires-scale F | --hires-size W H] [--hires-strength F] [--hires-steps N] [--hires-upscaler latent|pixel]
                                          [--hires-resample nearest|bilinear|bicubic]
                                          [--unet F] [--text-encoder F] [--text-encoder-2 F] [--vae F] [--tokenizer DIR]
@@ -42,9 +42,16 @@ sampled in one go (doubled subjects, tiled compositions), so the first pass samp
 bicubic) - noised again to --hires-strength (default 0.6) and the tail of a --hires-steps schedule (default --steps) runs at the large size: an
 ordinary img2img trajectory with the same sampler, noise levels and guidance controls.  All first passes run before the UNet is rebuilt once for the
 large shape.  It combines with --init-image (the first pass is then img2img), not with --mask.
+
+--freeu B1 B2 S1 S2 turns on FreeU (Si et al. 2024; diffusers' enable_freeu order, e.g. 1.3 1.4 0.9 0.2 for SDXL, 1.5 1.6 0.9 0.2 for SD1.5): in every UNet
+forward the skip features entering the first two decoder stages lose their lowest frequencies (factor S) and half of the backbone channels are amplified
+(factor B) - it takes the washed-out, over-smoothed look out of a strong --guidance, and needs no weights.  --freeu-v2 scales the backbone by its own
+normalised channel mean instead of a constant (the authors' current code; ComfyUI's FreeU_V2).  One more launch pair (sdlt_freeu) per affected resnet
+inside the replayed graph; both passes of a hires render use it; without the flag nothing changes.
 """
 import argparse
 import json
+import math
 import os
 
 import torch
@@ -246,7 +253,7 @@ def hires_args(hires, size, steps, f=8):
 @torch.no_grad()
 def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, guidance_scale=8.0, seed=None, images_per_batch=1, token_scale=None,
            graph=True, n_validation=4, init_image=None, strength=None, mask_image=None, sampler="euler", sigmas="trailing", eta=None,
-           guidance_rescale=0.0, guidance_interval=None, negative_prompt=None, hires=None):
+           guidance_rescale=0.0, guidance_interval=None, negative_prompt=None, hires=None, freeu=None):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
     seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
@@ -260,7 +267,9 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     the decoded picture, encoded again); then the UNet is rebuilt ONCE for the large shape and every second pass runs: sample(init_latents=the
     enlarged latents, strength, steps) with the same sampler, sigmas, eta and guidance controls.  Image i's generator (seed + i) gives the first
     pass's noise with its first draw and the second pass's with its second; the stochastic samplers key the second pass's per-step noise by
-    seed + i + 2^32.  SDXL's size conditioning is the base size in the first pass and the final size in the second.  -> {scale: [paths]}."""
+    seed + i + 2^32.  SDXL's size conditioning is the base size in the first pass and the final size in the second.
+    freeu: (b1, b2, s1, s2) or dict(b1, b2, s1, s2, version=1) - LatentSampler.sample's (sampler.freeu_args): FreeU in every forward, of both passes of a
+    hires render too (the setting travels with each sample() call, so the rebuilt UNet has it).  -> {scale: [paths]}."""
     from . import train as T
     from . import vae as _vae
     from PIL import Image
@@ -298,6 +307,7 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         guidance_interval = tuple(float(v) for v in guidance_interval)
         if len(guidance_interval) != 2 or not guidance_interval[0] < guidance_interval[1]:
             raise ValueError(f"guidance_interval must be (sigma_lo, sigma_hi) with sigma_lo < sigma_hi, got {guidance_interval!r}")
+    fz = SM.freeu_args(freeu)                                          # (raises before anything is built)
     hi = None
     if hires is not None:
         if mask_image is not None:
@@ -312,6 +322,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         img_kw.update(sampler=sampler, sigmas=sigmas)
     if sde:
         img_kw.update(eta=eta)
+    if fz is not None:
+        img_kw.update(freeu=fz)
     if init_image is None:
         if mask_image is not None:
             raise ValueError("mask_image needs init_image: the region to keep is taken from it")
@@ -415,6 +427,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             meta.update(negative_prompt=negative_prompt)
         if hi is not None:
             meta.update(hires=dict(hi, size=list(hi["size"]), base_size=list(hi["base_size"])))
+        if fz is not None:
+            meta.update(freeu=fz)
         json.dump(meta, fh, indent=2)
     return result
 
@@ -450,6 +464,9 @@ def main(argv=None, runtime=None):
     ap.add_argument("--hires-steps", type=int, default=None, help="step count of the second pass's schedule; default: --steps")
     ap.add_argument("--hires-upscaler", choices=HIRES_UPSCALERS, default=None, help="enlarge the latents (default), or the decoded picture through the VAE")
     ap.add_argument("--hires-resample", choices=("nearest", "bilinear", "bicubic"), default=None, help="resampling filter; default: bilinear for latent, bicubic for pixel")
+    ap.add_argument("--freeu", type=float, nargs=4, metavar=("B1", "B2", "S1", "S2"), default=None,
+                    help="FreeU: backbone factors B1, B2 and skip low-frequency factors S1, S2 of the first two decoder stages (e.g. 1.3 1.4 0.9 0.2)")
+    ap.add_argument("--freeu-v2", action="store_true", help="with --freeu: scale the backbone by its normalised channel mean (FreeU_V2) instead of a constant")
     ap.add_argument("--device", default="cuda:0")
     for flag, key, what in (("--unet", "path", "base UNet weights or synthetic:<version>"), ("--text-encoder", "text_encoder_path", "text encoder state dict"),
                             ("--text-encoder-2", "text_encoder_2_path", "SDXL's second text encoder"), ("--vae", "vae_path", "AutoencoderKL state dict"),
@@ -468,6 +485,11 @@ def main(argv=None, runtime=None):
         ap.error(f"--guidance-interval needs SIGMA_LO < SIGMA_HI, got {a.guidance_interval[0]} {a.guidance_interval[1]}")
     if a.strength is not None and not 0.0 < a.strength <= 1.0:
         ap.error(f"--strength must be in (0, 1], got {a.strength}")
+    if a.freeu_v2 and a.freeu is None:
+        ap.error("--freeu-v2 needs --freeu B1 B2 S1 S2")
+    if a.freeu is not None and not all(math.isfinite(v) and v > 0.0 for v in a.freeu):
+        ap.error(f"--freeu takes four finite positive numbers, got {' '.join(str(v) for v in a.freeu)}")
+    freeu = None if a.freeu is None else dict(zip(("b1", "b2", "s1", "s2"), a.freeu), version=2 if a.freeu_v2 else 1)
     hires = None
     if a.hires_scale is not None and a.hires_size is not None:
         ap.error("--hires-scale and --hires-size exclude each other")
@@ -492,7 +514,8 @@ def main(argv=None, runtime=None):
     res = render(loaded, a.prompt, a.out, lora_scales=a.lora_scale, size=a.size, steps=a.steps, guidance_scale=a.guidance, seed=a.seed,
                  images_per_batch=a.images_per_batch, graph=not a.eager, n_validation=a.n_validation, init_image=a.init_image, strength=a.strength,
                  mask_image=a.mask, sampler=a.sampler, sigmas=a.sigmas, eta=a.eta, guidance_rescale=a.guidance_rescale,
-                 guidance_interval=a.guidance_interval, negative_prompt=a.negative_prompt, **({} if hires is None else dict(hires=hires)))
+                 guidance_interval=a.guidance_interval, negative_prompt=a.negative_prompt, **({} if hires is None else dict(hires=hires)),
+                 **({} if freeu is None else dict(freeu=freeu)))
     for scale, paths in res.items():
         print(f"lora_scale {scale}: {len(paths)} image(s), {os.path.join(a.out, 'grid_scale' + _scale_tag(scale) + '.jpg')}")
     return res

@@ -23,6 +23,7 @@ blended with weight phi).  `guidance_table` holds (g_i, phi_i) per step; ops.gui
 launch, on all three paths.
 """
 import collections
+import math
 import numbers
 
 import numpy as np
@@ -372,6 +373,25 @@ def upscale_latents(ops, lat, H, W, mode="bilinear"):
     return ops.resize_planes(lat, out, RESAMPLE.index(mode))
 
 
+def freeu_args(freeu):
+    """sample()'s / render()'s `freeu`, checked -> None | dict(b1, b2, s1, s2, version).  None; four numbers (b1, b2, s1, s2) - diffusers'
+    enable_freeu order, version 1 - or a dict with those keys and optionally version (1: diffusers' constant backbone factor; 2: the authors' current
+    code, FreeU_V2: the factor follows the normalised channel mean).  All four finite and positive."""
+    if freeu is None:
+        return None
+    if isinstance(freeu, dict):
+        unknown, missing = sorted(set(freeu) - {"b1", "b2", "s1", "s2", "version"}), [k for k in ("b1", "b2", "s1", "s2") if k not in freeu]
+        if unknown or missing:
+            raise ValueError(f"freeu: keys b1, b2, s1, s2 and optionally version; unknown {unknown}, missing {missing}")
+        vals, version = [freeu[k] for k in ("b1", "b2", "s1", "s2")], freeu.get("version", 1)
+    else:
+        vals, version = list(freeu) if isinstance(freeu, (tuple, list)) else [freeu], 1
+    ok = len(vals) == 4 and all(isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) and v > 0 for v in vals)
+    if not ok or isinstance(version, bool) or version not in (1, 2):
+        raise ValueError(f"freeu takes four finite positive numbers (b1, b2, s1, s2) and version 1 or 2, got {freeu!r}")
+    return dict(b1=float(vals[0]), b2=float(vals[1]), s1=float(vals[2]), s2=float(vals[3]), version=int(version))
+
+
 def step_table_img(sched, guidance_scale):
     """step_table for ops.sampler_step_img, for a scheduler whose set_timesteps(n, start) has run: the rows of the k = n - start steps that run, and
     row 0 column 1 = the FIRST USED sigma (x = x0 + noise * sigma_0) instead of init_noise_sigma."""
@@ -466,7 +486,7 @@ class LatentSampler:
     @torch.no_grad()
     def sample(self, embeds, h, w, *, steps=25, guidance_scale=8.0, generator=None, size=None, latents=None, graph=False, fused=False, n_images=1,
                init_latents=None, strength=1.0, mask=None, sampler="euler", sigmas="trailing", eta=1.0, seeds=None, guidance_rescale=0.0,
-               guidance_interval=None):
+               guidance_interval=None, freeu=None):
         """embeds = (c [1,77,D], uc [1,77,D], pc [1,P] | None, puc | None); h, w latent size.  Returns latents [1,4,h,w] fp32
         (still multiplied by the VAE scaling factor, as the pipeline holds them before `vae.decode(latents / scaling_factor)`).
         fused: guidance, the Euler update and the next model input are ONE kernel between two forwards (ops.sampler_step) instead of torch
@@ -487,7 +507,13 @@ class LatentSampler:
         guidance_rescale phi in [0, 1]: the guided prediction rescaled to the positive one's standard deviation and blended with weight phi, on the
         steps with g_i != 1 (guidance_table).  With any of the three in use, ops.guidance forms the prediction on the device between the forward and
         the step launch - in the torch loop too, whose update is then taken in the step kernel's order: the three paths give the same bits.  A
-        scalar guidance_scale without the other two launches nothing new."""
+        scalar guidance_scale without the other two launches nothing new.
+        freeu: None, or (b1, b2, s1, s2) / dict(b1, b2, s1, s2, version=1): FreeU (freeu_args; UNet.set_freeu) in every forward of the trajectory - one
+        ops.freeu call in front of each resnet of the first two up-blocks, on all three paths, with every sampler, init latents and mask.  The values are
+        launch arguments, so the graph path keeps one capture per setting."""
+        fz = freeu_args(freeu)
+        if fz is not None or getattr(self.unet, "_freeu", None) is not None:
+            self.unet.set_freeu(fz)          # (None: the plain launch sequence; an op table without the kernel raises NotImplementedError here)
         if sampler not in SAMPLERS:
             raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
         if sampler in SDE_KINDS and not eta >= 0.0:       # (the deterministic samplers do not read eta)
@@ -658,6 +684,9 @@ class LatentSampler:
         key = (h, w, self.n, None if a is None else float(a.scale), bool(a is not None and a.dora))
         if f.suffix is not None:
             key += (bool(masked),) + f.suffix
+        fu = getattr(self.unet, "_freeu", None)
+        if fu is not None:                                # FreeU's b, s and version are launch arguments of ops.freeu: a capture per setting
+            key += (("freeu",) + fu,)
         graphs = getattr(self, f.graphs)
         if guided:
             key, graphs = key + (fam,), self._guided_graphs

@@ -1342,6 +1342,7 @@ class UNet(_Module):
             trainer.registering = False
             trainer.finalize()
         self._grad_plan = None
+        self._freeu = None               # set_freeu: (b1, b2, s1, s2, version) of an inference instance
         # time_emb_proj of every resnet reads the same silu(emb): ONE GEMM over the stacked weights [sum Cout, tdim] per pass instead of
         # one M = B launch per resnet (17 in SDXL, 22 in SD1.5); the same for their input gradients (dsemb) when B == 1.  Not with the
         # full fine-tune (the projections are trained layer by layer there).
@@ -1419,10 +1420,12 @@ class UNet(_Module):
         h = self.mid[0].forward(h, None, semb, B, ch, cw)
         h = self.mid[1].forward(h, ctx, B, ch * cw)
         h = self.mid[2].forward(h, None, semb, B, ch, cw)
-        for (res, att, us) in self.up:
+        for i, (res, att, us) in enumerate(self.up):
             for j, r in enumerate(res):
                 s, sh, sw = skips.pop()
                 assert (sh, sw) == (ch, cw)
+                if self._freeu is not None and i < 2:
+                    h, s = self._freeu_apply(i, j, h, s, B, ch, cw)
                 h = r.forward(h, s, semb, B, ch, cw)
                 if att:
                     h = att[j].forward(h, ctx, B, ch * cw)
@@ -1433,6 +1436,41 @@ class UNet(_Module):
         self._dims = (B, H, W)
         self._daam_forward()
         return self.conv_out.forward(hn, B, ch, cw, out=self.buf("pred", B * H * W, cfg["out_channels"], dtype=F32), train=False)
+
+    # ------------------------------------------------------------------------------------ FreeU (inference only)
+    def set_freeu(self, freeu):
+        """None: off (the launch sequence of forward is the plain one).  dict(b1, b2, s1, s2, version=1): FreeU (Si et al. 2024) by diffusers' block
+        rule - every resnet of up_blocks.0 takes (b1, s1), every resnet of up_blocks.1 (b2, s2), just before it reads (h, skip): ops.freeu filters the
+        skip's lowest frequencies by s and scales the first half of the backbone's channels by b (version 2: by the image's normalised channel mean).
+        The values are launch arguments: a capture made with one setting does not serve another (sampler.LatentSampler keys its captures by it)."""
+        if freeu is None:
+            self._freeu = None
+            return
+        unknown = sorted(set(freeu) - {"b1", "b2", "s1", "s2", "version"})
+        if unknown:
+            raise ValueError(f"freeu: unknown key(s) {unknown}; known: b1, b2, s1, s2, version")
+        vals = tuple(float(freeu[k]) for k in ("b1", "b2", "s1", "s2"))
+        version = freeu.get("version", 1)
+        if not all(math.isfinite(v) and v > 0.0 for v in vals) or version not in (1, 2):
+            raise ValueError(f"freeu takes four finite positive numbers b1, b2, s1, s2 and version 1 or 2, got {freeu!r}")
+        if not hasattr(self.rt.ops, "freeu"):
+            raise NotImplementedError("this op table has no freeu kernel: FreeU's skip filter and backbone scale are that launch (ops.freeu)")
+        self._freeu = vals + (int(version),)
+
+    def _freeu_apply(self, i, j, h, s, B, H, W):
+        """(h, skip) of up_blocks.i.resnets.j -> their FreeU forms in buffers of this resnet's own; tables per (H, W), allocated on first use (the warm-up
+        pass of a capture)."""
+        rt = self.rt
+        if H < 2 or W < 2:
+            raise ValueError(f"freeu: up_blocks.{i} runs at {H} x {W}; the filter needs at least 2 x 2 there (a larger image)")
+        b, sc, version = self._freeu[i], self._freeu[2 + i], self._freeu[4]
+        tabs = self._b.get(("freeu_tab", H, W))
+        if tabs is None:
+            tabs = self._b[("freeu_tab", H, W)] = getattr(rt.ops, "freeu_tables", _ops.freeu_tables)(H, W, rt.device)
+        wsf = getattr(rt.ops, "freeu_ws_floats", None)
+        ws = self.buf(("freeu_ws", i, j), wsf(B, H, W, h.shape[1], s.shape[1]) if wsf is not None else 1, dtype=F32)
+        ho, so = self.buf(("freeu_h", i, j), *h.shape), self.buf(("freeu_s", i, j), *s.shape)
+        return rt.ops.freeu(h, s, ho, so, tabs, ws, B=B, H=H, W=W, b=b, s=sc, version=version)
 
     def _daam_forward(self):
         """DAAM side output (ti_cross_attn_loss.py:201-212) of every hooked cross-attention layer: S_l = Q_l K_l^T / sqrt(d) summed
@@ -1469,6 +1507,8 @@ class UNet(_Module):
     def backward(self, dpred64, dctx):
         """dpred64: d loss / d eps_hat as NHWC [B*H*W, 64] (4 real channels); dctx [B*CTX_PAD, D] is ACCUMULATED into
         (caller zeroes it).  LoRA gradients land in arena.grads."""
+        if self._freeu is not None:
+            raise RuntimeError("UNet.backward with freeu set: FreeU is an inference-time change of the forward and has no backward here (set_freeu(None))")
         rt = self.rt
         rt.gn_clear("bwd")
         rt.gn_prezero = True

@@ -7,8 +7,10 @@ strength 1 (all 25, the mask blend in every one); their time is divided by the i
 each named combination other than the default one - e.g. `--sampler dpmpp_2m` times (f) the iteration whose step launch is sdlt_sampler_step_ms
 against (c) - and, with --img2img, its masked variant (`inp`).  The stochastic samplers (`euler_a`, `dpmpp_2m_sde`: step launch sdlt_sampler_step_sde)
 are timed at eta = 1 with fixed seeds.  --guidance-rescale F adds (r) the default iteration with the sdlt_guidance pre-pass in it (phi = F) against (c).
+--freeu B1 B2 S1 S2 adds the default iteration with FreeU in its forward - (u) version 1, (v) version 2: six sdlt_freeu calls per forward on SDXL - against
+(c); with --trace-iteration the traced loop runs it (version 2 with --freeu-v2).
 
-    python tools/render_bench.py [--out FILE] [--rounds 5] [--version sdxl] [--latent 128] [--n 1 2] [--img2img] [--sampler dpmpp_2m] [--sigmas karras] [--guidance-rescale 0.7]
+    python tools/render_bench.py [--out FILE] [--rounds 5] [--version sdxl] [--latent 128] [--n 1 2] [--img2img] [--sampler dpmpp_2m] [--sigmas karras] [--guidance-rescale 0.7] [--freeu 1.3 1.4 0.9 0.2]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/render_bench.py --trace-iteration --n 1      # kernel time of one iteration: sum the stats
 
 Prints one table: wall milliseconds per iteration (median over the rounds, min .. max) per variant and n, per image in brackets.
@@ -73,6 +75,8 @@ def main():
     ap.add_argument("--sampler", nargs="+", choices=("euler", "dpmpp_2m", "euler_a", "dpmpp_2m_sde"), default=["euler"], help="also time the graph sampler with these integrators")
     ap.add_argument("--sigmas", nargs="+", choices=("trailing", "karras"), default=["trailing"], help="... on these noise levels")
     ap.add_argument("--guidance-rescale", type=float, default=0.0, help="also time the default graph sampler with the guidance pre-pass at this rescale weight")
+    ap.add_argument("--freeu", type=float, nargs=4, metavar=("B1", "B2", "S1", "S2"), default=None, help="also time the default graph sampler with FreeU, versions 1 and 2")
+    ap.add_argument("--freeu-v2", action="store_true", help="with --trace-iteration --freeu: trace version 2")
     a = ap.parse_args()
     h = a.latent
     lines = [f"# {a.version} topology, {h} x {h} latent, rank {a.rank}, {a.steps} steps, guidance 8; wall ms per denoising iteration: median (min .. max) of {a.rounds} rounds, alternated",
@@ -100,6 +104,10 @@ def main():
             ran["d graph, init latents 0.6"], ran["e graph, inpaint 1.0"] = min(int(a.steps * 0.6), a.steps), a.steps
         if a.guidance_rescale:
             variants["r graph, guidance rescale"], ran["r graph, guidance rescale"] = (lambda: one(graph=True, guidance_rescale=a.guidance_rescale)), a.steps
+        if a.freeu:
+            for tag, ver in (("u", 1), ("v", 2)):
+                fz = dict(zip(("b1", "b2", "s1", "s2"), a.freeu), version=ver)
+                variants[f"{tag} graph, FreeU v{ver}"], ran[f"{tag} graph, FreeU v{ver}"] = (lambda fz=fz: one(graph=True, freeu=fz)), a.steps
         extra = [(s, k) for s in a.sampler for k in a.sigmas if (s, k) != ("euler", "trailing")]
         sd = lambda s: dict(seeds=list(range(n))) if s in ("euler_a", "dpmpp_2m_sde") else {}  # noqa: E731
         for tag, (s, k) in zip("fghij", extra):
@@ -108,7 +116,8 @@ def main():
             if a.img2img:
                 variants[name + " inp"], ran[name + " inp"] = (lambda s=s, k=k: one(graph=True, sampler=s, sigmas=k, init_latents=x0, strength=1.0, mask=mask, **sd(s))), a.steps
         if a.trace_iteration:                               # the kernels of `steps` eager iterations (+ the one-off weight packing of the first)
-            one(fused=True, **(dict(init_latents=x0, strength=1.0, mask=mask) if a.img2img else {}), **(dict(sampler=extra[0][0], sigmas=extra[0][1], **sd(extra[0][0])) if extra else {}))
+            fu = dict(freeu=dict(zip(("b1", "b2", "s1", "s2"), a.freeu), version=2 if a.freeu_v2 else 1)) if a.freeu else {}
+            one(fused=True, **(dict(init_latents=x0, strength=1.0, mask=mask) if a.img2img else {}), **(dict(sampler=extra[0][0], sigmas=extra[0][1], **sd(extra[0][0])) if extra else {}), **fu)
             torch.cuda.synchronize()
             return
         for fn in variants.values():                        # warm-up: buffers, packed weights, the capture
