@@ -715,6 +715,51 @@ int sdlt_freeu(const void* h, int64_t ld_h, const void* skip, int64_t ld_s, void
                int32_t B, int32_t H, int32_t W, int32_t C1, int32_t C2, float b, float s, int32_t version,
                const float* tab_y, const float* tab_x, float* ws, int64_t ws_floats, void* stream);
 
+/* sdlt_heatmap_accum : per-token cross-attention heat maps of a render (render.py: `heatmap`), one launch per denoising iteration between the UNet forward
+ * and the step launch.  sums[r] fp32 [B h_r w_r, ld]: the raw scores Q K^T / sqrt(d) of resolution r summed over its `layers[r]` hooked cross-attentions
+ * (Runtime.daam_sums), row = batch row block * h_r w_r + pixel, column = context position.  Image i reads row block row_off + i row_stride (the positive
+ * rows: negative | positive blocks have row_off = n, row_stride = 1; interleaved pairs 1 and 2; without guidance 0 and 1) - the caller guarantees it is < B.
+ * cols int32 [n_img, T, P]: the context positions whose columns make map t of image i (a word of several BPE pieces has several); < 0: unused slot; a map
+ * with no position >= 0 is an absent token and is left untouched.  Positions must be < ld (a larger one is read as ld - 1: the launch cannot look into device memory, and it never reads past a row).  With step = ctr[0] clamped to 0 .. weight_rows - 1 (read only):
+ *     scale = weights[step] * (1 / (float)(sum_r layers[r]))
+ *     total = sum over r (ascending), then over p (ascending, cols >= 0), of v_rp, added left to right from 0
+ *     heat[i, t, y, x] = heat[i, t, y, x] + scale * total
+ * v_rp = the column read as an h_r x w_r plane and resampled to gh x gw at (y, x) with sdlt_resize_planes' mode 2 arithmetic (bicubic, A = -0.75, border taps
+ * clamped, F.interpolate(mode="bicubic", align_corners=False)); where h_r == gh and w_r == gw the source value itself.  fp32, one rounding per operation,
+ * no contraction.  n_res 1 .. 4.  A null pointer, a size < 1, an axis > 16384, >= 2^31 outputs (-1) or a misaligned pointer (-2) launch nothing.
+ * The two blocks below are declared without a struct tag, like sdlt_resize_params: 152 and 80 bytes, no padding between fields. */
+typedef struct {
+  const float* sums[4];              /* fp32 [B h_r w_r, ld] per resolution; entries >= n_res are not read */
+  int32_t h[4], w[4], layers[4];
+  const int32_t* cols;               /* int32 [n_img, T, P] */
+  const int32_t* ctr;                /* int32 [>= 1]: ctr[0] = step row, read only (the sampler's counter) */
+  const float* weights;              /* fp32 [weight_rows]: the step's weight */
+  float* heat;                       /* fp32 [n_img, T, gh, gw], read-modify-written */
+  int32_t n_res, n_img, T, P;
+  int32_t gh, gw, row_off, row_stride;
+  int32_t weight_rows, ld;
+} sdlt_heatmap_accum_params;
+int sdlt_heatmap_accum(const sdlt_heatmap_accum_params* p, void* stream);
+
+/* sdlt_heatmap_overlay : the finish after the loop, two launches.  (1) Per image: lo, hi = min, max over its present maps of heat (one colour scale for all the
+ * tokens of a picture); norm = (heat - lo) / (hi - lo) for a present map, 0 for an absent one, and 0 everywhere where hi - lo is not > 0 (a constant image:
+ * no division).  (2) Per map and output pixel: v = norm sampled at the pixel with sdlt_resize_planes' mode 1 arithmetic (bilinear gh x gw -> H x W), clamped
+ * to [0, 1]; q = 255 v; k = min((int)q, 254); f = q - k; colour_c = lut[k, c] + f (lut[k + 1, c] - lut[k, c]);
+ *     out[i, t, y, x, c] = u8((1 - alpha) (255 image[i, c, y, x]) + alpha colour_c)        u8 = to nearest, ties to even, clamped to 0 .. 255
+ * and for an absent map u8(255 image): the untouched picture.  image fp32 [n_img, 3, H, W] in [0, 1]; lut uint8 [256, 3]; norm fp32 [n_img, T, gh, gw] (not
+ * heat itself); out uint8 [n_img, T, H, W, 3].  alpha in [0, 1].  Errors as sdlt_heatmap_accum. */
+typedef struct {
+  const float* heat;                 /* fp32 [n_img, T, gh, gw] */
+  const int32_t* cols;               /* int32 [n_img, T, P]: which maps are present */
+  const float* image;                /* fp32 [n_img, 3, H, W] */
+  const uint8_t* lut;                /* uint8 [256, 3] */
+  float* norm;                       /* fp32 [n_img, T, gh, gw] */
+  uint8_t* out;                      /* uint8 [n_img, T, H, W, 3] */
+  int32_t n_img, T, P, gh, gw, H, W;
+  float alpha;
+} sdlt_heatmap_overlay_params;
+int sdlt_heatmap_overlay(const sdlt_heatmap_overlay_params* p, void* stream);
+
 /* out[M,C] = a + b on strided 2-D bf16 views (gradient fan-in of the UNet skip connections). */
 int sdlt_add2d(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int32_t M, int32_t C, void* stream);
 

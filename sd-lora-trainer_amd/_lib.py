@@ -186,6 +186,18 @@ class ResizeParams(C.Structure):
     _fields_ = [("in_", vp), ("out", vp), ("planes", i32), ("planes_per_image", i32), ("h", i32), ("w", i32), ("H", i32), ("W", i32), ("mode", i32), ("pad_", i32)]
 
 
+class HeatAccumParams(C.Structure):
+    # sdlt_heatmap_accum_params / sdlt_heatmap_overlay_params: 152 and 80 bytes by the header's text (tagless, like sdlt_resize_params)
+    _fields_ = [("sums", vp * 4), ("h", i32 * 4), ("w", i32 * 4), ("layers", i32 * 4), ("cols", vp), ("ctr", vp), ("weights", vp), ("heat", vp),
+                ("n_res", i32), ("n_img", i32), ("T", i32), ("P", i32), ("gh", i32), ("gw", i32), ("row_off", i32), ("row_stride", i32),
+                ("weight_rows", i32), ("ld", i32)]
+
+
+class HeatOverlayParams(C.Structure):
+    _fields_ = [("heat", vp), ("cols", vp), ("image", vp), ("lut", vp), ("norm", vp), ("out", vp),
+                ("n_img", i32), ("T", i32), ("P", i32), ("gh", i32), ("gw", i32), ("H", i32), ("W", i32), ("alpha", f32)]
+
+
 class ShadowDesc(C.Structure):
     _fields_ = [("offset", i64), ("src_ld", i64), ("rows", i32), ("cols", i32), ("dst", vp), ("ld", i64), ("dstT", vp), ("ldT", i64)]
 
@@ -245,6 +257,8 @@ SYMBOLS = {
     "sdlt_resize_planes": (i32, [C.POINTER(ResizeParams), vp]),
     "sdlt_freeu_ws_floats": (i64, [i32, i32, i32, i32, i32]),
     "sdlt_freeu": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, f32, f32, i32, vp, vp, vp, i64, vp]),
+    "sdlt_heatmap_accum": (i32, [C.POINTER(HeatAccumParams), vp]),
+    "sdlt_heatmap_overlay": (i32, [C.POINTER(HeatOverlayParams), vp]),
     "sdlt_strip_gemm": (i32, [C.POINTER(StripParams), vp]),
     "sdlt_strip_gemm_pair": (i32, [C.POINTER(StripParams), C.POINTER(StripParams), vp]),
     "sdlt_attn_pair_ok": (i32, [C.POINTER(AttnParams), C.POINTER(AttnParams)]),
@@ -296,6 +310,9 @@ def load():
             raise KernelLibraryError(f"struct layout mismatch for {name}: C {lib.sdlt_struct_size(which)} vs binding {size}")
     if C.sizeof(ResizeParams) != 48:
         raise KernelLibraryError(f"struct layout mismatch for ResizeParams: header 48 vs binding {C.sizeof(ResizeParams)}")
+    for cls, size in ((HeatAccumParams, 152), (HeatOverlayParams, 80)):
+        if C.sizeof(cls) != size:
+            raise KernelLibraryError(f"struct layout mismatch for {cls.__name__}: header {size} vs binding {C.sizeof(cls)}")
     _lib = lib
     return lib
 

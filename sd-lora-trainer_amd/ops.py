@@ -1316,6 +1316,64 @@ def resize_planes(src, out, mode):
     return out
 
 
+def heatmap_colour_table():
+    """The colour table of the heat-map overlays, uint8 [256, 3], from a closed form of this project's own: with x = k / 255,
+    (r, g, b) = round(255 clip(3 x - (0, 1, 2), 0, 1)) - black at k = 0 through red and yellow to white at k = 255, one channel rising after the other,
+    so no channel ever falls and the luminance rises with k."""
+    x = torch.arange(256, dtype=torch.float64) / 255.0
+    return torch.stack([(3.0 * x - c).clamp(0.0, 1.0) for c in (0.0, 1.0, 2.0)], 1).mul(255.0).round().to(torch.uint8)
+
+
+def _heat_cols(cols, n_img, T):
+    _chk2(cols, torch.int32)
+    assert cols.dim() == 3 and tuple(cols.shape[:2]) == (n_img, T) and cols.shape[2] >= 1 and cols.is_contiguous(), f"cols int32 [{n_img}, {T}, P], got {tuple(cols.shape)}"
+    return cols.shape[2]
+
+
+def heatmap_accum(entries, cols, ctr, weights, heat, *, row_off, row_stride=1):
+    """sdlt_heatmap_accum: heat fp32 [n_img, T, gh, gw] += weights[ctr[0]] / (total layer count) * sum over the entries and the positions of a map of the
+    position's score column resampled (bicubic) to gh x gw.  entries: up to 4 of (sums fp32 [B h w, ld] contiguous, h, w, layer count) - Runtime.daam_sums with
+    the grid of each resolution; cols int32 [n_img, T, P] (< 0: unused; a map without a position is absent and untouched); image i reads the row block
+    row_off + i row_stride of every entry.  ctr int32 [>= 1] and weights fp32 [rows] are read on the device.  Positions must be < ld = sums.shape[1]: cols
+    is device memory, so nothing here can check them - the kernel reads a larger one as ld - 1 and never leaves the row (sampler.heatmap_args holds them to
+    0 .. 76)."""
+    lib = _lib.load()
+    _chk2(heat, F32), _chk2(ctr, torch.int32), _chk2(weights, F32)
+    assert heat.dim() == 4 and heat.is_contiguous() and weights.dim() == 1 and weights.is_contiguous() and ctr.numel() >= 1
+    n_img, T, gh, gw = heat.shape
+    P = _heat_cols(cols, n_img, T)
+    assert 1 <= len(entries) <= 4, "1 .. 4 resolutions"
+    p = _lib.HeatAccumParams(cols=cols.data_ptr(), ctr=ctr.data_ptr(), weights=weights.data_ptr(), heat=heat.data_ptr(), n_res=len(entries), n_img=n_img, T=T,
+                             P=P, gh=gh, gw=gw, row_off=row_off, row_stride=row_stride, weight_rows=weights.numel(), ld=entries[0][0].shape[1])
+    last = row_off + (n_img - 1) * row_stride
+    for r, (s, h, w, layers) in enumerate(entries):
+        _chk2(s, F32)
+        assert s.dim() == 2 and s.is_contiguous() and s.shape[1] == p.ld and s.shape[0] % (h * w) == 0, (tuple(s.shape), h, w)
+        assert 0 <= row_off and row_stride >= 1 and last < s.shape[0] // (h * w), f"row block {last} of {s.shape[0] // (h * w)}"
+        p.sums[r], p.h[r], p.w[r], p.layers[r] = s.data_ptr(), h, w, layers
+    _lib.check(lib.sdlt_heatmap_accum(C.byref(p), _stream()), "sdlt_heatmap_accum")
+    return heat
+
+
+def heatmap_overlay(heat, cols, image, lut, *, alpha=0.6):
+    """sdlt_heatmap_overlay: heat fp32 [n_img, T, gh, gw] -> (norm fp32 the same shape: the present maps of an image on ONE scale, (heat - min) / (max - min)
+    over all of them, absent maps and a constant image zero; overlay uint8 [n_img, T, H, W, 3]: norm resampled (bilinear) to the picture, coloured through lut
+    uint8 [256, 3] (heatmap_colour_table) and blended with weight alpha over image fp32 [n_img, 3, H, W] in [0, 1]; an absent map: the picture itself)."""
+    lib = _lib.load()
+    _chk2(heat, F32), _chk2(image, F32), _chk2(lut, torch.uint8)
+    assert heat.dim() == 4 and heat.is_contiguous() and image.dim() == 4 and image.is_contiguous() and tuple(image.shape[:2]) == (heat.shape[0], 3)
+    assert tuple(lut.shape) == (256, 3) and lut.is_contiguous()
+    n_img, T, gh, gw = heat.shape
+    P = _heat_cols(cols, n_img, T)
+    H, W = image.shape[2:]
+    norm = torch.empty_like(heat)
+    out = torch.empty(n_img, T, H, W, 3, dtype=torch.uint8, device=heat.device)
+    p = _lib.HeatOverlayParams(heat=heat.data_ptr(), cols=cols.data_ptr(), image=image.data_ptr(), lut=lut.data_ptr(), norm=norm.data_ptr(), out=out.data_ptr(),
+                               n_img=n_img, T=T, P=P, gh=gh, gw=gw, H=H, W=W, alpha=float(alpha))
+    _lib.check(lib.sdlt_heatmap_overlay(C.byref(p), _stream()), "sdlt_heatmap_overlay")
+    return norm, out
+
+
 def freeu_tables(H, W, device):
     """The cos / sin tables of sdlt_freeu for an H x W plane: fp32 [2 H + 2 W] = cos(2 pi y / H) | sin(2 pi y / H) | cos(2 pi x / W) | sin(2 pi x / W),
     evaluated in fp64 and rounded once."""

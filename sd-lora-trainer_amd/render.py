@@ -8,7 +8,7 @@ scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-squ
                                          [--sigmas trailing|karras] [--guidance-rescale F] [--guidance-interval SIGMA_LO SIGMA_HI]
                                          [--negative-prompt TEXT] [--freeu B1 B2 S1 S2 [--freeu-v2]]
                                          [--hires-scale F | --hires-size W H] [--hires-strength F] [--hires-steps N] [--hires-upscaler latent|pixel]
-                                         [--hires-resample nearest|bilinear|bicubic]
+                                         [--hires-resample nearest|bilinear|bicubic] [--heatmap [WORD ...]] [--heatmap-grid max|min]
                                          [--unet F] [--text-encoder F] [--text-encoder-2 F] [--vae F] [--tokenizer DIR]
 
 DIR is a checkpoint directory of train(): training_args.json (the job's TrainingConfig), adapter_config.json + the kohya adapter file
@@ -48,6 +48,14 @@ forward the skip features entering the first two decoder stages lose their lowes
 (factor B) - it takes the washed-out, over-smoothed look out of a strong --guidance, and needs no weights.  --freeu-v2 scales the backbone by its own
 normalised channel mean instead of a constant (the authors' current code; ComfyUI's FreeU_V2).  One more launch pair (sdlt_freeu) per affected resnet
 inside the replayed graph; both passes of a hires render use it; without the flag nothing changes.
+
+--heatmap [WORD ...] shows where the prompt's tokens look: per picture one cross-attention heat map for the checkpoint's trigger tokens (when it has any) and one
+per WORD, accumulated inside the replayed graph (sdlt_heatmap_accum after every forward: the mean over steps and hooked layers of the raw scores
+Q K^T / sqrt(d) of the token's context positions - what the token-attention loss of the training run sees, not softmax probabilities), finished by
+sdlt_heatmap_overlay and written beside the picture as <name>_heat_<token>.jpg (all maps of a picture on one colour scale) and <name>_heat.npy (the
+normalised maps, fp32 [T, gh, gw]).  A WORD of several BPE pieces is the sum of its pieces' columns; a WORD the prompt does not hold gives a warning, a zero
+map and the plain picture.  A map takes at most 8 context positions (HEAT_P: the launch's shape, so that one captured graph serves every prompt): a token
+that fills more - a word repeated many times - is mapped by its first 8, with a warning.  --heatmap-grid max (default) takes the finest hooked resolution, min the coarsest.  A hires render maps its second pass.
 """
 import argparse
 import json
@@ -59,6 +67,7 @@ from safetensors.torch import load_file
 
 from . import checkpoint as ckpt
 from . import merge as MG
+from . import ops as _ops
 from . import prompts as P
 from . import topology
 from .config import TrainingConfig
@@ -222,6 +231,46 @@ def encode_init(loaded, init_image, mask_image, size, latent_hw):
     return x0, mask
 
 
+HEAT_P = 8          # context positions per map (a launch shape: one capture serves every prompt)
+
+
+def heat_positions(tokenizers, prompt, words, trigger_tokens, P=HEAT_P, warn=None):
+    """The context positions behind each heat map of `prompt` (the text as it is encoded, learned tokens in place) -> (names, cols): names of the T maps -
+    "trigger" first when trigger_tokens is not empty, then the words - and cols [T][P] int, -1 padded.  The prompt's row is [bos, ids ..., eos, pad ...]
+    cut to 77 as the encoder reads it: id j sits at position 1 + j, and only the first 75 ids survive.  A map collects the positions of every id of
+    trigger_tokens, or of every occurrence of the word's BPE pieces as a run; an absent word: all -1 and a warning.  Every tokenizer of the model
+    (SDXL has two on one vocabulary) must give the same positions."""
+    import warnings
+    warn = warn or (lambda m: warnings.warn(m, stacklevel=3))
+    per_tok = []
+    for tk in tokenizers:
+        ids = tk.tokenize_ids(prompt)[: tk.max_length - 2]
+        rows = []
+        if trigger_tokens:
+            trig = set(tk.convert_tokens_to_ids(list(trigger_tokens)))
+            rows.append([1 + j for j, v in enumerate(ids) if v in trig])
+        for wd in words:
+            run = tk.tokenize_ids(wd)
+            rows.append([1 + j + q for j in range(len(ids) - len(run) + 1) if run and ids[j: j + len(run)] == run for q in range(len(run))])
+        per_tok.append(rows)
+    if any(r != per_tok[0] for r in per_tok[1:]):
+        raise ValueError(f"heatmap: the model's tokenizers place the tokens of {prompt!r} at different positions: {per_tok}")
+    names = (["trigger"] if trigger_tokens else []) + [str(wd) for wd in words]
+    cols = []
+    for name, pos in zip(names, per_tok[0]):
+        pos = sorted(set(pos))
+        if not pos:
+            warn(f"heatmap: {name!r} is not in the prompt {prompt!r} (or lies past its 77-token cut): its map is empty")
+        if len(pos) > P:
+            warn(f"heatmap: {name!r} occupies {len(pos)} positions of {prompt!r}; the first {P} are mapped")
+        cols.append((pos + [-1] * P)[:P])
+    return names, cols
+
+
+def _heat_tag(name):
+    return "".join(ch if ch.isalnum() or ch in "-_" else "_" for ch in name) or "_"
+
+
 HIRES_KEYS = ("scale", "size", "strength", "steps", "upscaler", "resample")
 HIRES_UPSCALERS = ("latent", "pixel")
 
@@ -253,7 +302,7 @@ def hires_args(hires, size, steps, f=8):
 @torch.no_grad()
 def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, guidance_scale=8.0, seed=None, images_per_batch=1, token_scale=None,
            graph=True, n_validation=4, init_image=None, strength=None, mask_image=None, sampler="euler", sigmas="trailing", eta=None,
-           guidance_rescale=0.0, guidance_interval=None, negative_prompt=None, hires=None, freeu=None):
+           guidance_rescale=0.0, guidance_interval=None, negative_prompt=None, hires=None, freeu=None, heatmap=None, heatmap_grid="max"):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
     seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
@@ -269,7 +318,11 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     pass's noise with its first draw and the second pass's with its second; the stochastic samplers key the second pass's per-step noise by
     seed + i + 2^32.  SDXL's size conditioning is the base size in the first pass and the final size in the second.
     freeu: (b1, b2, s1, s2) or dict(b1, b2, s1, s2, version=1) - LatentSampler.sample's (sampler.freeu_args): FreeU in every forward, of both passes of a
-    hires render too (the setting travels with each sample() call, so the rebuilt UNet has it).  -> {scale: [paths]}."""
+    hires render too (the setting travels with each sample() call, so the rebuilt UNet has it).
+    heatmap: None, or a list of words (may be empty): per picture one cross-attention heat map for the trigger tokens (unless the job trained none) and one
+    per word (heat_positions, on the prompt with the learned tokens), accumulated by LatentSampler.sample(heatmap=) on grid heatmap_grid ("max" | "min") -
+    in a hires render by the second pass - and written by ops.heatmap_overlay as `<picture>_heat_<token>.jpg` and `<picture>_heat.npy`.
+    -> {scale: [paths]}."""
     from . import train as T
     from . import vae as _vae
     from PIL import Image
@@ -308,6 +361,25 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         if len(guidance_interval) != 2 or not guidance_interval[0] < guidance_interval[1]:
             raise ValueError(f"guidance_interval must be (sigma_lo, sigma_hi) with sigma_lo < sigma_hi, got {guidance_interval!r}")
     fz = SM.freeu_args(freeu)                                          # (raises before anything is built)
+    hm_names = hm_cols = None
+    if heatmap is not None:
+        words = [heatmap] if isinstance(heatmap, str) else list(heatmap)
+        if heatmap_grid not in SM.HEAT_GRIDS:
+            raise ValueError(f"heatmap_grid must be one of {SM.HEAT_GRIDS}, got {heatmap_grid!r}")
+        triggers = [] if config.disable_ti else list(config.inserting_list_tokens or [])
+        if not triggers and not words:
+            raise ValueError("heatmap: this checkpoint has no trigger tokens (the job did not train any), so there is nothing to map without a word: "
+                             "name the prompt's words to look at (--heatmap WORD ...)")
+        for op in ("heatmap_accum", "heatmap_overlay"):
+            if not hasattr(stack.rt.ops, op):
+                raise NotImplementedError(f"this op table has no {op} kernel: the heat maps are made by that launch (ops.{op})")
+        hm_cols = []
+        for p_ in prompts:                                             # positions in the prompt as it is encoded, learned tokens in place
+            lora_p = P.prompt_pair(p_, config.token_dict, (config.training_attributes or {}).get("trigger_text", "TOK"), config.name, config.concept_mode,
+                                   use_lora=not config.disable_ti)[0]
+            hm_names, c_ = heat_positions(loaded.models.tokenizers, lora_p, words, triggers)
+            hm_cols.append(c_)
+        hm_cols = torch.tensor(hm_cols, dtype=torch.int32)            # [prompts, T, P]
     hi = None
     if hires is not None:
         if mask_image is not None:
@@ -340,24 +412,38 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     os.makedirs(out_dir, exist_ok=True)
     result = {}
 
-    def sample(embeds, idx, lh, lw, px, noise, kw, seed0, steps=steps):
-        """One batch: latents [n, 4, lh, lw].  px = (width, height) of the size conditioning; seed0 + i keys image i's per-step noise."""
+    def sample(embeds, idx, lh, lw, px, noise, kw, seed0, steps=steps, heat=False):
+        """One batch: latents [n, 4, lh, lw].  px = (width, height) of the size conditioning; seed0 + i keys image i's per-step noise.  heat: with the
+        batch's heat maps -> (latents, maps [n, T, gh, gw])."""
         smp = stack.sampler
         sd = (lambda js: dict(seeds=[seed0 + idx[j] for j in js])) if sde else (lambda js: {})
+        hm = (lambda js: dict(heatmap=dict(cols=hm_cols[[idx[j] for j in js]], grid=heatmap_grid))) if heat else (lambda js: {})
         if fused:
             return smp.sample([embeds[i] for i in idx] if n > 1 else embeds[idx[0]], lh, lw, steps=steps, guidance_scale=guidance_scale,
-                              size=(px[1], px[0]), latents=noise, graph=graph, fused=True, n_images=n, **kw, **sd(range(n)))
+                              size=(px[1], px[0]), latents=noise, graph=graph, fused=True, n_images=n, **kw, **sd(range(n)), **hm(range(n)))
         # an op table without the fused kernel: the torch loop, image by image
         one = lambda v, j: v[j:j + 1] if torch.is_tensor(v) and v.shape[0] == n and n > 1 else v  # noqa: E731
-        return torch.cat([smp.sample(embeds[i], lh, lw, steps=steps, guidance_scale=guidance_scale, size=(px[1], px[0]), latents=noise[j:j + 1],
-                                     **{k: one(v, j) for k, v in kw.items()}, **sd([j])) for j, i in enumerate(idx)])
+        outs = [smp.sample(embeds[i], lh, lw, steps=steps, guidance_scale=guidance_scale, size=(px[1], px[0]), latents=noise[j:j + 1],
+                           **{k: one(v, j) for k, v in kw.items()}, **sd([j]), **hm([j])) for j, i in enumerate(idx)]
+        return (torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])) if heat else torch.cat(outs)
 
     def save(lat, idx, s0, scale, paths):
+        lat, heat = lat if isinstance(lat, tuple) else (lat, None)
         for j, i in enumerate(idx[: len(prompts) - s0]):
-            img = _vae.postprocess(stack.decoder.decode(lat[j:j + 1] / cfg["scaling_factor"]))[0].permute(1, 2, 0)
+            chw = _vae.postprocess(stack.decoder.decode(lat[j:j + 1] / cfg["scaling_factor"]))
+            img = chw[0].permute(1, 2, 0)
             arr = (img.float().cpu().numpy() * 255).round().astype("uint8")
             paths.append(os.path.join(out_dir, f"img_{i:02d}_seed{seed + i}_scale{_scale_tag(scale)}.jpg"))
             Image.fromarray(arr).save(paths[-1], format="JPEG", quality=95)
+            if heat is not None:                # all maps of the picture on one scale; the overlays and the normalised maps beside the picture
+                import numpy as np
+                ops = stack.rt.ops
+                lut = getattr(ops, "heatmap_colour_table", _ops.heatmap_colour_table)().to(dev)
+                norm, over = ops.heatmap_overlay(heat[j:j + 1].contiguous(), hm_cols[i:i + 1].to(dev), chw[:1].float().contiguous(), lut)
+                stem = paths[-1][: -len(".jpg")]
+                np.save(stem + "_heat.npy", norm[0].cpu().numpy())
+                for t, name in enumerate(hm_names):
+                    Image.fromarray(over[0, t].cpu().numpy()).save(f"{stem}_heat_{_heat_tag(name)}.jpg", format="JPEG", quality=95)
 
     def finish(scale, paths):
         T.make_validation_img_grid(paths, os.path.join(out_dir, f"grid_scale{_scale_tag(scale)}.jpg"))
@@ -390,7 +476,7 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
                 idx = [min(s0 + j, len(prompts) - 1) for j in range(n)]          # a short last batch repeats its last prompt
                 gens = [torch.Generator(device=dev).manual_seed(seed + i) for i in idx]
                 noise = torch.cat([torch.randn(1, 4, h, w, generator=g, device=dev) for g in gens])
-                lat = sample(embeds, idx, h, w, size, noise, img_kw, seed)
+                lat = sample(embeds, idx, h, w, size, noise, img_kw, seed, heat=hm_cols is not None and hi is None)
                 if hi is None:
                     save(lat, idx, s0, scale, paths)
                 else:                                                            # each generator's second draw: the second pass's noise
@@ -406,7 +492,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
                 paths = []
                 for k1, embeds, s0, idx, x0, noise2 in second:
                     if k1 == k:
-                        lat = sample(embeds, idx, h2, w2, hi["size"], noise2, dict(kw2, init_latents=x0, strength=hi["strength"]), seed + 2 ** 32, hi["steps"])
+                        lat = sample(embeds, idx, h2, w2, hi["size"], noise2, dict(kw2, init_latents=x0, strength=hi["strength"]), seed + 2 ** 32, hi["steps"],
+                                     heat=hm_cols is not None)
                         save(lat, idx, s0, scale, paths)
                 finish(scale, paths)
     finally:
@@ -429,6 +516,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             meta.update(hires=dict(hi, size=list(hi["size"]), base_size=list(hi["base_size"])))
         if fz is not None:
             meta.update(freeu=fz)
+        if hm_cols is not None:
+            meta.update(heatmap=dict(maps=hm_names, grid=heatmap_grid, positions=hm_cols.tolist()))
         json.dump(meta, fh, indent=2)
     return result
 
@@ -467,6 +556,10 @@ def main(argv=None, runtime=None):
     ap.add_argument("--freeu", type=float, nargs=4, metavar=("B1", "B2", "S1", "S2"), default=None,
                     help="FreeU: backbone factors B1, B2 and skip low-frequency factors S1, S2 of the first two decoder stages (e.g. 1.3 1.4 0.9 0.2)")
     ap.add_argument("--freeu-v2", action="store_true", help="with --freeu: scale the backbone by its normalised channel mean (FreeU_V2) instead of a constant")
+    ap.add_argument("--heatmap", nargs="*", metavar="WORD", default=None,
+                    help="write cross-attention heat maps beside every picture: one for the checkpoint's trigger tokens and one per WORD of the prompt; a map takes "
+                    f"the first {HEAT_P} context positions of its token (trigger tokens, or a word's BPE pieces over all its occurrences) and warns about more")
+    ap.add_argument("--heatmap-grid", choices=("max", "min"), default=None, help="resolution of the maps: the finest (default) or the coarsest hooked attention grid")
     ap.add_argument("--device", default="cuda:0")
     for flag, key, what in (("--unet", "path", "base UNet weights or synthetic:<version>"), ("--text-encoder", "text_encoder_path", "text encoder state dict"),
                             ("--text-encoder-2", "text_encoder_2_path", "SDXL's second text encoder"), ("--vae", "vae_path", "AutoencoderKL state dict"),
@@ -485,6 +578,10 @@ def main(argv=None, runtime=None):
         ap.error(f"--guidance-interval needs SIGMA_LO < SIGMA_HI, got {a.guidance_interval[0]} {a.guidance_interval[1]}")
     if a.strength is not None and not 0.0 < a.strength <= 1.0:
         ap.error(f"--strength must be in (0, 1], got {a.strength}")
+    if a.heatmap_grid is not None and a.heatmap is None:
+        ap.error("--heatmap-grid needs --heatmap")
+    if a.heatmap is not None and any(not w_.strip() for w_ in a.heatmap):
+        ap.error("--heatmap takes non-empty words")
     if a.freeu_v2 and a.freeu is None:
         ap.error("--freeu-v2 needs --freeu B1 B2 S1 S2")
     if a.freeu is not None and not all(math.isfinite(v) and v > 0.0 for v in a.freeu):
@@ -515,7 +612,8 @@ def main(argv=None, runtime=None):
                  images_per_batch=a.images_per_batch, graph=not a.eager, n_validation=a.n_validation, init_image=a.init_image, strength=a.strength,
                  mask_image=a.mask, sampler=a.sampler, sigmas=a.sigmas, eta=a.eta, guidance_rescale=a.guidance_rescale,
                  guidance_interval=a.guidance_interval, negative_prompt=a.negative_prompt, **({} if hires is None else dict(hires=hires)),
-                 **({} if freeu is None else dict(freeu=freeu)))
+                 **({} if freeu is None else dict(freeu=freeu)),
+                 **({} if a.heatmap is None else dict(heatmap=a.heatmap, heatmap_grid=a.heatmap_grid or "max")))
     for scale, paths in res.items():
         print(f"lora_scale {scale}: {len(paths)} image(s), {os.path.join(a.out, 'grid_scale' + _scale_tag(scale) + '.jpg')}")
     return res

@@ -392,6 +392,57 @@ def freeu_args(freeu):
     return dict(b1=float(vals[0]), b2=float(vals[1]), s1=float(vals[2]), s2=float(vals[3]), version=int(version))
 
 
+HEAT_GRIDS = ("max", "min")
+
+
+def heatmap_args(heatmap, n, k=None):
+    """sample()'s `heatmap`, checked -> None | dict(cols int32 [n, T, P], grid, weights fp32 [k]).  Keys: cols - integer [n, T] or [n, T, P]: the context
+    positions (0 .. 76) whose score columns make map t of image i, -1: none (a map without any position is an absent token: it stays zero); grid "max"
+    (default: the finest hooked resolution) | "min" (the coarsest: the reference's resize='min' map); weights None (the plain mean over the k steps that
+    run) | one number per step that runs."""
+    if heatmap is None:
+        return None
+    unknown = sorted(set(heatmap) - {"cols", "grid", "weights"})
+    if unknown or "cols" not in heatmap:
+        raise ValueError(f"heatmap: keys cols and optionally grid, weights; unknown {unknown}")
+    cols = torch.as_tensor(heatmap["cols"])
+    if cols.dim() == 2:
+        cols = cols[:, :, None]
+    if cols.dim() != 3 or cols.shape[0] != n or cols.shape[1] < 1 or cols.shape[2] < 1 or cols.is_floating_point():
+        raise ValueError(f"heatmap cols: integer [{n}, T] or [{n}, T, P], got {tuple(cols.shape)} {cols.dtype}")
+    if int(cols.max()) >= 77 or int(cols.min()) < -1:
+        raise ValueError("heatmap cols: context positions 0 .. 76, or -1 for none")
+    grid = heatmap.get("grid") or "max"
+    if grid not in HEAT_GRIDS:
+        raise ValueError(f"heatmap grid must be one of {HEAT_GRIDS}, got {grid!r}")
+    weights = heatmap.get("weights")
+    if k is not None:
+        if weights is None:
+            weights = [1.0 / k] * k
+        weights = [float(v) for v in weights]
+        if len(weights) != k or not all(math.isfinite(v) for v in weights):
+            raise ValueError(f"heatmap weights: {len(weights)} value(s) for the {k} step(s) that run (one finite number each, or None)")
+        weights = torch.tensor(weights, dtype=torch.float32)
+    return dict(cols=cols.to(torch.int32).contiguous(), grid=grid, weights=weights)
+
+
+def heat_entries(rt, h, w):
+    """Runtime.daam_sums after a forward at latent size h x w -> [(sums fp32 [B h_r w_r, CTX_PAD], h_r, w_r, layer count)], finest resolution first."""
+    out = []
+    for N, ent in sorted(rt.daam_sums.items(), reverse=True):
+        k = next((k for k in range(16) if (h >> k) * (w >> k) == N), None)
+        if k is None or ent[1] < 1:
+            raise ValueError(f"heatmap: {N} tokens per image is no level of a {h} x {w} latent")
+        out.append((ent[0], h >> k, w >> k, ent[1]))
+    if not 1 <= len(out) <= 4:
+        raise ValueError(f"heatmap: {len(out)} hooked cross-attention resolution(s); the launch takes 1 .. 4")
+    return out
+
+
+def heat_grid(entries, grid):
+    return entries[0][1:3] if grid == "max" else entries[-1][1:3]
+
+
 def step_table_img(sched, guidance_scale):
     """step_table for ops.sampler_step_img, for a scheduler whose set_timesteps(n, start) has run: the rows of the k = n - start steps that run, and
     row 0 column 1 = the FIRST USED sigma (x = x0 + noise * sigma_0) instead of init_noise_sigma."""
@@ -486,7 +537,7 @@ class LatentSampler:
     @torch.no_grad()
     def sample(self, embeds, h, w, *, steps=25, guidance_scale=8.0, generator=None, size=None, latents=None, graph=False, fused=False, n_images=1,
                init_latents=None, strength=1.0, mask=None, sampler="euler", sigmas="trailing", eta=1.0, seeds=None, guidance_rescale=0.0,
-               guidance_interval=None, freeu=None):
+               guidance_interval=None, freeu=None, heatmap=None):
         """embeds = (c [1,77,D], uc [1,77,D], pc [1,P] | None, puc | None); h, w latent size.  Returns latents [1,4,h,w] fp32
         (still multiplied by the VAE scaling factor, as the pipeline holds them before `vae.decode(latents / scaling_factor)`).
         fused: guidance, the Euler update and the next model input are ONE kernel between two forwards (ops.sampler_step) instead of torch
@@ -510,7 +561,16 @@ class LatentSampler:
         scalar guidance_scale without the other two launches nothing new.
         freeu: None, or (b1, b2, s1, s2) / dict(b1, b2, s1, s2, version=1): FreeU (freeu_args; UNet.set_freeu) in every forward of the trajectory - one
         ops.freeu call in front of each resnet of the first two up-blocks, on all three paths, with every sampler, init latents and mask.  The values are
-        launch arguments, so the graph path keeps one capture per setting."""
+        launch arguments, so the graph path keeps one capture per setting.
+        heatmap: None, or dict(cols, grid="max", weights=None) (heatmap_args): per-token cross-attention heat maps.  After every forward one launch
+        (ops.heatmap_accum) adds the step's weight times the layer mean of the hooked cross-attentions' raw scores Q K^T / sqrt(d) - the positive row
+        of each image, the columns `cols` name, every resolution resampled to the grid - into fp32 maps [n_images, T, gh, gw]; the latents are the
+        same bits with and without.  The result is then (latents, maps).  On all three paths; columns and weights are device memory, so the graph
+        path keeps one capture per (grid, T, P)."""
+        hm = heatmap_args(heatmap, n_images)
+        if hm is not None and not hasattr(self.rt.ops, "heatmap_accum"):
+            raise NotImplementedError("this op table has no heatmap_accum kernel: the heat maps are accumulated by that launch (ops.heatmap_accum), in the "
+                                      "torch loop too")
         fz = freeu_args(freeu)
         if fz is not None or getattr(self.unet, "_freeu", None) is not None:
             self.unet.set_freeu(fz)          # (None: the plain launch sequence; an op table without the kernel raises NotImplementedError here)
@@ -526,7 +586,8 @@ class LatentSampler:
             raise NotImplementedError("this op table has no guidance kernel: a per-step guidance_scale, guidance_rescale and guidance_interval are evaluated "
                                       "by that launch (ops.guidance), in the torch loop too")
         if graph or fused:
-            return self._sample_fused(embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img, sampler, sigmas, eta, seeds, guide)
+            return self._sample_fused(embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img, sampler, sigmas, eta, seeds, guide,
+                                      heatmap)
         assert n_images == 1 and self.rt.B == 2, "the torch loop samples one image on a batch-2 runtime; several images together: fused=True or graph=True"
         rt, u, cfg = self.rt, self.unet, self.unet.cfg
         dev = rt.device
@@ -556,12 +617,21 @@ class LatentSampler:
             words, z = seed_words(seeds, 1, generator, dev), rt.zeros(1, 4, h, w, dtype=F32)
         if guide is not None:                      # the pre-pass reads its row index from a device counter, as in the fused path
             gtab, gctr = guidance_table(s, *guide).to(dev), torch.zeros(2, dtype=torch.int32, device=dev)
+        if hm is not None:                         # the accumulation reads its weight's index from a device counter, as in the fused path
+            hm = heatmap_args(heatmap, 1, len(s.timesteps))
+            hcols, hw_, hctr, heat = hm["cols"].to(dev), hm["weights"].to(dev), torch.zeros(2, dtype=torch.int32, device=dev), None
         x64 = rt.zeros(2 * h * w, 64)
         for i, t in enumerate(s.timesteps):
             xin = s.scale_model_input(x, i)
             x64[:, :4] = xin.permute(0, 2, 3, 1).reshape(h * w, 4).repeat(2, 1).to(x64.dtype)
             tf = torch.full((2,), float(t), device=dev, dtype=F32)
             eps = u.forward(x64, tf, self.ctx, self.pooled, tid, B=2, H=h, W=w)
+            if hm is not None:
+                ents = heat_entries(rt, h, w)
+                if heat is None:
+                    heat = rt.zeros(1, hcols.shape[1], *heat_grid(ents, hm["grid"]), dtype=F32)
+                hctr[0] = i
+                rt.ops.heatmap_accum(ents, hcols, hctr, hw_, heat, row_off=1, row_stride=2)
             if guide is not None:
                 gctr[0] = i
                 e = rt.ops.guidance(eps, gtab, gctr, 1).view(2, h, w, 4).permute(0, 3, 1, 2)[1:2]      # (both rows hold the prediction)
@@ -575,7 +645,7 @@ class LatentSampler:
             if m is not None:                      # the known region, noised to the sigma this step arrived at (0 after the last: init_latents itself)
                 k = x0 + noise * float(s.sigmas[i + 1])
                 x = k + m * (x - k)
-        return x
+        return x if hm is None else (x, heat)
 
     def _scheduler(self, sampler, steps, start, sigmas, eta, exact=False):
         """The scheduler of a trajectory, its timesteps set.  exact (the torch loop where the guidance pre-pass runs): the deterministic samplers in
@@ -659,19 +729,25 @@ class LatentSampler:
             kw["seeds"] = st["seeds"]
         getattr(self.rt.ops, f.op)(eps, sh["x"], sh["x64"], st["tf"], st[f.tab], st["ctr"], **kw)
 
-    def _iteration(self, st, sh, h, w, fam="euler", masked=None, guided=False):
+    def _iteration(self, st, sh, h, w, fam="euler", masked=None, guided=False, heat=None):
         """fam: the step launch (FAMILIES).  masked None: txt2img; False / True: from init latents, without / with the mask (sh["img"] holds them).
         The Euler launch from init latents takes them at every step; the multistep and stochastic launches read neither the init latents nor the
         noise without a mask, whatever the trajectory started from.  guided: ops.guidance rewrites eps first (row ctr[0] of st["gtab"]); the step
-        launch is the same."""
+        launch is the same.  heat (a dict of sh["heat"]): ops.heatmap_accum reads the forward's score sums first, with the weight of row ctr[0] of
+        st["hw"]; its maps are allocated at the first iteration (the eager warm-up of a capture), when the forward has told the resolutions."""
         u = self.unet
         eps = u.forward(sh["x64"], st["tf"], self.ctx, self.pooled, st["tid"] if u.cfg["addition"] else None, B=2 * self.n, H=h, W=w)
+        if heat is not None:
+            ents = heat_entries(self.rt, h, w)
+            if heat["heat"] is None:
+                heat["heat"] = self.rt.zeros(self.n, heat["cols"].shape[1], *heat_grid(ents, heat["grid"]), dtype=F32)
+            self.rt.ops.heatmap_accum(ents, heat["cols"], st["ctr"], st["hw"], heat["heat"], row_off=1, row_stride=2)
         if guided:
             self.rt.ops.guidance(eps, st["gtab"], st["ctr"], self.n)
         im = sh["img"] if masked or fam == "img" else dict(x0=None, noise=None, mask=None)
         self._step_launch(fam, st, sh, eps, im["x0"], im["noise"], im["mask"] if masked else None)
 
-    def _graph(self, st, sh, h, w, fam="euler", masked=None, guided=False):
+    def _graph(self, st, sh, h, w, fam="euler", masked=None, guided=False, heat=None):
         """The hipGraph of one iteration for this shape and the adapter scale in effect.  The scale is a launch argument of every adapted GEMM
         (baked by capture), hence part of the key; adapters, DoRA factors, token rows, conditioning, table and counter are device memory.
         Each family's step launch is another kernel: its captures live in a dict of their own (FAMILIES), keyed - txt2img Euler apart - by the mask
@@ -679,7 +755,9 @@ class LatentSampler:
         Step count, strength, schedule kind, coefficients, which stochastic sampler and eta are in the table; init latents, noise, mask, the previous
         denoised value and the seeds in persistent buffers: one capture serves all of them.
         guided: the captures with the guidance pre-pass in them, in a fifth dict, keyed by the key the iteration has above plus its family, so they
-        neither collide with those captures nor evict them; the scales, phi and the interval are in st["gtab"]: one capture per family serves all."""
+        neither collide with those captures nor evict them; the scales, phi and the interval are in st["gtab"]: one capture per family serves all.
+        heat: the captures with ops.heatmap_accum in them are keyed by ("heat", grid, T, P) as well - the launch's shape; which columns and which
+        step weights are device memory."""
         a, f = self.unet.arena, FAMILIES[fam]
         key = (h, w, self.n, None if a is None else float(a.scale), bool(a is not None and a.dora))
         if f.suffix is not None:
@@ -687,6 +765,8 @@ class LatentSampler:
         fu = getattr(self.unet, "_freeu", None)
         if fu is not None:                                # FreeU's b, s and version are launch arguments of ops.freeu: a capture per setting
             key += (("freeu",) + fu,)
+        if heat is not None:
+            key += (("heat", heat["grid"]) + tuple(heat["cols"].shape[1:]),)
         graphs = getattr(self, f.graphs)
         if guided:
             key, graphs = key + (fam,), self._guided_graphs
@@ -701,11 +781,11 @@ class LatentSampler:
         side.wait_stream(torch.cuda.current_stream())
         seq = None
         with torch.cuda.stream(side):
-            self._iteration(st, sh, h, w, fam, masked, guided)     # eager warm-up: every persistent buffer and packed-weight copy exists before the capture
+            self._iteration(st, sh, h, w, fam, masked, guided, heat)     # eager warm-up: every persistent buffer and packed-weight copy exists before the capture
             if prefetch:                                  # next-weight hints of the wave-split-K products, recorded from one eager pass (step.TrainStep.capture)
                 ops.pf_record_begin()
                 try:
-                    self._iteration(st, sh, h, w, fam, masked, guided)
+                    self._iteration(st, sh, h, w, fam, masked, guided, heat)
                 finally:
                     seq = ops.pf_record_end()
         torch.cuda.current_stream().wait_stream(side)
@@ -714,7 +794,7 @@ class LatentSampler:
             if seq:
                 ops.pf_replay_begin(seq)
             try:
-                self._iteration(st, sh, h, w, fam, masked, guided)
+                self._iteration(st, sh, h, w, fam, masked, guided, heat)
             finally:
                 if seq:
                     ops.pf_replay_end()
@@ -722,7 +802,7 @@ class LatentSampler:
         return g
 
     def _sample_fused(self, embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img=None, sampler="euler", sigmas="trailing",
-                      eta=1.0, seeds=None, guide=None):
+                      eta=1.0, seeds=None, guide=None, heatmap=None):
         rt, cfg, n = self.rt, self.unet.cfg, self.n
         guided = guide is not None
         if guided:
@@ -776,19 +856,30 @@ class LatentSampler:
         if f.seeds:                                       # after the initial latents, as in the torch loop; a captured launch holds the buffer
             st["seeds"].copy_(seed_words(seeds, n, generator, dev))
         x0, noise, masked = self._load_image_state(sh, h, w, img, noise)
+        heat = None
+        if heatmap is not None:                           # persistent buffers, rewritten per trajectory: a captured launch holds their pointers
+            hm = heatmap_args(heatmap, n, steps)
+            if "hw" not in st:
+                st["hw"] = rt.zeros(TABLE_ROWS, dtype=F32)
+            st["hw"][:steps].copy_(hm["weights"])
+            hkey = (hm["grid"],) + tuple(hm["cols"].shape[1:])
+            heat = sh.setdefault("heat", {}).setdefault(hkey, dict(grid=hm["grid"], cols=torch.zeros_like(hm["cols"], device=dev), heat=None))
+            heat["cols"].copy_(hm["cols"])
         init = lambda: self._step_launch(fam, st, sh, None, x0=x0, noise=noise)  # noqa: E731
         with self._scope():
             g = None
             if graph:
                 init()                                    # (a defined state for the warm-up passes)
-                g = self._graph(st, sh, h, w, fam, masked, guided)
+                g = self._graph(st, sh, h, w, fam, masked, guided, heat)
             init()
+            if heat is not None and heat["heat"] is not None:      # (the warm-up passes of a capture accumulated into it)
+                heat["heat"].zero_()
             for _ in range(steps):                        # no host read in here: the step index lives in ctr, its scalars in the table
                 if g is not None:
                     g.replay()
                 else:
-                    self._iteration(st, sh, h, w, fam, masked, guided)
-        return sh["x"].clone()
+                    self._iteration(st, sh, h, w, fam, masked, guided, heat)
+        return sh["x"].clone() if heat is None else (sh["x"].clone(), heat["heat"].clone())
 
 
 def render_images(sampler, decoder, embeds_list, render_size, out_dir, train_step, seed, *, scaling_factor, lora_scale,
