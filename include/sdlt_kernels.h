@@ -760,6 +760,22 @@ typedef struct {
 } sdlt_heatmap_overlay_params;
 int sdlt_heatmap_overlay(const sdlt_heatmap_overlay_params* p, void* stream);
 
+/* sdlt_token_pool : y = pool_f(LayerNorm(x)) in one launch - the key / value rows of a self-attention that takes its keys from a spatially downsampled
+ * copy of the tokens ("Token Downsampling", Smith et al. 2024; render.py: `kv_downsample`; inference only).  x bf16 [B H W, C] (row stride ldx): the
+ * block's residual stream, NHWC rows, image b = rows b H W .. ; gamma, beta fp32 [C] and eps: the LayerNorm of sdlt_layernorm_fwd (same lane layout, the
+ * same fp32 statistics: mean, then the centred variance).  f >= 1: Ho = ceil(H / f), Wo = ceil(W / f), Nk = Ho Wo.  y bf16 [B Nkp, C] (row stride ldy):
+ * image b owns rows b Nkp .. ; its first Nk rows are the pooled tokens in (oy, ox) order, its Nkp - Nk pad rows are written as ZEROS by this launch
+ * (sdlt_attn_fwd loads whole rows up to Nkp and masks the scores past Nk: Nkp is a multiple of 8, its rule for padded rows per batch).
+ *   mode 0 (nearest): y[oy, ox] = LN(x)[oy f, ox f].  Only the sampled rows are read.
+ *   mode 1 (area):    y[oy, ox] = fp32 mean of LN(x)[r, c] over oy f <= r < min(H, oy f + f), ox f <= c < min(W, ox f + f), added in (r, c) order and
+ *                     divided by the number of rows really inside: avg_pool2d(ceil_mode=True, count_include_pad=False).
+ * One rounding to bf16, at the store; f == 1 gives sdlt_layernorm_fwd's rows in either mode.  One wave per output row, no atomics, no workspace: the
+ * result repeats bit for bit.  A null pointer, B, H or W < 1, C not a multiple of 8 in 8 .. 1536, f < 1 or above H or W, Nkp < Nk or no multiple of 8,
+ * >= 2^31 rows on either side, a leading dimension below C, y overlapping x (-1); x, y, gamma or beta not 16-byte aligned, a leading dimension that is no
+ * multiple of 8 (-2); an unknown mode (-4): the code is returned and nothing is launched. */
+int sdlt_token_pool(const void* x, int64_t ldx, int32_t B, int32_t H, int32_t W, int32_t C, const float* gamma, const float* beta, float eps,
+                    int32_t f, int32_t mode, void* y, int64_t ldy, int32_t Nkp, void* stream);
+
 /* out[M,C] = a + b on strided 2-D bf16 views (gradient fan-in of the UNet skip connections). */
 int sdlt_add2d(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int32_t M, int32_t C, void* stream);
 

@@ -1407,6 +1407,35 @@ def freeu(h, skip, h_out, skip_out, tabs, ws, *, B, H, W, b, s, version=1):
     return h_out, skip_out
 
 
+TOKEN_POOL_MODES = ("nearest", "area")
+
+
+def token_pool_rows(H, W, f):
+    """(Ho, Wo, Nk, Nkp) of token_pool on an H x W grid: Ho = ceil(H / f), Wo = ceil(W / f), Nk = Ho Wo, Nkp = Nk rounded up to the 8 rows attn_fwd wants
+    every batch's keys to start on (sdlt_attn_fwd: Nkp % 8)."""
+    Ho, Wo = -(-H // f), -(-W // f)
+    return Ho, Wo, Ho * Wo, (Ho * Wo + 7) // 8 * 8
+
+
+def token_pool(x, y, *, B, H, W, gamma, beta, eps, f, mode):
+    """sdlt_token_pool: y bf16 [B Nkp, C] = pool_f(LayerNorm(x)) of x bf16 [B H W, C] (NHWC rows, any leading dimension) in one launch - mode "nearest" | 0:
+    the normalised row (oy f, ox f); "area" | 1: the fp32 mean of the normalised rows of the in-image part of each f x f window (partial edge windows
+    divide by their own row count).  (Ho, Wo, Nk, Nkp) = token_pool_rows(H, W, f); the Nkp - Nk pad rows of every image are written as zeros.  gamma,
+    beta fp32 [C].  One rounding to bf16; bitwise repeatable."""
+    lib = _lib.load()
+    _chk2(x), _chk2(y), _chk2(gamma, F32), _chk2(beta, F32)
+    mode = TOKEN_POOL_MODES.index(mode) if mode in TOKEN_POOL_MODES else mode
+    assert mode in (0, 1), f"mode must be one of {TOKEN_POOL_MODES} (or 0 / 1), got {mode!r}"
+    assert B >= 1 and 1 <= f <= min(H, W), f"token_pool: f={f} on a {H} x {W} grid (1 <= f <= H, W)"
+    Cc = x.shape[1]
+    Nkp = token_pool_rows(H, W, f)[3]
+    assert x.shape[0] == B * H * W and tuple(y.shape) == (B * Nkp, Cc), f"x {tuple(x.shape)} for B={B} H={H} W={W}; y {tuple(y.shape)}, wanted {(B * Nkp, Cc)}"
+    assert gamma.is_contiguous() and beta.is_contiguous() and gamma.numel() == Cc and beta.numel() == Cc, "gamma, beta: contiguous fp32 [C]"
+    assert Cc % 8 == 0 and x.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0 and _ld(x) % 8 == 0 and _ld(y) % 8 == 0, "16-byte rows: C, ld % 8, aligned pointers"
+    _lib.check(lib.sdlt_token_pool(_p(x), _ld(x), B, H, W, Cc, _p(gamma), _p(beta), float(eps), int(f), int(mode), _p(y), _ld(y), Nkp, _stream()), "sdlt_token_pool")
+    return y
+
+
 def masked_mse_fwd_bwd(pred, noise, noisy, mask, timesteps, alphas_cumprod, sums, loss_out, dpred, *, snr_gamma, v_prediction=False,
                        loss_scale=1.0):
     lib = _lib.load()

@@ -9,6 +9,7 @@ scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-squ
                                          [--negative-prompt TEXT] [--freeu B1 B2 S1 S2 [--freeu-v2]]
                                          [--hires-scale F | --hires-size W H] [--hires-strength F] [--hires-steps N] [--hires-upscaler latent|pixel]
                                          [--hires-resample nearest|bilinear|bicubic] [--heatmap [WORD ...]] [--heatmap-grid max|min]
+                                         [--kv-downsample F [F2 ...]] [--kv-downsample-mode nearest|area] [--kv-downsample-pass hires|all]
                                          [--unet F] [--text-encoder F] [--text-encoder-2 F] [--vae F] [--tokenizer DIR]
 
 DIR is a checkpoint directory of train(): training_args.json (the job's TrainingConfig), adapter_config.json + the kohya adapter file
@@ -56,6 +57,14 @@ sdlt_heatmap_overlay and written beside the picture as <name>_heat_<token>.jpg (
 normalised maps, fp32 [T, gh, gw]).  A WORD of several BPE pieces is the sum of its pieces' columns; a WORD the prompt does not hold gives a warning, a zero
 map and the plain picture.  A map takes at most 8 context positions (HEAT_P: the launch's shape, so that one captured graph serves every prompt): a token
 that fills more - a word repeated many times - is mapped by its first 8, with a warning.  --heatmap-grid max (default) takes the finest hooked resolution, min the coarsest.  A hires render maps its second pass.
+
+--kv-downsample F [F2 ...] is "Token Downsampling" (Smith et al. 2024) for large renders: the self-attentions keep every query but take their keys and
+values from the tokens downsampled by F per axis, which cuts their score work and their to_k | to_v products by F^2 and needs no weights.  The factors
+count from the largest token grid down: 2 is the largest grid only, 4 2 is 4 there and 2 on the next.  --kv-downsample-mode nearest (default, the
+paper's) takes every F-th token, area the mean of each F x F window.  One more launch (sdlt_token_pool: LayerNorm and pooling fused) per affected
+self-attention inside the replayed graph.  It is meant for the second pass of a hires render - where the grids are large, and after the first pass has
+decided the composition - so --kv-downsample-pass defaults to hires and the flag without --hires-scale / --hires-size is an error; all uses it in
+every pass.  Without the flag nothing changes.
 """
 import argparse
 import json
@@ -273,6 +282,7 @@ def _heat_tag(name):
 
 HIRES_KEYS = ("scale", "size", "strength", "steps", "upscaler", "resample")
 HIRES_UPSCALERS = ("latent", "pixel")
+KV_PASSES = ("hires", "all")      # which passes of a render carry kv_downsample
 
 
 def hires_args(hires, size, steps, f=8):
@@ -302,7 +312,8 @@ def hires_args(hires, size, steps, f=8):
 @torch.no_grad()
 def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, guidance_scale=8.0, seed=None, images_per_batch=1, token_scale=None,
            graph=True, n_validation=4, init_image=None, strength=None, mask_image=None, sampler="euler", sigmas="trailing", eta=None,
-           guidance_rescale=0.0, guidance_interval=None, negative_prompt=None, hires=None, freeu=None, heatmap=None, heatmap_grid="max"):
+           guidance_rescale=0.0, guidance_interval=None, negative_prompt=None, hires=None, freeu=None, heatmap=None, heatmap_grid="max",
+           kv_downsample=None, kv_downsample_mode="nearest", kv_downsample_pass="hires"):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
     seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
@@ -322,6 +333,10 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     heatmap: None, or a list of words (may be empty): per picture one cross-attention heat map for the trigger tokens (unless the job trained none) and one
     per word (heat_positions, on the prompt with the learned tokens), accumulated by LatentSampler.sample(heatmap=) on grid heatmap_grid ("max" | "min") -
     in a hires render by the second pass - and written by ops.heatmap_overlay as `<picture>_heat_<token>.jpg` and `<picture>_heat.npy`.
+    kv_downsample: integer factors, largest self-attention token grid first - (2,), (4, 2) - with kv_downsample_mode "nearest" | "area":
+    LatentSampler.sample's key / value token downsampling (sampler.kv_downsample_args; UNet.set_kv_downsample).  kv_downsample_pass "hires" (default):
+    only the second pass of a hires render carries it - that is where the self-attentions are large, and the first pass decides the composition -
+    so without `hires` it is refused; "all": every pass.
     -> {scale: [paths]}."""
     from . import train as T
     from . import vae as _vae
@@ -380,6 +395,16 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             hm_names, c_ = heat_positions(loaded.models.tokenizers, lora_p, words, triggers)
             hm_cols.append(c_)
         hm_cols = torch.tensor(hm_cols, dtype=torch.int32)            # [prompts, T, P]
+    kd = SM.kv_downsample_args(kv_downsample, kv_downsample_mode)    # (raises before anything is built)
+    if kv_downsample_pass not in KV_PASSES:
+        raise ValueError(f"kv_downsample_pass must be one of {KV_PASSES}, got {kv_downsample_pass!r}")
+    if kd is not None:
+        if kv_downsample_pass == "hires" and hires is None:
+            raise ValueError("kv_downsample applies to the second pass of a hires render by default and this render has none: pass "
+                             "kv_downsample_pass='all' (--kv-downsample-pass all) to use it in a single-pass render")
+        if not hasattr(stack.rt.ops, "token_pool"):
+            raise NotImplementedError("this op table has no token_pool kernel (sdlt_token_pool): kv_downsample pools the keys' tokens by that launch (ops.token_pool)")
+    kd_kw = {} if kd is None else dict(kv_downsample=kd[0], kv_downsample_mode=kd[1])
     hi = None
     if hires is not None:
         if mask_image is not None:
@@ -396,6 +421,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         img_kw.update(eta=eta)
     if fz is not None:
         img_kw.update(freeu=fz)
+    if kv_downsample_pass == "all":
+        img_kw.update(kd_kw)
     if init_image is None:
         if mask_image is not None:
             raise ValueError("mask_image needs init_image: the region to keep is taken from it")
@@ -464,7 +491,7 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         w2, h2 = hi["size"][0] // f, hi["size"][1] // f
         if not hasattr(stack.rt.ops, "resize_planes"):
             SM.upscale_latents(stack.rt.ops, None, h2, w2, hi["resample"])      # (raises: no kernel, no fallback)
-        kw2 = {k: v for k, v in img_kw.items() if k not in ("init_latents", "strength", "mask")}
+        kw2 = dict({k: v for k, v in img_kw.items() if k not in ("init_latents", "strength", "mask")}, **kd_kw)      # (kv_downsample: the second pass has it either way)
         enc = _vae_encoder(loaded) if hi["upscaler"] == "pixel" else None
         second = []                             # (index of the scale, embeds, first prompt of the batch, idx, enlarged latents, second noise)
     try:
@@ -516,6 +543,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             meta.update(hires=dict(hi, size=list(hi["size"]), base_size=list(hi["base_size"])))
         if fz is not None:
             meta.update(freeu=fz)
+        if kd is not None:
+            meta.update(kv_downsample=dict(factors=list(kd[0]), mode=kd[1], passes=kv_downsample_pass))
         if hm_cols is not None:
             meta.update(heatmap=dict(maps=hm_names, grid=heatmap_grid, positions=hm_cols.tolist()))
         json.dump(meta, fh, indent=2)
@@ -560,6 +589,12 @@ def main(argv=None, runtime=None):
                     help="write cross-attention heat maps beside every picture: one for the checkpoint's trigger tokens and one per WORD of the prompt; a map takes "
                     f"the first {HEAT_P} context positions of its token (trigger tokens, or a word's BPE pieces over all its occurrences) and warns about more")
     ap.add_argument("--heatmap-grid", choices=("max", "min"), default=None, help="resolution of the maps: the finest (default) or the coarsest hooked attention grid")
+    ap.add_argument("--kv-downsample", type=int, nargs="+", metavar="F", default=None,
+                    help="key / value token downsampling in the self-attentions: integer factors per axis, largest token grid first (2: the largest grid only; "
+                    "4 2: 4 there, 2 on the next); queries stay at full resolution")
+    ap.add_argument("--kv-downsample-mode", choices=("nearest", "area"), default=None, help="with --kv-downsample: take every F-th token (default), or the mean of each F x F window")
+    ap.add_argument("--kv-downsample-pass", choices=KV_PASSES, default=None,
+                    help="with --kv-downsample: hires (default) - only the second pass of a --hires-scale / --hires-size render; all - every pass")
     ap.add_argument("--device", default="cuda:0")
     for flag, key, what in (("--unet", "path", "base UNet weights or synthetic:<version>"), ("--text-encoder", "text_encoder_path", "text encoder state dict"),
                             ("--text-encoder-2", "text_encoder_2_path", "SDXL's second text encoder"), ("--vae", "vae_path", "AutoencoderKL state dict"),
@@ -586,6 +621,15 @@ def main(argv=None, runtime=None):
         ap.error("--freeu-v2 needs --freeu B1 B2 S1 S2")
     if a.freeu is not None and not all(math.isfinite(v) and v > 0.0 for v in a.freeu):
         ap.error(f"--freeu takes four finite positive numbers, got {' '.join(str(v) for v in a.freeu)}")
+    if a.kv_downsample is None and (a.kv_downsample_mode is not None or a.kv_downsample_pass is not None):
+        ap.error("--kv-downsample-mode and --kv-downsample-pass need --kv-downsample F [F2 ...]")
+    if a.kv_downsample is not None and not all(f_ >= 1 for f_ in a.kv_downsample):
+        ap.error(f"--kv-downsample takes integer factors >= 1, got {' '.join(str(f_) for f_ in a.kv_downsample)}")
+    if a.kv_downsample is not None and (a.kv_downsample_pass or "hires") == "hires" and a.hires_scale is None and a.hires_size is None:
+        ap.error("--kv-downsample applies to the second pass of a hires render by default and this render has none (--hires-scale / --hires-size): "
+                 "pass --kv-downsample-pass all to use it in a single-pass render")
+    kvd = {} if a.kv_downsample is None else dict(kv_downsample=tuple(a.kv_downsample), kv_downsample_mode=a.kv_downsample_mode or "nearest",
+                                                   kv_downsample_pass=a.kv_downsample_pass or "hires")
     freeu = None if a.freeu is None else dict(zip(("b1", "b2", "s1", "s2"), a.freeu), version=2 if a.freeu_v2 else 1)
     hires = None
     if a.hires_scale is not None and a.hires_size is not None:
@@ -612,7 +656,7 @@ def main(argv=None, runtime=None):
                  images_per_batch=a.images_per_batch, graph=not a.eager, n_validation=a.n_validation, init_image=a.init_image, strength=a.strength,
                  mask_image=a.mask, sampler=a.sampler, sigmas=a.sigmas, eta=a.eta, guidance_rescale=a.guidance_rescale,
                  guidance_interval=a.guidance_interval, negative_prompt=a.negative_prompt, **({} if hires is None else dict(hires=hires)),
-                 **({} if freeu is None else dict(freeu=freeu)),
+                 **({} if freeu is None else dict(freeu=freeu)), **kvd,
                  **({} if a.heatmap is None else dict(heatmap=a.heatmap, heatmap_grid=a.heatmap_grid or "max")))
     for scale, paths in res.items():
         print(f"lora_scale {scale}: {len(paths)} image(s), {os.path.join(a.out, 'grid_scale' + _scale_tag(scale) + '.jpg')}")

@@ -373,6 +373,24 @@ def upscale_latents(ops, lat, H, W, mode="bilinear"):
     return ops.resize_planes(lat, out, RESAMPLE.index(mode))
 
 
+KV_MODES = ("nearest", "area")      # ops.token_pool's modes 0, 1
+
+
+def kv_downsample_args(factors, mode="nearest"):
+    """sample()'s / render()'s `kv_downsample`, checked -> None | (factors, mode).  factors: None, an int or a sequence of ints >= 1, the largest
+    self-attention token grid first (UNet.set_kv_downsample); trailing ones are dropped, and nothing but ones is None: off.  mode "nearest" | "area"."""
+    if mode not in KV_MODES:
+        raise ValueError(f"kv_downsample_mode must be one of {KV_MODES}, got {mode!r}")
+    if factors is None:
+        return None
+    fs = [factors] if isinstance(factors, int) else list(factors)
+    if not all(isinstance(f, int) and not isinstance(f, bool) and f >= 1 for f in fs):
+        raise ValueError(f"kv_downsample takes integer factors >= 1, largest token grid first, got {factors!r}")
+    while fs and fs[-1] == 1:
+        fs.pop()
+    return (tuple(fs), mode) if fs else None
+
+
 def freeu_args(freeu):
     """sample()'s / render()'s `freeu`, checked -> None | dict(b1, b2, s1, s2, version).  None; four numbers (b1, b2, s1, s2) - diffusers'
     enable_freeu order, version 1 - or a dict with those keys and optionally version (1: diffusers' constant backbone factor; 2: the authors' current
@@ -506,7 +524,9 @@ class LatentSampler:
     reference's render loop, up to the latents.  `unet` is an inference instance built for batch 2 (negative | positive, the
     order diffusers concatenates them in); its LoRA arena holds the trained adapters."""
 
-    def __init__(self, rt, unet, prediction_type="epsilon"):
+    def __init__(self, rt, unet, prediction_type="epsilon", kv_downsample=None, kv_downsample_mode="nearest"):
+        """kv_downsample / kv_downsample_mode: the default of sample()'s keywords of the same names (kv_downsample_args)."""
+        self.kv_downsample = kv_downsample_args(kv_downsample, kv_downsample_mode)
         assert rt.B >= 2 and rt.B % 2 == 0, "classifier-free guidance runs the negative and the positive prompt of every image as one pair: an even batch"
         self.rt, self.unet = rt, unet
         self.n = rt.B // 2                 # images sampled together (fused / graph path); image j = rows 2j (negative), 2j + 1 (positive)
@@ -526,6 +546,11 @@ class LatentSampler:
         # ms_coefficients with d = 0)
         self.sched_exact = dict(euler=EulerStepOrder(prediction_type=prediction_type), dpmpp_2m=DpmSolverPP2MSDE(prediction_type=prediction_type, eta=0.0))
 
+    def _fwd_kw(self):
+        """Keywords of the UNet forward: with key / value downsampling set it is declared an inference forward (UNet.forward refuses a training one);
+        without, the call is the plain one."""
+        return {} if getattr(self.unet, "_kv_ds", None) is None else {"train": False}
+
     def set_lora_scale(self, lora_scale, train_scale=None):
         """set_adapter_scales (checkpoint.py:31-55): every adapter's contribution is multiplied by lora_scale."""
         a = self.unet.arena
@@ -537,7 +562,7 @@ class LatentSampler:
     @torch.no_grad()
     def sample(self, embeds, h, w, *, steps=25, guidance_scale=8.0, generator=None, size=None, latents=None, graph=False, fused=False, n_images=1,
                init_latents=None, strength=1.0, mask=None, sampler="euler", sigmas="trailing", eta=1.0, seeds=None, guidance_rescale=0.0,
-               guidance_interval=None, freeu=None, heatmap=None):
+               guidance_interval=None, freeu=None, heatmap=None, kv_downsample=None, kv_downsample_mode=None):
         """embeds = (c [1,77,D], uc [1,77,D], pc [1,P] | None, puc | None); h, w latent size.  Returns latents [1,4,h,w] fp32
         (still multiplied by the VAE scaling factor, as the pipeline holds them before `vae.decode(latents / scaling_factor)`).
         fused: guidance, the Euler update and the next model input are ONE kernel between two forwards (ops.sampler_step) instead of torch
@@ -566,7 +591,16 @@ class LatentSampler:
         (ops.heatmap_accum) adds the step's weight times the layer mean of the hooked cross-attentions' raw scores Q K^T / sqrt(d) - the positive row
         of each image, the columns `cols` name, every resolution resampled to the grid - into fp32 maps [n_images, T, gh, gw]; the latents are the
         same bits with and without.  The result is then (latents, maps).  On all three paths; columns and weights are device memory, so the graph
-        path keeps one capture per (grid, T, P)."""
+        path keeps one capture per (grid, T, P).
+        kv_downsample: a tuple of integer factors, largest self-attention token grid first - (2,), (4, 2) - with kv_downsample_mode "nearest" | "area":
+        key / value token downsampling (UNet.set_kv_downsample: one ops.token_pool launch per affected self-attention, whose k | v products and score
+        work shrink by factor^2) in every forward of the trajectory, on all three paths.  None: the constructor's setting; () or all ones: off, and
+        the launch sequence is the plain one.  The setting is part of the capture key."""
+        kd = self.kv_downsample
+        if kv_downsample is not None or kv_downsample_mode is not None:
+            kd = kv_downsample_args(kd[0] if kv_downsample is None and kd is not None else kv_downsample, kv_downsample_mode or (kd[1] if kd is not None else "nearest"))
+        if kd != getattr(self.unet, "_kv_ds", None):
+            self.unet.set_kv_downsample(*(kd or (None,)))      # (an op table without the kernel raises NotImplementedError here)
         hm = heatmap_args(heatmap, n_images)
         if hm is not None and not hasattr(self.rt.ops, "heatmap_accum"):
             raise NotImplementedError("this op table has no heatmap_accum kernel: the heat maps are accumulated by that launch (ops.heatmap_accum), in the "
@@ -625,7 +659,7 @@ class LatentSampler:
             xin = s.scale_model_input(x, i)
             x64[:, :4] = xin.permute(0, 2, 3, 1).reshape(h * w, 4).repeat(2, 1).to(x64.dtype)
             tf = torch.full((2,), float(t), device=dev, dtype=F32)
-            eps = u.forward(x64, tf, self.ctx, self.pooled, tid, B=2, H=h, W=w)
+            eps = u.forward(x64, tf, self.ctx, self.pooled, tid, B=2, H=h, W=w, **self._fwd_kw())
             if hm is not None:
                 ents = heat_entries(rt, h, w)
                 if heat is None:
@@ -736,7 +770,7 @@ class LatentSampler:
         launch is the same.  heat (a dict of sh["heat"]): ops.heatmap_accum reads the forward's score sums first, with the weight of row ctr[0] of
         st["hw"]; its maps are allocated at the first iteration (the eager warm-up of a capture), when the forward has told the resolutions."""
         u = self.unet
-        eps = u.forward(sh["x64"], st["tf"], self.ctx, self.pooled, st["tid"] if u.cfg["addition"] else None, B=2 * self.n, H=h, W=w)
+        eps = u.forward(sh["x64"], st["tf"], self.ctx, self.pooled, st["tid"] if u.cfg["addition"] else None, B=2 * self.n, H=h, W=w, **self._fwd_kw())
         if heat is not None:
             ents = heat_entries(self.rt, h, w)
             if heat["heat"] is None:
@@ -767,6 +801,9 @@ class LatentSampler:
             key += (("freeu",) + fu,)
         if heat is not None:
             key += (("heat", heat["grid"]) + tuple(heat["cols"].shape[1:]),)
+        kd = getattr(self.unet, "_kv_ds", None)
+        if kd is not None:                                # key / value downsampling changes the launch sequence: a capture per (factors, mode)
+            key += (("kv_downsample",) + kd,)
         graphs = getattr(self, f.graphs)
         if guided:
             key, graphs = key + (fam,), self._guided_graphs

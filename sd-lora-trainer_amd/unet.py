@@ -974,11 +974,58 @@ class Attention(_Module):
         self.d = self.C // heads
         self.scale = 1.0 / math.sqrt(self.d)
 
-    def forward(self, x, ctx, B, N, residual, parts_for=None):
-        """x [B*N, C]; ctx [B*CTX_PAD, D] for cross attention.  Returns residual + to_out(attn)."""
+    _kv = None          # (factor > 1, mode) of UNet.set_kv_downsample: this self-attention takes k | v from pooled tokens (inference only)
+    norm = None         # the LayerNorm in front of a self-attention (TransformerBlock.norm1): the pooling launch normalises with it
+
+    def _kv_forward(self, x, raw, B, N, grid):
+        """Key / value token downsampling (UNet.set_kv_downsample): q from all N tokens by the route it has without the option - the stack's operands
+        of to_q, the folded LayerNorm and ops.gemm's routing included; k | v by to_k | to_v (plain weights, their adapters at the scale in effect) from
+        ops.token_pool(raw): the pooled LayerNorm rows of the block's residual stream, pad rows zero.  -> q, k, v, Nk, Nkp."""
+        rt, C, st = self.rt, self.C, self.stack
+        f, mode = self._kv
+        if grid is None or grid[0] * grid[1] != N:
+            raise ValueError(f"kv_downsample: {self.name} needs its token grid (H, W) with H W = {N}, got {grid!r}")
+        H, W = grid
+        if H < f or W < f:
+            raise ValueError(f"kv_downsample: factor {f} does not fit the {H} x {W} token grid of {self.name} (a larger image, or a smaller factor)")
+        Ho, Wo, Nk, Nkp = getattr(rt.ops, "token_pool_rows", _ops.token_pool_rows)(H, W, f)
+        n, Mq = self.norm, B * N
+        pooled = rt.ops.token_pool(raw, self.buf(("kv_pool", B * Nkp), B * Nkp, C), B=B, H=H, W=W, gamma=n.gamma, beta=n.beta, eps=n.eps, f=f, mode=mode)
+        kv = self.buf(("kv_ds", B * Nkp), B * Nkp, 2 * C)       # (keyed by their rows: another factor on the same instance is another pair of buffers)
+        k, v = kv[:, :C], kv[:, C:]
+        if st.wide or st.dora or st.trainer is not None:        # no stacked operand serves a subset of the members there: member by member
+            q = self.to_q.forward(x, out=self.buf("q_ds", Mq, C), train=False)
+            self.to_k.forward(pooled, out=k, train=False)
+            self.to_v.forward(pooled, out=v, train=False)
+            return q, k, v, Nk, Nkp
+        Rp = st.arena.Rp if st.has_lora else 0
+        q = self.buf("q_ds", Mq, C)
+        lora, kw = None, {}
+        if st.has_lora:
+            lora = ((st.A_cat if st.ln is None else st.ln_Ag)[:Rp], st.B_cat[:C], st.arena.scale, None)
+        if st.ln is not None:
+            kw["ln"] = (st.ln_c1[:C], st.ln.stats_buf(), st.ln.eps, st.ln_consts[:32] if st.has_lora else None) + (st.ln._parts or (None, 0))
+        rt.ops.gemm(x, st.W[:C], q, lora=lora, bias=st.bias[:C] if st.bias is not None else None, **kw)
+        if st.ln is None:
+            Wkv, bkv = st.W[C:], st.bias[C:] if st.bias is not None else None
+        else:       # the stack's forward operand is W o gamma: the plain rows of to_k | to_v come back from its dX operand W^T, once
+            if "Wkv_plain" not in self._b:
+                self._b["Wkv_plain"] = (st.Wt[:, C:].t().contiguous(),
+                                        torch.cat([self.to_k.bias, self.to_v.bias]).contiguous() if self.to_k.bias is not None else None)
+            Wkv, bkv = self._b["Wkv_plain"]
+        lora = (st.A_cat[Rp:], st.B_cat[C:], st.arena.scale, None) if st.has_lora else None
+        rt.ops.gemm(pooled, Wkv, kv, lora=lora, bias=bkv, lora_group_n=C if st.has_lora else 0)
+        return q, k, v, Nk, Nkp
+
+    def forward(self, x, ctx, B, N, residual, parts_for=None, grid=None):
+        """x [B*N, C]; ctx [B*CTX_PAD, D] for cross attention.  Returns residual + to_out(attn).  grid (H, W): the token grid, read by a
+        self-attention with key / value downsampling only."""
         rt, C = self.rt, self.C
         kv = ctx if self.cross else x
         Nk, Nkp = (77, CTX_PAD) if self.cross else (N, N)
+        pooled_kv = not self.cross and self._kv is not None
+        if pooled_kv:
+            q, k, v, Nk, Nkp = self._kv_forward(x, residual, B, N, grid)
         Mq, Mk = B * N, B * Nkp
         # transposed copies of Q and K are only needed as GEMM operands of the score side output's backward (hooked
         # cross-attention); the attention kernels themselves read every tile in its natural layout
@@ -992,19 +1039,19 @@ class Attention(_Module):
                 k, v = self.stack.forward(kv, Ct=KVt)
                 if need_t:
                     self._b["Kt"] = KVt[:C]
-        else:
+        elif not pooled_kv:
             q, k, v = self.stack.forward(x)
         O = self.buf("O", Mq, C)
         L = self.buf("L", B * self.heads * N, dtype=F32)
         self._dims = (B, N, Nk, Nkp)
         # self-attention whose to_out.0 input gradient runs on the wave-split-K kernel: that product leaves the backward's row term D = rowsum(dO o O) as a side output
         # (no D pre-pass launch); its slots are cleared here, by the forward kernel's epilogue
-        self._rowdot = (not self.cross and getattr(self, "_rowdot_ok", True) and self.to_out.trainer is None
+        self._rowdot = (not self.cross and not pooled_kv and getattr(self, "_rowdot_ok", True) and self.to_out.trainer is None
                         and not (self.to_out.lora is not None and self.to_out.arena.wide)
                         and getattr(rt.ops, "wsk_rowdot_shape", None) is not None and rt.ops.wsk_rowdot_shape(Mq, C, C, self.to_out.lora is not None, self.d))
         kwz = {"zero_D": self.buf("D", B * self.heads * N, dtype=F32)} if self._rowdot else {}
         if N % 8:
-            self._attn_fwd_padded(q, k, v, O, L, B, N, Nk, Nkp)
+            self._attn_fwd_padded(q, k, v, O, L, B, N, Nk, Nkp, kv_padded=pooled_kv)
         else:
             rt.ops.attn_fwd(q, k, v, None, O, L, B=B, H=self.heads, Nq=N, Nk=Nk, Nqp=N, Nkp=Nkp, d=self.d, scale=self.scale, **kwz)
         if self.cross and self.hooked:
@@ -1029,7 +1076,7 @@ class Attention(_Module):
                 rt.daam.append((self.name, S.view(B, N, CTX_PAD)))
         return self.to_out.forward(O, residual=residual, parts_for=parts_for)
 
-    def _attn_fwd_padded(self, q, k, v, O, L, B, N, Nk, Nkp):
+    def _attn_fwd_padded(self, q, k, v, O, L, B, N, Nk, Nkp, kv_padded=False):
         """A map of 4 or 6 tokens per image (the innermost level of the toy topologies at an 8 x 8 / 8 x 12 latent; no real model gets here): the kernel
         wants every batch to start on an 8-row boundary, so q - and k | v of self-attention - move into zeroed padded rows (keys past Nk are masked and
         their V rows meet P == 0) and the N real rows of O come back.  Forward only: the backward kernels refuse such a map (sdlt_attn_bwd's own row check)."""
@@ -1037,7 +1084,7 @@ class Attention(_Module):
         self._rowdot = False
         qp = self.buf("q_pad", B * Np, C, zero=True)
         qp.view(B, Np, C)[:, :N].copy_(q.reshape(B, N, C))
-        if not self.cross:
+        if not self.cross and not kv_padded:        # (kv_padded: the pooled keys of _kv_forward already sit in Nkp rows per image)
             kvp = self.buf("kv_pad", 2, B * Np, C, zero=True)
             for dst, src in zip(kvp, (k, v)):
                 dst.view(B, Np, C)[:, :N].copy_(src.reshape(B, N, C))
@@ -1121,6 +1168,7 @@ class TransformerBlock(_Module):
         super().__init__(rt, name)
         self.norm1 = LayerNorm(rt, name + ".norm1", sd)
         self.attn1 = Attention(rt, name + ".attn1", sd, arena, heads, cross=False, hooked=False)
+        self.attn1.norm = self.norm1
         self.norm2 = LayerNorm(rt, name + ".norm2", sd)
         self.attn2 = Attention(rt, name + ".attn2", sd, arena, heads, cross=True, hooked=hooked)
         self.norm3 = LayerNorm(rt, name + ".norm3", sd)
@@ -1160,9 +1208,9 @@ class TransformerBlock(_Module):
                 w3 = w(self.ff1.name).to(rt.device)
                 self.ff1.fold_ln(self.norm3, w3[perm], keep_plain=True)
 
-    def forward(self, x, ctx, B, N, next_norm=None):
-        """next_norm: the LayerNorm that reads this block's output (the next block's norm1) - see Linear.forward parts_for."""
-        x1 = self.attn1.forward(self.norm1.forward(x), None, B, N, residual=x, parts_for=self.norm2)
+    def forward(self, x, ctx, B, N, next_norm=None, grid=None):
+        """next_norm: the LayerNorm that reads this block's output (the next block's norm1) - see Linear.forward parts_for.  grid: Attention.forward."""
+        x1 = self.attn1.forward(self.norm1.forward(x), None, B, N, residual=x, parts_for=self.norm2, grid=grid)
         x2 = self.attn2.forward(self.norm2.forward(x1), ctx, B, N, residual=x1, parts_for=self.norm3)
         if self.fused_geglu:
             g = self.buf("g", x.shape[0], self.ff2.K)
@@ -1196,11 +1244,11 @@ class Transformer2D(_Module):
         self.blocks = [TransformerBlock(rt, f"{name}.transformer_blocks.{k}", sd, arena, heads, hooked) for k in range(nlayers)]
         self.proj_out = Linear(rt, name + ".proj_out", sd)
 
-    def forward(self, x, ctx, B, HW):
+    def forward(self, x, ctx, B, HW, grid=None):
         h = self.proj_in.forward(self.norm.forward(x, None, B, HW))
         self.blocks[0].norm1._parts = None            # (proj_in leaves no row partials)
         for i, blk in enumerate(self.blocks):
-            h = blk.forward(h, ctx, B, HW, next_norm=self.blocks[i + 1].norm1 if i + 1 < len(self.blocks) else None)
+            h = blk.forward(h, ctx, B, HW, next_norm=self.blocks[i + 1].norm1 if i + 1 < len(self.blocks) else None, grid=grid)
         return self.proj_out.forward(h, residual=x)
 
     def backward(self, dout, dctx):
@@ -1343,6 +1391,7 @@ class UNet(_Module):
             trainer.finalize()
         self._grad_plan = None
         self._freeu = None               # set_freeu: (b1, b2, s1, s2, version) of an inference instance
+        self._kv_ds = None               # set_kv_downsample: (factors, mode) of an inference instance
         # time_emb_proj of every resnet reads the same silu(emb): ONE GEMM over the stacked weights [sum Cout, tdim] per pass instead of
         # one M = B launch per resnet (17 in SDXL, 22 in SD1.5); the same for their input gradients (dsemb) when B == 1.  Not with the
         # full fine-tune (the projections are trained layer by layer there).
@@ -1367,10 +1416,14 @@ class UNet(_Module):
             a.kv_batched = ok
 
     # ------------------------------------------------------------------------------------ forward
-    def forward(self, x, timesteps_f, ctx, pooled=None, time_ids=None, *, B, H, W):
+    def forward(self, x, timesteps_f, ctx, pooled=None, time_ids=None, *, B, H, W, train=True):
         """x: noisy latent NHWC padded to 64 channels [B*H*W, 64]; timesteps_f fp32 [B]; ctx [B*CTX_PAD, D];
-        pooled [B, P] (act dtype), time_ids fp32 [B*6] (SDXL).  Returns eps_hat fp32 [B*H*W, 4]."""
+        pooled [B, P] (act dtype), time_ids fp32 [B*6] (SDXL).  Returns eps_hat fp32 [B*H*W, 4].  train=False: no backward follows (the sampler's
+        forwards) - the launches are the same; only such a forward runs with set_kv_downsample."""
         rt, cfg = self.rt, self.cfg
+        if train and self._kv_ds is not None:
+            raise NotImplementedError("kv_downsample is an inference option: a training forward (train=True, TrainStep) has no backward through the pooled "
+                                      "keys and values - set_kv_downsample(None) first")
         rt.gn_clear("fwd")          # one fill for the statistics of every GroupNorm of this pass
         rt.gn_prezero = True
         try:
@@ -1411,14 +1464,14 @@ class UNet(_Module):
             for j, r in enumerate(res):
                 h = r.forward(h, None, semb, B, ch, cw)
                 if att:
-                    h = att[j].forward(h, ctx, B, ch * cw)
+                    h = att[j].forward(h, ctx, B, ch * cw, grid=(ch, cw))
                 skips.append((h, ch, cw))
             if ds is not None:
                 h = ds.forward(h, B, ch, cw, train=False)
                 ch, cw = ch // 2, cw // 2
                 skips.append((h, ch, cw))
         h = self.mid[0].forward(h, None, semb, B, ch, cw)
-        h = self.mid[1].forward(h, ctx, B, ch * cw)
+        h = self.mid[1].forward(h, ctx, B, ch * cw, grid=(ch, cw))
         h = self.mid[2].forward(h, None, semb, B, ch, cw)
         for i, (res, att, us) in enumerate(self.up):
             for j, r in enumerate(res):
@@ -1428,7 +1481,7 @@ class UNet(_Module):
                     h, s = self._freeu_apply(i, j, h, s, B, ch, cw)
                 h = r.forward(h, s, semb, B, ch, cw)
                 if att:
-                    h = att[j].forward(h, ctx, B, ch * cw)
+                    h = att[j].forward(h, ctx, B, ch * cw, grid=(ch, cw))
             if us is not None:
                 h = us.forward(h, B, ch, cw, train=False)
                 ch, cw = ch * 2, cw * 2
@@ -1456,6 +1509,53 @@ class UNet(_Module):
         if not hasattr(self.rt.ops, "freeu"):
             raise NotImplementedError("this op table has no freeu kernel: FreeU's skip filter and backbone scale are that launch (ops.freeu)")
         self._freeu = vals + (int(version),)
+
+    # ------------------------------------------------------------------------------------ key / value token downsampling (inference only)
+    def _attn_levels(self):
+        """[(Transformer2D, level)] of every transformer; level l runs on the (H / 2^l) x (W / 2^l) token grid."""
+        last = len(self.cfg["block_out_channels"]) - 1
+        out = [(t, i) for i, (_, att, _) in enumerate(self.down) for t in att] + [(self.mid[1], last)]
+        return out + [(t, last - i) for i, (_, att, _) in enumerate(self.up) for t in att]
+
+    def set_kv_downsample(self, factors, mode="nearest"):
+        """"Token Downsampling" (Smith et al. 2024) for the self-attentions of inference forwards (forward(train=False)): queries stay at full
+        resolution, keys and values come from the LayerNorm rows pooled by an integer factor per axis (ops.token_pool: "nearest" - the paper's - or
+        "area"), which cuts the score work and the to_k | to_v products by factor^2.  factors: a tuple counted from the LARGEST self-attention token
+        grid downwards - (2,): factor 2 on the largest grid only; (4, 2): 4 there and 2 on the next.  Grids not named, and a factor of 1, keep the plain
+        path launch for launch; None, () or all ones: off.  Cross-attention, FreeU and the heat maps are untouched.  The factors are launch arguments
+        and change the launch sequence: a capture made with one setting does not serve another (sampler.LatentSampler keys its captures by it).
+        -> {transformer name: factor} of the transformers it applies to."""
+        levels = self._attn_levels()
+        for t, _ in levels:
+            for blk in t.blocks:
+                blk.attn1._kv = None
+        self._kv_ds = None
+        if factors is None:
+            return {}
+        factors = (factors,) if isinstance(factors, int) and not isinstance(factors, bool) else tuple(factors)
+        if not all(isinstance(f, int) and not isinstance(f, bool) and f >= 1 for f in factors):
+            raise ValueError(f"kv_downsample takes integer factors >= 1, largest token grid first, got {factors!r}")
+        if mode not in _ops.TOKEN_POOL_MODES:
+            raise ValueError(f"kv_downsample mode must be one of {_ops.TOKEN_POOL_MODES}, got {mode!r}")
+        grids = sorted({lv for _, lv in levels})
+        if len(factors) > len(grids):
+            raise ValueError(f"kv_downsample: {len(factors)} factors, but this UNet has self-attention on {len(grids)} token grid(s)")
+        if all(f == 1 for f in factors):
+            return {}
+        if not hasattr(self.rt.ops, "token_pool"):
+            raise NotImplementedError("this op table has no token_pool kernel (sdlt_token_pool): the pooled LayerNorm rows of kv_downsample are that launch "
+                                      "(ops.token_pool)")
+        by_level = {lv: f for lv, f in zip(grids, factors) if f > 1}
+        applied = {}
+        for t, lv in levels:
+            if lv in by_level:
+                applied[t.name] = by_level[lv]
+                for blk in t.blocks:
+                    blk.attn1._kv = (by_level[lv], _ops.TOKEN_POOL_MODES.index(mode))
+        while factors[-1] == 1:
+            factors = factors[:-1]
+        self._kv_ds = (factors, mode)
+        return applied
 
     def _freeu_apply(self, i, j, h, s, B, H, W):
         """(h, skip) of up_blocks.i.resnets.j -> their FreeU forms in buffers of this resnet's own; tables per (H, W), allocated on first use (the warm-up
@@ -1509,6 +1609,8 @@ class UNet(_Module):
         (caller zeroes it).  LoRA gradients land in arena.grads."""
         if self._freeu is not None:
             raise RuntimeError("UNet.backward with freeu set: FreeU is an inference-time change of the forward and has no backward here (set_freeu(None))")
+        if self._kv_ds is not None:
+            raise NotImplementedError("UNet.backward with kv_downsample set: the pooled keys and values have no backward here (set_kv_downsample(None))")
         rt = self.rt
         rt.gn_clear("bwd")
         rt.gn_prezero = True

@@ -9,8 +9,12 @@ against (c) - and, with --img2img, its masked variant (`inp`).  The stochastic s
 are timed at eta = 1 with fixed seeds.  --guidance-rescale F adds (r) the default iteration with the sdlt_guidance pre-pass in it (phi = F) against (c).
 --freeu B1 B2 S1 S2 adds the default iteration with FreeU in its forward - (u) version 1, (v) version 2: six sdlt_freeu calls per forward on SDXL - against
 (c); with --trace-iteration the traced loop runs it (version 2 with --freeu-v2).
+--kv-downsample SPEC [SPEC ...] adds (k, l, m, ...) the default iteration with key / value token downsampling - SPEC = factors, largest grid first, and
+optionally a mode: `2`, `2:area`, `4,2` - against (c); with --trace-iteration the traced loop runs the first SPEC.  --graph-only drops (a) and (b), which
+take long at large latents.  --dump FILE saves the final latents of (c), for a bit comparison between two builds.
 
     python tools/render_bench.py [--out FILE] [--rounds 5] [--version sdxl] [--latent 128] [--n 1 2] [--img2img] [--sampler dpmpp_2m] [--sigmas karras] [--guidance-rescale 0.7] [--freeu 1.3 1.4 0.9 0.2]
+                                  [--kv-downsample 2 2:area 4,2] [--graph-only] [--dump FILE]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/render_bench.py --trace-iteration --n 1      # kernel time of one iteration: sum the stats
 
 Prints one table: wall milliseconds per iteration (median over the rounds, min .. max) per variant and n, per image in brackets.
@@ -77,7 +81,12 @@ def main():
     ap.add_argument("--guidance-rescale", type=float, default=0.0, help="also time the default graph sampler with the guidance pre-pass at this rescale weight")
     ap.add_argument("--freeu", type=float, nargs=4, metavar=("B1", "B2", "S1", "S2"), default=None, help="also time the default graph sampler with FreeU, versions 1 and 2")
     ap.add_argument("--freeu-v2", action="store_true", help="with --trace-iteration --freeu: trace version 2")
+    ap.add_argument("--kv-downsample", nargs="+", metavar="SPEC", default=[], help="also time the default graph sampler with key / value token downsampling: "
+                    "factors, largest grid first, optionally :mode - 2  2:area  4,2")
+    ap.add_argument("--graph-only", action="store_true", help="time the graph variants only (no torch loop, no eager fused loop)")
+    ap.add_argument("--dump", default=None, help="save the final latents of variant c to this file (torch.save)")
     a = ap.parse_args()
+    kvs = [(tuple(int(f) for f in spec.split(":")[0].split(",")), (spec.split(":") + ["nearest"])[1]) for spec in a.kv_downsample]
     h = a.latent
     lines = [f"# {a.version} topology, {h} x {h} latent, rank {a.rank}, {a.steps} steps, guidance 8; wall ms per denoising iteration: median (min .. max) of {a.rounds} rounds, alternated",
              f"# {torch.cuda.get_device_name(0)}, torch {torch.__version__}",
@@ -93,6 +102,8 @@ def main():
             "b eager + fused kernel": lambda: one(fused=True),
             "c hipGraph per iteration": lambda: one(graph=True),
         }
+        if a.graph_only:
+            variants = {k: v for k, v in variants.items() if k.startswith("c ")}
         ran = {k: a.steps for k in variants}                # iterations a call runs
         x0 = mask = None
         if a.img2img:
@@ -108,6 +119,9 @@ def main():
             for tag, ver in (("u", 1), ("v", 2)):
                 fz = dict(zip(("b1", "b2", "s1", "s2"), a.freeu), version=ver)
                 variants[f"{tag} graph, FreeU v{ver}"], ran[f"{tag} graph, FreeU v{ver}"] = (lambda fz=fz: one(graph=True, freeu=fz)), a.steps
+        for tag, (fs, mode) in zip("klmnop", kvs):
+            name = f"{tag} graph, kv {','.join(map(str, fs))} {mode}"
+            variants[name], ran[name] = (lambda fs=fs, mode=mode: one(graph=True, kv_downsample=fs, kv_downsample_mode=mode)), a.steps
         extra = [(s, k) for s in a.sampler for k in a.sigmas if (s, k) != ("euler", "trailing")]
         sd = lambda s: dict(seeds=list(range(n))) if s in ("euler_a", "dpmpp_2m_sde") else {}  # noqa: E731
         for tag, (s, k) in zip("fghij", extra):
@@ -117,11 +131,15 @@ def main():
                 variants[name + " inp"], ran[name + " inp"] = (lambda s=s, k=k: one(graph=True, sampler=s, sigmas=k, init_latents=x0, strength=1.0, mask=mask, **sd(s))), a.steps
         if a.trace_iteration:                               # the kernels of `steps` eager iterations (+ the one-off weight packing of the first)
             fu = dict(freeu=dict(zip(("b1", "b2", "s1", "s2"), a.freeu), version=2 if a.freeu_v2 else 1)) if a.freeu else {}
+            if kvs:
+                fu.update(kv_downsample=kvs[0][0], kv_downsample_mode=kvs[0][1])
             one(fused=True, **(dict(init_latents=x0, strength=1.0, mask=mask) if a.img2img else {}), **(dict(sampler=extra[0][0], sigmas=extra[0][1], **sd(extra[0][0])) if extra else {}), **fu)
             torch.cuda.synchronize()
             return
-        for fn in variants.values():                        # warm-up: buffers, packed weights, the capture
-            fn()
+        for k, fn in variants.items():                      # warm-up: buffers, packed weights, the capture
+            out = fn()
+            if a.dump and k.startswith("c "):
+                torch.save(out.cpu(), a.dump)
         times = {k: [] for k in variants}
         for _ in range(a.rounds):
             for k, fn in variants.items():
