@@ -224,6 +224,27 @@ typedef struct sdlt_attn_params {
 } sdlt_attn_params;
 int sdlt_attn_fwd(const sdlt_attn_params* p, void* stream);
 int sdlt_attn_bwd(const sdlt_attn_params* p, void* stream);
+/* Which kernel sdlt_attn_fwd (backward == 0) / sdlt_attn_bwd (backward != 0) would run for *p, without launching anything: host code only, no pointer field
+ * of p is dereferenced (their values count for the alignment terms).  Returns the negative SDLT_ERR_* the launch entry would return (sdlt_last_error set
+ * alike), or route | dp << DP_SHIFT | ks << KS_SHIFT | flags: dp = padded head width (64 / 96 / 128 / 160), ks = wave groups per workgroup (1 / 2 / 4). */
+enum {
+  SDLT_ATTN_ROUTE_FWD32 = 0,           /* attn32_fwd_kernel<ks> */
+  SDLT_ATTN_ROUTE_FWD16_KS2 = 1,       /* attn_fwd_kernel<64, 2> */
+  SDLT_ATTN_ROUTE_FWD16 = 2,           /* attn_fwd_kernel<dp>, <64, 1, 48> with DV48 */
+  SDLT_ATTN_ROUTE_BWD_CROSS_ROLES = 3, /* attn_bwd_cross_roles_kernel<64, five> */
+  SDLT_ATTN_ROUTE_BWD_CROSS = 4,       /* attn_bwd_cross_kernel<dp, five> */
+  SDLT_ATTN_ROUTE_BWD_BOTH32 = 5,      /* attn32_bwd_both_kernel<ks> */
+  SDLT_ATTN_ROUTE_BWD_BOTH16 = 6,      /* attn_bwd_both_kernel<dp> */
+  SDLT_ATTN_ROUTE_BWD_SPLIT = 7,       /* attn_bwd_dq_kernel + attn_bwd_dkdv_kernel <dp>, <64, 48> with DV48 */
+  SDLT_ATTN_ROUTE_MASK = 0xf,
+  SDLT_ATTN_ROUTE_DP_SHIFT = 4,  SDLT_ATTN_ROUTE_DP_MASK = 0xff,
+  SDLT_ATTN_ROUTE_KS_SHIFT = 12, SDLT_ATTN_ROUTE_KS_MASK = 0x7,
+  SDLT_ATTN_ROUTE_DV48 = 1 << 15,      /* three 16-column output blocks (heads of <= 48 columns) */
+  SDLT_ATTN_ROUTE_FIVE = 1 << 16,      /* cross-attention: 65..80 keys on five 16-key blocks */
+  SDLT_ATTN_ROUTE_PREP = 1 << 17,      /* the D pre-pass launch precedes the main launch */
+  SDLT_ATTN_ROUTE_SPLITSUM = 1 << 18   /* the slab-sum launch follows it */
+};
+int32_t sdlt_attn_route(const sdlt_attn_params* p, int32_t backward);
 /* out0 / out1 [B*Nkp, C] bf16 = sum over nsplit slabs of s0 / s1 (fp32 [nsplit][B*Nkp][ld32]) in slab order (rows with key >= Nk: zeros;
  * acc0: out0 += instead of =), for a table of layers: block_desc[b] = descriptor of block b, block_first[d] = first block of descriptor d,
  * a layer owns ceil(B*Nkp*C/2 / 256) blocks (capped at 64; the kernel strides). */

@@ -95,6 +95,21 @@ class AttnParams(C.Structure):
     ]
 
 
+# the packed code of sdlt_attn_route (include/sdlt_kernels.h, SDLT_ATTN_ROUTE_*)
+ATTN_ROUTES = ("FWD32", "FWD16_KS2", "FWD16", "BWD_CROSS_ROLES", "BWD_CROSS", "BWD_BOTH32", "BWD_BOTH16", "BWD_SPLIT")
+ATTN_ROUTE_MASK = 0xF
+ATTN_ROUTE_DP_SHIFT, ATTN_ROUTE_DP_MASK = 4, 0xFF
+ATTN_ROUTE_KS_SHIFT, ATTN_ROUTE_KS_MASK = 12, 0x7
+ATTN_ROUTE_DV48, ATTN_ROUTE_FIVE, ATTN_ROUTE_PREP, ATTN_ROUTE_SPLITSUM = 1 << 15, 1 << 16, 1 << 17, 1 << 18
+
+
+def attn_route_decode(code):
+    """A non-negative code of sdlt_attn_route as a dict (route name, dp, ks and the four flags)."""
+    assert code >= 0, code
+    return dict(route=ATTN_ROUTES[code & ATTN_ROUTE_MASK], dp=code >> ATTN_ROUTE_DP_SHIFT & ATTN_ROUTE_DP_MASK, ks=code >> ATTN_ROUTE_KS_SHIFT & ATTN_ROUTE_KS_MASK,
+                dv48=bool(code & ATTN_ROUTE_DV48), five=bool(code & ATTN_ROUTE_FIVE), prep=bool(code & ATTN_ROUTE_PREP), splitsum=bool(code & ATTN_ROUTE_SPLITSUM))
+
+
 class GroupNormParams(C.Structure):
     _fields_ = [
         ("x1", vp), ("ldx1", i64), ("C1", i32),
@@ -214,6 +229,7 @@ SYMBOLS = {
     "sdlt_lora_grad_wide": (i32, [vp, vp, i32, i32, i32, vp]),
     "sdlt_attn_fwd": (i32, [C.POINTER(AttnParams), vp]),
     "sdlt_attn_bwd": (i32, [C.POINTER(AttnParams), vp]),
+    "sdlt_attn_route": (i32, [C.POINTER(AttnParams), i32]),
     "sdlt_attn_splitsum_batch": (i32, [vp, vp, vp, i32, vp]),
     "sdlt_groupnorm_ws_floats": (i32, [i32, i32, i32]),
     "sdlt_colsum_finish_batch": (i32, [vp, i32, i32, vp]),

@@ -62,7 +62,7 @@ __device__ __forceinline__ bf16x8 lds_tr_frag(const char* p, int stride) {
 // CONTIGUOUS range of the (tile fastest, then head, then batch) order: the tiles of one head - which all stream the same K / V (forward,
 // dQ) or Q / dO (dK / dV) rows - then sit on one or two XCDs instead of all eight, and those rows are fetched into one L2, not eight.
 struct WgId { int x, y, z; };
-__device__ int g_attn_xcd = 1;          // SDLT_ATTN_XCD=0 (A/B): plain blockIdx order
+__device__ int g_attn_xcd = 1;          // 0 (AttnSwitches::xcd, A/B): plain blockIdx order
 __device__ __forceinline__ WgId xcd_wg() {
   if (!g_attn_xcd) { WgId w; w.x = blockIdx.x; w.y = blockIdx.y; w.z = blockIdx.z; return w; }
   const int gx = gridDim.x, gy = gridDim.y, n = gx * gy * gridDim.z;
@@ -89,6 +89,14 @@ template <int DP>
 __device__ __host__ constexpr int tile_stride() { return DP == 64 ? 128 : DP * 2 + 16; }
 template <int DP>
 __device__ __forceinline__ int row_sw(int row) { return DP == 64 ? ((((row >> 1) & 1) << 1) | (((row >> 3) & 1) << 2)) : 0; }
+// Dynamic LDS bytes of each kernel at padded head width dp (host side; a [64 rows][dp] tile takes 64 * tile_stride bytes)
+constexpr int tile_bytes(int dp) { return 64 * (dp == 64 ? tile_stride<64>() : dp == 96 ? tile_stride<96>() : dp == 128 ? tile_stride<128>() : tile_stride<160>()); }
+constexpr int smem_fwd(int dp, int ks = 1) { return ks * 2 * 2 * tile_bytes(dp); }      // forward, dQ: (K, V) x two buffers per wave group
+constexpr int smem_both(int dp) { return 2 * (2 * tile_bytes(dp) + 512); }               // dK / dV, dQ + dK / dV in one launch: (Q, dO, L and D rows) x two buffers
+constexpr int smem_cross(int dp) { return 2 * 2 * tile_bytes(dp) + 2 * 2 * tile_bytes(dp) + 512; }      // resident K, V of 128 rows + (Q, dO) x two buffers + L / D rows
+constexpr int smem_cross_roles(int dp) {      // the larger of the q-major role (= the single-role kernel) and the key-major role, (Q, dO, O) x two buffers
+  return 2 * 3 * tile_bytes(dp) + 512 > smem_cross(dp) ? 2 * 3 * tile_bytes(dp) + 512 : smem_cross(dp);
+}
 
 // Tiles are staged global -> registers -> LDS in two halves so the HBM/L2 latency of tile t+1 hides under the MFMAs
 // of tile t (registers are loaded before the compute phase and written to the other LDS buffer after it).
@@ -1115,157 +1123,220 @@ int attn_check(const sdlt_attn_params& p, const char* fn) {
   if ((p.ldq % 8) || (p.ldk % 8) || (p.ldv % 8)) SDLT_FAIL(SDLT_ERR_ALIGN, "%s: ld %% 8", fn);
   return SDLT_OK;
 }
-
-template <typename F>
-int set_smem(F f, int bytes) { return sdlt_raise_smem((const void*)f, bytes); }   // once per (kernel, device), thread-safe (capi.cpp)
-
-#define ATTN_DISPATCH(DPV, KERNEL, GRID, SMEM)                                                  \
-  switch (DPV) {                                                                                \
-    case 64: set_smem(KERNEL<64>, SMEM(64)); hipLaunchKernelGGL(KERNEL<64>, GRID, dim3(256), SMEM(64), s, p); break;     \
-    case 96: set_smem(KERNEL<96>, SMEM(96)); hipLaunchKernelGGL(KERNEL<96>, GRID, dim3(256), SMEM(96), s, p); break;     \
-    case 128: set_smem(KERNEL<128>, SMEM(128)); hipLaunchKernelGGL(KERNEL<128>, GRID, dim3(256), SMEM(128), s, p); break; \
-    default: set_smem(KERNEL<160>, SMEM(160)); hipLaunchKernelGGL(KERNEL<160>, GRID, dim3(256), SMEM(160), s, p); break; \
-  }
-
-}  // namespace
-
-static bool attn32_on() {
-  static const bool on = !(getenv("SDLT_ATTN_R32") && atoi(getenv("SDLT_ATTN_R32")) == 0);
-  return on;
-}
-static void attn_env_once() {
-  static bool done = false;
-  if (done) return;
-  done = true;
-  if (getenv("SDLT_ATTN_XCD") && atoi(getenv("SDLT_ATTN_XCD")) == 0) {
-    const int zero = 0;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_attn_xcd), &zero, sizeof(int));
-  }
+// the operands of a backward; pair: dK / dV belong to them (the single entry checks those together with the slabs of a query split)
+int attn_check_bwd(const sdlt_attn_params& p, const char* fn, bool pair) {
+  int rc = attn_check(p, fn);
+  if (rc) return rc;
+  if (!p.L || !p.D || !p.O || !p.dO || !p.dQ || (pair && (!p.dK || !p.dV)))
+    SDLT_FAIL(SDLT_ERR_SHAPE, pair ? "%s: missing operand" : "%s: missing operand (L, D, O, dO, dQ are required)", fn);
+  if ((p.lddo % 8) || (p.ldo % 8) || (p.lddq % 4) || (pair && ((p.lddk % 4) || (p.lddv % 4)))) SDLT_FAIL(SDLT_ERR_ALIGN, "%s: ld alignment", fn);
+  return SDLT_OK;
 }
 
-extern "C" int sdlt_attn_fwd(const sdlt_attn_params* pp, void* stream) {
-  attn_env_once();
-  const sdlt_attn_params& p = *pp;
-  hipStream_t s = (hipStream_t)stream;
+// Every environment switch of the attention dispatch (README), parsed once per process.
+struct AttnSwitches {
+  bool r32, xcd, dv48, five, roles;
+  int ks, ks32_fwd, ks32_bwd, qdiv;
+};
+const AttnSwitches& attn_switches() {
+  static const AttnSwitches sw = [] {
+    auto num = [](const char* name, int unset) { const char* v = getenv(name); return v ? atoi(v) : unset; };
+    AttnSwitches s;
+    s.r32 = num("SDLT_ATTN_R32", 1) != 0;           // 0: head-width-64 self-attention stays on the 16-row kernels (A/B)
+    s.xcd = num("SDLT_ATTN_XCD", 1) != 0;           // 0: plain blockIdx order (A/B; g_attn_xcd, set by attn_env_once - no plan looks at it)
+    s.ks = num("SDLT_ATTN_KS", 2);                  // 1: no key split in the 16-row forward (A/B)
+    s.dv48 = num("SDLT_ATTN_DV48", 1) != 0;         // 0: four output blocks for heads of <= 48 columns too (A/B)
+    s.ks32_fwd = num("SDLT_ATTN32_KS_FWD", 0);      // wave groups of the 32-row kernels; 0: by shape
+    s.ks32_bwd = num("SDLT_ATTN32_KS_BWD", 0);
+    s.five = num("SDLT_XATTN_FIVE", 1) != 0;        // 0: the 65..80 keys of a cross-attention as two 64-key blocks
+    s.roles = num("SDLT_XATTN_ROLES", 1) != 0;      // 0: both orientations in one workgroup (the single-role kernel)
+    const int qdiv = num("SDLT_XATTN_QDIV", 1);     // q-major workgroups of the roles kernel = qsplit / this
+    s.qdiv = qdiv > 0 ? qdiv : 1;
+    return s;
+  }();
+  return sw;
+}
+
+// What one sdlt_attn_fwd / sdlt_attn_bwd call launches.  attn_plan_fwd / attn_plan_bwd are the ONE place that picks a kernel (every threshold lives
+// there); they call nothing from HIP, so sdlt_attn_route can report the choice on a machine without a GPU.
+struct AttnPlan {
+  int route = 0;                       // SDLT_ATTN_ROUTE_*
+  int dp = 64, ks = 1;                 // padded head width; wave groups per workgroup
+  bool dv48 = false, five = false, prep = false, splitsum = false;     // prep: the D pre-pass launch first; splitsum: the slab-sum launch last
+  dim3 grid, grid2;                    // grid2, smem2: the dK / dV launch of BWD_SPLIT (grid, smem: its dQ launch)
+  int block = 256, smem = 0, smem2 = 0;
+  int nq_roles = 0;                    // BWD_CROSS_ROLES: q-major workgroups (grid.x = nq_roles + qsplit)
+};
+int attn32_ks(int env, bool two) { return env >= 4 ? 4 : env >= 2 ? 2 : env > 0 ? 1 : two ? 2 : 1; }
+
+int attn_plan_fwd(const sdlt_attn_params& p, const AttnSwitches& sw, AttnPlan& pl) {
   int rc = attn_check(p, "sdlt_attn_fwd");
   if (rc) return rc;
   if (p.ldo % 4) SDLT_FAIL(SDLT_ERR_ALIGN, "sdlt_attn_fwd: ldo %% 4");
-  const int dp = attn_dp(p.d);
-  dim3 grid((p.Nq + 63) / 64, p.H, p.B);
-  // head width 64, whole 64-row tiles, no mask: 32 rows per wave on the 32x32x16 MFMA (attn32.hip).  SDLT_ATTN_R32=0 keeps the 16-row kernels (A/B).
+  pl = AttnPlan{};
+  pl.dp = attn_dp(p.d);
+  pl.grid = dim3((p.Nq + 63) / 64, p.H, p.B);
+  // head width 64, whole 64-row tiles, no mask: 32 rows per wave on the 32x32x16 MFMA (attn32.hip).
   // Two wave groups per workgroup split the key tiles wherever there are >= 2 of them (tools/attn32_probe.sh, 1 / 2 / 4 groups: 1024 tokens x 20 heads
   // 23.8 / 16.7 / 20.6 us, 4096 x 10 90.5 / 80.0 / 84.3, 4 x 256 x 20 8.9 / 7.5 / 11.5, 4 x 1024 x 10 26.2 / 24.5 / 29.7)
-  if (attn32_on() && sdlt_attn32_ok(p) && ((uintptr_t)p.O % 16) == 0 && (p.ldo % 8) == 0) {      // (16-byte epilogue stores)
-    static const int ks_env = getenv("SDLT_ATTN32_KS_FWD") ? atoi(getenv("SDLT_ATTN32_KS_FWD")) : 0;
-    return sdlt_attn32_fwd(p, ks_env > 0 ? ks_env : (p.Nk >= 128 ? 2 : 1), s);      // (zeroes D in its epilogue)
+  if (sw.r32 && sdlt_attn32_ok(p) && ((uintptr_t)p.O % 16) == 0 && (p.ldo % 8) == 0) {      // (16-byte epilogue stores)
+    pl.route = SDLT_ATTN_ROUTE_FWD32;
+    pl.ks = attn32_ks(sw.ks32_fwd, p.Nk >= 128);
+    pl.block = 128 * pl.ks;
+    pl.smem = sdlt_attn32_fwd(pl.ks).smem;
+    return SDLT_OK;
   }
-  if (p.D) sdlt_zero_async(p.D, sizeof(float) * (size_t)p.B * p.H * p.Nq, s);
-#define NSTRH(D_) ((D_) == 64 ? 128 : (D_) * 2 + 16)
-#define SMEM_FWD(D_) (2 * (2 * 64 * NSTRH(D_)))
   // the key split (two wave groups per workgroup) pays on latency-bound grids only - less than two workgroups per CU and a chain of >= 4
-  // key tiles (tools/attn_probe.py: 1024 tokens x 20 heads 25.6 -> 22.9 us; 4096 x 10, 640 workgroups: 102 -> 114 us, so not there);
-  // SDLT_ATTN_KS=1 switches it off (A/B)
-  static const int ks_env = getenv("SDLT_ATTN_KS") ? atoi(getenv("SDLT_ATTN_KS")) : 2;
-  if (dp == 64 && ks_env == 2 && p.Nk >= 256 && (int64_t)grid.x * grid.y * grid.z <= 512) {
-    set_smem(attn_fwd_kernel<64, 2>, 2 * SMEM_FWD(64));
-    hipLaunchKernelGGL((attn_fwd_kernel<64, 2>), grid, dim3(512), 2 * SMEM_FWD(64), s, p);
-    SDLT_CHECK_LAUNCH();
-    return SDLT_OK;
-  }
-  static const bool dv48 = !(getenv("SDLT_ATTN_DV48") && atoi(getenv("SDLT_ATTN_DV48")) == 0);      // (A/B switch: 0 = four output blocks for heads of <= 48 columns too)
-  if (dv48 && dp == 64 && p.d <= 48) {
-    set_smem((attn_fwd_kernel<64, 1, 48>), SMEM_FWD(64));
-    hipLaunchKernelGGL((attn_fwd_kernel<64, 1, 48>), grid, dim3(256), SMEM_FWD(64), s, p);
-    SDLT_CHECK_LAUNCH();
-    return SDLT_OK;
-  }
-  ATTN_DISPATCH(dp, attn_fwd_kernel, grid, SMEM_FWD)
-  SDLT_CHECK_LAUNCH();
+  // key tiles (tools/attn_probe.py: 1024 tokens x 20 heads 25.6 -> 22.9 us; 4096 x 10, 640 workgroups: 102 -> 114 us, so not there)
+  const bool ks2 = pl.dp == 64 && sw.ks == 2 && p.Nk >= 256 && (int64_t)pl.grid.x * pl.grid.y * pl.grid.z <= 512;
+  pl.route = ks2 ? SDLT_ATTN_ROUTE_FWD16_KS2 : SDLT_ATTN_ROUTE_FWD16;
+  pl.ks = ks2 ? 2 : 1;
+  pl.dv48 = !ks2 && sw.dv48 && pl.dp == 64 && p.d <= 48;
+  pl.block = 256 * pl.ks;
+  pl.smem = smem_fwd(pl.dp, pl.ks);
   return SDLT_OK;
 }
 
-extern "C" int sdlt_attn_bwd(const sdlt_attn_params* pp, void* stream) {
-  attn_env_once();
-  const sdlt_attn_params& p = *pp;
-  hipStream_t s = (hipStream_t)stream;
-  int rc = attn_check(p, "sdlt_attn_bwd");
+int attn_plan_bwd(const sdlt_attn_params& p, const AttnSwitches& sw, AttnPlan& pl) {
+  int rc = attn_check_bwd(p, "sdlt_attn_bwd", false);
   if (rc) return rc;
-  if (!p.L || !p.D || !p.O || !p.dO || !p.dQ)
-    SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_attn_bwd: missing operand (L, D, O, dO, dQ are required)");
-  if ((p.lddo % 8) || (p.ldo % 8) || (p.lddq % 4))
-    SDLT_FAIL(SDLT_ERR_ALIGN, "sdlt_attn_bwd: ld alignment");
   if (p.qsplit < 1) SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_attn_bwd: qsplit=%d", p.qsplit);
   if (!p.dK || !p.dV || (p.lddk % 4) || (p.lddv % 4) || (p.qsplit > 1 && (!p.dK32 || !p.dV32 || (p.ld32 % 4))))
     SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_attn_bwd: dK/dV outputs for qsplit=%d", p.qsplit);
-  const int dp = attn_dp(p.d);
-  const int C = p.H * p.d, krows = p.B * p.Nkp;
-  if (p.qsplit > 1 && !p.causal && p.Nk <= 128 && p.Nkp <= 128 && dp <= 96) {
+  pl = AttnPlan{};
+  pl.dp = attn_dp(p.d);
+  const int tq = (p.Nq + 63) / 64, tk = (p.Nk + 63) / 64;
+  if (p.qsplit > 1 && !p.causal && p.Nk <= 128 && p.Nkp <= 128 && pl.dp <= 96) {
     // cross-attention: prep + dQ + dK/dV in one kernel (see attn_bwd_cross_kernel); qsplit = workgroups along the queries,
     // dK32 / dV32 = [qsplit][B*Nkp][ld32] partial slabs (any contents)
-    dim3 gx(p.qsplit, p.H, p.B);
-#define SMEM_X(D_) (2 * 128 * NSTRH(D_) + 2 * (2 * 64 * NSTRH(D_)) + 512)
-    static const bool five_env = !(getenv("SDLT_XATTN_FIVE") && atoi(getenv("SDLT_XATTN_FIVE")) == 0);
-    const bool five = five_env && p.Nk > 64 && p.Nk <= 80;
-    // SDLT_XATTN_ROLES=0: both orientations in one workgroup (the single-role kernel)
-    static const bool roles_env = !(getenv("SDLT_XATTN_ROLES") && atoi(getenv("SDLT_XATTN_ROLES")) == 0);
-    static const int qdiv_env = getenv("SDLT_XATTN_QDIV") ? atoi(getenv("SDLT_XATTN_QDIV")) : 1;      // q-major workgroups = qsplit / this
-    const int nq_roles = p.qsplit / (qdiv_env > 0 ? qdiv_env : 1) > 0 ? p.qsplit / (qdiv_env > 0 ? qdiv_env : 1) : 1;
-#define SMEM_XR(D_) (3 * 2 * 64 * NSTRH(D_) > 2 * 128 * NSTRH(D_) + 2 * 2 * 64 * NSTRH(D_) ? 3 * 2 * 64 * NSTRH(D_) + 512 : 2 * 128 * NSTRH(D_) + 2 * 2 * 64 * NSTRH(D_) + 512)
-#define XLAUNCH(D_, F_) do { \
-      if (roles_env && (D_) == 64) {       /* (head width 96: the split roles spill) */  set_smem(attn_bwd_cross_roles_kernel<D_, F_>, SMEM_XR(D_)); hipLaunchKernelGGL((attn_bwd_cross_roles_kernel<D_, F_>), dim3(nq_roles + p.qsplit, p.H, p.B), dim3(256), SMEM_XR(D_), s, p); } \
-      else { set_smem(attn_bwd_cross_kernel<D_, F_>, SMEM_X(D_)); hipLaunchKernelGGL((attn_bwd_cross_kernel<D_, F_>), gx, dim3(256), SMEM_X(D_), s, p); } } while (0)
-    if (dp == 64) { if (five) XLAUNCH(64, true); else XLAUNCH(64, false); }
-    else { if (five) XLAUNCH(96, true); else XLAUNCH(96, false); }
-    if (!p.defer_splitsum) {
-      int blocks = (int)(((int64_t)krows * C / 2 + 255) / 256);
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(attn_splitsum_kernel, dim3(blocks), dim3(256), 0, s, p.dK32, p.dV32, p.qsplit, p.ld32, (bf16_t*)p.dK, p.lddk,
-                         (bf16_t*)p.dV, p.lddv, p.B, p.Nk, p.Nkp, C, p.accumulate_dk);
-    }
-    SDLT_CHECK_LAUNCH();
+    const bool roles = sw.roles && pl.dp == 64;      // (head width 96: the split roles spill)
+    pl.route = roles ? SDLT_ATTN_ROUTE_BWD_CROSS_ROLES : SDLT_ATTN_ROUTE_BWD_CROSS;
+    pl.five = sw.five && p.Nk > 64 && p.Nk <= 80;
+    if (roles) pl.nq_roles = p.qsplit / sw.qdiv > 0 ? p.qsplit / sw.qdiv : 1;
+    pl.grid = dim3(pl.nq_roles + p.qsplit, p.H, p.B);
+    pl.smem = roles ? smem_cross_roles(pl.dp) : smem_cross(pl.dp);
+    pl.splitsum = !p.defer_splitsum;
     return SDLT_OK;
   }
-  if (p.qsplit == 1 && !p.accumulate_dq && !p.accumulate_dk &&
-      (int64_t)((p.Nq + 63) / 64 + (p.Nk + 63) / 64) * p.H * p.B <= 2048) {   // (bigger grids are throughput-bound: two launches are 5 % faster there)
+  if (p.qsplit == 1 && !p.accumulate_dq && !p.accumulate_dk && (int64_t)(tq + tk) * p.H * p.B <= 2048) {   // (bigger grids are throughput-bound: two launches are 5 % faster there)
     // self-attention (UNet, text encoders): D, then dQ and dK/dV tiles in one launch (see attn_bwd_both_kernel)
-    int64_t groups = (int64_t)p.B * p.Nqp * p.H;
+    const int64_t groups = (int64_t)p.B * p.Nqp * p.H;
     if (groups >= (1 << 22)) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_attn_bwd: B * Nq * H = %lld rows (the D pre-pass indexes < 2^22)", (long long)groups);
-    int blocks = (int)((groups * 8 + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    if (!p.d_ready)      // (d_ready: sdlt_wsk_gemm_rowdot left D while it produced dO)
-      hipLaunchKernelGGL(attn_prep_kernel, dim3(blocks), dim3(256), 0, s, (const bf16_t*)p.O, p.ldo, (const bf16_t*)p.dO, p.lddo, p.B, p.H, p.Nq, p.Nqp, p.d, p.D);
-    if (attn32_on() && sdlt_attn32_ok(p) && ((uintptr_t)p.L % 16) == 0 && ((uintptr_t)p.D % 16) == 0 &&
+    pl.prep = !p.d_ready;      // (d_ready: sdlt_wsk_gemm_rowdot left D while it produced dO)
+    pl.grid = dim3(tq + tk, p.H, p.B);
+    if (sw.r32 && sdlt_attn32_ok(p) && ((uintptr_t)p.L % 16) == 0 && ((uintptr_t)p.D % 16) == 0 &&
         (((uintptr_t)p.dQ | (uintptr_t)p.dK | (uintptr_t)p.dV) % 16) == 0 && ((p.lddq | p.lddk | p.lddv) % 8) == 0) {      // (16-byte epilogue stores)
-      static const int ks_env = getenv("SDLT_ATTN32_KS_BWD") ? atoi(getenv("SDLT_ATTN32_KS_BWD")) : 0;
+      pl.route = SDLT_ATTN_ROUTE_BWD_BOTH32;
       // (1 / 2 / 4 groups: 1024 x 20 44.0 / 38.1 / 46.4 us, 4096 x 10 219.9 / 203.3 / 201.5, 4 x 1024 x 10 72.0 / 60.1 / 75.1)
-      return sdlt_attn32_bwd_both(p, ks_env > 0 ? ks_env : (p.Nk >= 128 && p.Nq >= 128 ? 2 : 1), s);
+      pl.ks = attn32_ks(sw.ks32_bwd, p.Nk >= 128 && p.Nq >= 128);
+      pl.block = 128 * pl.ks;
+      pl.smem = sdlt_attn32_bwd_both(pl.ks).smem;
+    } else {
+      pl.route = SDLT_ATTN_ROUTE_BWD_BOTH16;
+      pl.smem = smem_both(pl.dp);
     }
-    dim3 gb((p.Nq + 63) / 64 + (p.Nk + 63) / 64, p.H, p.B);
-#define SMEM_BOTH(D_) (2 * (2 * 64 * NSTRH(D_) + 512))
-    ATTN_DISPATCH(dp, attn_bwd_both_kernel, gb, SMEM_BOTH)
-    SDLT_CHECK_LAUNCH();
     return SDLT_OK;
   }
   if (p.accumulate_dq || p.accumulate_dk) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_attn_bwd: accumulate_dq/dk exist for the single-pass cross-attention kernel only");
-  dim3 gq((p.Nq + 63) / 64, p.H, p.B);
-#define SMEM_DQ(D_) (2 * (2 * 64 * NSTRH(D_)))
-  static const bool dv48 = !(getenv("SDLT_ATTN_DV48") && atoi(getenv("SDLT_ATTN_DV48")) == 0);
-  const bool v48 = dv48 && dp == 64 && p.d <= 48;
-  if (v48) { set_smem((attn_bwd_dq_kernel<64, 48>), SMEM_DQ(64)); hipLaunchKernelGGL((attn_bwd_dq_kernel<64, 48>), gq, dim3(256), SMEM_DQ(64), s, p); }
-  else { ATTN_DISPATCH(dp, attn_bwd_dq_kernel, gq, SMEM_DQ) }
-  if (p.qsplit > 1 && (((uintptr_t)p.dK32 | (uintptr_t)p.dV32) & 15 || (p.ld32 & 3) || (C & 3)))
+  if (p.qsplit > 1 && (((uintptr_t)p.dK32 | (uintptr_t)p.dV32) & 15 || (p.ld32 & 3) || ((p.H * p.d) & 3)))
     SDLT_FAIL(SDLT_ERR_ALIGN, "sdlt_attn_bwd: the dK / dV slabs of a query-split backward need 16-byte rows (ld32 %% 4, C %% 4)");
-  dim3 gk(((p.Nk + 63) / 64) * p.qsplit, p.H, p.B);
-#define SMEM_DKV(D_) (2 * (2 * 64 * NSTRH(D_) + 512))
-  if (v48) { set_smem((attn_bwd_dkdv_kernel<64, 48>), SMEM_DKV(64)); hipLaunchKernelGGL((attn_bwd_dkdv_kernel<64, 48>), gk, dim3(256), SMEM_DKV(64), s, p); }
-  else { ATTN_DISPATCH(dp, attn_bwd_dkdv_kernel, gk, SMEM_DKV) }
-  if (p.qsplit > 1) {      // [qsplit][B * Nkp][ld32] partial slabs -> bf16 dK / dV, summed in slab order (bitwise reproducible)
-    int blocks = (int)(((int64_t)krows * C / 2 + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(attn_splitsum_kernel, dim3(blocks), dim3(256), 0, s, p.dK32, p.dV32, p.qsplit, p.ld32, (bf16_t*)p.dK, p.lddk, (bf16_t*)p.dV, p.lddv, p.B, p.Nk, p.Nkp, C, 0);
-  }
-  SDLT_CHECK_LAUNCH();
+  pl.route = SDLT_ATTN_ROUTE_BWD_SPLIT;
+  pl.dv48 = sw.dv48 && pl.dp == 64 && p.d <= 48;
+  pl.grid = dim3(tq, p.H, p.B);
+  pl.grid2 = dim3(tk * p.qsplit, p.H, p.B);
+  pl.smem = smem_fwd(pl.dp);
+  pl.smem2 = smem_both(pl.dp);
+  pl.splitsum = p.qsplit > 1;      // [qsplit][B * Nkp][ld32] partial slabs -> bf16 dK / dV, summed in slab order (bitwise reproducible)
   return SDLT_OK;
+}
+
+// the kernel of a plan: one table per kernel template, the key-split / three-output-block variants first, then by dp; second: the dK / dV launch of BWD_SPLIT
+typedef void (*AttnKernel)(const sdlt_attn_params);
+AttnKernel attn_kernel(const AttnPlan& pl, bool second) {
+  static const AttnKernel fwd[6] = {attn_fwd_kernel<64, 2>, attn_fwd_kernel<64, 1, 48>, attn_fwd_kernel<64>, attn_fwd_kernel<96>, attn_fwd_kernel<128>, attn_fwd_kernel<160>};
+  static const AttnKernel cross[2][2][2] = {      // [dp 96][128-key blocks][single role]; (roles<96>: never planned, it spills)
+      {{attn_bwd_cross_roles_kernel<64, true>, attn_bwd_cross_kernel<64, true>}, {attn_bwd_cross_roles_kernel<64, false>, attn_bwd_cross_kernel<64, false>}},
+      {{attn_bwd_cross_roles_kernel<96, true>, attn_bwd_cross_kernel<96, true>}, {attn_bwd_cross_roles_kernel<96, false>, attn_bwd_cross_kernel<96, false>}}};
+  static const AttnKernel both[4] = {attn_bwd_both_kernel<64>, attn_bwd_both_kernel<96>, attn_bwd_both_kernel<128>, attn_bwd_both_kernel<160>};
+  static const AttnKernel dq[5] = {attn_bwd_dq_kernel<64, 48>, attn_bwd_dq_kernel<64>, attn_bwd_dq_kernel<96>, attn_bwd_dq_kernel<128>, attn_bwd_dq_kernel<160>};
+  static const AttnKernel dkdv[5] = {attn_bwd_dkdv_kernel<64, 48>, attn_bwd_dkdv_kernel<64>, attn_bwd_dkdv_kernel<96>, attn_bwd_dkdv_kernel<128>, attn_bwd_dkdv_kernel<160>};
+  const int i = (pl.dp - 64) / 32;
+  switch (pl.route) {
+    case SDLT_ATTN_ROUTE_FWD32: return sdlt_attn32_fwd(pl.ks).fn;
+    case SDLT_ATTN_ROUTE_FWD16_KS2: return fwd[0];
+    case SDLT_ATTN_ROUTE_FWD16: return fwd[pl.dv48 ? 1 : 2 + i];
+    case SDLT_ATTN_ROUTE_BWD_CROSS_ROLES: return cross[i][!pl.five][0];
+    case SDLT_ATTN_ROUTE_BWD_CROSS: return cross[i][!pl.five][1];
+    case SDLT_ATTN_ROUTE_BWD_BOTH32: return sdlt_attn32_bwd_both(pl.ks).fn;
+    case SDLT_ATTN_ROUTE_BWD_BOTH16: return both[i];
+    default: return (second ? dkdv : dq)[pl.dv48 ? 0 : 1 + i];
+  }
+}
+
+// raise the kernel's dynamic-LDS limit (once per (kernel, device), capi.cpp) and launch it; fn: the entry's name for the message
+template <typename... A>
+int attn_launch_kernel(void (*k)(A...), dim3 grid, int block, int smem, hipStream_t s, const char* fn, const A&... args) {
+  if (sdlt_raise_smem((const void*)k, smem)) SDLT_FAIL(SDLT_ERR_LAUNCH, "%s: LDS attribute", fn);
+  hipLaunchKernelGGL(k, grid, dim3(block), smem, s, args...);
+  return SDLT_OK;
+}
+int attn_launched(const char* fn) {      // an entry's closing check of everything it enqueued
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) SDLT_FAIL(SDLT_ERR_LAUNCH, "%s: %s", fn, hipGetErrorString(e));
+  return SDLT_OK;
+}
+
+int attn_launch(const AttnPlan& pl, const sdlt_attn_params& p, hipStream_t s, const char* fn) {
+  const int C = p.H * p.d;
+  const bool fwd16 = pl.route == SDLT_ATTN_ROUTE_FWD16 || pl.route == SDLT_ATTN_ROUTE_FWD16_KS2;
+  if (fwd16 && p.D) sdlt_zero_async(p.D, sizeof(float) * (size_t)p.B * p.H * p.Nq, s);      // (attn32_fwd_kernel zeroes D in its epilogue)
+  if (pl.prep) {
+    int blocks = (int)(((int64_t)p.B * p.Nqp * p.H * 8 + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(attn_prep_kernel, dim3(blocks), dim3(256), 0, s, (const bf16_t*)p.O, p.ldo, (const bf16_t*)p.dO, p.lddo, p.B, p.H, p.Nq, p.Nqp, p.d, p.D);
+  }
+  int rc = attn_launch_kernel(attn_kernel(pl, false), pl.grid, pl.block, pl.smem, s, fn, p);
+  if (rc) return rc;
+  if (pl.route == SDLT_ATTN_ROUTE_BWD_SPLIT && (rc = attn_launch_kernel(attn_kernel(pl, true), pl.grid2, pl.block, pl.smem2, s, fn, p))) return rc;
+  if (pl.splitsum) {
+    int blocks = (int)(((int64_t)p.B * p.Nkp * C / 2 + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(attn_splitsum_kernel, dim3(blocks), dim3(256), 0, s, p.dK32, p.dV32, p.qsplit, p.ld32, (bf16_t*)p.dK, p.lddk, (bf16_t*)p.dV, p.lddv,
+                       p.B, p.Nk, p.Nkp, C, p.accumulate_dk);      // (dK += on the cross routes only: BWD_SPLIT refuses the flag)
+  }
+  return attn_launched(fn);
+}
+
+void attn_env_once() {
+  static const bool applied = [] {
+    const int zero = 0;
+    if (!attn_switches().xcd) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_attn_xcd), &zero, sizeof(int));
+    return true;
+  }();
+  (void)applied;
+}
+
+int attn_plan(const sdlt_attn_params& p, bool backward, AttnPlan& pl) {
+  return backward ? attn_plan_bwd(p, attn_switches(), pl) : attn_plan_fwd(p, attn_switches(), pl);
+}
+int attn_run(const sdlt_attn_params& p, bool backward, void* stream) {      // check -> plan -> launch
+  attn_env_once();
+  AttnPlan pl;
+  const int rc = attn_plan(p, backward, pl);
+  return rc ? rc : attn_launch(pl, p, (hipStream_t)stream, backward ? "sdlt_attn_bwd" : "sdlt_attn_fwd");
+}
+
+}  // namespace
+
+extern "C" int sdlt_attn_fwd(const sdlt_attn_params* p, void* stream) { return attn_run(*p, false, stream); }
+extern "C" int sdlt_attn_bwd(const sdlt_attn_params* p, void* stream) { return attn_run(*p, true, stream); }
+
+extern "C" int32_t sdlt_attn_route(const sdlt_attn_params* pp, int32_t backward) {
+  AttnPlan pl;
+  const int rc = attn_plan(*pp, backward != 0, pl);
+  if (rc) return rc;
+  return pl.route | pl.dp << SDLT_ATTN_ROUTE_DP_SHIFT | pl.ks << SDLT_ATTN_ROUTE_KS_SHIFT | (pl.dv48 ? SDLT_ATTN_ROUTE_DV48 : 0) | (pl.five ? SDLT_ATTN_ROUTE_FIVE : 0) |
+         (pl.prep ? SDLT_ATTN_ROUTE_PREP : 0) | (pl.splitsum ? SDLT_ATTN_ROUTE_SPLITSUM : 0);
 }
 
 extern "C" int sdlt_attn_splitsum_batch(const sdlt_splitsum_desc* descs_dev, const int32_t* block_desc_dev, const int32_t* block_first_dev, int32_t n_blocks,
@@ -1295,10 +1366,8 @@ extern "C" int sdlt_attn_fwd_pair(const sdlt_attn_params* pa, const sdlt_attn_pa
   if (!attn_pair_shape_ok(a, b)) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_attn_fwd_pair: shapes (d <= 64, Nk < 256 both)");
   const int ta = (a.Nq + 63) / 64, tb = (b.Nq + 63) / 64;
   dim3 grid(ta > tb ? ta : tb, a.H + b.H, a.B > b.B ? a.B : b.B);
-  set_smem(attn_fwd_pair_kernel<64>, SMEM_FWD(64));
-  hipLaunchKernelGGL(attn_fwd_pair_kernel<64>, grid, dim3(256), SMEM_FWD(64), (hipStream_t)stream, a, b);
-  SDLT_CHECK_LAUNCH();
-  return SDLT_OK;
+  rc = attn_launch_kernel(attn_fwd_pair_kernel<64>, grid, 256, smem_fwd(64), (hipStream_t)stream, "sdlt_attn_fwd_pair", a, b);
+  return rc ? rc : attn_launched("sdlt_attn_fwd_pair");
 }
 
 extern "C" int sdlt_attn_bwd_pair(const sdlt_attn_params* pa, const sdlt_attn_params* pb, void* stream) {
@@ -1306,11 +1375,8 @@ extern "C" int sdlt_attn_bwd_pair(const sdlt_attn_params* pa, const sdlt_attn_pa
   const sdlt_attn_params &a = *pa, &b = *pb;
   hipStream_t s = (hipStream_t)stream;
   for (const sdlt_attn_params* q : {pa, pb}) {
-    const sdlt_attn_params& p = *q;
-    int rc = attn_check(p, "sdlt_attn_bwd_pair");
+    int rc = attn_check_bwd(*q, "sdlt_attn_bwd_pair", true);
     if (rc) return rc;
-    if (!p.L || !p.D || !p.O || !p.dO || !p.dQ || !p.dK || !p.dV) SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_attn_bwd_pair: missing operand");
-    if ((p.lddo % 8) || (p.ldo % 8) || (p.lddq % 4) || (p.lddk % 4) || (p.lddv % 4)) SDLT_FAIL(SDLT_ERR_ALIGN, "sdlt_attn_bwd_pair: ld alignment");
   }
   if (!attn_pair_shape_ok(a, b)) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_attn_bwd_pair: shapes");
   const int64_t ga = (int64_t)a.B * a.Nqp * a.H, gb = (int64_t)b.B * b.Nqp * b.H;
@@ -1319,8 +1385,6 @@ extern "C" int sdlt_attn_bwd_pair(const sdlt_attn_params* pa, const sdlt_attn_pa
   hipLaunchKernelGGL(attn_prep_pair_kernel, dim3(blocks, 2), dim3(256), 0, s, a, b);
   const int xa = (a.Nq + 63) / 64 + (a.Nk + 63) / 64, xb = (b.Nq + 63) / 64 + (b.Nk + 63) / 64;
   dim3 grid(xa > xb ? xa : xb, a.H + b.H, a.B > b.B ? a.B : b.B);
-  set_smem(attn_bwd_both_pair_kernel<64>, SMEM_BOTH(64));
-  hipLaunchKernelGGL(attn_bwd_both_pair_kernel<64>, grid, dim3(256), SMEM_BOTH(64), s, a, b);
-  SDLT_CHECK_LAUNCH();
-  return SDLT_OK;
+  const int rc = attn_launch_kernel(attn_bwd_both_pair_kernel<64>, grid, 256, smem_both(64), s, "sdlt_attn_bwd_pair", a, b);
+  return rc ? rc : attn_launched("sdlt_attn_bwd_pair");
 }

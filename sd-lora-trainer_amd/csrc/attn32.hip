@@ -717,41 +717,18 @@ __global__ __launch_bounds__(128 * KS) void attn32_bwd_both_kernel(const sdlt_at
   else attn32_dkdv_body<KS>(p, smem, wg.x - ndq, wg);
 }
 
-template <typename F>
-int set_smem32(F f, int bytes) { return sdlt_raise_smem((const void*)f, bytes); }
-
 }  // namespace
 
 bool sdlt_attn32_ok(const sdlt_attn_params& p) {
   return p.d == 64 && !p.causal && p.Nq >= 64 && p.Nk >= 64 && (p.Nq % 64) == 0 && (p.Nk % 64) == 0 && p.Nqp >= p.Nq && p.Nkp >= p.Nk;
 }
 
-int sdlt_attn32_fwd(const sdlt_attn_params& p, int ks, hipStream_t s) {
-  dim3 grid(p.Nq / 64, p.H, p.B);
-#define FWD32(KS_)                                                                                           \
-  do {                                                                                                       \
-    const int sm = (KS_) * 4 * TILE;                                                                         \
-    if (set_smem32(attn32_fwd_kernel<KS_>, sm)) SDLT_FAIL(SDLT_ERR_LAUNCH, "sdlt_attn32_fwd: LDS attribute"); \
-    hipLaunchKernelGGL((attn32_fwd_kernel<KS_>), grid, dim3(128 * (KS_)), sm, s, p);                          \
-  } while (0)
-  if (ks >= 4) FWD32(4);
-  else if (ks >= 2) FWD32(2);
-  else FWD32(1);
-  SDLT_CHECK_LAUNCH();
-  return SDLT_OK;
+sdlt_attn32_kernel sdlt_attn32_fwd(int ks) {      // (K, V) x two buffers per wave group
+  static void (*const fn[3])(const sdlt_attn_params) = {attn32_fwd_kernel<4>, attn32_fwd_kernel<2>, attn32_fwd_kernel<1>};
+  return {fn[ks == 4 ? 0 : ks == 2 ? 1 : 2], ks * 4 * TILE};
 }
 
-int sdlt_attn32_bwd_both(const sdlt_attn_params& p, int ks, hipStream_t s) {
-  dim3 grid(p.Nq / 64 + p.Nk / 64, p.H, p.B);
-#define BWD32(KS_)                                                                                                 \
-  do {                                                                                                             \
-    const int sm = (KS_) * 2 * (2 * TILE + 512);                                                                   \
-    if (set_smem32(attn32_bwd_both_kernel<KS_>, sm)) SDLT_FAIL(SDLT_ERR_LAUNCH, "sdlt_attn32_bwd: LDS attribute"); \
-    hipLaunchKernelGGL((attn32_bwd_both_kernel<KS_>), grid, dim3(128 * (KS_)), sm, s, p);                           \
-  } while (0)
-  if (ks >= 4) BWD32(4);
-  else if (ks >= 2) BWD32(2);
-  else BWD32(1);
-  SDLT_CHECK_LAUNCH();
-  return SDLT_OK;
+sdlt_attn32_kernel sdlt_attn32_bwd_both(int ks) {      // (Q, dO, L and D rows) x two buffers per wave group
+  static void (*const fn[3])(const sdlt_attn_params) = {attn32_bwd_both_kernel<4>, attn32_bwd_both_kernel<2>, attn32_bwd_both_kernel<1>};
+  return {fn[ks == 4 ? 0 : ks == 2 ? 1 : 2], ks * 2 * (2 * TILE + 512)};
 }

@@ -933,9 +933,10 @@ def attn_bwd(Q, K, V, Kt, Qt, O, L, dO, dOt, D, dQ, dK, dV, *, B, H, Nq, Nk, Nqp
     p.accumulate_dq, p.accumulate_dk = int(accumulate_dq), int(accumulate_dk)
     if qsplit > 1:
         _chk2(dK32, F32), _chk2(dV32, F32)
-        if not causal and Nkp <= 128 and d <= 96:   # single-pass cross-attention kernel: one partial slab per query split
-            assert dK32.shape[0] >= qsplit * B * Nkp and dV32.shape[0] >= qsplit * B * Nkp, "dK32/dV32 must hold qsplit slabs"
         p.dK32, p.dV32, p.ld32 = _p(dK32), _p(dV32), _ld(dK32)
+        code = lib.sdlt_attn_route(C.byref(p), 1)      # (a negative code is an error, which the launch below reports)
+        if code >= 0 and _lib.attn_route_decode(code)["route"] in ("BWD_CROSS", "BWD_CROSS_ROLES"):   # single-pass kernel: one partial slab per query split
+            assert dK32.shape[0] >= qsplit * B * Nkp and dV32.shape[0] >= qsplit * B * Nkp, "dK32/dV32 must hold qsplit slabs"
     _issue("attn_bwd", p)
 
 
