@@ -797,6 +797,21 @@ int sdlt_heatmap_overlay(const sdlt_heatmap_overlay_params* p, void* stream);
 int sdlt_token_pool(const void* x, int64_t ldx, int32_t B, int32_t H, int32_t W, int32_t C, const float* gamma, const float* beta, float eps,
                     int32_t f, int32_t mode, void* y, int64_t ldy, int32_t Nkp, void* stream);
 
+/* sdlt_tile_blend : one tile of a tiled VAE decode / encode added into the whole picture with its feather weights (vae.py: decode_tiled,
+ * encode_moments_tiled; render.py: `vae_tile`; inference only):
+ *   out[c, y0 + p, x0 + q] += (wy[p] * wx[q]) * tile[(p tw + q) ld + c]          c < C, p < th, q < tw
+ * tile fp32 NHWC rows [th tw, ld] (ld floats between rows: the decoder's image rows have ld = 4, C = 3; the encoder's moment rows ld = C = 8); out fp32
+ * planar [C, H, W], contiguous, zeroed once by the caller; wy fp32 [th], wx fp32 [tw]: the tile's normalised 1-D weights (vae.tile_weights), whose
+ * products sum to 1 over the tiles that cover a sample.  One launch per tile, the tiles of a picture in row-major order on one stream; no atomics, so the
+ * picture repeats bit for bit.  The arithmetic is three fp32 operations with one rounding each and no contraction - t = wy[p] * wx[q], u = t * v,
+ * out = out + u - which a torch fp32 restatement reproduces exactly.  One thread per (p, q), 64 consecutive x per wave (every plane access of a wave is one
+ * 256-byte run), one 16-byte load per 4 channels of a tile row where ld % 4 == 0 and tile is 16-byte aligned, scalar loads otherwise; 64-bit plane offsets.
+ * A null pointer, a non-positive extent (th, tw, C, H, W), H or W above 2^20, C > 16 (the kernel's limit), C > ld, a tile that reaches outside H x W
+ * (y0 < 0, x0 < 0, y0 + th > H, x0 + tw > W), th > 262140, out overlapping tile (-1); a pointer that is not 4-byte aligned (-2): the code is returned,
+ * sdlt_last_error names the entry point and nothing is launched. */
+int sdlt_tile_blend(const float* tile, int64_t ld, int32_t th, int32_t tw, int32_t C, const float* wy, const float* wx,
+                    float* out, int32_t H, int32_t W, int32_t y0, int32_t x0, void* stream);
+
 /* out[M,C] = a + b on strided 2-D bf16 views (gradient fan-in of the UNet skip connections). */
 int sdlt_add2d(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int32_t M, int32_t C, void* stream);
 

@@ -276,6 +276,7 @@ SYMBOLS = {
     "sdlt_heatmap_accum": (i32, [C.POINTER(HeatAccumParams), vp]),
     "sdlt_heatmap_overlay": (i32, [C.POINTER(HeatOverlayParams), vp]),
     "sdlt_token_pool": (i32, [vp, i64, i32, i32, i32, i32, vp, vp, f32, i32, i32, vp, i64, i32, vp]),
+    "sdlt_tile_blend": (i32, [vp, i64, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
     "sdlt_strip_gemm": (i32, [C.POINTER(StripParams), vp]),
     "sdlt_strip_gemm_pair": (i32, [C.POINTER(StripParams), C.POINTER(StripParams), vp]),
     "sdlt_attn_pair_ok": (i32, [C.POINTER(AttnParams), C.POINTER(AttnParams)]),

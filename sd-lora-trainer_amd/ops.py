@@ -1437,6 +1437,28 @@ def token_pool(x, y, *, B, H, W, gamma, beta, eps, f, mode):
     return y
 
 
+TILE_BLEND_MAX_C = 16      # planes per sdlt_tile_blend launch
+
+
+def tile_blend(tile, out, wy, wx, y0, x0, C):
+    """sdlt_tile_blend: out[c, y0 + p, x0 + q] += (wy[p] * wx[q]) * tile[p tw + q, c] for c < C - one tile of a tiled VAE decode / encode added into the
+    picture with its feather weights.  tile fp32 [th tw, ld] (NHWC rows as the last conv left them, any leading dimension >= C), out fp32 [C, H, W]
+    contiguous (zeroed once by the caller), wy fp32 [th] and wx fp32 [tw] the tile's normalised 1-D weights (vae.tile_weights).  t = wy wx, t v and the
+    add are three fp32 roundings in that order (tests/vaetile_ref.py: blend32 gives the same bits); one launch per tile, tiles in row-major order on one
+    stream: no atomics, bitwise repeatable."""
+    lib = _lib.load()
+    _chk2(tile, F32), _chk2(out, F32), _chk2(wy, F32), _chk2(wx, F32)
+    assert wy.dim() == 1 and wx.dim() == 1 and wy.is_contiguous() and wx.is_contiguous(), "wy [th], wx [tw]: contiguous 1-D fp32"
+    th, tw = wy.numel(), wx.numel()
+    assert out.dim() == 3 and out.is_contiguous() and out.shape[0] == C, f"out must be contiguous fp32 [C={C}, H, W], got {tuple(out.shape)}"
+    assert tile.dim() == 2 and tile.shape[0] == th * tw and 1 <= C <= min(tile.shape[1], TILE_BLEND_MAX_C), \
+        f"tile {tuple(tile.shape)} for th={th} tw={tw} C={C} (rows th tw, C of at most {TILE_BLEND_MAX_C} of its columns)"
+    H, W = out.shape[1:]
+    assert 0 <= y0 and y0 + th <= H and 0 <= x0 and x0 + tw <= W, f"a {th} x {tw} tile at ({y0}, {x0}) reaches outside the {H} x {W} output"
+    _lib.check(lib.sdlt_tile_blend(_p(tile), _ld(tile), th, tw, int(C), _p(wy), _p(wx), _p(out), H, W, int(y0), int(x0), _stream()), "sdlt_tile_blend")
+    return out
+
+
 def masked_mse_fwd_bwd(pred, noise, noisy, mask, timesteps, alphas_cumprod, sums, loss_out, dpred, *, snr_gamma, v_prediction=False,
                        loss_scale=1.0):
     lib = _lib.load()

@@ -10,6 +10,7 @@ scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-squ
                                          [--hires-scale F | --hires-size W H] [--hires-strength F] [--hires-steps N] [--hires-upscaler latent|pixel]
                                          [--hires-resample nearest|bilinear|bicubic] [--heatmap [WORD ...]] [--heatmap-grid max|min]
                                          [--kv-downsample F [F2 ...]] [--kv-downsample-mode nearest|area] [--kv-downsample-pass hires|all]
+                                         [--vae-tile [T]] [--vae-tile-overlap O]
                                          [--unet F] [--text-encoder F] [--text-encoder-2 F] [--vae F] [--tokenizer DIR]
 
 DIR is a checkpoint directory of train(): training_args.json (the job's TrainingConfig), adapter_config.json + the kohya adapter file
@@ -65,6 +66,13 @@ paper's) takes every F-th token, area the mean of each F x F window.  One more l
 self-attention inside the replayed graph.  It is meant for the second pass of a hires render - where the grids are large, and after the first pass has
 decided the composition - so --kv-downsample-pass defaults to hires and the flag without --hires-scale / --hires-size is an error; all uses it in
 every pass.  Without the flag nothing changes.
+
+--vae-tile [T] (diffusers' enable_vae_tiling) runs the VAE in tiles of T x T latent units (default 64: 512 px) that overlap by at least --vae-tile-overlap O
+(default 16: 128 px) and are put together on the device with a normalised feather (sdlt_tile_blend; vae.VaeDecoder.decode_tiled,
+vae.VaeEncoder.encode_moments_tiled): the decode of every picture, the decode and encode of --hires-upscaler pixel, and the encode of --init-image.  The
+VAE's mid-block attention materialises a [pixels, pixels] score matrix - 17 GB at 2048 px, beyond the card at 4096 px - and with tiles it always runs at
+the one tile shape, so the decoder is built once and a hires render rebuilds only the UNet.  GroupNorm statistics are per tile: a tiled picture differs
+slightly from an untiled one.  Without the flag nothing changes.
 """
 import argparse
 import json
@@ -89,18 +97,32 @@ class Loaded:
         self.config, self.models, self.stack, self.checkpoint_dir = config, models, stack, checkpoint_dir
         self.lora, self.te_lora, self.embeddings = lora, te_lora, embeddings
         self.shape = None                       # (images per batch, h, w) the UNet's buffers were allocated for
+        self.dec_shape = None                   # (h, w) the VAE decoder's buffers were allocated for: the latent's, or the tile's of a tiled decode
 
     def load_adapters(self):
         """The checkpoint's adapters into the (re)built UNet."""
         if self.lora is not None:
             self.stack.unet.arena.load(self.lora)
 
-    def prepare(self, n_images, h, w):
-        """The UNet's activation buffers belong to the first latent shape it runs: another batch or size starts from fresh instances."""
+    def prepare(self, n_images, h, w, keep_decoder=False):
+        """The UNet's activation buffers belong to the first latent shape it runs: another batch or size starts from fresh instances.  keep_decoder: the
+        VAE decoder is not rebuilt with them (a tiled decode runs at the tile's shape whatever the picture's: prepare_decoder)."""
         if self.shape is not None and self.shape != (n_images, h, w) or n_images != self.stack.n_images:
-            self.stack.build_sampler(n_images)
+            self.stack.keep_decoder = keep_decoder
+            try:
+                self.stack.build_sampler(n_images)
+            finally:
+                self.stack.keep_decoder = False
+            if not keep_decoder:
+                self.dec_shape = None
             self.load_adapters()
         self.shape = (n_images, h, w)
+
+    def prepare_decoder(self, h, w):
+        """The decoder's buffers belong to the first latent shape it decodes, (h, w): another shape starts from a fresh decoder (the UNet stays)."""
+        if self.dec_shape is not None and self.dec_shape != (h, w):
+            self.stack.build_decoder()
+        self.dec_shape = (h, w)
 
 
 def _find(checkpoint_dir, suffix):
@@ -214,26 +236,44 @@ def _vae_encoder(loaded):
     return V.VaeEncoder(M.Runtime(rt.device, 1, act_dtype=rt.act, ops=rt.ops), loaded.models.vae_state())
 
 
+VAE_TILE, VAE_TILE_OVERLAP = 64, 16      # --vae-tile's defaults, in latent units (512 and 128 px with the SD / SDXL VAE)
+
+
+def vae_tile_args(vae_tile):
+    """render()'s `vae_tile`, checked -> None | (tile, overlap) in latent units.  None: off; an int: that tile with the default overlap; (tile, overlap).
+    ValueError unless tile >= 2 and 0 <= 2 overlap <= tile (vae.tile_starts)."""
+    from . import vae as V
+    if vae_tile is None:
+        return None
+    if isinstance(vae_tile, bool) or not (isinstance(vae_tile, int) or (isinstance(vae_tile, (tuple, list)) and len(vae_tile) == 2
+                                                                        and all(isinstance(v, int) and not isinstance(v, bool) for v in vae_tile))):
+        raise ValueError(f"vae_tile must be None, a tile length or (tile, overlap) in latent units, got {vae_tile!r}")
+    tile, overlap = (vae_tile, VAE_TILE_OVERLAP) if isinstance(vae_tile, int) else vae_tile
+    V.tile_starts(tile, tile, overlap)
+    return int(tile), int(overlap)
+
+
 @torch.no_grad()
-def encode_image(loaded, img, enc=None):
-    """img [1, 3, H, W] fp32 in about [-1, 1] -> init latents [1, 4, H/f, W/f] fp32: the posterior's mean times the scaling factor (deterministic)."""
+def encode_image(loaded, img, enc=None, vae_tile=None):
+    """img [1, 3, H, W] fp32 in about [-1, 1] -> init latents [1, 4, H/f, W/f] fp32: the posterior's mean times the scaling factor (deterministic).
+    vae_tile (tile, overlap): through VaeEncoder.encode_moments_tiled."""
     enc = enc or _vae_encoder(loaded)
-    mom = enc.encode_moments(img)
+    mom = enc.encode_moments(img) if vae_tile is None else enc.encode_moments_tiled(img, *vae_tile)
     x0 = mom[:, : mom.shape[1] // 2].float() * loaded.models.cfg["scaling_factor"]
     return x0.contiguous()
 
 
 @torch.no_grad()
-def encode_init(loaded, init_image, mask_image, size, latent_hw):
+def encode_init(loaded, init_image, mask_image, size, latent_hw, vae_tile=None):
     """-> (init latents [1, 4, h, w] fp32 = posterior mean of the image, resized to `size` = (width, height), times the scaling factor;
-    mask [1, 1, h, w] fp32 | None: dataset.latent_mask's resize, 1 regenerate / 0 keep).  Images are paths or PIL images."""
+    mask [1, 1, h, w] fp32 | None: dataset.latent_mask's resize, 1 regenerate / 0 keep).  Images are paths or PIL images.  vae_tile: encode_image's."""
     from . import dataset as D
     enc = _vae_encoder(loaded)
     f = 2 ** (len(enc.downs) - 1)
     h, w = latent_hw
     if (size[0], size[1]) != (f * w, f * h):
         raise ValueError(f"an init image needs a size that is a multiple of {f}, got {size[0]} x {size[1]}")
-    x0 = encode_image(loaded, D.prepare_image(_open(init_image).convert("RGB"), size[0], size[1]), enc)
+    x0 = encode_image(loaded, D.prepare_image(_open(init_image).convert("RGB"), size[0], size[1]), enc, vae_tile)
     mask = None
     if mask_image is not None:
         mask = D.latent_mask(_open(mask_image), size, (h, w), channels=1).reshape(1, 1, h, w).to(loaded.stack.rt.device)
@@ -313,7 +353,7 @@ def hires_args(hires, size, steps, f=8):
 def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, guidance_scale=8.0, seed=None, images_per_batch=1, token_scale=None,
            graph=True, n_validation=4, init_image=None, strength=None, mask_image=None, sampler="euler", sigmas="trailing", eta=None,
            guidance_rescale=0.0, guidance_interval=None, negative_prompt=None, hires=None, freeu=None, heatmap=None, heatmap_grid="max",
-           kv_downsample=None, kv_downsample_mode="nearest", kv_downsample_pass="hires"):
+           kv_downsample=None, kv_downsample_mode="nearest", kv_downsample_pass="hires", vae_tile=None):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
     seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
@@ -337,6 +377,9 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     LatentSampler.sample's key / value token downsampling (sampler.kv_downsample_args; UNet.set_kv_downsample).  kv_downsample_pass "hires" (default):
     only the second pass of a hires render carries it - that is where the self-attentions are large, and the first pass decides the composition -
     so without `hires` it is refused; "all": every pass.
+    vae_tile: None, a tile length or (tile, overlap) in latent units (vae_tile_args; the overlap defaults to 16): every VAE pass of the render - the
+    decode of each picture, the decode and encode of the pixel upscaler, the encode of init_image - runs in tiles (VaeDecoder.decode_tiled,
+    VaeEncoder.encode_moments_tiled; ops.tile_blend).  The decoder then runs at the tile's shape and is not rebuilt with the UNet by the hires pass.
     -> {scale: [paths]}."""
     from . import train as T
     from . import vae as _vae
@@ -405,6 +448,9 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         if not hasattr(stack.rt.ops, "token_pool"):
             raise NotImplementedError("this op table has no token_pool kernel (sdlt_token_pool): kv_downsample pools the keys' tokens by that launch (ops.token_pool)")
     kd_kw = {} if kd is None else dict(kv_downsample=kd[0], kv_downsample_mode=kd[1])
+    vt = vae_tile_args(vae_tile)                                     # (raises before anything is built)
+    if vt is not None and not hasattr(stack.rt.ops, "tile_blend"):
+        raise NotImplementedError("this op table has no tile_blend kernel (sdlt_tile_blend): vae_tile puts the VAE's tiles together by that launch (ops.tile_blend)")
     hi = None
     if hires is not None:
         if mask_image is not None:
@@ -431,9 +477,9 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     else:
         strength = 0.6 if strength is None else strength
         SM.img2img_steps(steps, strength)               # (raises before anything is built)
-        x0, mask = encode_init(loaded, init_image, mask_image, size, (h, w))
+        x0, mask = encode_init(loaded, init_image, mask_image, size, (h, w), **({} if vt is None else dict(vae_tile=vt)))
         img_kw.update(init_latents=x0, strength=strength, mask=mask)
-    loaded.prepare(n, h, w)
+    loaded.prepare(n, h, w, **({} if vt is None else dict(keep_decoder=True)))
     fused = hasattr(stack.rt.ops, "sampler_step_sde" if sde else "sampler_step_ms" if sampler == "dpmpp_2m" else "sampler_step")
     graph = graph and dev.type == "cuda"
     os.makedirs(out_dir, exist_ok=True)
@@ -454,10 +500,19 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
                            **{k: one(v, j) for k, v in kw.items()}, **sd([j]), **hm([j])) for j, i in enumerate(idx)]
         return (torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])) if heat else torch.cat(outs)
 
+    def decode(z):
+        """One image's latents [1, 4, lh, lw] -> picture [1, 3, f lh, f lw]; the decoder's buffers follow the shape it runs at (the tile's with vae_tile)."""
+        lh, lw = z.shape[2:]
+        if vt is None:
+            loaded.prepare_decoder(lh, lw)
+            return stack.decoder.decode(z)
+        loaded.prepare_decoder(min(lh, vt[0]), min(lw, vt[0]))
+        return stack.decoder.decode_tiled(z, *vt)
+
     def save(lat, idx, s0, scale, paths):
         lat, heat = lat if isinstance(lat, tuple) else (lat, None)
         for j, i in enumerate(idx[: len(prompts) - s0]):
-            chw = _vae.postprocess(stack.decoder.decode(lat[j:j + 1] / cfg["scaling_factor"]))
+            chw = _vae.postprocess(decode(lat[j:j + 1] / cfg["scaling_factor"]))
             img = chw[0].permute(1, 2, 0)
             arr = (img.float().cpu().numpy() * 255).round().astype("uint8")
             paths.append(os.path.join(out_dir, f"img_{i:02d}_seed{seed + i}_scale{_scale_tag(scale)}.jpg"))
@@ -483,8 +538,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             return SM.upscale_latents(ops, lat, h2, w2, hi["resample"])
         out = []
         for j in range(n):                      # through the VAE: the decoder's output as it is (not clamped), enlarged, the encoder's posterior mean
-            img = stack.decoder.decode(lat[j:j + 1] / cfg["scaling_factor"])
-            out.append(encode_image(loaded, SM.upscale_latents(ops, img, f * h2, f * w2, hi["resample"]), enc))
+            img = decode(lat[j:j + 1] / cfg["scaling_factor"])
+            out.append(encode_image(loaded, SM.upscale_latents(ops, img, f * h2, f * w2, hi["resample"]), enc, **({} if vt is None else dict(vae_tile=vt))))
         return torch.cat(out)
 
     if hi is not None:
@@ -513,7 +568,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
                 finish(scale, paths)
         if hi is not None:
             del enc
-            loaded.prepare(n, h2, w2)           # the one rebuild: the UNet's (and the decoder's) buffers belong to the first shape they ran
+            # the one rebuild: the UNet's (and the decoder's) buffers belong to the first shape they ran; a tiled decoder runs at the tile's shape and stays
+            loaded.prepare(n, h2, w2, **({} if vt is None else dict(keep_decoder=True)))
             for k, scale in enumerate(lora_scales):
                 stack.sampler.set_lora_scale(scale)
                 paths = []
@@ -547,6 +603,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             meta.update(kv_downsample=dict(factors=list(kd[0]), mode=kd[1], passes=kv_downsample_pass))
         if hm_cols is not None:
             meta.update(heatmap=dict(maps=hm_names, grid=heatmap_grid, positions=hm_cols.tolist()))
+        if vt is not None:
+            meta.update(vae_tile=dict(tile=vt[0], overlap=vt[1]))
         json.dump(meta, fh, indent=2)
     return result
 
@@ -595,6 +653,11 @@ def main(argv=None, runtime=None):
     ap.add_argument("--kv-downsample-mode", choices=("nearest", "area"), default=None, help="with --kv-downsample: take every F-th token (default), or the mean of each F x F window")
     ap.add_argument("--kv-downsample-pass", choices=KV_PASSES, default=None,
                     help="with --kv-downsample: hires (default) - only the second pass of a --hires-scale / --hires-size render; all - every pass")
+    ap.add_argument("--vae-tile", type=int, nargs="?", const=VAE_TILE, default=None, metavar="T",
+                    help=f"run the VAE in tiles of T x T latent units (default {VAE_TILE}: {8 * VAE_TILE} px with the SD / SDXL VAE) blended on the device: bounded memory "
+                    "and one decoder shape at any picture size")
+    ap.add_argument("--vae-tile-overlap", type=int, default=None, metavar="O",
+                    help=f"with --vae-tile: least overlap of neighbouring tiles in latent units, 0 <= 2 O <= T (default {VAE_TILE_OVERLAP})")
     ap.add_argument("--device", default="cuda:0")
     for flag, key, what in (("--unet", "path", "base UNet weights or synthetic:<version>"), ("--text-encoder", "text_encoder_path", "text encoder state dict"),
                             ("--text-encoder-2", "text_encoder_2_path", "SDXL's second text encoder"), ("--vae", "vae_path", "AutoencoderKL state dict"),
@@ -630,6 +693,15 @@ def main(argv=None, runtime=None):
                  "pass --kv-downsample-pass all to use it in a single-pass render")
     kvd = {} if a.kv_downsample is None else dict(kv_downsample=tuple(a.kv_downsample), kv_downsample_mode=a.kv_downsample_mode or "nearest",
                                                    kv_downsample_pass=a.kv_downsample_pass or "hires")
+    if a.vae_tile is None and a.vae_tile_overlap is not None:
+        ap.error("--vae-tile-overlap needs --vae-tile [T]")
+    vtile = {}
+    if a.vae_tile is not None:
+        vtile = dict(vae_tile=(a.vae_tile, VAE_TILE_OVERLAP if a.vae_tile_overlap is None else a.vae_tile_overlap))
+        try:
+            vae_tile_args(vtile["vae_tile"])
+        except ValueError as e:
+            ap.error(f"--vae-tile / --vae-tile-overlap: {e}")
     freeu = None if a.freeu is None else dict(zip(("b1", "b2", "s1", "s2"), a.freeu), version=2 if a.freeu_v2 else 1)
     hires = None
     if a.hires_scale is not None and a.hires_size is not None:
@@ -656,7 +728,7 @@ def main(argv=None, runtime=None):
                  images_per_batch=a.images_per_batch, graph=not a.eager, n_validation=a.n_validation, init_image=a.init_image, strength=a.strength,
                  mask_image=a.mask, sampler=a.sampler, sigmas=a.sigmas, eta=a.eta, guidance_rescale=a.guidance_rescale,
                  guidance_interval=a.guidance_interval, negative_prompt=a.negative_prompt, **({} if hires is None else dict(hires=hires)),
-                 **({} if freeu is None else dict(freeu=freeu)), **kvd,
+                 **({} if freeu is None else dict(freeu=freeu)), **kvd, **vtile,
                  **({} if a.heatmap is None else dict(heatmap=a.heatmap, heatmap_grid=a.heatmap_grid or "max")))
     for scale, paths in res.items():
         print(f"lora_scale {scale}: {len(paths)} image(s), {os.path.join(a.out, 'grid_scale' + _scale_tag(scale) + '.jpg')}")

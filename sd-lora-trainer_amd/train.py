@@ -298,19 +298,30 @@ class RenderStack:
 
     def build_sampler(self, n_images):
         """(Re)build the UNet, its sampler and the VAE decoder for n_images images sampled together.  Their activation buffers are allocated for
-        the first latent shape they run, so a render at another size or batch starts from fresh instances (the caller reloads the adapters)."""
+        the first latent shape they run, so a render at another size or batch starts from fresh instances (the caller reloads the adapters).  With
+        `keep_decoder` set on the stack an existing decoder stays: a tiled decode runs at the tile's shape, not the picture's (render.Loaded.prepare)."""
         from . import sampler as SM
         from . import unet as M
-        from . import vae as V
         config, models = self.config, self.models
         dev = models.rt.device
         self.n_images = n_images
-        self.unet = self.sampler = self.decoder = None
+        keep = getattr(self, "keep_decoder", False) and getattr(self, "decoder", None) is not None
+        self.unet = self.sampler = None
+        if not keep:
+            self.decoder = None
         self.rt = M.Runtime(dev, 2 * n_images, ops=models.rt.ops)
         kw = dict(lora_rank=config.lora_rank, lora_alpha_multiplier=config.lora_alpha_multiplier, use_dora=config.use_dora) if self.is_lora else {}
         self.unet = M.UNet(self.rt, models.cfg, models.unet_state(), **kw)
         self.sampler = SM.LatentSampler(self.rt, self.unet)
-        self.decoder = V.VaeDecoder(M.Runtime(dev, 1, ops=models.rt.ops), models.vae_state())
+        if not keep:
+            self.build_decoder()
+
+    def build_decoder(self):
+        """(Re)build the VAE decoder alone: its buffers belong to the first latent shape it decodes."""
+        from . import unet as M
+        from . import vae as V
+        self.decoder = None
+        self.decoder = V.VaeDecoder(M.Runtime(self.models.rt.device, 1, ops=self.models.rt.ops), self.models.vae_state())
 
     def encode(self, prompt, negative):
         """pipe.encode_prompt(prompt, do_classifier_free_guidance=True, negative_prompt=...) -> (c, uc[, pc, puc]); batch row 0 = negative."""
