@@ -139,6 +139,24 @@ typedef struct sdlt_gemm_params {
   int32_t x2_group_n;
 } sdlt_gemm_params;
 int sdlt_gemm_bf16(const sdlt_gemm_params* p, void* stream);
+/* What sdlt_gemm_bf16 would launch for *p, without launching anything: host code only, no pointer field of p is dereferenced (their values count for the
+ * alignment and workspace terms).  Returns the negative SDLT_ERR_* the launch entry would return (sdlt_last_error set alike) and leaves *out alone, or 0 with
+ * *out = the kernel gemm_kernel<MI, NI, WN, mode, r16, stages, kg, bt, WM, epi, ln> of tile `tile` (ids above, 7 = 256x160 and 8 = 128x160 included), its grid
+ * and its scratch.  p and out must not be NULL (as with every entry point, neither is checked).  The block is declared without a struct tag and has no index
+ * in sdlt_struct_size() (see sdlt_resize_params); it is 64 bytes, fourteen int32 and one int64. */
+typedef struct {
+  int32_t tile;                      /* 1..8, after the heuristics and the moves that options force */
+  int32_t mode;                      /* 0 plain, 1 3x3 convolution, 2 convolution + second K segment */
+  int32_t r16;                       /* lora_R / 16 */
+  int32_t stages;                    /* LDS ring depth the kernel runs with (2, 3 or 4) */
+  int32_t kg, bt, epi, ln;           /* K-grouped adapters (0 / 4); batched (0 / 1); fused epilogue (0..4); folded LayerNorm (0, 1, 2 = from ln_parts) */
+  int32_t splitk;                    /* >= 1; the kernel receives it as sdlt_gemm_params.splitk */
+  int32_t grid_x, grid_y, threads;   /* grid_x = tiles * splitk, grid_y = n_batch or 1 */
+  int32_t lds_bytes;                 /* dynamic LDS of the launch */
+  int32_t stages_req;                /* ring depth the variant was asked for: 2, or 4 = as deep as the LDS allows (stages is what that gave) */
+  int64_t slab_bytes;                /* split-K scratch per workgroup: ws_slab must hold grid_x of them when splitk > 1 */
+} sdlt_gemm_plan;
+int sdlt_gemm_route(const sdlt_gemm_params* p, sdlt_gemm_plan* out);
 
 /* ------------------------------------------------------------------------------------------------
  * Optional transposed copy of C written by the sdlt_gemm_bf16 epilogue: set via sdlt_gemm_params.Ct

@@ -44,6 +44,24 @@ class GemmParams(C.Structure):
     ]
 
 
+class GemmPlan(C.Structure):
+    # sdlt_gemm_plan, the answer of sdlt_gemm_route: 64 bytes by the header's text (tagless, like sdlt_resize_params)
+    _fields_ = [("tile", i32), ("mode", i32), ("r16", i32), ("stages", i32), ("kg", i32), ("bt", i32), ("epi", i32), ("ln", i32), ("splitk", i32),
+                ("grid_x", i32), ("grid_y", i32), ("threads", i32), ("lds_bytes", i32), ("stages_req", i32), ("slab_bytes", i64)]
+
+
+# the kernel families of csrc/gemm.hip by their template tail (kg, bt, epi, ln): a hand-kept copy of the tails in GEMM_FAMILIES, to be kept in step with it
+# (a tail added there alone shows as a KeyError in gemm_variant, not as "a variant no case reaches" in tests/test_gemm_route_cpu.py)
+GEMM_VARIANTS = {(0, 0, 0, 0): "PLAIN", (0, 0, 0, 1): "LN_ADAPTER", (0, 0, 0, 2): "LN_ADAPTER_PARTS", (0, 0, 1, 1): "LN_GEGLU", (0, 0, 1, 2): "LN_GEGLU_PARTS",
+                 (0, 1, 0, 0): "BATCH", (4, 0, 0, 0): "KGROUP", (4, 1, 0, 0): "KGROUP_BATCH",
+                 (0, 0, 1, 0): "EPI1", (0, 0, 2, 0): "EPI2", (0, 0, 3, 0): "EPI3", (0, 0, 4, 0): "EPI4"}
+
+
+def gemm_variant(plan):
+    """The family name of a GemmPlan that sdlt_gemm_route filled."""
+    return GEMM_VARIANTS[(plan.kg, plan.bt, plan.epi, plan.ln)]
+
+
 class LnFoldDesc(C.Structure):
     _fields_ = [("A32", vp), ("lda", i64), ("gamma", vp), ("beta", vp), ("Ag", vp), ("ldag", i64), ("consts", vp), ("rank", i32), ("K", i32)]
 
@@ -224,6 +242,7 @@ SYMBOLS = {
     "sdlt_struct_size": (i32, [i32]),
     "sdlt_add2d": (i32, [vp, i64, vp, i64, vp, i64, i32, i32, vp]),
     "sdlt_gemm_bf16": (i32, [C.POINTER(GemmParams), vp]),
+    "sdlt_gemm_route": (i32, [C.POINTER(GemmParams), C.POINTER(GemmPlan)]),
     "sdlt_lora_grad_grouped": (i32, [vp, vp, i32, i32, i32, vp]),
     "sdlt_lora_grad_block_cols": (i32, []),
     "sdlt_lora_grad_wide": (i32, [vp, vp, i32, i32, i32, vp]),
@@ -328,7 +347,7 @@ def load():
             raise KernelLibraryError(f"struct layout mismatch for {name}: C {lib.sdlt_struct_size(which)} vs binding {size}")
     if C.sizeof(ResizeParams) != 48:
         raise KernelLibraryError(f"struct layout mismatch for ResizeParams: header 48 vs binding {C.sizeof(ResizeParams)}")
-    for cls, size in ((HeatAccumParams, 152), (HeatOverlayParams, 80)):
+    for cls, size in ((HeatAccumParams, 152), (HeatOverlayParams, 80), (GemmPlan, 64)):
         if C.sizeof(cls) != size:
             raise KernelLibraryError(f"struct layout mismatch for {cls.__name__}: header {size} vs binding {C.sizeof(cls)}")
     _lib = lib

@@ -975,303 +975,132 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_kernel(const sdlt_gemm_para
   GTR(11);
 }
 
-template <int MI, int NI, int WN, int MODE, int R16, int NSREQ, int KG = 0, int BT = 0, int WM = 2, int EPI = 0, int LN = 0>
-int launch(const sdlt_gemm_params& p, hipStream_t stream) {
-  constexpr int NTHR = 64 * WM * WN;
-  constexpr int BM = WM * MI * 16, BN = WN * NI * 16;
-  constexpr int STAGE = (BM + BN + R16 * 16) * ROW_BYTES;
-  constexpr int TSH = (R16 ? BM * ((KG ? KG * R16 : R16) * 16 + 4) * 2 : 0) + (LN ? BM * 8 : 0);
-  // LDS ring depth: NSREQ == 2 keeps the footprint small (several workgroups per CU overlap each other);
-  // otherwise as deep as 160 KB allows, up to 4.
-  constexpr int NS = NSREQ <= 2 ? NSREQ : ((4 * STAGE + TSH <= 160 * 1024) ? 4 : ((3 * STAGE + TSH <= 160 * 1024) ? 3 : 2));
-  constexpr int NBUF = NS == 1 ? 2 : NS;
-  if constexpr (NBUF * STAGE + TSH > 160 * 1024) {
-    SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: tile %dx%d with LoRA rank pad %d does not fit the 160 KB LDS", BM, BN, R16 * 16);
-  } else {
-  const int smem = NBUF * STAGE + TSH;
-  if (sdlt_raise_smem((const void*)gemm_kernel<MI, NI, WN, MODE, R16, NS, KG, BT, WM, EPI, LN>, smem))
-    SDLT_FAIL(SDLT_ERR_LAUNCH, "sdlt_gemm_bf16: cannot raise the dynamic LDS limit to %d bytes", smem);
-  const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-  const int splitk = p.splitk > 1 ? p.splitk : 1;
-  if (splitk > 1) {
-    constexpr int TMI = MI >= WN ? MI / WN : 1;
-    const size_t slab_bytes = (size_t)(NI * MI + (R16 ? R16 * TMI : 0)) * NTHR * 16;
-    if (!p.ws_slab || !p.ws_cnt || (size_t)nbm * nbn * splitk * slab_bytes > (size_t)p.ws_slab_bytes || nbm * nbn > p.ws_cnt_len)
-      SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_gemm_bf16: split-K workspace too small (%d tiles x %d splits x %zu B)", nbm * nbn, splitk, slab_bytes);
-  }
-  hipLaunchKernelGGL((gemm_kernel<MI, NI, WN, MODE, R16, NS, KG, BT, WM, EPI, LN>), dim3(nbm * nbn * splitk, BT ? p.n_batch : 1), dim3(NTHR), smem, stream, p);
-  }
-  return SDLT_OK;
-}
+// ---- host side: gemm_validate -> gemm_plan -> gemm_launch.  gemm_plan is the ONE place that picks a tile, a ring depth, a split and a kernel variant (every
+// threshold lives there); it and gemm_validate call nothing from HIP, so sdlt_gemm_route reports the choice on a machine without a GPU. ----
 
 // tile ids: 1 = 128x128 (8 waves), 2 = 64x128 (8 waves), 3 = 64x64 (4 waves), 4 = 256x128 (8 waves), 5 = 128x128 (4 waves),
 //           6 = 256x256 (8 waves), 7 = 256x160 (8 waves, 4x2), 8 = 128x160 (8 waves, 4x2)
 // (round 6, measured and dropped - tools/conv_tile_probe.py, profiles/r06_conv_tile_probe.txt: 128 x 80 tiles of 4 waves (4 x 1) that cut a 4096 x 640 convolution into exactly
 //  256 workgroups WITHOUT a K split - no fp32 slabs, no last-arriver seam - run 47-76 % SLOWER than the 128 x 160 tiles with their 2-3 splits (64 x 64 x 640 -> 640: 88.0 vs
 //  59.9 us); 128 x 160 unsplit: +27-48 %.  The slabs' traffic is not what bounds these launches, the 8-wave K loop's DMA / MFMA staggering is what makes them fast.)
-void tile_dims(int tile, int& bm, int& bn) {
-  switch (tile) {
-    case 7: bm = 256; bn = 160; break;
-    case 8: bm = 128; bn = 160; break;
-    case 1: case 5: bm = 128; bn = 128; break;
-    case 2: bm = 64; bn = 128; break;
-    case 4: bm = 256; bn = 128; break;
-    case 6: bm = 256; bn = 256; break;
-    default: bm = 64; bn = 64; break;
+struct GemmTile {
+  int mi, ni, wn, wm;      // gemm_kernel's MI, NI, WN, WM
+  constexpr int bm() const { return wm * mi * 16; }
+  constexpr int bn() const { return wn * ni * 16; }
+  constexpr int threads() const { return 64 * wm * wn; }
+};
+constexpr int GEMM_NTILES = 8;
+constexpr GemmTile GEMM_TILES[GEMM_NTILES + 1] = {{2, 2, 2, 2}, {4, 2, 4, 2}, {2, 2, 4, 2}, {2, 2, 2, 2}, {8, 2, 4, 2}, {4, 4, 2, 2}, {8, 4, 4, 2}, {4, 5, 2, 4}, {2, 5, 2, 4}};
+constexpr GemmTile gemm_tile(int id) { return GEMM_TILES[id >= 1 && id <= GEMM_NTILES ? id : 0]; }      // (an id that names no tile counts as 64x64 until it is refused)
+
+// LDS and split-K scratch of a variant: the plan, the kernel table and its static_assert all read these.
+constexpr int GEMM_LDS_MAX = 160 * 1024;
+constexpr int gemm_stage_bytes(GemmTile t, int r16) { return (t.bm() + t.bn() + r16 * 16) * ROW_BYTES; }
+constexpr int gemm_ttile_bytes(GemmTile t, int r16, int kg, int ln) { return (r16 ? t.bm() * ((kg ? kg * r16 : r16) * 16 + 4) * 2 : 0) + (ln ? t.bm() * 8 : 0); }
+// LDS ring depth: a request of 2 keeps the footprint small (several workgroups per CU overlap each other);
+// otherwise as deep as 160 KB allows, up to 4.
+constexpr int gemm_ring_depth(GemmTile t, int r16, int kg, int ln, int req) {
+  const int stage = gemm_stage_bytes(t, r16), tsh = gemm_ttile_bytes(t, r16, kg, ln);
+  return req <= 2 ? req : ((4 * stage + tsh <= GEMM_LDS_MAX) ? 4 : ((3 * stage + tsh <= GEMM_LDS_MAX) ? 3 : 2));
+}
+constexpr int gemm_lds_bytes(GemmTile t, int r16, int kg, int ln, int req) {
+  const int ns = gemm_ring_depth(t, r16, kg, ln, req);
+  return (ns == 1 ? 2 : ns) * gemm_stage_bytes(t, r16) + gemm_ttile_bytes(t, r16, kg, ln);
+}
+constexpr int64_t gemm_slab_bytes(GemmTile t, int r16) {      // fp32 partials of one workgroup of a split: its accumulators and its share of T
+  const int tmi = t.mi >= t.wn ? t.mi / t.wn : 1;
+  return (int64_t)(t.ni * t.mi + (r16 ? r16 * tmi : 0)) * t.threads() * 16;
+}
+
+// The kernel variants, each family once: gemm_kernel's template tail <KG, BT, EPI, LN> and the tiles, modes, rank pads (lora_R / 16) and requested ring depths
+// it is built for (bit i of a mask = value i).  gemm_plan asks gemm_listed() at run time, gemm_variant() instantiates from the same rows at compile time.
+// (a depth of 1, the register-staged loader, is kept in the kernel source but not instantiated: hipcc places its
+//  staging registers in scratch - measured 3-6x slower than the LDS-DMA ring on every SDXL shape.)
+struct GemmFamily {
+  int kg, bt, epi, ln;
+  unsigned tiles, modes, r16s, depths;
+};
+constexpr unsigned bits() { return 0; }
+template <typename... I>
+constexpr unsigned bits(int i, I... rest) { return 1u << i | bits(rest...); }
+constexpr GemmFamily GEMM_FAMILIES[] = {
+    {0, 0, 0, 0, bits(1, 2, 3, 4, 5, 6), bits(0, 1), bits(0, 1, 2, 4), bits(2, 4)},            // plain product / 3x3 convolution (256x256 with rank pad 64: listed, the LDS refuses it)
+    {0, 0, 0, 0, bits(7, 8), bits(0, 1), bits(0, 1), bits(2, 4)},                              //   ... on the 160-column tiles: rank pad 16 at most
+    {0, 0, 0, 0, bits(1, 2, 3, 4, 5, 6, 7, 8), bits(2), bits(0), bits(2, 4)},                  // convolution + second K segment
+    {0, 0, 0, 1, bits(1, 2, 3, 8), bits(0), bits(1), bits(2, 4)},                              // folded LayerNorm, rank-16 adapter
+    {0, 0, 0, 2, bits(1, 2), bits(0), bits(1), bits(4)},                                       //   ... statistics from the producer's partials
+    {0, 0, 1, 1, bits(1, 2, 3, 7, 8), bits(0), bits(0), bits(4)},                              // folded LayerNorm, ff.net.0.proj + GEGLU
+    {0, 0, 1, 2, bits(7), bits(0), bits(0), bits(4)},                                          //   ... statistics from the producer's partials
+    {0, 1, 0, 0, bits(1, 2, 3), bits(0), bits(0, 1, 2, 4), bits(4)},                           // batched
+    {4, 0, 0, 0, bits(1, 2, 3), bits(0), bits(1, 2, 4), bits(4)},                              // K-grouped adapters
+    {4, 1, 0, 0, bits(1, 2, 3), bits(0), bits(1, 2, 4), bits(4)},                              // K-grouped adapters, batched
+    {0, 0, 1, 0, bits(1, 2, 3, 7, 8), bits(0), bits(0), bits(4)},                              // fused epilogues: GEGLU forward,
+    {0, 0, 2, 0, bits(1, 2, 3, 7, 8), bits(0), bits(0), bits(4)},                              //   GEGLU backward,
+    {0, 0, 3, 0, bits(1, 2, 3, 7, 8), bits(0), bits(0), bits(4)},                              //   activation side output,
+    {0, 0, 4, 0, bits(1, 2, 3, 7, 8), bits(0), bits(0), bits(4)},                              //   activation backward
+};
+constexpr int GEMM_NFAMILIES = sizeof(GEMM_FAMILIES) / sizeof(GEMM_FAMILIES[0]);
+constexpr bool in_mask(unsigned mask, int i) { return i >= 0 && i < 32 && (mask >> i & 1); }
+constexpr bool gemm_family_lists(const GemmFamily& f, int tile, int mode, int r16, int req) {
+  return in_mask(f.tiles, tile) && in_mask(f.modes, mode) && in_mask(f.r16s, r16) && in_mask(f.depths, req);
+}
+constexpr bool gemm_listed(int kg, int bt, int epi, int ln, int tile, int mode, int r16, int req) {
+  for (const GemmFamily& f : GEMM_FAMILIES)
+    if (f.kg == kg && f.bt == bt && f.epi == epi && f.ln == ln && gemm_family_lists(f, tile, mode, r16, req)) return true;
+  return false;
+}
+
+typedef void (*GemmKernelFn)(const sdlt_gemm_params);
+struct GemmKernel {
+  GemmKernelFn fn;
+  int lds;
+};
+// row F of the list at <tile, mode, rank pad, requested depth>: the instantiation, or {nullptr, bytes} where the row does not list it or the LDS refuses it
+template <int F, int TILE, int MODE, int R16, int REQ>
+GemmKernel gemm_variant() {
+  constexpr GemmFamily f = GEMM_FAMILIES[F];
+  constexpr GemmTile t = GEMM_TILES[TILE];
+  constexpr int lds = gemm_lds_bytes(t, R16, f.kg, f.ln, REQ);
+  if constexpr (gemm_family_lists(f, TILE, MODE, R16, REQ)) {
+    static_assert(lds <= GEMM_LDS_MAX || F == 0, "only the plain family lists a variant that the LDS refuses (256x256 with rank pad 64)");
+    if constexpr (lds <= GEMM_LDS_MAX) return {gemm_kernel<t.mi, t.ni, t.wn, MODE, R16, gemm_ring_depth(t, R16, f.kg, f.ln, REQ), f.kg, f.bt, t.wm, f.epi, f.ln>, lds};
+  }
+  return {nullptr, lds};
+}
+// f(std::integral_constant<int, v>) for the one V that equals v
+template <int... V, typename Fn>
+void pick(int v, Fn&& f) { (void)((v == V && (f(std::integral_constant<int, V>{}), true)) || ...); }
+template <int F = 0, typename Fn>
+void each_family(Fn&& f) {
+  if constexpr (F < GEMM_NFAMILIES) {
+    f(std::integral_constant<int, F>{});
+    each_family<F + 1>(f);
   }
 }
 
-template <int MODE, int R16>
-int dispatch_tile(const sdlt_gemm_params& pin, hipStream_t s) {
-  sdlt_gemm_params p = pin;
-  if (p.lora_group_k > 0) {
-    // K-grouped adapters: either one workgroup walks the whole K range (T flushed per group) or exactly one split per group
-    const int G = p.K / p.lora_group_k;
-    const long t128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
-    p.splitk = (pin.splitk == G || (pin.splitk == 0 && G > 1 && t128 * G <= 320 && p.ws_slab && p.ws_cnt)) ? G : 1;
-  }
-  if (p.batch) p.splitk = 1;            // batched launch: the problems fill the chip, the split-K scratch is per launch
-  if (p.ln_c1) p.splitk = 1;            // folded LayerNorm: a row's statistics come out of one K walk
-  const int ktot = p.K + p.K2;
-  if (p.tile == 0) {
-    // Shape heuristics from the tools/gemm_probe.py sweep on MI355X (DESIGN.md, "GEMM tile selection"):
-    //  * plenty of 128x128 tiles: 8-wave 128x128; with >= 2 tiles per CU use the shallow ring so 2 workgroups share a CU
-    //  * 160..511 tiles: short K -> 64x64 tiles, 2+ workgroups per CU; long K -> 128x128 with the deep ring
-    //  * fewer: 64x128 (8 waves) when K is short, otherwise 128x128 + split-K
-    const long t128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
-    const int nk = ktot / BK;
-    const bool ws = p.ws_slab && p.ws_cnt;
-    // 160-column tiles (tools/tile160_probe.py on MI355X): every UNet width is a multiple of 320, so 256x160 / 128x160 tiles cut
-    // the wide feed-forward products and the top-resolution convolutions into exactly 256 (or 512, 1024) workgroups with no
-    // padded columns, and their 64x80 / 32x80 wave tiles read fewer LDS bytes per MFMA than the 32x32 ones of the 64x128 tile.
-    //   1024 x 10240 x 1280: 48.5 -> 34.0 us (256x160);  1024 x 5120 x 1280: 24.4 -> 19.8 (128x160);  4096 x 2560 x 640: 25.7 -> 19.4;
-    //   16384 x 320 conv K 2880: 56.1 -> 42.6, K 8640: 156.6 -> 118.6;  4096 x 640 conv: 63.0 -> 56.2 with 2 splits.
-    // Not for the attention projections (1024 x 1280 x 1280: 64 tiles) nor the long-K / narrow-N products (split-K 128x128 is as good).
-    if (R16 <= 1 && !p.batch && !p.lora_group_k && p.N % 160 == 0 && p.M > 128 && !p.throughput_hint) {
-      const long t7 = (long)((p.M + 255) / 256) * (p.N / 160), t8 = (long)((p.M + 127) / 128) * (p.N / 160);
-      if (MODE == 0 && R16 == 0 && ktot <= 2560) {
-        if (t7 >= 256) p.tile = 7;
-        else if (t8 >= 224) p.tile = 8;
-      } else if (MODE == 0 && R16 == 1 && !p.lora_group_n && ktot <= 640 && t8 >= 224 && t8 <= 320) {
-        p.tile = 8;
-      } else if (MODE != 0 && (t8 == 256 || t8 == 128 || t8 == 64)) {
-        const int sk = (int)(256 / t8);
-        if (sk == 1 || (ws && !p.splitk && nk / sk >= 16)) { p.tile = 8; if (sk > 1) p.splitk = sk; }
-      }
-      if (p.tile && !p.splitk) p.splitk = 1;
-    }
-    if (p.tile) {}
-    else if (p.M <= 64) p.tile = p.N > 64 ? 2 : 3;
-    else if (p.N <= 64) p.tile = 3;
-    else if (p.M <= 128) {
-      // text encoders / text-conditioning projections (M = 128): a few 64x64 tiles, latency-bound; split K only while the
-      // grid is far from one workgroup per CU (120+ tiles: none; 60+: 3; fewer: 4)
-      p.tile = 3;
-      if (!p.splitk) {
-        const long tiles = (long)((p.M + 63) / 64) * ((p.N + 63) / 64);
-        int sk = !ws ? 1 : (tiles >= 100 ? 1 : (tiles >= 60 ? (nk >= 24 ? 3 : 1) : 4));   // (60+ tiles and a short K, CLIP-L fc1 / qkv: 10.8 -> 6.9 us unsplit)
-        while (sk > 1 && nk / sk < 4) --sk;
-        p.splitk = sk;
-      }
-    }
-    else if (p.throughput_hint && !p.batch && !p.lora_group_k && (t128 >= 320 || (MODE != 0 && t128 >= 160))) {
-      // several jobs share the device (whole-step A/B with two concurrent SDXL jobs: 85.0 -> 82.8 ms per pair): the other job
-      // fills the CUs a launch leaves idle, so the 256x128 tile (0.75 operand-path cycles per MFMA cycle instead of 1.0) wins
-      // although it halves the workgroup count.  With ONE job the same rule loses 0.3 ms.
-      p.tile = 4;
-    }
-    else if (!R16 && MODE == 0 && t128 >= 320 && t128 <= 512 && p.N >= 1024) p.tile = 4;    // 4096x1920x640: 17.6 vs 19.7 us
-    else if (t128 >= 320) { p.tile = ktot <= 640 ? 1 : 2; if (!p.stages) p.stages = 2; }     // >= 2 workgroups per CU, shallow ring
-    else if (t128 >= 160) {
-      // measured in the whole step (not in the hot-loop probe, where the 64x64 tile wins): 160..319 tiles of a plain / LoRA GEMM
-      // run best as 128x128 tiles with the deep ring (55.2 -> 54.5 ms per SDXL step); the short-K convs keep 64x64
-      // (the other classes were re-checked the same way, whole-step A/B per class: every alternative tile / ring / split was slower)
-      if (MODE == 0 && ktot <= 6144) { p.tile = 1; if (!p.stages) p.stages = 4; }
-      else if (ktot <= 2560 || (MODE == 0 && ktot <= 6144)) { p.tile = 3; if (!p.stages) p.stages = 2; }
-      else {
-        // 4096 x 640 with a long K (3x3 convs of the 64x64 blocks): 160 tiles x 3 splits, two workgroups per CU
-        p.tile = 1;
-        if (!p.stages) p.stages = 2;
-        if (!p.splitk && ws && nk / 3 >= 8) p.splitk = 3;
-      }
-    } else if (ktot <= 2560 && t128 > 32) { p.tile = 2; if (!p.splitk) p.splitk = 1; }
-    else if (ktot <= 2560) p.tile = 2;
-    else if (t128 <= 24 && !p.batch && !p.lora_group_k && !p.out_fp32) {     // (fp32 outputs: the weight-gradient products keep their rule)
-      // a handful of 128x128 tiles and a long K (SD1.5's 8x8-pixel level at batch 4): 64x128 tiles, split until ~one workgroup per CU
-      // while every split keeps >= 20 K-steps.  tools/gemm_probe4.py: conv 256 x 1280 x 11520 41.7 -> 28.2 us (with adapter 48.5 -> 33.8),
-      // x 23040 61.2 -> 41.2, ff2 256 x 1280 x 5120 31.2 -> 18.0 (the 128x128 tile split 13 ways moved 17 MB of partial slabs).
-      p.tile = 2;
-      if (!p.splitk) {
-        const long t2 = (long)((p.M + 63) / 64) * ((p.N + 127) / 128);
-        int sk = (int)((256 + t2 / 2) / t2);
-        if (sk > nk / 20) sk = nk / 20;
-        p.splitk = (ws && sk > 1) ? sk : 1;
-      }
-    }
-    else p.tile = 1;
-  }
-  int bm, bn;
-  tile_dims(p.tile, bm, bn);
-  if (!R16 && p.x2_group_n > 0 && (p.x2_group_n % bn) && pin.tile == 0 && p.x2_group_n % 64 == 0) {
-    p.tile = 3;   // grouped second segment: the 64x64 tile never straddles two groups
-    tile_dims(p.tile, bm, bn);
-  }
-  if (!R16 && p.x2_group_n > 0 && (p.x2_group_n % bn))
-    SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_gemm_bf16: x2_group_n=%d is not a multiple of the %d-column tile", p.x2_group_n, bn);
-  if (R16 && p.lora_group_n > 0 && (p.lora_group_n % bn) && pin.tile == 0 && p.lora_group_n % 64 == 0) {
-    p.tile = 3;   // narrow groups (head width 64): the 64x64 tile never straddles two adapters
-    tile_dims(p.tile, bm, bn);
-  }
-  if (R16 && p.lora_group_n > 0 && (p.lora_group_n % bn))
-    SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_gemm_bf16: lora_group_n=%d is not a multiple of the %d-column tile", p.lora_group_n, bn);
-  if (p.splitk == 0) {
-    // Split K until ~one workgroup per CU exists, keeping >= 8 K-steps per split (the fenced hand-off costs a few us).
-    const long tiles = (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn);
-    const int nk = ktot / BK;
-    int sk = 1;
-    if (p.ws_slab && p.ws_cnt && tiles <= 96) {
-      sk = (int)((256 + tiles / 2) / tiles);
-      const int min_steps = tiles <= 32 ? 3 : 8;    // a handful of tiles (text encoders, M = 128): latency-bound, split harder
-      if (sk > nk / min_steps) sk = nk / min_steps;
-      if (sk > 16) sk = 16;
-      if (sk < 1) sk = 1;
-    }
-    p.splitk = sk;
-  }
-#define SDLT_TILE_CASES(NSV)                                         \
-  switch (p.tile) {                                                  \
-    case 1: return launch<4, 2, 4, MODE, R16, NSV>(p, s);            \
-    case 2: return launch<2, 2, 4, MODE, R16, NSV>(p, s);            \
-    case 3: return launch<2, 2, 2, MODE, R16, NSV>(p, s);            \
-    case 4: return launch<8, 2, 4, MODE, R16, NSV>(p, s);            \
-    case 5: return launch<4, 4, 2, MODE, R16, NSV>(p, s);            \
-    case 6: return launch<8, 4, 4, MODE, R16, NSV>(p, s);            \
-    case 7: if constexpr (R16 <= 1) return launch<4, 5, 2, MODE, R16, NSV, 0, 0, 4>(p, s); else break; \
-    case 8: if constexpr (R16 <= 1) return launch<2, 5, 2, MODE, R16, NSV, 0, 0, 4>(p, s); else break; \
-  }
-  // (stages == 1, the register-staged loader, is kept in the kernel source but not instantiated: hipcc places its
-  //  staging registers in scratch - measured 3-6x slower than the LDS-DMA ring on every SDXL shape.)
-  if (p.ln_c1) {   // folded LayerNorm: rank pad 16 on tiles 1, 2, 3, 8 (either ring depth), ff.net.0.proj + GEGLU on tiles 1, 2, 3, 7, 8 (deep ring)
-    // ln_parts (the producer left row partials: no statistics in the K walk) exists for the shapes of the 1280-wide blocks; anything else
-    // computes the statistics itself
-    const bool parts = p.ln_parts && p.ln_nparts >= 2 && p.ln_nparts <= 16 && !(p.ln_nparts & 1) && !(((uintptr_t)p.ln_parts) & 15);
-    if constexpr (MODE == 0 && R16 == 1) {
-      if (p.tile != 1 && p.tile != 2 && p.tile != 3 && p.tile != 8) p.tile = (p.lora_group_n > 0 && (p.lora_group_n % 128)) ? 3 : 1;
-      if (parts && p.stages != 2) {
-        switch (p.tile) {
-          case 1: return launch<4, 2, 4, 0, 1, 4, 0, 0, 2, 0, 2>(p, s);
-          case 2: return launch<2, 2, 4, 0, 1, 4, 0, 0, 2, 0, 2>(p, s);
-        }
-      }
-      if (p.stages == 2) {
-        switch (p.tile) {
-          case 1: return launch<4, 2, 4, 0, 1, 2, 0, 0, 2, 0, 1>(p, s);
-          case 2: return launch<2, 2, 4, 0, 1, 2, 0, 0, 2, 0, 1>(p, s);
-          case 3: return launch<2, 2, 2, 0, 1, 2, 0, 0, 2, 0, 1>(p, s);
-          case 8: return launch<2, 5, 2, 0, 1, 2, 0, 0, 4, 0, 1>(p, s);
-        }
-      } else {
-        switch (p.tile) {
-          case 1: return launch<4, 2, 4, 0, 1, 4, 0, 0, 2, 0, 1>(p, s);
-          case 2: return launch<2, 2, 4, 0, 1, 4, 0, 0, 2, 0, 1>(p, s);
-          case 3: return launch<2, 2, 2, 0, 1, 4, 0, 0, 2, 0, 1>(p, s);
-          case 8: return launch<2, 5, 2, 0, 1, 4, 0, 0, 4, 0, 1>(p, s);
-        }
-      }
-    }
-    if constexpr (MODE == 0 && R16 == 0) {
-      if (p.epi_op == 1) {
-        if (p.tile == 4 || p.tile == 5 || p.tile == 6) p.tile = 1;
-        if (parts && p.tile == 7) return launch<4, 5, 2, 0, 0, 4, 0, 0, 4, 1, 2>(p, s);
-        switch (p.tile) {
-          case 1: return launch<4, 2, 4, 0, 0, 4, 0, 0, 2, 1, 1>(p, s);
-          case 2: return launch<2, 2, 4, 0, 0, 4, 0, 0, 2, 1, 1>(p, s);
-          case 3: return launch<2, 2, 2, 0, 0, 4, 0, 0, 2, 1, 1>(p, s);
-          case 7: return launch<4, 5, 2, 0, 0, 4, 0, 0, 4, 1, 1>(p, s);
-          case 8: return launch<2, 5, 2, 0, 0, 4, 0, 0, 4, 1, 1>(p, s);
-        }
-      }
-    }
-    SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: folded LayerNorm exists for rank-16 adapter products and for ff.net.0.proj + GEGLU (lora_R %d, epi_op %d, tile %d)", p.lora_R, p.epi_op, p.tile);
-  }
-  if (p.lora_group_k > 0 && pin.tile == 0) {
-    // only the deep-ring variants of tiles 1..3 exist for K-grouped adapters; with the long K = G*C loop the 128x128 tile
-    // wins as soon as it yields >= 64 workgroups (4096x640x1920: 31 us vs 61 us for 64x64)
-    const long t128k = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
-    if (t128k >= 64 || p.tile < 1 || p.tile > 3) p.tile = 1;
-  }
-  if (p.batch) {   // batched launches exist for what uses them: plain GEMM mode, no LoRA or rank pad 16, tiles 1..3, deep ring
-    if constexpr (MODE == 0 && R16 == 0) {
-      if (p.n_batch < 1 || p.n_batch > 65535) SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_gemm_bf16: n_batch=%d", p.n_batch);
-      switch (p.tile) {
-        case 1: return launch<4, 2, 4, 0, 0, 4, 0, 1>(p, s);
-        case 2: return launch<2, 2, 4, 0, 0, 4, 0, 1>(p, s);
-        case 3: return launch<2, 2, 2, 0, 0, 4, 0, 1>(p, s);
-      }
-    }
-    if constexpr (MODE == 0 && R16 >= 1) {
-      if (p.n_batch < 1 || p.n_batch > 65535) SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_gemm_bf16: n_batch=%d", p.n_batch);
-      if (p.lora_group_k > 0) {
-        switch (p.tile) {
-          case 1: return launch<4, 2, 4, 0, R16, 4, 4, 1>(p, s);
-          case 2: return launch<2, 2, 4, 0, R16, 4, 4, 1>(p, s);
-          case 3: return launch<2, 2, 2, 0, R16, 4, 4, 1>(p, s);
-        }
-      } else {
-        switch (p.tile) {
-          case 1: return launch<4, 2, 4, 0, R16, 4, 0, 1>(p, s);
-          case 2: return launch<2, 2, 4, 0, R16, 4, 0, 1>(p, s);
-          case 3: return launch<2, 2, 2, 0, R16, 4, 0, 1>(p, s);
-        }
-      }
-    }
-    SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: batched launch needs mode 0 and tile 1..3 (tile %d)", p.tile);
-  }
-  if (p.lora_group_k > 0) {   // K-grouped adapters: plain GEMM mode, tiles 1..3, deep ring (as deep as the G x rank T tile leaves room for)
-    if constexpr (MODE == 0 && R16 >= 1) {
-      switch (p.tile) {
-        case 1: return launch<4, 2, 4, 0, R16, 4, 4>(p, s);
-        case 2: return launch<2, 2, 4, 0, R16, 4, 4>(p, s);
-        case 3: return launch<2, 2, 2, 0, R16, 4, 4>(p, s);
-      }
-    }
-    SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: lora_group_k needs mode 0 and tile 1..3 (tile %d)", p.tile);
-  }
-  if (p.epi_op) {   // fused GEGLU / activation epilogues: plain GEMM mode without LoRA, tiles 1, 2, 3, 7, 8 with the deep ring
-    if constexpr (MODE == 0 && R16 == 0) {
-      if (p.tile == 4 || p.tile == 5 || p.tile == 6) p.tile = 1;
-#define SDLT_EPI_CASES(E)                                                      \
-      switch (p.tile) {                                                        \
-        case 1: return launch<4, 2, 4, 0, 0, 4, 0, 0, 2, E>(p, s);             \
-        case 2: return launch<2, 2, 4, 0, 0, 4, 0, 0, 2, E>(p, s);             \
-        case 3: return launch<2, 2, 2, 0, 0, 4, 0, 0, 2, E>(p, s);             \
-        case 7: return launch<4, 5, 2, 0, 0, 4, 0, 0, 4, E>(p, s);             \
-        case 8: return launch<2, 5, 2, 0, 0, 4, 0, 0, 4, E>(p, s);             \
-      }
-      switch (p.epi_op) {
-        case 1: SDLT_EPI_CASES(1) break;
-        case 2: SDLT_EPI_CASES(2) break;
-        case 3: SDLT_EPI_CASES(3) break;
-        case 4: SDLT_EPI_CASES(4) break;
-      }
-#undef SDLT_EPI_CASES
-    }
-    SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: fused epilogue %d needs mode 0 without LoRA (tile %d)", p.epi_op, p.tile);
-  }
-  if (p.stages == 2) { SDLT_TILE_CASES(2) } else { SDLT_TILE_CASES(4) }
-#undef SDLT_TILE_CASES
-  SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: tile id %d", p.tile);
+// the kernel of a plan and its LDS bytes (fn == nullptr: the list has no such variant)
+GemmKernel gemm_kernel_of(const sdlt_gemm_plan& pl) {
+  GemmKernel k = {nullptr, 0};
+  pick<1, 2, 3, 4, 5, 6, 7, 8>(pl.tile, [&](auto tile) {
+    pick<0, 1, 2>(pl.mode, [&](auto mode) {
+      pick<0, 1, 2, 4>(pl.r16, [&](auto r16) {
+        pick<2, 4>(pl.stages_req, [&](auto req) {
+          each_family([&](auto row) {
+            constexpr int F = decltype(row)::value;
+            constexpr GemmFamily f = GEMM_FAMILIES[F];
+            if (f.kg != pl.kg || f.bt != pl.bt || f.epi != pl.epi || f.ln != pl.ln) return;
+            const GemmKernel v = gemm_variant<F, decltype(tile)::value, decltype(mode)::value, decltype(r16)::value, decltype(req)::value>();
+            if (v.fn) k = v;
+          });
+        });
+      });
+    });
+  });
+  return k;
 }
 
-}  // namespace
-
-#ifdef SDLT_GEMM_TRACE
-extern "C" int sdlt_gemm_trace_read(long long* out16) { return (int)hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_gemm_tr), sizeof(long long) * 16); }
-#endif
-
-extern "C" int sdlt_gemm_bf16(const sdlt_gemm_params* pp, void* stream) {
-  const sdlt_gemm_params& p = *pp;
-  hipStream_t s = (hipStream_t)stream;
+// The argument checks of sdlt_gemm_bf16 / sdlt_gemm_route: what no variant takes, whatever the plan.
+int gemm_validate(const sdlt_gemm_params& p) {
   if (p.M <= 0 || p.N <= 0) SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_gemm_bf16: M=%d N=%d", p.M, p.N);
   if (p.K <= 0 || (p.K % BK) || (p.K2 % BK) || p.K2 < 0)
     SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_gemm_bf16: K=%d K2=%d must be positive multiples of 64", p.K, p.K2);
@@ -1313,30 +1142,233 @@ extern "C" int sdlt_gemm_bf16(const sdlt_gemm_params* pp, void* stream) {
       SDLT_FAIL(SDLT_ERR_ALIGN, "sdlt_gemm_bf16: ln_c1 / ln_adapter 16-byte, ln_stats 8-byte aligned");
   }
   if (p.accumulate && !p.out_fp32) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: accumulate needs an fp32 output (use R for bf16)");
-  int r16 = 0;
   if (p.col_scale && !p.lora_R) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: col_scale (DoRA) is an option of adapter launches (lora_R > 0)");
   if (p.col_scale && (((uintptr_t)p.col_scale) & 15)) SDLT_FAIL(SDLT_ERR_ALIGN, "sdlt_gemm_bf16: col_scale must be 16-byte aligned");
   if (p.lora_R) {
     if (p.lora_R != 16 && p.lora_R != 32 && p.lora_R != 64) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: padded LoRA rank %d (16/32/64)", p.lora_R);
     if (p.K2) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: LoRA + second segment");
     if ((p.ld_adown % 8) || (p.ld_bup % 4) || (p.T_out && (p.ld_t % 4))) SDLT_FAIL(SDLT_ERR_ALIGN, "sdlt_gemm_bf16: LoRA operand alignment");
-    r16 = p.lora_R / 16;
     if (p.lora_group_k > 0) {
       if (p.lora_group_n > 0 || p.mode != 0 || (p.lora_group_k % BK) || (p.K % p.lora_group_k) || p.K / p.lora_group_k > 4)
         SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: lora_group_k=%d needs mode 0, K = G*group_k with G <= 4, group_k %% 64 == 0", p.lora_group_k);
     }
   }
-  int rc;
-#define DISPATCH(MODE_)                                                 \
-  switch (r16) {                                                        \
-    case 0: rc = dispatch_tile<MODE_, 0>(p, s); break;                  \
-    case 1: rc = dispatch_tile<MODE_, 1>(p, s); break;                  \
-    case 2: rc = dispatch_tile<MODE_, 2>(p, s); break;                  \
-    default: rc = dispatch_tile<MODE_, 4>(p, s); break;                 \
+  return SDLT_OK;
+}
+
+// What one sdlt_gemm_bf16 call of a validated block launches: first the tile, the split and the requested ring depth (heuristics, then the moves that the
+// options force), then the variant, which the list above either has for that tile or the call is refused.
+int gemm_plan(const sdlt_gemm_params& p, sdlt_gemm_plan& pl) {
+  const int mode = p.mode == 0 ? 0 : (p.K2 ? 2 : 1), r16 = p.lora_R / 16;
+  const bool ws = p.ws_slab && p.ws_cnt;
+  const int ktot = p.K + p.K2, nk = ktot / BK;
+  const long t128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
+  int tile = p.tile, splitk = p.splitk, stages = p.stages;
+  if (p.lora_group_k > 0) {
+    // K-grouped adapters: either one workgroup walks the whole K range (T flushed per group) or exactly one split per group
+    const int G = p.K / p.lora_group_k;
+    splitk = (p.splitk == G || (p.splitk == 0 && G > 1 && t128 * G <= 320 && ws)) ? G : 1;
   }
-  if (p.mode == 0) { DISPATCH(0) } else if (p.K2) { rc = dispatch_tile<2, 0>(p, s); } else { DISPATCH(1) }
-#undef DISPATCH
+  if (p.batch) splitk = 1;            // batched launch: the problems fill the chip, the split-K scratch is per launch
+  if (p.ln_c1) splitk = 1;            // folded LayerNorm: a row's statistics come out of one K walk
+  if (tile == 0) {
+    // Shape heuristics from the tools/gemm_probe.py sweep on MI355X (DESIGN.md, "GEMM tile selection"):
+    //  * plenty of 128x128 tiles: 8-wave 128x128; with >= 2 tiles per CU use the shallow ring so 2 workgroups share a CU
+    //  * 160..511 tiles: short K -> 64x64 tiles, 2+ workgroups per CU; long K -> 128x128 with the deep ring
+    //  * fewer: 64x128 (8 waves) when K is short, otherwise 128x128 + split-K
+    // 160-column tiles (tools/tile160_probe.py on MI355X): every UNet width is a multiple of 320, so 256x160 / 128x160 tiles cut
+    // the wide feed-forward products and the top-resolution convolutions into exactly 256 (or 512, 1024) workgroups with no
+    // padded columns, and their 64x80 / 32x80 wave tiles read fewer LDS bytes per MFMA than the 32x32 ones of the 64x128 tile.
+    //   1024 x 10240 x 1280: 48.5 -> 34.0 us (256x160);  1024 x 5120 x 1280: 24.4 -> 19.8 (128x160);  4096 x 2560 x 640: 25.7 -> 19.4;
+    //   16384 x 320 conv K 2880: 56.1 -> 42.6, K 8640: 156.6 -> 118.6;  4096 x 640 conv: 63.0 -> 56.2 with 2 splits.
+    // Not for the attention projections (1024 x 1280 x 1280: 64 tiles) nor the long-K / narrow-N products (split-K 128x128 is as good).
+    if (r16 <= 1 && !p.batch && !p.lora_group_k && p.N % 160 == 0 && p.M > 128 && !p.throughput_hint) {
+      const long t7 = (long)((p.M + 255) / 256) * (p.N / 160), t8 = (long)((p.M + 127) / 128) * (p.N / 160);
+      if (mode == 0 && r16 == 0 && ktot <= 2560) {
+        if (t7 >= 256) tile = 7;
+        else if (t8 >= 224) tile = 8;
+      } else if (mode == 0 && r16 == 1 && !p.lora_group_n && ktot <= 640 && t8 >= 224 && t8 <= 320) {
+        tile = 8;
+      } else if (mode != 0 && (t8 == 256 || t8 == 128 || t8 == 64)) {
+        const int sk = (int)(256 / t8);
+        if (sk == 1 || (ws && !splitk && nk / sk >= 16)) { tile = 8; if (sk > 1) splitk = sk; }
+      }
+      if (tile && !splitk) splitk = 1;
+    }
+    if (tile) {}
+    else if (p.M <= 64) tile = p.N > 64 ? 2 : 3;
+    else if (p.N <= 64) tile = 3;
+    else if (p.M <= 128) {
+      // text encoders / text-conditioning projections (M = 128): a few 64x64 tiles, latency-bound; split K only while the
+      // grid is far from one workgroup per CU (120+ tiles: none; 60+: 3; fewer: 4)
+      tile = 3;
+      if (!splitk) {
+        const long tiles = (long)((p.M + 63) / 64) * ((p.N + 63) / 64);
+        int sk = !ws ? 1 : (tiles >= 100 ? 1 : (tiles >= 60 ? (nk >= 24 ? 3 : 1) : 4));   // (60+ tiles and a short K, CLIP-L fc1 / qkv: 10.8 -> 6.9 us unsplit)
+        while (sk > 1 && nk / sk < 4) --sk;
+        splitk = sk;
+      }
+    }
+    else if (p.throughput_hint && !p.batch && !p.lora_group_k && (t128 >= 320 || (mode != 0 && t128 >= 160))) {
+      // several jobs share the device (whole-step A/B with two concurrent SDXL jobs: 85.0 -> 82.8 ms per pair): the other job
+      // fills the CUs a launch leaves idle, so the 256x128 tile (0.75 operand-path cycles per MFMA cycle instead of 1.0) wins
+      // although it halves the workgroup count.  With ONE job the same rule loses 0.3 ms.
+      tile = 4;
+    }
+    else if (!r16 && mode == 0 && t128 >= 320 && t128 <= 512 && p.N >= 1024) tile = 4;    // 4096x1920x640: 17.6 vs 19.7 us
+    else if (t128 >= 320) { tile = ktot <= 640 ? 1 : 2; if (!stages) stages = 2; }     // >= 2 workgroups per CU, shallow ring
+    else if (t128 >= 160) {
+      // measured in the whole step (not in the hot-loop probe, where the 64x64 tile wins): 160..319 tiles of a plain / LoRA GEMM
+      // run best as 128x128 tiles with the deep ring (55.2 -> 54.5 ms per SDXL step); the short-K convs keep 64x64
+      // (the other classes were re-checked the same way, whole-step A/B per class: every alternative tile / ring / split was slower)
+      if (mode == 0 && ktot <= 6144) { tile = 1; if (!stages) stages = 4; }
+      else if (ktot <= 2560 || (mode == 0 && ktot <= 6144)) { tile = 3; if (!stages) stages = 2; }
+      else {
+        // 4096 x 640 with a long K (3x3 convs of the 64x64 blocks): 160 tiles x 3 splits, two workgroups per CU
+        tile = 1;
+        if (!stages) stages = 2;
+        if (!splitk && ws && nk / 3 >= 8) splitk = 3;
+      }
+    } else if (ktot <= 2560 && t128 > 32) { tile = 2; if (!splitk) splitk = 1; }
+    else if (ktot <= 2560) tile = 2;
+    else if (t128 <= 24 && !p.batch && !p.lora_group_k && !p.out_fp32) {     // (fp32 outputs: the weight-gradient products keep their rule)
+      // a handful of 128x128 tiles and a long K (SD1.5's 8x8-pixel level at batch 4): 64x128 tiles, split until ~one workgroup per CU
+      // while every split keeps >= 20 K-steps.  tools/gemm_probe4.py: conv 256 x 1280 x 11520 41.7 -> 28.2 us (with adapter 48.5 -> 33.8),
+      // x 23040 61.2 -> 41.2, ff2 256 x 1280 x 5120 31.2 -> 18.0 (the 128x128 tile split 13 ways moved 17 MB of partial slabs).
+      tile = 2;
+      if (!splitk) {
+        const long t2 = (long)((p.M + 63) / 64) * ((p.N + 127) / 128);
+        int sk = (int)((256 + t2 / 2) / t2);
+        if (sk > nk / 20) sk = nk / 20;
+        splitk = (ws && sk > 1) ? sk : 1;
+      }
+    }
+    else tile = 1;
+  }
+  // column groups (one adapter per lora_group_n columns, or one slice of the second segment per x2_group_n columns) must not straddle a tile
+  const int group_n = r16 ? p.lora_group_n : p.x2_group_n;
+  if (group_n > 0 && (group_n % gemm_tile(tile).bn()) && p.tile == 0 && group_n % 64 == 0)
+    tile = 3;   // narrow groups (head width 64) / grouped second segment: the 64x64 tile never straddles two of them
+  if (group_n > 0 && (group_n % gemm_tile(tile).bn()))
+    SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_gemm_bf16: %s=%d is not a multiple of the %d-column tile", r16 ? "lora_group_n" : "x2_group_n", group_n, gemm_tile(tile).bn());
+  if (splitk == 0) {
+    // Split K until ~one workgroup per CU exists, keeping >= 8 K-steps per split (the fenced hand-off costs a few us).
+    const long tiles = (long)((p.M + gemm_tile(tile).bm() - 1) / gemm_tile(tile).bm()) * ((p.N + gemm_tile(tile).bn() - 1) / gemm_tile(tile).bn());
+    int sk = 1;
+    if (ws && tiles <= 96) {
+      sk = (int)((256 + tiles / 2) / tiles);
+      const int min_steps = tiles <= 32 ? 3 : 8;    // a handful of tiles (text encoders, M = 128): latency-bound, split harder
+      if (sk > nk / min_steps) sk = nk / min_steps;
+      if (sk > 16) sk = 16;
+      if (sk < 1) sk = 1;
+    }
+    splitk = sk;
+  }
+
+  // the variant <KG, BT, EPI, LN> and the ring depth it is asked for; `lists`: the family has this call's mode and rank pad on that tile
+  int kg = 0, bt = 0, epi = 0, ln = 0, req = 4;
+  const auto lists = [&](int kg_, int bt_, int epi_, int ln_, int tile_, int req_) { return gemm_listed(kg_, bt_, epi_, ln_, tile_, mode, r16, req_); };
+  if (p.ln_c1) {   // folded LayerNorm: rank pad 16 on tiles 1, 2, 3, 8 (either ring depth), ff.net.0.proj + GEGLU on tiles 1, 2, 3, 7, 8 (deep ring)
+    // ln_parts (the producer left row partials: no statistics in the K walk) exists for the shapes of the 1280-wide blocks; anything else
+    // computes the statistics itself
+    const bool parts = p.ln_parts && p.ln_nparts >= 2 && p.ln_nparts <= 16 && !(p.ln_nparts & 1) && !(((uintptr_t)p.ln_parts) & 15);
+    if (mode == 0 && r16 == 1) {
+      req = stages == 2 ? 2 : 4;
+      if (!lists(0, 0, 0, 1, tile, req)) tile = (p.lora_group_n > 0 && (p.lora_group_n % 128)) ? 3 : 1;
+      ln = (parts && lists(0, 0, 0, 2, tile, req)) ? 2 : 1;
+    } else if (mode == 0 && r16 == 0 && p.epi_op == 1) {
+      if (tile == 4 || tile == 5 || tile == 6) tile = 1;
+      epi = 1;
+      ln = (parts && lists(0, 0, 1, 2, tile, req)) ? 2 : 1;
+    }
+    if (!ln || !lists(0, 0, epi, ln, tile, req))
+      SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: folded LayerNorm exists for rank-16 adapter products and for ff.net.0.proj + GEGLU (lora_R %d, epi_op %d, tile %d)", p.lora_R, p.epi_op, tile);
+  } else {
+    if (p.lora_group_k > 0 && p.tile == 0) {
+      // only the deep-ring variants of tiles 1..3 exist for K-grouped adapters; with the long K = G*C loop the 128x128 tile
+      // wins as soon as it yields >= 64 workgroups (4096x640x1920: 31 us vs 61 us for 64x64)
+      if (t128 >= 64 || tile < 1 || tile > 3) tile = 1;
+    }
+    if (p.batch) {   // batched launches exist for what uses them: plain GEMM mode, no LoRA or rank pad 16, tiles 1..3, deep ring
+      if (mode == 0 && (p.n_batch < 1 || p.n_batch > 65535)) SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_gemm_bf16: n_batch=%d", p.n_batch);
+      bt = 1;
+      kg = (r16 && p.lora_group_k > 0) ? 4 : 0;
+      if (!lists(kg, bt, 0, 0, tile, req)) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: batched launch needs mode 0 and tile 1..3 (tile %d)", tile);
+    } else if (p.lora_group_k > 0) {   // K-grouped adapters: plain GEMM mode, tiles 1..3, deep ring (as deep as the G x rank T tile leaves room for)
+      kg = 4;
+      if (!lists(kg, 0, 0, 0, tile, req)) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: lora_group_k needs mode 0 and tile 1..3 (tile %d)", tile);
+    } else if (p.epi_op) {   // fused GEGLU / activation epilogues: plain GEMM mode without LoRA, tiles 1, 2, 3, 7, 8 with the deep ring
+      if (mode == 0 && r16 == 0 && (tile == 4 || tile == 5 || tile == 6)) tile = 1;
+      epi = p.epi_op;
+      if (!lists(0, 0, epi, 0, tile, req)) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: fused epilogue %d needs mode 0 without LoRA (tile %d)", p.epi_op, tile);
+    } else {
+      req = stages == 2 ? 2 : 4;
+      if (!lists(0, 0, 0, 0, tile, req)) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: tile id %d", tile);
+    }
+  }
+  const GemmTile t = gemm_tile(tile);
+  if (gemm_lds_bytes(t, r16, kg, ln, req) > GEMM_LDS_MAX)
+    SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: tile %dx%d with LoRA rank pad %d does not fit the 160 KB LDS", t.bm(), t.bn(), r16 * 16);
+  pl.tile = tile; pl.mode = mode; pl.r16 = r16;
+  pl.stages = gemm_ring_depth(t, r16, kg, ln, req);
+  pl.kg = kg; pl.bt = bt; pl.epi = epi; pl.ln = ln;
+  pl.splitk = splitk > 1 ? splitk : 1;
+  pl.grid_x = ((p.M + t.bm() - 1) / t.bm()) * ((p.N + t.bn() - 1) / t.bn()) * pl.splitk;
+  pl.grid_y = bt ? p.n_batch : 1;
+  pl.threads = t.threads();
+  pl.lds_bytes = gemm_lds_bytes(t, r16, kg, ln, req);
+  pl.stages_req = req;
+  pl.slab_bytes = gemm_slab_bytes(t, r16);
+  return SDLT_OK;
+}
+
+// a split needs its scratch: one fp32 slab per workgroup and one arrival counter per tile
+int gemm_check_workspace(const sdlt_gemm_plan& pl, const sdlt_gemm_params& p) {
+  const int tiles = pl.grid_x / pl.splitk;
+  if (pl.splitk > 1 && (!p.ws_slab || !p.ws_cnt || (size_t)tiles * pl.splitk * (size_t)pl.slab_bytes > (size_t)p.ws_slab_bytes || tiles > p.ws_cnt_len))
+    SDLT_FAIL(SDLT_ERR_SHAPE, "sdlt_gemm_bf16: split-K workspace too small (%d tiles x %d splits x %zu B)", tiles, pl.splitk, (size_t)pl.slab_bytes);
+  return SDLT_OK;
+}
+
+int gemm_launch(const sdlt_gemm_plan& pl, const sdlt_gemm_params& pin, hipStream_t stream) {
+  const int rc = gemm_check_workspace(pl, pin);
+  if (rc) return rc;
+  const GemmKernel k = gemm_kernel_of(pl);
+  if (!k.fn) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_gemm_bf16: the kernel list has no variant for the plan (tile %d, mode %d, rank pad %d)", pl.tile, pl.mode, pl.r16 * 16);
+  if (sdlt_raise_smem((const void*)k.fn, k.lds))
+    SDLT_FAIL(SDLT_ERR_LAUNCH, "sdlt_gemm_bf16: cannot raise the dynamic LDS limit to %d bytes", k.lds);
+  sdlt_gemm_params p = pin;
+  p.splitk = pl.splitk;      // (the one planned field the kernel reads)
+  hipLaunchKernelGGL(k.fn, dim3(pl.grid_x, pl.grid_y), dim3(pl.threads), k.lds, stream, p);
+  return SDLT_OK;
+}
+
+int gemm_route(const sdlt_gemm_params& p, sdlt_gemm_plan& pl) {
+  const int rc = gemm_validate(p);
+  return rc ? rc : gemm_plan(p, pl);
+}
+
+}  // namespace
+
+#ifdef SDLT_GEMM_TRACE
+extern "C" int sdlt_gemm_trace_read(long long* out16) { return (int)hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_gemm_tr), sizeof(long long) * 16); }
+#endif
+
+extern "C" int sdlt_gemm_bf16(const sdlt_gemm_params* pp, void* stream) {
+  sdlt_gemm_plan pl;
+  int rc = gemm_route(*pp, pl);
+  if (!rc) rc = gemm_launch(pl, *pp, (hipStream_t)stream);
   if (rc != SDLT_OK) return rc;
   SDLT_CHECK_LAUNCH();
+  return SDLT_OK;
+}
+
+static_assert(sizeof(sdlt_gemm_plan) == 64, "sdlt_gemm_plan has no index in sdlt_struct_size: its size is part of the header's text");
+extern "C" int sdlt_gemm_route(const sdlt_gemm_params* pp, sdlt_gemm_plan* out) {
+  sdlt_gemm_plan pl;
+  int rc = gemm_route(*pp, pl);
+  if (!rc) rc = gemm_check_workspace(pl, *pp);
+  if (rc != SDLT_OK) return rc;
+  *out = pl;
   return SDLT_OK;
 }

@@ -4,7 +4,7 @@ sdlt_wsk_conv, against the fp64 reference of tests/conv_exact_ref.py on small-in
 torch.equal, there is no tolerance.  Outputs are views of larger sentinel-filled buffers (stray writes), X is a column view of a wider buffer
 whose other columns hold NaN (stray reads).
 
-Instantiations of gemm_kernel<MODE != 0> reachable from sdlt_gemm_bf16 (SDLT_TILE_CASES), all launched here with both ring depths (stages 0 / 2):
+Instantiations of gemm_kernel<MODE != 0> that gemm_plan reaches (csrc/gemm.hip, the plain rows of GEMM_FAMILIES), all launched here with both ring depths (stages 0 / 2):
   mode 1, rank pad 0:          tiles 1..8                         test_every_tile
   mode 1, rank pad 16:         tiles 1..8                         test_adapter_every_instantiation
   mode 1, rank pads 32 / 64:   tiles 1..6 except (6, 64)          test_adapter_every_instantiation

@@ -8,8 +8,8 @@ an fp32 output, a second segment or adapter groups - so ops.gemm takes the tiled
 The nonlinear epilogues of mode 0 (GEGLU forward / backward, activation side output / backward: EPI 1..4, and the folded LayerNorm: LN 1 / 2)
 cannot be exact and are out of scope; tests/test_kernels_gpu.py keeps them under a tolerance.
 
-Linear instantiations gemm_kernel<MI, NI, WN, MODE 0, R16, NS, KG, BT, WM> reachable from dispatch_tile<0, R16> (csrc/gemm.hip), R16 = rank pad / 16:
-  SDLT_TILE_CASES(2) and (4), KG 0, BT 0
+Linear instantiations gemm_kernel<MI, NI, WN, MODE 0, R16, NS, KG, BT, WM> that gemm_plan reaches in mode 0 (csrc/gemm.hip, rows of GEMM_FAMILIES), R16 = rank pad / 16:
+  plain family, requested ring depth 2 and 4, KG 0, BT 0
     R16 0:          tiles 1..8                      test_plain (both rings); second segment K2 / x2_group_n are runtime options of the same
                                                     kernels: test_second_segment_every_tile, test_second_segment_grouped
     R16 1:          tiles 1..8                      test_adapter_every_instantiation; lora_group_n is a runtime option: test_group_n
@@ -271,7 +271,7 @@ def test_group_n_rejected(ops, tile, w):
 @pytest.mark.parametrize("pad", R.PADS)
 @pytest.mark.parametrize("tile", [1, 2, 3])
 def test_group_k(ops, tile, pad, G):
-    """One adapter per group of K columns, with residual.  The host check (dispatch_tile, `p.splitk = pin.splitk == G ... ? G : 1`) has two sides: splitk = G is
+    """One adapter per group of K columns, with residual.  The host check (gemm_plan, `splitk = p.splitk == G ... ? G : 1`) has two sides: splitk = G is
     one split per group, every other forced count (1, G + 1) runs unsplit - each must give the same bits, twice into the same workspace."""
     for M, dtype in ((105, BF), (280, F32)):
         case = (M, N0, G * 64, f"gk{pad}c64", 0)
