@@ -666,7 +666,51 @@ int sdlt_sampler_step_sde(const sdlt_sampler_sde_params* p, void* stream);
 /* sdlt_sampler_noise : out fp32 [n, 4, hw] = the z that sdlt_sampler_step_sde adds at step row `step` for these seeds (the same device function). */
 int sdlt_sampler_noise(const uint32_t* seeds, int32_t step, int32_t n, int32_t hw, float* out, void* stream);
 
-/* sdlt_guidance : the guidance pre-pass, issued between the UNet forward and whichever of the four step launches follows.  It rewrites eps in
+/* sdlt_sampler_step_dd : the same launch with a per-pixel HOLD map - Differential Diffusion (Levin & Fried 2023, "Giving Each Pixel Its Strength"):
+ * every pixel gets an img2img strength of its own, by selection and never by mixing.  `form` names the update and the table width: 0 Euler
+ * (sdlt_sampler_step_img's table and step; dprev and seeds are ignored), 1 multistep (sdlt_sampler_step_ms's), 2 SDE (sdlt_sampler_step_sde's).
+ * hold fp32 [n, hw], integer-valued (sampler.hold_map), is read at every step where the blend reads the mask, with x0 and noise:
+ *     init != 0:  x = x0 + noise * sigma_0 everywhere (x0 required), as the form's own entry; hold is not read
+ *     init == 0:  xn = the form's update, for SDE including the fresh noise (step 4b) ;  k = x0 + noise * sigma_next (one multiply, one add)
+ *                 xn = ((float)(i + 1) < hold) ? k : xn          i = the step row the counter holds; no arithmetic touches a released pixel
+ *                 x = xn ;  dprev = D (forms 1, 2) ;  xin, timesteps, ctr as the form's own entry
+ * hold = 0 never holds: the launch gives the maskless step's bits.  hold > steps holds after the last step too, where sigma_next = 0 and the pixel is
+ * x0 bit for bit.  What the form's own entry refuses is refused alike; so are a null hold on a step, hold aliasing x or dprev (-1) and a form
+ * outside 0..2 (-4).  Alignment as sdlt_sampler_step; hold 4-byte aligned.
+ * The block is declared without a struct tag and has no index in sdlt_struct_size(), like sdlt_resize_params: it is 128 bytes - sdlt_sampler_sde_params'
+ * 112, one pointer and two int32 - with no padding between fields. */
+typedef struct {
+  const float* eps;                  /* fp32 [2n * hw, 4]: UNet.forward's output (step only) */
+  float* x;                          /* fp32 [n, 4, hw] latent state, in place */
+  const float* x0;                   /* fp32 [n, 4, hw]: init, and every step */
+  const float* noise;                /* fp32 [n, 4, hw]: init, and every step */
+  const float* mask;                 /* unused (the block continues sdlt_sampler_sde_params): a hold map excludes a mask */
+  float* dprev;                      /* fp32 [n, 4, hw]: forms 1, 2 (step only) */
+  void* xin; int64_t ld_xin;         /* bf16 [2n * hw, ld_xin] NHWC model input */
+  float* timesteps;                  /* fp32 [2n] */
+  const float* table;                /* fp32 [table_rows, 4] (form 0) | [table_rows, 8] (forms 1, 2) */
+  int32_t* ctr;
+  int32_t n, hw, table_rows, init;
+  const uint32_t* seeds;             /* uint32 [n, 2]: form 2 (step only) */
+  const float* hold;                 /* fp32 [n, hw]: the pixel is held while (float)(i + 1) < hold (step only) */
+  int32_t form, pad_;
+} sdlt_sampler_dd_params;
+int sdlt_sampler_step_dd(const sdlt_sampler_dd_params* p, void* stream);
+
+/* sdlt_blur_planes : a separable Gaussian blur of fp32 planes [C, H, W] with replicated edges - a hard mask made into a soft change map on the latent grid
+ * (render.py: `mask_blur`).  taps fp32 [2 R + 1]: the normalised weights of offsets -R .. +R (ops.blur_taps: exp(-d^2 / (2 sigma^2)), normalised in fp64,
+ * rounded once), 0 <= R <= 64.  Two launches on the stream, rows then columns, through `scratch` (C H W floats):
+ *     scratch[c, y, x] = sum over t = -R .. +R, in that order, of taps[t + R] * in[c, y, clamp(x + t, 0, W - 1)]
+ *     out[c, y, x]     = sum over t = -R .. +R, in that order, of taps[t + R] * scratch[c, clamp(y + t, 0, H - 1), x] ;  clamp01 != 0: min(max(out, 0), 1)
+ * each sum started from the first product, one multiply and one add per tap, each rounded once, no contraction (tests/blur_ref.py gives the same bits).
+ * The clamp is two compares and selects: a NaN stays a NaN.  out may be in, or overlap it in any way (the row pass has read `in` before the column pass
+ * writes `out`: stream order); scratch may overlap neither.  One thread per output sample, 64 consecutive x per wave, 64-bit plane offsets.  A null
+ * pointer, a non-positive extent, H or W above 16384, C above 65535, R outside 0 .. 64, scratch overlapping in or out (-1), a pointer that is not 4-byte
+ * aligned (-2): the code is returned, sdlt_last_error names the entry point and nothing is launched. */
+int sdlt_blur_planes(const float* in, float* out, float* scratch, int32_t C, int32_t H, int32_t W, const float* taps, int32_t R, int32_t clamp01,
+                     void* stream);
+
+/* sdlt_guidance : the guidance pre-pass, issued between the UNet forward and whichever of the step launches follows.  It rewrites eps in
  * place so that both row blocks of image j (rows 2j negative, 2j + 1 positive) hold the final prediction e; the step launch then forms
  * e + g (e - e) = e (exact for finite values, the sign of a zero apart) whatever guidance scale its own table holds.
  * gtab fp32 [gtab_rows, 4]: row 0 = (k, 0, 0, 0), row 1 + i = (g_i, phi_i, 0, 0), k <= gtab_rows - 1.  ctr: the sampler's counter; ctr[0] is READ

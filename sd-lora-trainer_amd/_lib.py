@@ -210,6 +210,11 @@ class SamplerSdeParams(C.Structure):
     _fields_ = SamplerMsParams._fields_ + [("seeds", vp)]
 
 
+class SamplerDdParams(C.Structure):
+    # sdlt_sampler_dd_params: 128 bytes by the header's text (tagless, like sdlt_resize_params)
+    _fields_ = SamplerSdeParams._fields_ + [("hold", vp), ("form", i32), ("pad_", i32)]
+
+
 class GuidanceParams(C.Structure):
     _fields_ = [("eps", vp), ("gtab", vp), ("ctr", vp), ("n", i32), ("hw", i32), ("gtab_rows", i32), ("pad_", i32)]
 
@@ -287,9 +292,11 @@ SYMBOLS = {
     "sdlt_sampler_step_img": (i32, [C.POINTER(SamplerImgParams), vp]),
     "sdlt_sampler_step_ms": (i32, [C.POINTER(SamplerMsParams), vp]),
     "sdlt_sampler_step_sde": (i32, [C.POINTER(SamplerSdeParams), vp]),
+    "sdlt_sampler_step_dd": (i32, [C.POINTER(SamplerDdParams), vp]),
     "sdlt_sampler_noise": (i32, [vp, i32, i32, i32, vp, vp]),
     "sdlt_guidance": (i32, [C.POINTER(GuidanceParams), vp]),
     "sdlt_resize_planes": (i32, [C.POINTER(ResizeParams), vp]),
+    "sdlt_blur_planes": (i32, [vp, vp, vp, i32, i32, i32, vp, i32, i32, vp]),
     "sdlt_freeu_ws_floats": (i64, [i32, i32, i32, i32, i32]),
     "sdlt_freeu": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, f32, f32, i32, vp, vp, vp, i64, vp]),
     "sdlt_heatmap_accum": (i32, [C.POINTER(HeatAccumParams), vp]),
@@ -347,7 +354,7 @@ def load():
             raise KernelLibraryError(f"struct layout mismatch for {name}: C {lib.sdlt_struct_size(which)} vs binding {size}")
     if C.sizeof(ResizeParams) != 48:
         raise KernelLibraryError(f"struct layout mismatch for ResizeParams: header 48 vs binding {C.sizeof(ResizeParams)}")
-    for cls, size in ((HeatAccumParams, 152), (HeatOverlayParams, 80), (GemmPlan, 64)):
+    for cls, size in ((HeatAccumParams, 152), (HeatOverlayParams, 80), (GemmPlan, 64), (SamplerDdParams, 128)):
         if C.sizeof(cls) != size:
             raise KernelLibraryError(f"struct layout mismatch for {cls.__name__}: header {size} vs binding {C.sizeof(cls)}")
     _lib = lib

@@ -1,6 +1,7 @@
 // The step launch of the latent sampler (sampler.py): classifier-free guidance + the sampler's update + repack of the next model input, the ONE
-// launch between two UNet forwards, for n images sampled together (UNet batch 2n: image j = rows 2j negative, 2j + 1 positive).  Four C entry
-// points (sdlt_sampler_step, _img, _ms, _sde) share one init kernel, one step kernel body in three compile-time forms, and one host launch path.
+// launch between two UNet forwards, for n images sampled together (UNet batch 2n: image j = rows 2j negative, 2j + 1 positive).  Five C entry
+// points (sdlt_sampler_step, _img, _ms, _sde, _dd) share one init kernel, one step kernel body in three compile-time forms and three mask modes, and
+// one host launch path.
 //
 // Shared contract.  x fp32 [n, 4, h, w] is the unscaled latent, updated in place; the model input is x / sqrt(sigma^2 + 1).
 //   init:  x   = noise * sigma_0  |  x0 + noise * sigma_0 (x0 given)       sigma_0 = table row 0, column 1 (init_noise_sigma, or the FIRST USED sigma
@@ -8,6 +9,7 @@
 //   step:  e   = eps_neg + g (eps_pos - eps_neg)
 //          xn  = the form's update (below)
 //          k   = x0 + noise * sigma_{i+1} ;  xn = k + m (xn - k)            with a mask only: m = 0 gives k, and k = x0 after the last step (sigma = 0)
+//          k   as above ;  xn = (float)(i + 1) < hold ? k : xn              with a hold map only (sdlt_sampler_step_dd): a SELECT, no arithmetic on xn
 //          x   = xn ;  xin = bf16(xn * 1 / sqrt(sigma_{i+1}^2 + 1))         columns 0..3 of BOTH rows of the pair in the NHWC buffer [2n h w, ld]
 //   both:  t[0 .. 2n) = next timestep, counter = 0 (init) | (i + 1) mod steps
 // Everything a sample() call chooses lives in device memory, so a hipGraph that holds this launch serves any step count, strength, guidance scale,
@@ -16,7 +18,10 @@
 //   row 2 + i: sigma_i, sigma_{i+1}, 1 / sqrt(sigma_{i+1}^2 + 1), timestep of step i + 1 [, a_i, b_i, c_i, d_i]
 // and ctr[0] is the step counter i (ctr[1]: the ticket that orders its update after every workgroup's read); the counter's wrap to 0 starts the
 // next trajectory on row 0.  x0 [n, 4, h, w] (the encoded init latents times the scaling factor), noise [n, 4, h, w] (ONE draw for the whole
-// trajectory) and mask [n, 1, h, w] (1 = regenerate, 0 = keep) are read by init and by a masked step only.
+// trajectory) and mask [n, 1, h, w] (1 = regenerate, 0 = keep) are read by init and by a masked step only.  hold [n, 1, h, w] (differential
+// diffusion, sampler.hold_map: integer-valued, the pixel stays on the init latents' noised trajectory while i + 1 < hold) takes the mask's place in
+// sdlt_sampler_step_dd, whose parameter block names the form: a held step reads x0, noise and hold where a masked step reads x0, noise and mask.
+// hold = 0 never holds (the maskless step's bits); hold > steps holds after the last step too, where sigma = 0 and k = x0 bit for bit.
 //
 // The forms.
 //   EULER      (sdlt_sampler_step, sdlt_sampler_step_img; W = 4)
@@ -30,7 +35,7 @@
 //          2. D   = x - sigma e (epsilon)  |  e * (-sigma / sqrt(sigma^2 + 1)) + x / (sigma^2 + 1) (v prediction)
 //          3. xn  = a x + b D
 //          4. c != 0 only (uniform over the launch: a scalar branch around the four history loads):  xn = xn + c dprev
-//          5. the mask blend
+//          5. the mask blend | the hold select
 //          6. x = xn ;  dprev = D ;  xin, timesteps, counter
 //   SDE        (sdlt_sampler_step_sde; W = 8) Euler ancestral and DPM-Solver++ (2M) SDE (k-diffusion's sample_euler_ancestral and sample_dpmpp_2m_sde,
 //          midpoint, s_noise = 1): one more term on the multistep form,  x_{i+1} = a x + b D_i + c D_{i-1} + d z_i,  z_i ~ N(0, I) fresh per step,
@@ -48,8 +53,8 @@
 //          sdlt_sampler_noise writes z alone through the same device function: the torch loop and the tests take the kernel's own noise from it.
 //
 // A pure HBM kernel of a few hundred KB: one thread per pixel, coalesced 4-byte reads of the planes (the mask once per pixel), one 16-byte read per
-// eps row, two 8-byte bf16 stores.  Every load of a pixel is requested before the first use; form and mask are template parameters and `c != 0`,
-// `d != 0` are uniform over the launch, so no load sits under a per-thread condition.  Vector stores only.  All arithmetic in fp32, each operation
+// eps row, two 8-byte bf16 stores.  Every load of a pixel is requested before the first use; form and mask mode are template parameters and `c != 0`,
+// `d != 0` are uniform over the launch, so no load sits under a per-thread condition (the hold select is per thread, on values already loaded).  Vector stores only.  All arithmetic in fp32, each operation
 // rounded once (no contraction: the tests compare bits).
 #include "common.h"
 #include "../../include/sdlt_kernels.h"
@@ -59,8 +64,9 @@
 namespace {
 
 enum Form { EULER, MULTISTEP, SDE };
+enum Mask { MASK_NONE, MASK_BLEND, MASK_HOLD };
 
-// The four public parameter blocks, widened to one: an operand an entry point does not have is NULL.
+// The five public parameter blocks, widened to one: an operand an entry point does not have is NULL.
 struct step_args {
   const float* eps;
   float* x;
@@ -73,6 +79,7 @@ struct step_args {
   int32_t* ctr;
   const uint32_t* seeds;
   int32_t n, hw, table_rows;
+  const float* hold;
 };
 
 constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u, PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
@@ -171,6 +178,12 @@ __device__ __forceinline__ float mask_blend(float v, float z, float nz, float sn
   return k + m * (v - k);
 }
 
+// The same k, selected while the pixel is held: step row i leaves it on the noised trajectory iff i + 1 < hold.  A released pixel keeps v's bits.
+__device__ __forceinline__ float hold_select(float v, float z, float nz, float sn, float hold, int i) {
+  const float k = z + nz * sn;
+  return (float)(i + 1) < hold ? k : v;
+}
+
 // x and the bf16 model input, into both rows of the pair.
 __device__ __forceinline__ void store_repack(const step_args& p, int j, int px, const float xn[4], float inv) {
   const int hw = p.hw;
@@ -226,7 +239,7 @@ __global__ __launch_bounds__(256) void sampler_init_kernel(step_args p) {
   ticket_tail<true>(p, tnext, 0);
 }
 
-template <Form FORM, bool MASK>
+template <Form FORM, Mask MASK>
 __global__ __launch_bounds__(256) void sampler_step_kernel(step_args p) {
   const step_row r = read_row<FORM>(p);
   const bool hist = FORM != EULER && r.c != 0.f;        // uniform: the table row is the same for every thread
@@ -242,10 +255,10 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(step_args p) {
     float xv[4], dv[4] = {0.f, 0.f, 0.f, 0.f}, zv[4] = {0.f, 0.f, 0.f, 0.f}, nv[4] = {0.f, 0.f, 0.f, 0.f}, m = 1.f;
     uint32_t k0 = 0u, k1 = 0u;
     load_planes(p.x + base, hw, xv);
-    if (MASK) {
+    if (MASK != MASK_NONE) {
       load_planes(p.x0 + base, hw, zv);
       load_planes(p.noise + base, hw, nv);
-      m = p.mask[(size_t)j * hw + px];
+      m = (MASK == MASK_HOLD ? p.hold : p.mask)[(size_t)j * hw + px];
     }
     if (hist) load_planes(p.dprev + base, hw, dv);
     if (noisy) {
@@ -282,7 +295,8 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(step_args p) {
         if (noisy) v = v + r.d * fresh[c];
         dn[c] = D;
       }
-      if (MASK) v = mask_blend(v, zv[c], nv[c], sn, m);
+      if (MASK == MASK_BLEND) v = mask_blend(v, zv[c], nv[c], sn, m);
+      if (MASK == MASK_HOLD) v = hold_select(v, zv[c], nv[c], sn, m, r.i);
       xn[c] = v;
     }
     if (FORM != EULER) store_planes(p.dprev + base, hw, dn);
@@ -300,14 +314,17 @@ struct entry_rules {
   bool img;                  // the entry has x0 / mask operands (its null-pointer text names the mask)
   bool init_needs_x0;        // sdlt_sampler_step_img: init is x0 + noise * sigma_0, always
   const char* alias_text;    // x0 / noise aliasing x: refused with this text; NULL: allowed (sdlt_sampler_step's init, noise == x)
+  bool dd;                   // sdlt_sampler_step_dd: every step takes a hold map (its null-pointer text names it)
 };
 
 template <Form FORM>
-void launch_step(bool masked, dim3 grid, hipStream_t stream, const step_args& a) {
-  if (masked)
-    hipLaunchKernelGGL((sampler_step_kernel<FORM, true>), grid, dim3(256), 0, stream, a);
+void launch_step(Mask mode, dim3 grid, hipStream_t stream, const step_args& a) {
+  if (mode == MASK_HOLD)
+    hipLaunchKernelGGL((sampler_step_kernel<FORM, MASK_HOLD>), grid, dim3(256), 0, stream, a);
+  else if (mode == MASK_BLEND)
+    hipLaunchKernelGGL((sampler_step_kernel<FORM, MASK_BLEND>), grid, dim3(256), 0, stream, a);
   else
-    hipLaunchKernelGGL((sampler_step_kernel<FORM, false>), grid, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((sampler_step_kernel<FORM, MASK_NONE>), grid, dim3(256), 0, stream, a);
 }
 
 int sampler_launch(const entry_rules& r, const step_args& a, int init_flag, void* stream) {
@@ -315,21 +332,24 @@ int sampler_launch(const entry_rules& r, const step_args& a, int init_flag, void
   const bool ms = r.form != EULER, sde = r.form == SDE;
   if (a.n < 1 || a.hw < 1 || (int64_t)a.n * a.hw > (1 << 28)) SDLT_FAIL(SDLT_ERR_SHAPE, "%s: n=%d hw=%d", nm, a.n, a.hw);
   if (a.table_rows < 3) SDLT_FAIL(SDLT_ERR_SHAPE, "%s: table_rows=%d (two header rows + at least one step)", nm, a.table_rows);
-  const bool init = init_flag != 0, masked = !init && a.mask != nullptr;
-  if (!a.x || !a.xin || !a.timesteps || !a.table || !a.ctr || (!init && (!a.eps || (ms && !a.dprev) || (sde && !a.seeds))) ||
+  const bool init = init_flag != 0, held = !init && r.dd, masked = !init && (held || a.mask != nullptr);      // masked: the step reads x0 and noise
+  if (!a.x || !a.xin || !a.timesteps || !a.table || !a.ctr || (!init && (!a.eps || (ms && !a.dprev) || (sde && !a.seeds))) || (held && !a.hold) ||
       ((init || masked) && !a.noise) || ((masked || (init && r.init_needs_x0)) && !a.x0)) {
+    if (r.dd) SDLT_FAIL(SDLT_ERR_SHAPE, "%s: null pointer (init=%d, hold=%d)", nm, init_flag, (int)(a.hold != nullptr));
     if (r.img) SDLT_FAIL(SDLT_ERR_SHAPE, "%s: null pointer (init=%d, mask=%d)", nm, init_flag, (int)(a.mask != nullptr));
     SDLT_FAIL(SDLT_ERR_SHAPE, "%s: null pointer (init=%d)", nm, init_flag);
   }
   if (a.ld_xin < 4 || (a.ld_xin & 3) || ((uintptr_t)a.xin & 7)) SDLT_FAIL(SDLT_ERR_ALIGN, "%s: xin needs 8-byte rows (ld=%lld)", nm, (long long)a.ld_xin);
   if (!init && ((uintptr_t)a.eps & 15)) SDLT_FAIL(SDLT_ERR_ALIGN, "%s: eps must be 16-byte aligned", nm);
   if ((((uintptr_t)a.x | (uintptr_t)a.x0 | (uintptr_t)a.noise | (uintptr_t)a.mask | (uintptr_t)a.dprev | (uintptr_t)a.timesteps | (uintptr_t)a.table |
-        (uintptr_t)a.ctr) & 3))
+        (uintptr_t)a.ctr | (uintptr_t)a.hold) & 3))
     SDLT_FAIL(SDLT_ERR_ALIGN, "%s: fp32 / int32 pointers must be 4-byte aligned", nm);
   if (!init && ((uintptr_t)a.seeds & 3)) SDLT_FAIL(SDLT_ERR_ALIGN, "%s: seeds must be 4-byte aligned", nm);
   if (r.alias_text && (init || masked) && ((a.x0 != nullptr && a.x0 == a.x) || a.noise == a.x)) SDLT_FAIL(SDLT_ERR_SHAPE, "%s: %s", nm, r.alias_text);
   if (ms && !init && (a.dprev == a.x || (masked && (a.dprev == a.x0 || a.dprev == a.noise))))
     SDLT_FAIL(SDLT_ERR_SHAPE, "%s: dprev is written at every step and may not alias x, x0 or noise", nm);
+  if (held && (a.hold == a.x || (ms && a.hold == a.dprev))) SDLT_FAIL(SDLT_ERR_SHAPE, "%s: hold is read while x and dprev are written and may alias neither", nm);
+  const Mask mode = held ? MASK_HOLD : masked ? MASK_BLEND : MASK_NONE;
   const dim3 grid((unsigned)(((int64_t)a.n * a.hw + 255) / 256));
   hipStream_t st = (hipStream_t)stream;
   if (init && a.x0 != nullptr)
@@ -337,11 +357,11 @@ int sampler_launch(const entry_rules& r, const step_args& a, int init_flag, void
   else if (init)
     hipLaunchKernelGGL((sampler_init_kernel<false>), grid, dim3(256), 0, st, a);
   else if (r.form == EULER)
-    launch_step<EULER>(masked, grid, st, a);
+    launch_step<EULER>(mode, grid, st, a);
   else if (r.form == MULTISTEP)
-    launch_step<MULTISTEP>(masked, grid, st, a);
+    launch_step<MULTISTEP>(mode, grid, st, a);
   else
-    launch_step<SDE>(masked, grid, st, a);
+    launch_step<SDE>(mode, grid, st, a);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) SDLT_FAIL(SDLT_ERR_LAUNCH, "%s: %s", nm, hipGetErrorString(e));
   return SDLT_OK;
@@ -375,6 +395,17 @@ extern "C" int sdlt_sampler_step_sde(const sdlt_sampler_sde_params* p, void* str
   if (p == nullptr) SDLT_FAIL(SDLT_ERR_SHAPE, "%s: null parameter block", R.name);
   const step_args a = {p->eps, p->x, p->x0, p->noise, p->mask, p->dprev, p->xin, p->ld_xin, p->timesteps, p->table, p->ctr, p->seeds, p->n, p->hw, p->table_rows};
   return sampler_launch(R, a, p->init, stream);
+}
+
+extern "C" int sdlt_sampler_step_dd(const sdlt_sampler_dd_params* p, void* stream) {
+  static const entry_rules R[3] = {{EULER, "sdlt_sampler_step_dd", true, true, "x0 and noise are read at every step and may not alias x", true},
+                                   {MULTISTEP, "sdlt_sampler_step_dd", true, true, "x0 and noise are read at every step and may not alias x", true},
+                                   {SDE, "sdlt_sampler_step_dd", true, true, "x0 and noise are read at every step and may not alias x", true}};
+  if (p == nullptr) SDLT_FAIL(SDLT_ERR_SHAPE, "%s: null parameter block", R[0].name);
+  if (p->form < 0 || p->form > 2) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "%s: form=%d (0 Euler, 1 multistep, 2 SDE)", R[0].name, p->form);
+  const step_args a = {p->eps, p->x, p->x0, p->noise, nullptr, p->form != EULER ? p->dprev : nullptr, p->xin, p->ld_xin, p->timesteps, p->table, p->ctr,
+                       p->form == SDE ? p->seeds : nullptr, p->n, p->hw, p->table_rows, p->hold};
+  return sampler_launch(R[p->form], a, p->init, stream);
 }
 
 extern "C" int sdlt_sampler_noise(const uint32_t* seeds, int32_t step, int32_t n, int32_t hw, float* out, void* stream) {

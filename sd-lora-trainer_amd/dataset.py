@@ -54,6 +54,14 @@ def latent_mask(mask_image, size, latent_hw, channels=4):
     return m.repeat(1, channels, 1, 1).squeeze()
 
 
+def latent_change_map(map_image, size, latent_hw):
+    """A change map for differential diffusion (render.py: `change_map_image`): the picture's luminance / 255 at `size` = (width, height) (prepare_mask),
+    AREA-resized to the latent grid - every latent cell is the mean of the pixels it covers, so grey levels and soft edges survive, where latent_mask's
+    nearest resize picks one pixel.  White is full strength, black is keep: all white gives exactly 1, all black exactly 0.  -> fp32 [1, 1, h, w] in [0, 1]."""
+    m = prepare_mask(map_image, size[0], size[1]).float()
+    return torch.nn.functional.interpolate(m, size=tuple(latent_hw), mode="area").clamp_(0.0, 1.0)
+
+
 def process_captions(captions, substitute_caption_map=None):
     """dataset.py:46-52: lower-case, substitute (keys lower-cased too, plain substring replacement), NaN -> ''."""
     out = []

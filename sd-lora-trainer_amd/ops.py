@@ -5,6 +5,7 @@ Conventions: activations are 2-D bf16 matrices [rows, C] with un
 arbitrary row stride (views of wider buffers are fine); "NHWC" means rows = B*H*W.
 """
 import ctypes as C
+import math
 import os
 import weakref
 
@@ -1211,13 +1212,13 @@ def add_noise_nhwc(x0, noise, timesteps, alphas_cumprod, out, noisy_nchw=None):
 
 def _sampler_launch(entry, params, width, eps, x, xin, timesteps, table, ctr, init, **operands):
     """What the four sampler_step* wrappers share: the checks on the common operands, the entry's parameter block `params` filled from them and from
-    `operands` (the entry's own: x0 / noise / dprev fp32 shaped like x, mask fp32 [n, 1, h, w], seeds int32 [n, 2]; None where absent), and the call."""
+    `operands` (the entry's own: x0 / noise / dprev fp32 shaped like x, mask / hold fp32 [n, 1, h, w], seeds int32 [n, 2]; None where absent), and the call."""
     lib = _lib.load()
     n, c4, h, w = x.shape
     _chk2(x, F32), _chk2(xin), _chk2(timesteps, F32), _chk2(table, F32), _chk2(ctr, torch.int32)
     assert c4 == 4 and x.is_contiguous() and table.is_contiguous() and table.dim() == 2 and table.shape[1] == width and ctr.numel() >= 2
     assert xin.shape[0] == 2 * n * h * w and timesteps.numel() >= 2 * n and timesteps.is_contiguous()
-    shapes = dict(mask=(n, 1, h, w), seeds=(n, 2))
+    shapes = dict(mask=(n, 1, h, w), hold=(n, 1, h, w), seeds=(n, 2))
     for name, t in operands.items():
         if t is not None:
             _chk2(t, torch.int32 if name == "seeds" else F32)
@@ -1277,6 +1278,49 @@ def sampler_step_sde(eps, x, xin, timesteps, table, ctr, *, dprev, seeds, x0=Non
     _sampler_history_checks(x, dprev, x0, noise, mask, init)
     return _sampler_launch("sdlt_sampler_step_sde", _lib.SamplerSdeParams, 8, eps, x, xin, timesteps, table, ctr, init, dprev=dprev, seeds=seeds, x0=x0,
                            noise=noise, mask=mask)
+
+
+def sampler_step_dd(eps, x, xin, timesteps, table, ctr, *, x0, noise, hold, form, dprev=None, seeds=None, init=False):
+    """sdlt_sampler_step_dd: the step launch with a per-pixel hold map (differential diffusion).  form 0 | 1 | 2: the update and table of
+    sampler_step_img | sampler_step_ms | sampler_step_sde (dprev with forms 1, 2; seeds with form 2).  hold fp32 [n, 1, h, w], integer-valued
+    (sampler.hold_map): after the form's update a pixel is x0 + noise * sigma_next while (step row + 1) < hold, selected, and the update's own bits
+    otherwise.  init: x = x0 + noise * (first used sigma); hold is not read.  The other operands as the form's own wrapper."""
+    assert form in (0, 1, 2), form
+    assert x0.data_ptr() != x.data_ptr() and noise.data_ptr() != x.data_ptr(), "x0 and noise are read at every step: they may not alias x"
+    assert hold.data_ptr() != x.data_ptr() and (dprev is None or hold.data_ptr() != dprev.data_ptr()), "hold may alias neither x nor dprev"
+    operands = dict(x0=x0, noise=noise, hold=hold)
+    if form >= 1:
+        _sampler_history_checks(x, dprev, x0, noise, None, init)
+        operands["dprev"] = dprev
+    if form == 2:
+        operands["seeds"] = seeds
+    params = lambda **kw: _lib.SamplerDdParams(form=form, **kw)  # noqa: E731
+    return _sampler_launch("sdlt_sampler_step_dd", params, 4 if form == 0 else 8, eps, x, xin, timesteps, table, ctr, init, **operands)
+
+
+def blur_taps(sigma):
+    """The tap table of blur_planes for a Gaussian of standard deviation sigma > 0 (samples): fp32 [2 R + 1] on the CPU, R = min(ceil(3 sigma), 64),
+    weights exp(-d^2 / (2 sigma^2)) for d = -R .. R, normalised in fp64 and rounded once to fp32."""
+    if not (isinstance(sigma, (int, float)) and not isinstance(sigma, bool) and math.isfinite(sigma) and sigma > 0.0):
+        raise ValueError(f"blur_taps: sigma must be a finite number > 0, got {sigma!r}")
+    R = min(int(math.ceil(3.0 * sigma)), 64)
+    d = torch.arange(-R, R + 1, dtype=torch.float64)
+    wgt = torch.exp(-(d * d) / (2.0 * float(sigma) ** 2))
+    return (wgt / wgt.sum()).to(F32)
+
+
+def blur_planes(src, out, scratch, taps, clamp01=False):
+    """sdlt_blur_planes: out = src blurred with `taps` (blur_taps) along x, then along y, edges replicated; every leading dimension of the contiguous fp32
+    tensors [.., h, w] is a plane.  scratch: a third tensor of the same shape (overlapping neither); out may be src.  clamp01: the result clamped to
+    [0, 1].  Each sum runs over the taps from -R to +R in that order, one multiply and one add per tap (tests/blur_ref.py gives the same bits)."""
+    lib = _lib.load()
+    _chk2(src, F32), _chk2(out, F32), _chk2(scratch, F32), _chk2(taps, F32)
+    assert src.dim() >= 2 and src.shape == out.shape == scratch.shape and src.is_contiguous() and out.is_contiguous() and scratch.is_contiguous()
+    assert taps.dim() == 1 and taps.numel() % 2 == 1 and taps.is_contiguous() and taps.device == src.device, "taps: fp32 [2 R + 1] on the planes' device"
+    h, w = src.shape[-2:]
+    _lib.check(lib.sdlt_blur_planes(src.data_ptr(), out.data_ptr(), scratch.data_ptr(), src.numel() // (h * w), h, w, taps.data_ptr(), taps.numel() // 2,
+                                    int(bool(clamp01)), _stream()), "sdlt_blur_planes")
+    return out
 
 
 def sampler_noise(seeds, step, out):

@@ -4,7 +4,7 @@ scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-squ
 
     python -m sd_lora_trainer_amd.render --checkpoint DIR --out DIR [--prompt TEXT ...] [--n-validation N] [--lora-scale X ...] [--size W H]
                                          [--steps N] [--guidance G] [--seed S] [--images-per-batch N] [--eager]
-                                         [--init-image PATH [--strength S] [--mask PATH]] [--sampler euler|dpmpp_2m|euler_a|dpmpp_2m_sde] [--eta F]
+                                         [--init-image PATH [--strength S] [--mask PATH | --change-map PATH] [--mask-blur SIGMA]] [--sampler euler|dpmpp_2m|euler_a|dpmpp_2m_sde] [--eta F]
                                          [--sigmas trailing|karras] [--guidance-rescale F] [--guidance-interval SIGMA_LO SIGMA_HI]
                                          [--negative-prompt TEXT] [--freeu B1 B2 S1 S2 [--freeu-v2]]
                                          [--hires-scale F | --hires-size W H] [--hires-strength F] [--hires-steps N] [--hires-upscaler latent|pixel]
@@ -23,6 +23,14 @@ as one replayed hipGraph (sampler.LatentSampler.sample(graph=True)); --eager iss
 of the loaded stack (the posterior's mean times the scaling factor: deterministic) and noised to the point of the schedule that --strength
 selects (default 0.6; the last int(steps * strength) steps run).  --mask (white: regenerate, black: keep; nearest-resized to the latent grid)
 keeps the black region of the init image: it is put back after every step, and comes out as the encoded image exactly.
+
+--change-map MAP.png is differential diffusion (Levin & Fried 2023, "Giving Each Pixel Its Strength"): the map's luminance, area-resized to the latent
+grid, gives every pixel a strength of its own - white the whole --strength, black keep (the encoded image exactly, like a black mask), grey in between.
+A pixel with value c is held on the init image's noised trajectory for the first (1 - c) share of the steps that run, then released to finish on its
+own: a selection per pixel and step inside the step launch (sdlt_sampler_step_dd), never a mix of two pictures, so a soft edge leaves no halo where
+--mask's fixed blend does.  --mask-blur SIGMA (latent pixels) blurs the map on the device first (sdlt_blur_planes, edges replicated) - a hard mask
+painted by hand becomes a soft change map; with --mask it blurs the mask, which then goes down the blend path as before.  --change-map excludes --mask
+and the hires pass; with every sampler and noise schedule.  Without the flags nothing changes.
 
 --sampler dpmpp_2m integrates with DPM-Solver++ (2M), the second-order multistep solver (sampler.DpmSolverPP2M; the step launch is then
 sdlt_sampler_step_ms), instead of first-order Euler: the same trajectory error in about half the steps.  --sigmas karras spaces the noise levels as
@@ -353,7 +361,7 @@ def hires_args(hires, size, steps, f=8):
 def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, guidance_scale=8.0, seed=None, images_per_batch=1, token_scale=None,
            graph=True, n_validation=4, init_image=None, strength=None, mask_image=None, sampler="euler", sigmas="trailing", eta=None,
            guidance_rescale=0.0, guidance_interval=None, negative_prompt=None, hires=None, freeu=None, heatmap=None, heatmap_grid="max",
-           kv_downsample=None, kv_downsample_mode="nearest", kv_downsample_pass="hires", vae_tile=None):
+           kv_downsample=None, kv_downsample_mode="nearest", kv_downsample_pass="hires", vae_tile=None, change_map_image=None, mask_blur=None):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
     seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
@@ -380,6 +388,9 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     vae_tile: None, a tile length or (tile, overlap) in latent units (vae_tile_args; the overlap defaults to 16): every VAE pass of the render - the
     decode of each picture, the decode and encode of the pixel upscaler, the encode of init_image - runs in tiles (VaeDecoder.decode_tiled,
     VaeEncoder.encode_moments_tiled; ops.tile_blend).  The decoder then runs at the tile's shape and is not rebuilt with the UNet by the hires pass.
+    change_map_image (path or PIL image; needs init_image, excludes mask_image and hires): differential diffusion - its luminance, area-resized to the
+    latent grid (dataset.latent_change_map), is LatentSampler.sample's change_map: white the whole `strength`, black keep.  mask_blur (a sigma in latent
+    pixels, >= 0): the change map - or mask_image's mask, which then takes the blend path as before - is blurred on the device first (sampler.blur_map).
     -> {scale: [paths]}."""
     from . import train as T
     from . import vae as _vae
@@ -451,6 +462,19 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     vt = vae_tile_args(vae_tile)                                     # (raises before anything is built)
     if vt is not None and not hasattr(stack.rt.ops, "tile_blend"):
         raise NotImplementedError("this op table has no tile_blend kernel (sdlt_tile_blend): vae_tile puts the VAE's tiles together by that launch (ops.tile_blend)")
+    if init_image is None and (change_map_image is not None or mask_blur is not None):
+        raise ValueError("change_map_image and mask_blur need init_image: the pixels to keep are taken from it")
+    if change_map_image is not None and mask_image is not None:
+        raise ValueError("change_map_image and mask_image exclude each other: the map selects per pixel and step, the mask blends after every step")
+    if change_map_image is not None and hires is not None:
+        raise ValueError("hires does not combine with change_map_image: the second pass would need the original at the large size")
+    if mask_blur is not None:
+        if mask_image is None and change_map_image is None:
+            raise ValueError("mask_blur blurs mask_image's mask or change_map_image's map: give one of them")
+        if not (isinstance(mask_blur, (int, float)) and not isinstance(mask_blur, bool) and math.isfinite(mask_blur) and mask_blur >= 0.0):
+            raise ValueError(f"mask_blur must be a finite number >= 0 (latent pixels), got {mask_blur!r}")
+        if mask_blur > 0.0 and not hasattr(stack.rt.ops, "blur_planes"):
+            raise NotImplementedError("this op table has no blur_planes kernel: mask_blur blurs the map on the device by that launch (ops.blur_planes)")
     hi = None
     if hires is not None:
         if mask_image is not None:
@@ -478,9 +502,16 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         strength = 0.6 if strength is None else strength
         SM.img2img_steps(steps, strength)               # (raises before anything is built)
         x0, mask = encode_init(loaded, init_image, mask_image, size, (h, w), **({} if vt is None else dict(vae_tile=vt)))
+        if mask is not None and mask_blur:
+            mask = SM.blur_map(stack.rt.ops, mask, mask_blur)
         img_kw.update(init_latents=x0, strength=strength, mask=mask)
+        if change_map_image is not None:
+            from . import dataset as D
+            cmap = D.latent_change_map(_open(change_map_image), size, (h, w)).to(dev)
+            img_kw.update(change_map=SM.blur_map(stack.rt.ops, cmap, mask_blur or 0.0))
     loaded.prepare(n, h, w, **({} if vt is None else dict(keep_decoder=True)))
-    fused = hasattr(stack.rt.ops, "sampler_step_sde" if sde else "sampler_step_ms" if sampler == "dpmpp_2m" else "sampler_step")
+    fused = hasattr(stack.rt.ops, "sampler_step_dd" if change_map_image is not None else "sampler_step_sde" if sde else "sampler_step_ms" if sampler == "dpmpp_2m"
+                    else "sampler_step")
     graph = graph and dev.type == "cuda"
     os.makedirs(out_dir, exist_ok=True)
     result = {}
@@ -585,6 +616,10 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         meta = dict(prompts=prompts, lora_scales=list(lora_scales), size=list(size), steps=steps, guidance_scale=guidance_scale, seed=seed)
         if init_image is not None:
             meta.update(strength=strength, masked=mask_image is not None)
+        if change_map_image is not None:
+            meta.update(change_map=dict(file=change_map_image if isinstance(change_map_image, str) else None, mask_blur=float(mask_blur or 0.0)))
+        elif mask_blur:
+            meta.update(mask_blur=float(mask_blur))
         if (sampler, sigmas) != ("euler", "trailing"):
             meta.update(sampler=sampler, sigmas=sigmas)
         if sde:
@@ -625,6 +660,9 @@ def main(argv=None, runtime=None):
     ap.add_argument("--init-image", default=None, help="start from this picture instead of pure noise (img2img); resized to --size")
     ap.add_argument("--strength", type=float, default=None, help="how much of the schedule runs on the init image, in (0, 1]; default 0.6 with --init-image")
     ap.add_argument("--mask", default=None, help="inpainting mask for --init-image: white is regenerated, black is kept")
+    ap.add_argument("--change-map", default=None, help="differential diffusion for --init-image: the map's luminance is a strength per pixel - white the "
+                    "whole --strength, black keep, grey in between")
+    ap.add_argument("--mask-blur", type=float, default=None, metavar="SIGMA", help="blur --change-map's map (or --mask's mask) by a Gaussian of SIGMA latent pixels first")
     ap.add_argument("--sampler", choices=("euler", "dpmpp_2m", "euler_a", "dpmpp_2m_sde"), default="euler",
                     help="integrator: first-order Euler, DPM-Solver++ (2M) (second order: about half the steps), or their stochastic forms - Euler ancestral, "
                     "DPM-Solver++ (2M) SDE - which add fresh noise after every step")
@@ -666,6 +704,14 @@ def main(argv=None, runtime=None):
     a = ap.parse_args(argv)
     if a.init_image is None and (a.mask is not None or a.strength is not None):
         ap.error("--mask and --strength need --init-image")
+    if a.init_image is None and (a.change_map is not None or a.mask_blur is not None):
+        ap.error("--change-map and --mask-blur need --init-image")
+    if a.change_map is not None and a.mask is not None:
+        ap.error("--change-map and --mask exclude each other")
+    if a.mask_blur is not None and a.mask is None and a.change_map is None:
+        ap.error("--mask-blur needs --change-map or --mask")
+    if a.mask_blur is not None and not (math.isfinite(a.mask_blur) and a.mask_blur >= 0.0):
+        ap.error(f"--mask-blur must be a finite number >= 0, got {a.mask_blur}")
     if a.eta is not None and a.sampler not in ("euler_a", "dpmpp_2m_sde"):
         ap.error(f"--eta needs --sampler euler_a or dpmpp_2m_sde: --sampler {a.sampler} adds no noise")
     if a.eta is not None and not a.eta >= 0.0:
@@ -712,6 +758,8 @@ def main(argv=None, runtime=None):
     else:
         if a.mask is not None:
             ap.error("--hires-scale / --hires-size do not combine with --mask")
+        if a.change_map is not None:
+            ap.error("--hires-scale / --hires-size do not combine with --change-map")
         if a.hires_strength is not None and not 0.0 < a.hires_strength <= 1.0:
             ap.error(f"--hires-strength must be in (0, 1], got {a.hires_strength}")
         if a.hires_steps is not None and a.hires_steps < 1:
@@ -729,6 +777,7 @@ def main(argv=None, runtime=None):
                  mask_image=a.mask, sampler=a.sampler, sigmas=a.sigmas, eta=a.eta, guidance_rescale=a.guidance_rescale,
                  guidance_interval=a.guidance_interval, negative_prompt=a.negative_prompt, **({} if hires is None else dict(hires=hires)),
                  **({} if freeu is None else dict(freeu=freeu)), **kvd, **vtile,
+                 **({} if a.change_map is None else dict(change_map_image=a.change_map)), **({} if a.mask_blur is None else dict(mask_blur=a.mask_blur)),
                  **({} if a.heatmap is None else dict(heatmap=a.heatmap, heatmap_grid=a.heatmap_grid or "max")))
     for scale, paths in res.items():
         print(f"lora_scale {scale}: {len(paths)} image(s), {os.path.join(a.out, 'grid_scale' + _scale_tag(scale) + '.jpg')}")

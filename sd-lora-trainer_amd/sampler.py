@@ -16,6 +16,10 @@ entries of the trailing schedule (StableDiffusionImg2ImgPipeline.get_timesteps) 
 (EulerDiscreteScheduler.add_noise); with a mask (1 regenerate, 0 keep) the known region is put back after every step, noised to the sigma the
 step arrived at, from the same noise draw (the legacy inpainting loop of diffusers: latents = init_latents_proper * (1 - mask) + latents * mask).
 
+Differential diffusion (`sample(init_latents=, change_map=)`; Levin & Fried 2023, "Giving Each Pixel Its Strength"): a change map c in [0, 1] gives
+every pixel an img2img strength of its own.  A pixel is held on the init latents' noised trajectory (x0 + noise * sigma, the same noise draw) for the
+first (1 - c) share of the steps that run, then released to finish on its own - by selection, never by mixing (`hold_map`; c = 0 is kept exactly).
+
 Guidance controls (`sample(guidance_scale=[...], guidance_rescale=, guidance_interval=)`): a guidance scale per step, guidance applied only where
 sigma_i lies in (sigma_lo, sigma_hi] (Kynkaanniemi et al. 2024, "Applying Guidance in a Limited Interval"; g_i = 1 elsewhere) and the rescale of Lin et
 al. 2024, section 3.4 (diffusers' rescale_noise_cfg: the guided prediction is scaled to the standard deviation of the positive one, per image, and
@@ -338,6 +342,41 @@ def img2img_steps(steps, strength):
     return k, steps - k
 
 
+def hold_map(c, k):
+    """The hold map of a change map for a trajectory of k steps (after strength): c fp32 [..] in [0, 1] -> fp32, integer-valued, same shape and device.
+    Step row i (0-based) leaves a pixel on the init latents' noised trajectory iff i + 1 < hold (sdlt_sampler_step_dd; the torch loop alike):
+      hold = k + 1                 where c == 0: held after the last step too, where sigma = 0 - the pixel ends as the init latents bit for bit
+      hold = ceil((1 - c) k - g)   otherwise (c = 1: 0, never held), in fp64 from the fp32 value, g = k 2^-24
+    - the paper's rule "keep before step i iff (1 - c) > i / k", restated for a select after the step; a pixel with c > 0 has hold <= k and always runs
+    at least the last step free (in the paper c = 0 does too: the exact keep is this project's addition).  g: an fp32 c stands for a real number
+    within 2^-25 of it, so (1 - c) k is known to k 2^-25 only; a product that exceeds an integer by less than twice that counts as the integer.  Without
+    it the answer at c = i / k would follow the direction fp32 happened to round c in: fp32(0.9) = 0.89999998 at k = 10 gives (1 - c) k = 1.0000002,
+    ceil 2, where 0.9 means 1.  Values outside [0, 1] or non-finite: ValueError."""
+    if not (isinstance(k, int) and not isinstance(k, bool) and k >= 1):
+        raise ValueError(f"hold_map: k must be a positive step count, got {k!r}")
+    c = torch.as_tensor(c)
+    if c.dtype != torch.float32:
+        raise ValueError(f"change_map must be fp32, got {c.dtype}")
+    if c.numel() == 0 or not bool(torch.isfinite(c).all()) or float(c.min()) < 0.0 or float(c.max()) > 1.0:
+        raise ValueError("change_map values must be finite and lie in [0, 1] (1 full strength, 0 keep)")
+    c64 = c.double()
+    held = torch.ceil((1.0 - c64) * k - k * 2.0 ** -24).clamp_(min=0.0)
+    return torch.where(c64 == 0.0, torch.full_like(held, float(k + 1)), held).to(torch.float32)
+
+
+def blur_map(ops, m, sigma):
+    """m fp32 [n, 1, h, w] in [0, 1] on the device -> the same blurred by a Gaussian of `sigma` latent pixels (ops.blur_planes with ops.blur_taps, edges
+    replicated, the result clamped to [0, 1]: the rounded weights do not sum to exactly 1).  sigma 0: m itself, nothing is launched."""
+    if not (isinstance(sigma, (int, float)) and not isinstance(sigma, bool) and math.isfinite(sigma) and sigma >= 0.0):
+        raise ValueError(f"mask_blur must be a finite number >= 0 (latent pixels), got {sigma!r}")
+    if sigma == 0.0:
+        return m
+    if not hasattr(ops, "blur_planes"):
+        raise NotImplementedError("this op table has no blur_planes kernel: mask_blur blurs the map on the device by that launch (ops.blur_planes)")
+    m = m.to(F32).contiguous()
+    return ops.blur_planes(m, torch.empty_like(m), torch.empty_like(m), ops.blur_taps(sigma).to(m.device), clamp01=True)
+
+
 RESAMPLE = ("nearest", "bilinear", "bicubic")      # ops.resize_planes' modes 0, 1, 2 (PyTorch's nearest-exact / bilinear / bicubic, align_corners=False)
 
 
@@ -505,17 +544,23 @@ def seed_words(seeds, n, generator=None, device="cpu"):
 # The four step launches of the fused / graph path, as data: the op (looked up on the op table when it is called), the builder of its device table,
 # that table's key in the persistent state and its row width, whether the launch takes the history buffer and the seeds, the dict of LatentSampler that
 # holds its captures, and what the capture key gains: None: nothing; a tuple: (the mask's presence,) + the tuple.
-Family = collections.namedtuple("Family", "op table tab width dprev seeds graphs suffix")
+# form: None, or the `form` argument of ops.sampler_step_dd - the launch with a hold map (sample(change_map=)), one family per update it can take.
+Family = collections.namedtuple("Family", "op table tab width dprev seeds graphs suffix form", defaults=(None,))
 FAMILIES = dict(
     euler=Family("sampler_step", step_table, "table", 4, False, False, "_graphs", None),
     img=Family("sampler_step_img", step_table_img, "table", 4, False, False, "_img_graphs", ()),
     multistep=Family("sampler_step_ms", step_table_ms, "table_ms", 8, True, False, "_ms_graphs", ("multistep",)),
     sde=Family("sampler_step_sde", step_table_sde, "table_ms", 8, True, True, "_sde_graphs", ("sde",)),
+    dd_euler=Family("sampler_step_dd", step_table_img, "table", 4, False, False, "_dd_graphs", ("dd", 0), 0),
+    dd_ms=Family("sampler_step_dd", step_table_ms, "table_ms", 8, True, False, "_dd_graphs", ("dd", 1), 1),
+    dd_sde=Family("sampler_step_dd", step_table_sde, "table_ms", 8, True, True, "_dd_graphs", ("dd", 2), 2),
 )
 
 
-def step_family(sampler, img):
-    """The family of sample(sampler=...): img None: txt2img."""
+def step_family(sampler, img, held=False):
+    """The family of sample(sampler=...): img None: txt2img; held: with a change map."""
+    if held:
+        return "dd_sde" if sampler in SDE_KINDS else "dd_ms" if sampler == "dpmpp_2m" else "dd_euler"
     return "sde" if sampler in SDE_KINDS else "multistep" if sampler == "dpmpp_2m" else "euler" if img is None else "img"
 
 
@@ -541,6 +586,7 @@ class LatentSampler:
         self._img_graphs = {}              # the same key + (masked,) -> hipGraph of one iteration whose step launch is ops.sampler_step_img
         self._ms_graphs = {}               # the same key + (masked, "multistep") -> hipGraph of one iteration whose step launch is ops.sampler_step_ms
         self._sde_graphs = {}              # the same key + (masked, "sde") -> hipGraph of one iteration whose step launch is ops.sampler_step_sde
+        self._dd_graphs = {}               # the same key + (False, "dd", form) -> hipGraph of one iteration whose step launch is ops.sampler_step_dd
         self._guided_graphs = {}           # any of the four keys above + (its family,) -> hipGraph of that iteration with ops.guidance before the step launch
         # the torch loop where the pre-pass runs: the deterministic samplers in their step kernels' order (dpmpp_2m: the SDE form's eta = 0 rows are
         # ms_coefficients with d = 0)
@@ -562,7 +608,7 @@ class LatentSampler:
     @torch.no_grad()
     def sample(self, embeds, h, w, *, steps=25, guidance_scale=8.0, generator=None, size=None, latents=None, graph=False, fused=False, n_images=1,
                init_latents=None, strength=1.0, mask=None, sampler="euler", sigmas="trailing", eta=1.0, seeds=None, guidance_rescale=0.0,
-               guidance_interval=None, freeu=None, heatmap=None, kv_downsample=None, kv_downsample_mode=None):
+               guidance_interval=None, freeu=None, heatmap=None, kv_downsample=None, kv_downsample_mode=None, change_map=None):
         """embeds = (c [1,77,D], uc [1,77,D], pc [1,P] | None, puc | None); h, w latent size.  Returns latents [1,4,h,w] fp32
         (still multiplied by the VAE scaling factor, as the pipeline holds them before `vae.decode(latents / scaling_factor)`).
         fused: guidance, the Euler update and the next model input are ONE kernel between two forwards (ops.sampler_step) instead of torch
@@ -595,7 +641,20 @@ class LatentSampler:
         kv_downsample: a tuple of integer factors, largest self-attention token grid first - (2,), (4, 2) - with kv_downsample_mode "nearest" | "area":
         key / value token downsampling (UNet.set_kv_downsample: one ops.token_pool launch per affected self-attention, whose k | v products and score
         work shrink by factor^2) in every forward of the trajectory, on all three paths.  None: the constructor's setting; () or all ones: off, and
-        the launch sequence is the plain one.  The setting is part of the capture key."""
+        the launch sequence is the plain one.  The setting is part of the capture key.
+        change_map [n_images | 1, 1, h, w] fp32 in [0, 1] (needs init_latents; excludes mask): differential diffusion - 1 gives a pixel the whole
+        `strength`, 0 keeps it as init_latents exactly, a value between holds it on the init latents' noised trajectory for the first (1 - c) share of
+        the steps that run and then releases it (hold_map): a SELECT after every step, never a mix.  With every sampler on all three paths; fused /
+        graph: the step launch is ops.sampler_step_dd, whose captures are keyed apart from all others, and the hold map lives in a persistent buffer
+        refilled per call, so one capture serves every map, strength and step count.  A map of ones gives the bits of the call without it at
+        strength < 1; at strength 1 the trajectory starts from init_latents + noise * sigma_0 (without a map: from the noise alone)."""
+        if change_map is not None:                         # refused before anything is built
+            if init_latents is None:
+                raise ValueError("change_map needs init_latents: a held pixel follows their noised trajectory")
+            if mask is not None:
+                raise ValueError("change_map and mask exclude each other: the map selects per pixel and step, the mask blends after every step")
+            if (graph or fused) and not hasattr(self.rt.ops, "sampler_step_dd"):
+                raise NotImplementedError("this op table has no sampler_step_dd kernel: sample(change_map=..., graph=False, fused=False) is the torch loop")
         kd = self.kv_downsample
         if kv_downsample is not None or kv_downsample_mode is not None:
             kd = kv_downsample_args(kd[0] if kv_downsample is None and kd is not None else kv_downsample, kv_downsample_mode or (kd[1] if kd is not None else "nearest"))
@@ -614,14 +673,15 @@ class LatentSampler:
             raise ValueError(f"eta must be >= 0, got {eta!r}")
         if sigmas not in SIGMAS:
             raise ValueError(f"sigmas must be one of {SIGMAS}, got {sigmas!r}")
-        img = self._img_args(init_latents, strength, mask, steps, h, w, n_images)
+        img = self._img_args(init_latents, strength, mask, steps, h, w, n_images, keep=change_map is not None)
+        hold = None if change_map is None else self._hold_args(change_map, steps - img[2], h, w, n_images)
         guide = (guidance_scale, guidance_rescale, guidance_interval) if guidance_in_use(guidance_scale, guidance_rescale, guidance_interval) else None
         if guide is not None and not hasattr(self.rt.ops, "guidance"):
             raise NotImplementedError("this op table has no guidance kernel: a per-step guidance_scale, guidance_rescale and guidance_interval are evaluated "
                                       "by that launch (ops.guidance), in the torch loop too")
         if graph or fused:
             return self._sample_fused(embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img, sampler, sigmas, eta, seeds, guide,
-                                      heatmap)
+                                      heatmap, hold)
         assert n_images == 1 and self.rt.B == 2, "the torch loop samples one image on a batch-2 runtime; several images together: fused=True or graph=True"
         rt, u, cfg = self.rt, self.unet, self.unet.cfg
         dev = rt.device
@@ -679,6 +739,9 @@ class LatentSampler:
             if m is not None:                      # the known region, noised to the sigma this step arrived at (0 after the last: init_latents itself)
                 k = x0 + noise * float(s.sigmas[i + 1])
                 x = k + m * (x - k)
+            if hold is not None:                   # differential diffusion: the same k, selected while the pixel is held (step row i: i + 1 < hold)
+                k = x0 + noise * float(s.sigmas[i + 1])
+                x = torch.where(hold > float(i + 1), k, x)
         return x if hm is None else (x, heat)
 
     def _scheduler(self, sampler, steps, start, sigmas, eta, exact=False):
@@ -693,8 +756,15 @@ class LatentSampler:
             s = self.sched_ms if sampler == "dpmpp_2m" else self.sched
         return s.set_timesteps(steps, start, sigmas)
 
-    def _img_args(self, init_latents, strength, mask, steps, h, w, n):
-        """-> None (txt2img: no init_latents, or strength 1 without a mask) | (x0 [n, 4, h, w], mask [n, 1, h, w] | None, first step) on the device."""
+    def _hold_args(self, change_map, k, h, w, n):
+        """-> hold_map of sample()'s change_map for the k steps that run, fp32 [n, 1, h, w] on the device."""
+        if not torch.is_tensor(change_map) or change_map.dim() != 4 or tuple(change_map.shape[1:]) != (1, h, w) or change_map.shape[0] not in (1, n):
+            raise ValueError(f"change_map {tuple(getattr(change_map, 'shape', ()))}: expected a tensor [{n} or 1, 1, {h}, {w}]")
+        return hold_map(change_map.to(self.rt.device), k).expand(n, 1, h, w).contiguous()
+
+    def _img_args(self, init_latents, strength, mask, steps, h, w, n, keep=False):
+        """-> None (txt2img: no init_latents, or strength 1 without a mask) | (x0 [n, 4, h, w], mask [n, 1, h, w] | None, first step) on the device.
+        keep (a change map follows): never None from init latents."""
         if init_latents is None:
             if mask is not None:
                 raise ValueError("mask needs init_latents: the region to keep is taken from them")
@@ -715,7 +785,7 @@ class LatentSampler:
                 raise ValueError(f"mask values must lie in [0, 1] (1 regenerate, 0 keep), got [{lo}, {hi}]")
             # ones everywhere: nothing to keep.  (k + 1 (x - k) rounds twice where the plain step does not, so it is not left to the blend.)
             mask = None if lo == 1.0 else mask.expand(n, 1, h, w).contiguous()
-        if mask is None and start == 0:
+        if mask is None and start == 0 and not keep:
             return None
         return x0, mask, start
 
@@ -738,8 +808,8 @@ class LatentSampler:
             st["shapes"][(h, w)] = dict(x=rt.zeros(n, 4, h, w, dtype=F32), x64=rt.zeros(2 * n * h * w, 64))
         return st, st["shapes"][(h, w)]
 
-    def _load_image_state(self, sh, h, w, img, noise):
-        """-> (x0, noise, masked) of the init launch.  From init latents: x0, the noise and the mask are copied into the persistent buffers of the shape
+    def _load_image_state(self, sh, h, w, img, noise, hold=None):
+        """-> (x0, noise, masked) of the init launch.  hold (a change map's hold map): copied into its persistent buffer beside them.  From init latents: x0, the noise and the mask are copied into the persistent buffers of the shape
         (a captured step launch holds their pointers) and those are returned; txt2img: (None, the noise as given, None)."""
         if img is None:
             return None, noise, None
@@ -751,12 +821,18 @@ class LatentSampler:
         im["noise"].copy_(noise)
         if masked:
             im["mask"].copy_(img[1])
+        if hold is not None:
+            if "hold" not in im:
+                im["hold"] = self.rt.zeros(self.n, 1, h, w, dtype=F32)
+            im["hold"].copy_(hold)
         return im["x0"], im["noise"], masked
 
     def _step_launch(self, fam, st, sh, eps, x0=None, noise=None, mask=None):
         """The launch of family `fam` (FAMILIES) on the persistent state; eps None: its init entry."""
         f, init = FAMILIES[fam], eps is None
         kw = dict(x0=x0, noise=noise, mask=mask, init=init) if fam != "euler" else dict(noise=noise) if init else {}
+        if f.form is not None:                            # the launch with a hold map: no mask; the map is read by a step only
+            kw = dict(x0=x0, noise=noise, hold=sh["img"]["hold"], form=f.form, init=init)
         if f.dprev:
             kw["dprev"] = sh["dprev"]
         if f.seeds:
@@ -778,7 +854,7 @@ class LatentSampler:
             self.rt.ops.heatmap_accum(ents, heat["cols"], st["ctr"], st["hw"], heat["heat"], row_off=1, row_stride=2)
         if guided:
             self.rt.ops.guidance(eps, st["gtab"], st["ctr"], self.n)
-        im = sh["img"] if masked or fam == "img" else dict(x0=None, noise=None, mask=None)
+        im = sh["img"] if masked or fam == "img" or FAMILIES[fam].form is not None else dict(x0=None, noise=None, mask=None)
         self._step_launch(fam, st, sh, eps, im["x0"], im["noise"], im["mask"] if masked else None)
 
     def _graph(self, st, sh, h, w, fam="euler", masked=None, guided=False, heat=None):
@@ -839,12 +915,12 @@ class LatentSampler:
         return g
 
     def _sample_fused(self, embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img=None, sampler="euler", sigmas="trailing",
-                      eta=1.0, seeds=None, guide=None, heatmap=None):
+                      eta=1.0, seeds=None, guide=None, heatmap=None, hold=None):
         rt, cfg, n = self.rt, self.unet.cfg, self.n
         guided = guide is not None
         if guided:
             guidance_scale = 1.0                          # the step launch's own scale multiplies e - e = 0: any value gives the same bits
-        fam = step_family(sampler, img)
+        fam = step_family(sampler, img, hold is not None)
         ms, sde = fam == "multistep", fam == "sde"
         if sde and not hasattr(rt.ops, "sampler_step_sde"):
             raise NotImplementedError(f"this op table has no sampler_step_sde kernel: sample(sampler={sampler!r}) draws its per-step noise inside that launch")
@@ -852,7 +928,7 @@ class LatentSampler:
             raise NotImplementedError("this op table has no sampler_step_ms kernel: sample(sampler='dpmpp_2m', graph=False, fused=False) is the torch loop")
         if not hasattr(rt.ops, "sampler_step"):
             raise NotImplementedError("this op table has no sampler_step kernel: sample(graph=False, fused=False) is the torch loop")
-        if img is not None and not hasattr(rt.ops, "sampler_step_img"):
+        if img is not None and hold is None and not hasattr(rt.ops, "sampler_step_img"):
             raise NotImplementedError("this op table has no sampler_step_img kernel: sample(init_latents=..., graph=False, fused=False) is the torch loop")
         assert n_images == n, f"the runtime's batch {rt.B} samples {n} image(s) together, not {n_images}"
         assert 1 <= steps <= TABLE_ROWS - 2
@@ -892,7 +968,7 @@ class LatentSampler:
         assert tuple(noise.shape) == (n, 4, h, w)
         if f.seeds:                                       # after the initial latents, as in the torch loop; a captured launch holds the buffer
             st["seeds"].copy_(seed_words(seeds, n, generator, dev))
-        x0, noise, masked = self._load_image_state(sh, h, w, img, noise)
+        x0, noise, masked = self._load_image_state(sh, h, w, img, noise, hold)
         heat = None
         if heatmap is not None:                           # persistent buffers, rewritten per trajectory: a captured launch holds their pointers
             hm = heatmap_args(heatmap, n, steps)
