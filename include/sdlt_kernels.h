@@ -874,6 +874,36 @@ int sdlt_token_pool(const void* x, int64_t ldx, int32_t B, int32_t H, int32_t W,
 int sdlt_tile_blend(const float* tile, int64_t ld, int32_t th, int32_t tw, int32_t C, const float* wy, const float* wx,
                     float* out, int32_t H, int32_t W, int32_t y0, int32_t x0, void* stream);
 
+/* sdlt_window_gather / sdlt_window_blend : the two launches tiled diffusion adds to a denoising iteration (MultiDiffusion, Bar-Tal et al. 2023; sampler.py:
+ * sample(tile=); inference only).  The UNet runs on overlapping th x tw windows of the full H x W latent as one batch; the step launches and sdlt_guidance
+ * stay at full size.  n images, ty x tx windows per image at ys[iy], xs[ix] (int32, DEVICE memory, like the weights: a captured graph serves every
+ * overlap with the same tile counts).
+ *   full-size rows   ((2 j + s) H + y) W + x                  image j, s = 0 negative | 1 positive (what the step launches read and write)
+ *   tile batch       b = 2 (j ty tx + iy tx + ix) + s ; pixel row (b th + p) tw + q
+ * sdlt_window_gather: x_tiles[b, p, q, 0 .. ld) = x_full[j, s, ys[iy] + p, xs[ix] + q, 0 .. ld) - whole bf16 model-input rows of ld elements (64 today:
+ *   128 bytes, columns past 3 included, as the step launch left them), 16-byte pieces, eight lanes per row - and tf_tiles[b] = tf_full[2 j + s].  wy, wx are
+ *   not read and may be null.
+ * sdlt_window_blend: eps_full[j, s, y, x, 0 .. 4) = the sum over the windows (iy, ix) with ys[iy] <= y < ys[iy] + th and xs[ix] <= x < xs[ix] + tw, taken iy
+ *   ascending and then ix ascending, of  t = wy[iy th + y - ys[iy]] * wx[ix tw + x - xs[ix]] rounded, u = t * eps_tiles[b, p, q, c] rounded, acc = acc + u
+ *   rounded, from +0.0 - three fp32 operations per term, no contraction, which a torch fp32 restatement reproduces exactly.  wy fp32 [ty, th], wx fp32
+ *   [tx, tw]: vae.tile_weights' normalised tables, whose products sum to 1 over the windows that cover a sample.  A gather: one thread per full-size row,
+ *   one 16-byte store; every row of eps_full is written exactly once (a row no window covers: zeros) - no zeroing launch, no atomics, bit-reproducible.
+ *   All ty and tx starts are scanned: any number of windows may cover a sample.
+ * 64-bit row offsets, vector stores only.  A null block or pointer, a non-positive extent, ty or tx above 64, H or W above 16384, n above 32767, a window
+ * larger than the grid (th > H or tw > W), more than 2^40 tile rows, ld below 8 or above 4096, x_tiles overlapping x_full or eps_full overlapping eps_tiles (-1); x_full, x_tiles, eps_tiles or
+ * eps_full not 16-byte aligned, a table or timestep pointer not 4-byte aligned, ld no multiple of 8 (-2): the code is returned, sdlt_last_error names the
+ * entry point and nothing is launched.  The starts are device memory, so a start that puts a window outside the grid cannot be refused here: gather then
+ * copies no row from outside the grid (the tile row keeps its contents), and neither kernel reads or writes out of bounds.
+ * The block is declared without a struct tag and has no index in sdlt_struct_size(), like sdlt_resize_params: it is 64 bytes - four pointers and eight
+ * int32 - with no padding between fields. */
+typedef struct {
+  const int32_t* ys; const int32_t* xs;      /* int32 [ty], [tx]: window starts */
+  const float* wy; const float* wx;          /* fp32 [ty, th], [tx, tw]: normalised 1-D weights (blend only) */
+  int32_t n, H, W, th, tw, ty, tx, pad_;
+} sdlt_window_params;
+int sdlt_window_gather(const sdlt_window_params* p, const void* x_full, void* x_tiles, int64_t ld, const float* tf_full, float* tf_tiles, void* stream);
+int sdlt_window_blend(const sdlt_window_params* p, const float* eps_tiles, float* eps_full, void* stream);
+
 /* out[M,C] = a + b on strided 2-D bf16 views (gradient fan-in of the UNet skip connections). */
 int sdlt_add2d(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int32_t M, int32_t C, void* stream);
 

@@ -236,6 +236,12 @@ class HeatOverlayParams(C.Structure):
                 ("n_img", i32), ("T", i32), ("P", i32), ("gh", i32), ("gw", i32), ("H", i32), ("W", i32), ("alpha", f32)]
 
 
+class WindowParams(C.Structure):
+    # sdlt_window_params: 64 bytes by the header's text (tagless, like sdlt_resize_params)
+    _fields_ = [("ys", vp), ("xs", vp), ("wy", vp), ("wx", vp), ("n", i32), ("H", i32), ("W", i32), ("th", i32), ("tw", i32), ("ty", i32), ("tx", i32),
+                ("pad_", i32)]
+
+
 class ShadowDesc(C.Structure):
     _fields_ = [("offset", i64), ("src_ld", i64), ("rows", i32), ("cols", i32), ("dst", vp), ("ld", i64), ("dstT", vp), ("ldT", i64)]
 
@@ -303,6 +309,8 @@ SYMBOLS = {
     "sdlt_heatmap_overlay": (i32, [C.POINTER(HeatOverlayParams), vp]),
     "sdlt_token_pool": (i32, [vp, i64, i32, i32, i32, i32, vp, vp, f32, i32, i32, vp, i64, i32, vp]),
     "sdlt_tile_blend": (i32, [vp, i64, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "sdlt_window_gather": (i32, [C.POINTER(WindowParams), vp, vp, i64, vp, vp, vp]),
+    "sdlt_window_blend": (i32, [C.POINTER(WindowParams), vp, vp, vp]),
     "sdlt_strip_gemm": (i32, [C.POINTER(StripParams), vp]),
     "sdlt_strip_gemm_pair": (i32, [C.POINTER(StripParams), C.POINTER(StripParams), vp]),
     "sdlt_attn_pair_ok": (i32, [C.POINTER(AttnParams), C.POINTER(AttnParams)]),
@@ -354,7 +362,7 @@ def load():
             raise KernelLibraryError(f"struct layout mismatch for {name}: C {lib.sdlt_struct_size(which)} vs binding {size}")
     if C.sizeof(ResizeParams) != 48:
         raise KernelLibraryError(f"struct layout mismatch for ResizeParams: header 48 vs binding {C.sizeof(ResizeParams)}")
-    for cls, size in ((HeatAccumParams, 152), (HeatOverlayParams, 80), (GemmPlan, 64), (SamplerDdParams, 128)):
+    for cls, size in ((HeatAccumParams, 152), (HeatOverlayParams, 80), (GemmPlan, 64), (SamplerDdParams, 128), (WindowParams, 64)):
         if C.sizeof(cls) != size:
             raise KernelLibraryError(f"struct layout mismatch for {cls.__name__}: header {size} vs binding {C.sizeof(cls)}")
     _lib = lib

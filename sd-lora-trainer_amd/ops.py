@@ -4,6 +4,7 @@ the device memory and the stream; all arithmetic happens in libsdlt_kernels.so.
 Conventions: activations are 2-D bf16 matrices [rows, C] with unit column stride and an
 arbitrary row stride (views of wider buffers are fine); "NHWC" means rows = B*H*W.
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -1501,6 +1502,65 @@ def tile_blend(tile, out, wy, wx, y0, x0, C):
     assert 0 <= y0 and y0 + th <= H and 0 <= x0 and x0 + tw <= W, f"a {th} x {tw} tile at ({y0}, {x0}) reaches outside the {H} x {W} output"
     _lib.check(lib.sdlt_tile_blend(_p(tile), _ld(tile), th, tw, int(C), _p(wy), _p(wx), _p(out), H, W, int(y0), int(x0), _stream()), "sdlt_tile_blend")
     return out
+
+
+WINDOW_MAX_TILES = 64      # windows per axis of sdlt_window_gather / sdlt_window_blend
+
+WindowTables = collections.namedtuple("WindowTables", "ys xs wy wx th tw ty tx")
+
+
+def window_tables(h, w, T, O, device=None):
+    """The tables of window_gather / window_blend for an h x w latent cut into windows of T with least overlap O (latent units) -> WindowTables: ys int32
+    [ty], xs int32 [tx] (vae.tile_starts), wy fp32 [ty, th], wx fp32 [tx, tw] (vae.tile_weights with g = 1: normalised, the products of the windows that
+    cover a sample sum to 1) on `device` (None: the CPU), and th = min(h, T), tw = min(w, T), ty, tx."""
+    from . import vae as V
+    ys, xs = V.tile_starts(h, T, O), V.tile_starts(w, T, O)
+    if max(len(ys), len(xs)) > WINDOW_MAX_TILES:
+        raise ValueError(f"window_tables: {len(ys)} x {len(xs)} windows of {T} for a {h} x {w} latent (at most {WINDOW_MAX_TILES} per axis)")
+    tabs = (torch.tensor(ys, dtype=torch.int32), torch.tensor(xs, dtype=torch.int32), torch.stack(V.tile_weights(h, T, O, 1)), torch.stack(V.tile_weights(w, T, O, 1)))
+    if device is not None:
+        tabs = tuple(t.to(device) for t in tabs)
+    return WindowTables(*tabs, min(int(h), int(T)), min(int(w), int(T)), len(ys), len(xs))
+
+
+def _window_params(tabs, n, H, W, weights):
+    _chk2(tabs.ys, torch.int32), _chk2(tabs.xs, torch.int32)
+    assert tuple(tabs.ys.shape) == (tabs.ty,) and tuple(tabs.xs.shape) == (tabs.tx,) and tabs.ys.is_contiguous() and tabs.xs.is_contiguous(), "ys [ty], xs [tx]"
+    if weights:
+        _chk2(tabs.wy, F32), _chk2(tabs.wx, F32)
+        assert tuple(tabs.wy.shape) == (tabs.ty, tabs.th) and tuple(tabs.wx.shape) == (tabs.tx, tabs.tw) and tabs.wy.is_contiguous() and tabs.wx.is_contiguous(), \
+            "wy [ty, th], wx [tx, tw]"
+    return _lib.WindowParams(ys=tabs.ys.data_ptr(), xs=tabs.xs.data_ptr(), wy=tabs.wy.data_ptr() if weights else None, wx=tabs.wx.data_ptr() if weights else None,
+                             n=int(n), H=int(H), W=int(W), th=tabs.th, tw=tabs.tw, ty=tabs.ty, tx=tabs.tx)
+
+
+def window_gather(tabs, x_full, x_tiles, tf_full, tf_tiles, *, n, H, W):
+    """sdlt_window_gather: the windows of tiled diffusion cut out of the model input.  x_full bf16 [2n H W, ld] (row ((2 j + s) H + y) W + x, as the step
+    launch left it) -> x_tiles bf16 [2n ty tx th tw, ld], batch row b = 2 (j ty tx + iy tx + ix) + s: whole rows, every column; tf_full fp32 [2n] ->
+    tf_tiles fp32 [2n ty tx], each pair's timestep on all of its windows.  tabs: window_tables' (on the device; the weights are not read)."""
+    lib = _lib.load()
+    p = _window_params(tabs, n, H, W, False)
+    _chk2(x_full), _chk2(x_tiles), _chk2(tf_full, F32), _chk2(tf_tiles, F32)
+    B = 2 * n * tabs.ty * tabs.tx
+    assert x_full.dim() == 2 and x_tiles.dim() == 2 and x_full.shape[0] == 2 * n * H * W and x_tiles.shape[0] == B * tabs.th * tabs.tw, \
+        f"x_full {tuple(x_full.shape)} / x_tiles {tuple(x_tiles.shape)} for n={n} H={H} W={W} and {tabs.ty} x {tabs.tx} windows of {tabs.th} x {tabs.tw}"
+    assert _ld(x_full) == _ld(x_tiles) == x_full.shape[1] == x_tiles.shape[1], "whole rows are copied: both sides contiguous with the same width"
+    assert tf_full.numel() >= 2 * n and tf_tiles.numel() >= B and tf_full.is_contiguous() and tf_tiles.is_contiguous()
+    _lib.check(lib.sdlt_window_gather(C.byref(p), _p(x_full), _p(x_tiles), _ld(x_full), _p(tf_full), _p(tf_tiles), _stream()), "sdlt_window_gather")
+    return x_tiles
+
+
+def window_blend(tabs, eps_tiles, eps_full, *, n, H, W):
+    """sdlt_window_blend: the windows' predictions fused into one for the whole latent.  eps_tiles fp32 [2n ty tx th tw, 4] (UNet.forward's output on
+    window_gather's batch) -> eps_full fp32 [2n H W, 4], every row written once: the sum over the windows covering it, iy then ix ascending, of
+    (wy * wx) * v - t = wy wx, u = t v, acc + u, three fp32 roundings per term from +0.0 (tests/tilediff_ref.py: blend32 gives the same bits)."""
+    lib = _lib.load()
+    p = _window_params(tabs, n, H, W, True)
+    _chk2(eps_tiles, F32), _chk2(eps_full, F32)
+    assert eps_tiles.is_contiguous() and tuple(eps_tiles.shape) == (2 * n * tabs.ty * tabs.tx * tabs.th * tabs.tw, 4), tuple(eps_tiles.shape)
+    assert eps_full.is_contiguous() and tuple(eps_full.shape) == (2 * n * H * W, 4), tuple(eps_full.shape)
+    _lib.check(lib.sdlt_window_blend(C.byref(p), _p(eps_tiles), _p(eps_full), _stream()), "sdlt_window_blend")
+    return eps_full
 
 
 def masked_mse_fwd_bwd(pred, noise, noisy, mask, timesteps, alphas_cumprod, sums, loss_out, dpred, *, snr_gamma, v_prediction=False,

@@ -10,7 +10,7 @@ scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-squ
                                          [--hires-scale F | --hires-size W H] [--hires-strength F] [--hires-steps N] [--hires-upscaler latent|pixel]
                                          [--hires-resample nearest|bilinear|bicubic] [--heatmap [WORD ...]] [--heatmap-grid max|min]
                                          [--kv-downsample F [F2 ...]] [--kv-downsample-mode nearest|area] [--kv-downsample-pass hires|all]
-                                         [--vae-tile [T]] [--vae-tile-overlap O]
+                                         [--vae-tile [T]] [--vae-tile-overlap O] [--tile-diffusion [T]] [--tile-diffusion-overlap O]
                                          [--unet F] [--text-encoder F] [--text-encoder-2 F] [--vae F] [--tokenizer DIR]
 
 DIR is a checkpoint directory of train(): training_args.json (the job's TrainingConfig), adapter_config.json + the kohya adapter file
@@ -81,6 +81,13 @@ vae.VaeEncoder.encode_moments_tiled): the decode of every picture, the decode an
 VAE's mid-block attention materialises a [pixels, pixels] score matrix - 17 GB at 2048 px, beyond the card at 4096 px - and with tiles it always runs at
 the one tile shape, so the decoder is built once and a hires render rebuilds only the UNet.  GroupNorm statistics are per tile: a tiled picture differs
 slightly from an untiled one.  Without the flag nothing changes.
+
+--tile-diffusion [T] (MultiDiffusion, Bar-Tal et al. 2023; "Tiled Diffusion" of A1111 / ComfyUI) is the UNet's counterpart: in every pass whose latent
+exceeds T x T latent units (default: the job's resolution // 8) the UNet runs on overlapping T x T windows - neighbours share at least
+--tile-diffusion-overlap O, default T // 4 - as one batch, cut out of the model input by sdlt_window_gather and fused into one prediction for the whole
+latent by sdlt_window_blend at every step; guidance and the step launch run on the whole latent as before (sampler.LatentSampler.sample(tile=)).  One
+UNet shape at any picture size, attention cost linear in the picture's area, every window at the size the adapters were trained at.  A pass that fits one
+window - the first pass of a hires render at the model's size - stays plain.  Not with --heatmap.  Without the flag nothing changes.
 """
 import argparse
 import json
@@ -104,7 +111,7 @@ class Loaded:
     def __init__(self, config, models, stack, checkpoint_dir, lora, te_lora, embeddings):
         self.config, self.models, self.stack, self.checkpoint_dir = config, models, stack, checkpoint_dir
         self.lora, self.te_lora, self.embeddings = lora, te_lora, embeddings
-        self.shape = None                       # (images per batch, h, w) the UNet's buffers were allocated for
+        self.shape = None                       # (images per batch, h, w) the UNet's buffers were allocated for; tiled diffusion: (images, th, tw, ty, tx)
         self.dec_shape = None                   # (h, w) the VAE decoder's buffers were allocated for: the latent's, or the tile's of a tiled decode
 
     def load_adapters(self):
@@ -112,19 +119,23 @@ class Loaded:
         if self.lora is not None:
             self.stack.unet.arena.load(self.lora)
 
-    def prepare(self, n_images, h, w, keep_decoder=False):
+    def prepare(self, n_images, h, w, keep_decoder=False, plan=None):
         """The UNet's activation buffers belong to the first latent shape it runs: another batch or size starts from fresh instances.  keep_decoder: the
-        VAE decoder is not rebuilt with them (a tiled decode runs at the tile's shape whatever the picture's: prepare_decoder)."""
-        if self.shape is not None and self.shape != (n_images, h, w) or n_images != self.stack.n_images:
+        VAE decoder is not rebuilt with them (a tiled decode runs at the tile's shape whatever the picture's: prepare_decoder).  plan (a
+        sampler.TilePlan): tiled diffusion - the UNet runs at the window's shape on 2 n_images ty tx rows whatever the picture's size, so the shape
+        is the windows' extents and counts: another picture size with the same ones keeps the instances."""
+        shape = (n_images, h, w) if plan is None else (n_images,) + tuple(plan[2:])
+        tiles = 1 if plan is None else plan.ty * plan.tx
+        if self.shape is not None and self.shape != shape or n_images != self.stack.n_images or tiles != getattr(self.stack, "tiles", 1):
             self.stack.keep_decoder = keep_decoder
             try:
-                self.stack.build_sampler(n_images)
+                self.stack.build_sampler(n_images, **({} if tiles == 1 else dict(tiles=tiles)))
             finally:
                 self.stack.keep_decoder = False
             if not keep_decoder:
                 self.dec_shape = None
             self.load_adapters()
-        self.shape = (n_images, h, w)
+        self.shape = shape
 
     def prepare_decoder(self, h, w):
         """The decoder's buffers belong to the first latent shape it decodes, (h, w): another shape starts from a fresh decoder (the UNet stays)."""
@@ -261,6 +272,14 @@ def vae_tile_args(vae_tile):
     return int(tile), int(overlap)
 
 
+TILE_DIFFUSION_JOB = object()      # --tile-diffusion without a value: no number a user can type
+
+
+def tile_diffusion_default(config):
+    """--tile-diffusion without a value: the job's training resolution in latent units (the size its adapters were trained at)."""
+    return int(config.resolution) // 8
+
+
 @torch.no_grad()
 def encode_image(loaded, img, enc=None, vae_tile=None):
     """img [1, 3, H, W] fp32 in about [-1, 1] -> init latents [1, 4, H/f, W/f] fp32: the posterior's mean times the scaling factor (deterministic).
@@ -361,7 +380,7 @@ def hires_args(hires, size, steps, f=8):
 def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, guidance_scale=8.0, seed=None, images_per_batch=1, token_scale=None,
            graph=True, n_validation=4, init_image=None, strength=None, mask_image=None, sampler="euler", sigmas="trailing", eta=None,
            guidance_rescale=0.0, guidance_interval=None, negative_prompt=None, hires=None, freeu=None, heatmap=None, heatmap_grid="max",
-           kv_downsample=None, kv_downsample_mode="nearest", kv_downsample_pass="hires", vae_tile=None, change_map_image=None, mask_blur=None):
+           kv_downsample=None, kv_downsample_mode="nearest", kv_downsample_pass="hires", vae_tile=None, change_map_image=None, mask_blur=None, tile_diffusion=None):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
     seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
@@ -391,6 +410,9 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     change_map_image (path or PIL image; needs init_image, excludes mask_image and hires): differential diffusion - its luminance, area-resized to the
     latent grid (dataset.latent_change_map), is LatentSampler.sample's change_map: white the whole `strength`, black keep.  mask_blur (a sigma in latent
     pixels, >= 0): the change map - or mask_image's mask, which then takes the blend path as before - is blurred on the device first (sampler.blur_map).
+    tile_diffusion: None, a window length T or (T, overlap) in latent units (sampler.tile_plan; the overlap defaults to T // 4): tiled diffusion -
+    LatentSampler.sample's `tile` - in every pass whose latent exceeds T on an axis: the UNet then runs at the window's shape on 2 images_per_batch ty tx
+    rows.  A pass that fits one window - the first pass of a hires render at the model's size - stays plain.  Not with heatmap.
     -> {scale: [paths]}."""
     from . import train as T
     from . import vae as _vae
@@ -462,6 +484,14 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     vt = vae_tile_args(vae_tile)                                     # (raises before anything is built)
     if vt is not None and not hasattr(stack.rt.ops, "tile_blend"):
         raise NotImplementedError("this op table has no tile_blend kernel (sdlt_tile_blend): vae_tile puts the VAE's tiles together by that launch (ops.tile_blend)")
+    td_plan = SM.tile_plan(h, w, tile_diffusion)                     # (raises before anything is built)
+    td_plan2 = None
+    if tile_diffusion is not None:
+        if heatmap is not None:
+            raise ValueError("heatmap does not combine with tile_diffusion: the hooked score sums are per window, and stitching them is not built")
+        if not hasattr(stack.rt.ops, "window_blend"):
+            raise NotImplementedError("this op table has no window_blend kernel (sdlt_window_blend): tile_diffusion cuts and fuses the windows by two "
+                                      "launches (ops.window_gather, ops.window_blend)")
     if init_image is None and (change_map_image is not None or mask_blur is not None):
         raise ValueError("change_map_image and mask_blur need init_image: the pixels to keep are taken from it")
     if change_map_image is not None and mask_image is not None:
@@ -480,6 +510,11 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         if mask_image is not None:
             raise ValueError("hires does not combine with mask_image: the mask would need a resize of its own")
         hi = hires_args(hires, size, steps, f)                         # (raises before anything is built)
+        td_plan2 = SM.tile_plan(hi["size"][1] // f, hi["size"][0] // f, tile_diffusion)
+    for pl in (td_plan, td_plan2):
+        m = 1 if pl is None else SM.grid_multiple(cfg)
+        if pl is not None and (pl.th % m or pl.tw % m):
+            raise ValueError(f"tile_diffusion: a {pl.th} x {pl.tw} window is no multiple of {m} on both axes, which this UNet's downsampling needs")
     img_kw = {}
     if guidance_rescale != 0.0:
         img_kw.update(guidance_rescale=guidance_rescale)
@@ -509,7 +544,9 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             from . import dataset as D
             cmap = D.latent_change_map(_open(change_map_image), size, (h, w)).to(dev)
             img_kw.update(change_map=SM.blur_map(stack.rt.ops, cmap, mask_blur or 0.0))
-    loaded.prepare(n, h, w, **({} if vt is None else dict(keep_decoder=True)))
+    td_kw = lambda pl: {} if pl is None else dict(plan=pl)  # noqa: E731
+    tile_kw = lambda pl: {} if pl is None else dict(tile=(pl.T, pl.O))  # noqa: E731
+    loaded.prepare(n, h, w, **({} if vt is None else dict(keep_decoder=True)), **td_kw(td_plan))
     fused = hasattr(stack.rt.ops, "sampler_step_dd" if change_map_image is not None else "sampler_step_sde" if sde else "sampler_step_ms" if sampler == "dpmpp_2m"
                     else "sampler_step")
     graph = graph and dev.type == "cuda"
@@ -589,7 +626,7 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
                 idx = [min(s0 + j, len(prompts) - 1) for j in range(n)]          # a short last batch repeats its last prompt
                 gens = [torch.Generator(device=dev).manual_seed(seed + i) for i in idx]
                 noise = torch.cat([torch.randn(1, 4, h, w, generator=g, device=dev) for g in gens])
-                lat = sample(embeds, idx, h, w, size, noise, img_kw, seed, heat=hm_cols is not None and hi is None)
+                lat = sample(embeds, idx, h, w, size, noise, dict(img_kw, **tile_kw(td_plan)), seed, heat=hm_cols is not None and hi is None)
                 if hi is None:
                     save(lat, idx, s0, scale, paths)
                 else:                                                            # each generator's second draw: the second pass's noise
@@ -600,13 +637,13 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         if hi is not None:
             del enc
             # the one rebuild: the UNet's (and the decoder's) buffers belong to the first shape they ran; a tiled decoder runs at the tile's shape and stays
-            loaded.prepare(n, h2, w2, **({} if vt is None else dict(keep_decoder=True)))
+            loaded.prepare(n, h2, w2, **({} if vt is None else dict(keep_decoder=True)), **td_kw(td_plan2))
             for k, scale in enumerate(lora_scales):
                 stack.sampler.set_lora_scale(scale)
                 paths = []
                 for k1, embeds, s0, idx, x0, noise2 in second:
                     if k1 == k:
-                        lat = sample(embeds, idx, h2, w2, hi["size"], noise2, dict(kw2, init_latents=x0, strength=hi["strength"]), seed + 2 ** 32, hi["steps"],
+                        lat = sample(embeds, idx, h2, w2, hi["size"], noise2, dict(kw2, init_latents=x0, strength=hi["strength"], **tile_kw(td_plan2)), seed + 2 ** 32, hi["steps"],
                                      heat=hm_cols is not None)
                         save(lat, idx, s0, scale, paths)
                 finish(scale, paths)
@@ -640,6 +677,10 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             meta.update(heatmap=dict(maps=hm_names, grid=heatmap_grid, positions=hm_cols.tolist()))
         if vt is not None:
             meta.update(vae_tile=dict(tile=vt[0], overlap=vt[1]))
+        if tile_diffusion is not None:                  # (tiles: of the last pass; [1, 1]: every pass fitted one window and ran plain)
+            T_, O_ = (tile_diffusion, tile_diffusion // 4) if isinstance(tile_diffusion, int) else tile_diffusion
+            pl = td_plan2 if hi is not None else td_plan
+            meta.update(tile_diffusion=dict(tile=T_, overlap=O_, tiles=[1, 1] if pl is None else [pl.ty, pl.tx]))
         json.dump(meta, fh, indent=2)
     return result
 
@@ -696,6 +737,11 @@ def main(argv=None, runtime=None):
                     "and one decoder shape at any picture size")
     ap.add_argument("--vae-tile-overlap", type=int, default=None, metavar="O",
                     help=f"with --vae-tile: least overlap of neighbouring tiles in latent units, 0 <= 2 O <= T (default {VAE_TILE_OVERLAP})")
+    ap.add_argument("--tile-diffusion", type=int, nargs="?", const=TILE_DIFFUSION_JOB, default=None, metavar="T",
+                    help="tiled diffusion (MultiDiffusion): where a pass's latent exceeds T x T latent units the UNet runs on overlapping T x T windows, fused "
+                    "on the device at every step - one UNet shape at any picture size (default T: the job's resolution // 8)")
+    ap.add_argument("--tile-diffusion-overlap", type=int, default=None, metavar="O",
+                    help="with --tile-diffusion: least overlap of neighbouring windows in latent units, 0 <= 2 O <= T (default T // 4)")
     ap.add_argument("--device", default="cuda:0")
     for flag, key, what in (("--unet", "path", "base UNet weights or synthetic:<version>"), ("--text-encoder", "text_encoder_path", "text encoder state dict"),
                             ("--text-encoder-2", "text_encoder_2_path", "SDXL's second text encoder"), ("--vae", "vae_path", "AutoencoderKL state dict"),
@@ -748,6 +794,16 @@ def main(argv=None, runtime=None):
             vae_tile_args(vtile["vae_tile"])
         except ValueError as e:
             ap.error(f"--vae-tile / --vae-tile-overlap: {e}")
+    if a.tile_diffusion is None and a.tile_diffusion_overlap is not None:
+        ap.error("--tile-diffusion-overlap needs --tile-diffusion [T]")
+    if a.tile_diffusion is not None and a.tile_diffusion is not TILE_DIFFUSION_JOB:
+        from . import sampler as SM
+        try:                                            # (without T the overlap is checked by render(), once the job's T is known)
+            SM.tile_plan(1, 1, (a.tile_diffusion, a.tile_diffusion // 4 if a.tile_diffusion_overlap is None else a.tile_diffusion_overlap))
+        except ValueError as e:
+            ap.error(f"--tile-diffusion / --tile-diffusion-overlap: {e}")
+    if a.tile_diffusion is not None and a.heatmap is not None:
+        ap.error("--tile-diffusion does not combine with --heatmap")
     freeu = None if a.freeu is None else dict(zip(("b1", "b2", "s1", "s2"), a.freeu), version=2 if a.freeu_v2 else 1)
     hires = None
     if a.hires_scale is not None and a.hires_size is not None:
@@ -772,11 +828,15 @@ def main(argv=None, runtime=None):
         with open(os.path.join(a.checkpoint, "training_args.json")) as f:
             pm = dict(json.load(f).get("pretrained_model") or {}, **over)
     loaded = load_for_inference(a.checkpoint, pm, device=a.device, runtime=runtime)
+    tdiff = {}
+    if a.tile_diffusion is not None:                    # T defaults to the job's training resolution in latent units
+        T_ = tile_diffusion_default(loaded.config) if a.tile_diffusion is TILE_DIFFUSION_JOB else a.tile_diffusion
+        tdiff = dict(tile_diffusion=(T_, T_ // 4 if a.tile_diffusion_overlap is None else a.tile_diffusion_overlap))
     res = render(loaded, a.prompt, a.out, lora_scales=a.lora_scale, size=a.size, steps=a.steps, guidance_scale=a.guidance, seed=a.seed,
                  images_per_batch=a.images_per_batch, graph=not a.eager, n_validation=a.n_validation, init_image=a.init_image, strength=a.strength,
                  mask_image=a.mask, sampler=a.sampler, sigmas=a.sigmas, eta=a.eta, guidance_rescale=a.guidance_rescale,
                  guidance_interval=a.guidance_interval, negative_prompt=a.negative_prompt, **({} if hires is None else dict(hires=hires)),
-                 **({} if freeu is None else dict(freeu=freeu)), **kvd, **vtile,
+                 **({} if freeu is None else dict(freeu=freeu)), **kvd, **vtile, **tdiff,
                  **({} if a.change_map is None else dict(change_map_image=a.change_map)), **({} if a.mask_blur is None else dict(mask_blur=a.mask_blur)),
                  **({} if a.heatmap is None else dict(heatmap=a.heatmap, heatmap_grid=a.heatmap_grid or "max")))
     for scale, paths in res.items():

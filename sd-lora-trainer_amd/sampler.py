@@ -449,6 +449,37 @@ def freeu_args(freeu):
     return dict(b1=float(vals[0]), b2=float(vals[1]), s1=float(vals[2]), s2=float(vals[3]), version=int(version))
 
 
+TilePlan = collections.namedtuple("TilePlan", "T O th tw ty tx")
+
+
+def tile_plan(h, w, tile):
+    """sample()'s / render()'s `tile` for an h x w latent, checked -> None | TilePlan(T, O, th, tw, ty, tx).  tile: None (off), T, or (T, O): windows of
+    T x T latent units whose neighbours overlap by at least O (default T // 4; vae.tile_starts).  None as well where h <= T and w <= T: a pass that fits
+    in one window is the plain path.  Otherwise ty x tx windows of th = min(h, T) by tw = min(w, T).  T >= 2 and 0 <= 2 O <= T, or ValueError."""
+    if tile is None:
+        return None
+    ok_int = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
+    if not (ok_int(tile) or (isinstance(tile, (tuple, list)) and len(tile) == 2 and all(ok_int(v) for v in tile))):
+        raise ValueError(f"tile must be None, a window length or (window, overlap) in latent units, got {tile!r}")
+    T, O = (tile, tile // 4) if ok_int(tile) else tile
+    if T < 2 or O < 0 or 2 * O > T:
+        raise ValueError(f"tiled diffusion needs a window length >= 2 and an overlap with 0 <= 2 * overlap <= window, got window={T} overlap={O}")
+    if h < 1 or w < 1:
+        raise ValueError(f"tile_plan: a {h} x {w} latent")
+    if h <= T and w <= T:
+        return None
+    from .vae import tile_starts
+    ty, tx = len(tile_starts(h, T, O)), len(tile_starts(w, T, O))
+    if max(ty, tx) > 64:
+        raise ValueError(f"tiled diffusion: {ty} x {tx} windows of {T} for a {h} x {w} latent (at most 64 per axis: a larger window)")
+    return TilePlan(T, O, min(h, T), min(w, T), ty, tx)
+
+
+def grid_multiple(cfg):
+    """What both axes of a latent grid the UNet runs at must be a multiple of: every downsampler halves it, every upsampler doubles it back."""
+    return 2 ** (len(cfg["block_out_channels"]) - 1)
+
+
 HEAT_GRIDS = ("max", "min")
 
 
@@ -569,12 +600,16 @@ class LatentSampler:
     reference's render loop, up to the latents.  `unet` is an inference instance built for batch 2 (negative | positive, the
     order diffusers concatenates them in); its LoRA arena holds the trained adapters."""
 
-    def __init__(self, rt, unet, prediction_type="epsilon", kv_downsample=None, kv_downsample_mode="nearest"):
-        """kv_downsample / kv_downsample_mode: the default of sample()'s keywords of the same names (kv_downsample_args)."""
+    def __init__(self, rt, unet, prediction_type="epsilon", kv_downsample=None, kv_downsample_mode="nearest", n_images=None):
+        """kv_downsample / kv_downsample_mode: the default of sample()'s keywords of the same names (kv_downsample_args).  n_images: the images sampled
+        together where the runtime's batch is 2 n_images ty tx - a sampler for tiled diffusion (sample(tile=)) with ty tx windows per image; None:
+        rt.B // 2, no windows."""
         self.kv_downsample = kv_downsample_args(kv_downsample, kv_downsample_mode)
         assert rt.B >= 2 and rt.B % 2 == 0, "classifier-free guidance runs the negative and the positive prompt of every image as one pair: an even batch"
         self.rt, self.unet = rt, unet
-        self.n = rt.B // 2                 # images sampled together (fused / graph path); image j = rows 2j (negative), 2j + 1 (positive)
+        self.n = rt.B // 2 if n_images is None else n_images      # images sampled together; image j = rows 2j (negative), 2j + 1 (positive)
+        assert self.n >= 1 and rt.B % (2 * self.n) == 0, f"a batch of {rt.B} does not hold the pairs of {self.n} image(s) times a whole number of windows"
+        self.tiles = rt.B // (2 * self.n)  # windows per image of the UNet batch (1: the UNet runs on the whole latent)
         self.sched = EulerDiscrete(prediction_type=prediction_type)
         self.sched_ms = DpmSolverPP2M(prediction_type=prediction_type)
         self.sched_sde = dict(euler_a=EulerAncestral(prediction_type=prediction_type), dpmpp_2m_sde=DpmSolverPP2MSDE(prediction_type=prediction_type))
@@ -608,7 +643,7 @@ class LatentSampler:
     @torch.no_grad()
     def sample(self, embeds, h, w, *, steps=25, guidance_scale=8.0, generator=None, size=None, latents=None, graph=False, fused=False, n_images=1,
                init_latents=None, strength=1.0, mask=None, sampler="euler", sigmas="trailing", eta=1.0, seeds=None, guidance_rescale=0.0,
-               guidance_interval=None, freeu=None, heatmap=None, kv_downsample=None, kv_downsample_mode=None, change_map=None):
+               guidance_interval=None, freeu=None, heatmap=None, kv_downsample=None, kv_downsample_mode=None, change_map=None, tile=None):
         """embeds = (c [1,77,D], uc [1,77,D], pc [1,P] | None, puc | None); h, w latent size.  Returns latents [1,4,h,w] fp32
         (still multiplied by the VAE scaling factor, as the pipeline holds them before `vae.decode(latents / scaling_factor)`).
         fused: guidance, the Euler update and the next model input are ONE kernel between two forwards (ops.sampler_step) instead of torch
@@ -647,7 +682,30 @@ class LatentSampler:
         the steps that run and then releases it (hold_map): a SELECT after every step, never a mix.  With every sampler on all three paths; fused /
         graph: the step launch is ops.sampler_step_dd, whose captures are keyed apart from all others, and the hold map lives in a persistent buffer
         refilled per call, so one capture serves every map, strength and step count.  A map of ones gives the bits of the call without it at
-        strength < 1; at strength 1 the trajectory starts from init_latents + noise * sigma_0 (without a map: from the noise alone)."""
+        strength < 1; at strength 1 the trajectory starts from init_latents + noise * sigma_0 (without a map: from the noise alone).
+        tile: None, T or (T, O) in latent units (tile_plan; O defaults to T // 4): tiled diffusion (MultiDiffusion, Bar-Tal et al. 2023).  Where the
+        latent exceeds T on an axis the UNet runs on ty x tx overlapping windows of min(h, T) x min(w, T) as ONE batch of 2 n_images ty tx rows - the
+        sampler is built on a runtime of that batch (LatentSampler(n_images=)) - between two launches: ops.window_gather cuts the windows out of the
+        model input, ops.window_blend fuses their predictions with normalised feather weights into one prediction for the whole latent.  Guidance, the
+        step launch, init latents, mask, change map and the per-step noise stay at full size and unchanged: every step is affine in the prediction, so
+        stepping once on the fused prediction equals stepping every window and averaging.  Every window row of an image carries that image's
+        conditioning (SDXL: the whole picture's size).  On all three paths, with every sampler; freeu and kv_downsample act per window.  Starts and
+        weights are device memory: one capture per (shape, window counts) serves every overlap.  A latent that fits one window (h <= T and w <= T) is the
+        plain path: the same launches and bits as without `tile`.  Not with heatmap (the hooked score sums are per window)."""
+        plan = tile_plan(h, w, tile)                        # refused before anything is built
+        if plan is not None:
+            if heatmap is not None:
+                raise ValueError("heatmap does not combine with tile: the hooked score sums are per window, and stitching them is not built")
+            m = grid_multiple(self.unet.cfg)
+            if plan.th % m or plan.tw % m:
+                raise ValueError(f"tile: a {plan.th} x {plan.tw} window is no multiple of {m} on both axes, which this UNet's downsampling needs "
+                                 "(the rule the latent size itself obeys without windows)")
+            if not (hasattr(self.rt.ops, "window_blend") and hasattr(self.rt.ops, "window_gather")):
+                raise NotImplementedError("this op table has no window_blend kernel (sdlt_window_blend): sample(tile=...) cuts and fuses the windows by "
+                                          "two launches (ops.window_gather, ops.window_blend), in the torch loop too")
+        if (1 if plan is None else plan.ty * plan.tx) != self.tiles:
+            raise ValueError(f"this sampler's runtime holds {self.tiles} window(s) per image (batch {self.rt.B}, {self.n} image(s)); the call needs "
+                             f"{1 if plan is None else plan.ty * plan.tx}: build it on a runtime of batch 2 n_images ty tx (LatentSampler(n_images=))")
         if change_map is not None:                         # refused before anything is built
             if init_latents is None:
                 raise ValueError("change_map needs init_latents: a held pixel follows their noised trajectory")
@@ -681,8 +739,8 @@ class LatentSampler:
                                       "by that launch (ops.guidance), in the torch loop too")
         if graph or fused:
             return self._sample_fused(embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img, sampler, sigmas, eta, seeds, guide,
-                                      heatmap, hold)
-        assert n_images == 1 and self.rt.B == 2, "the torch loop samples one image on a batch-2 runtime; several images together: fused=True or graph=True"
+                                      heatmap, hold, plan)
+        assert n_images == 1 and self.n == 1, "the torch loop samples one image on a batch-2 runtime; several images together: fused=True or graph=True"
         rt, u, cfg = self.rt, self.unet, self.unet.cfg
         dev = rt.device
         sde = sampler in SDE_KINDS
@@ -690,15 +748,15 @@ class LatentSampler:
             raise NotImplementedError(f"this op table has no sampler_step_sde kernel: sample(sampler={sampler!r}) takes its per-step noise from that kernel's "
                                       "generator (ops.sampler_noise), in the torch loop too")
         c, uc, pc, puc = (tuple(embeds) + (None, None))[:4]
-        cv = self.ctx.view(2, CTX_PAD, -1)
-        cv[0, :77].copy_(uc[0])
-        cv[1, :77].copy_(c[0])
+        cv = self.ctx.view(rt.B, CTX_PAD, -1)               # (with windows: every window row of the pair carries the image's conditioning)
+        cv[0::2, :77].copy_(uc[0])
+        cv[1::2, :77].copy_(c[0])
         tid = None
         if cfg["addition"]:
-            self.pooled[0].copy_(puc[0])
-            self.pooled[1].copy_(pc[0])
+            self.pooled[0::2].copy_(puc[0])
+            self.pooled[1::2].copy_(pc[0])
             H, W = size if size is not None else (8 * h, 8 * w)
-            tid = torch.tensor([float(H), float(W), 0.0, 0.0, float(H), float(W)] * 2, device=dev)   # original_size, crop, target_size
+            tid = torch.tensor([float(H), float(W), 0.0, 0.0, float(H), float(W)] * rt.B, device=dev)   # original_size, crop, target_size
         x0, m, start = img if img is not None else (None, None, 0)
         s = self._scheduler(sampler, steps, start, sigmas, eta, exact=guide is not None)
         x = latents if latents is not None else torch.randn(1, 4, h, w, generator=generator, device=dev, dtype=F32)
@@ -715,11 +773,15 @@ class LatentSampler:
             hm = heatmap_args(heatmap, 1, len(s.timesteps))
             hcols, hw_, hctr, heat = hm["cols"].to(dev), hm["weights"].to(dev), torch.zeros(2, dtype=torch.int32, device=dev), None
         x64 = rt.zeros(2 * h * w, 64)
+        win = None if plan is None else self._window_state(dict(), h, w, plan)
         for i, t in enumerate(s.timesteps):
             xin = s.scale_model_input(x, i)
             x64[:, :4] = xin.permute(0, 2, 3, 1).reshape(h * w, 4).repeat(2, 1).to(x64.dtype)
             tf = torch.full((2,), float(t), device=dev, dtype=F32)
-            eps = u.forward(x64, tf, self.ctx, self.pooled, tid, B=2, H=h, W=w, **self._fwd_kw())
+            if win is None:
+                eps = u.forward(x64, tf, self.ctx, self.pooled, tid, B=2, H=h, W=w, **self._fwd_kw())
+            else:
+                eps = self._window_forward(win, x64, tf, tid, h, w)
             if hm is not None:
                 ents = heat_entries(rt, h, w)
                 if heat is None:
@@ -798,15 +860,44 @@ class LatentSampler:
             return contextlib.nullcontext()
         return own(id(self))
 
-    def _state(self, h, w):
+    def _state(self, h, w, plan=None):
+        """plan (a TilePlan): the shape's state is keyed by the window extents and counts as well, and holds the windows' buffers (_window_state)."""
         rt, n = self.rt, self.n
-        if self._fused is None:
-            self._fused = dict(tf=rt.zeros(2 * n, dtype=F32), tid=rt.zeros(2 * n * 6, dtype=F32), table=rt.zeros(TABLE_ROWS, 4, dtype=F32),
+        if self._fused is None:      # (tid: one row of six per UNET batch row - 2 n without windows)
+            self._fused = dict(tf=rt.zeros(2 * n, dtype=F32), tid=rt.zeros(rt.B * 6, dtype=F32), table=rt.zeros(TABLE_ROWS, 4, dtype=F32),
                                ctr=torch.zeros(2, dtype=torch.int32, device=rt.device), shapes={})
         st = self._fused
-        if (h, w) not in st["shapes"]:
-            st["shapes"][(h, w)] = dict(x=rt.zeros(n, 4, h, w, dtype=F32), x64=rt.zeros(2 * n * h * w, 64))
-        return st, st["shapes"][(h, w)]
+        key = (h, w) if plan is None else (h, w) + tuple(plan[2:])
+        if key not in st["shapes"]:
+            st["shapes"][key] = dict(x=rt.zeros(n, 4, h, w, dtype=F32), x64=rt.zeros(2 * n * h * w, 64))
+        if plan is not None:
+            self._window_state(st["shapes"][key], h, w, plan)
+        return st, st["shapes"][key]
+
+    def _window_state(self, sh, h, w, plan):
+        """-> sh["win"]: the persistent buffers of tiled diffusion for this shape - the windows' model input x64_tiles and timesteps tf_tiles, the fused
+        prediction eps_full fp32 [2 n h w, 4], and the tables (ops.window_tables) - allocated once (a captured launch holds their pointers); starts and
+        weights are rewritten per call: another overlap with the same window counts is the same buffers and the same capture."""
+        rt, n, ops = self.rt, self.n, self.rt.ops
+        fresh = ops.window_tables(h, w, plan.T, plan.O)
+        assert (fresh.th, fresh.tw, fresh.ty, fresh.tx) == tuple(plan[2:])
+        win = sh.get("win")
+        if win is None:
+            tabs = fresh._replace(**{k: torch.zeros_like(getattr(fresh, k), device=rt.device) for k in ("ys", "xs", "wy", "wx")})
+            win = sh["win"] = dict(plan=plan, tabs=tabs, x64_tiles=rt.zeros(rt.B * plan.th * plan.tw, 64), tf_tiles=rt.zeros(rt.B, dtype=F32),
+                                   eps_full=rt.zeros(2 * n * h * w, 4, dtype=F32))
+        for k in ("ys", "xs", "wy", "wx"):
+            getattr(win["tabs"], k).copy_(getattr(fresh, k))
+        win["plan"] = plan
+        return win
+
+    def _window_forward(self, win, x64, tf, tid, h, w):
+        """The forward of tiled diffusion: cut the windows out of the model input, run the UNet on them as one batch, fuse their predictions ->
+        eps fp32 [2 n h w, 4], the prediction for the whole latent (what the forward returns without windows)."""
+        rt, plan = self.rt, win["plan"]
+        rt.ops.window_gather(win["tabs"], x64, win["x64_tiles"], tf, win["tf_tiles"], n=self.n, H=h, W=w)
+        e = self.unet.forward(win["x64_tiles"], win["tf_tiles"], self.ctx, self.pooled, tid, B=rt.B, H=plan.th, W=plan.tw, **self._fwd_kw())
+        return rt.ops.window_blend(win["tabs"], e, win["eps_full"], n=self.n, H=h, W=w)
 
     def _load_image_state(self, sh, h, w, img, noise, hold=None):
         """-> (x0, noise, masked) of the init launch.  hold (a change map's hold map): copied into its persistent buffer beside them.  From init latents: x0, the noise and the mask are copied into the persistent buffers of the shape
@@ -846,7 +937,11 @@ class LatentSampler:
         launch is the same.  heat (a dict of sh["heat"]): ops.heatmap_accum reads the forward's score sums first, with the weight of row ctr[0] of
         st["hw"]; its maps are allocated at the first iteration (the eager warm-up of a capture), when the forward has told the resolutions."""
         u = self.unet
-        eps = u.forward(sh["x64"], st["tf"], self.ctx, self.pooled, st["tid"] if u.cfg["addition"] else None, B=2 * self.n, H=h, W=w, **self._fwd_kw())
+        tid = st["tid"] if u.cfg["addition"] else None
+        if "win" in sh:                                   # tiled diffusion: gather, the forward on the windows, blend (sh is the state of a tile plan)
+            eps = self._window_forward(sh["win"], sh["x64"], st["tf"], tid, h, w)
+        else:
+            eps = u.forward(sh["x64"], st["tf"], self.ctx, self.pooled, tid, B=2 * self.n, H=h, W=w, **self._fwd_kw())
         if heat is not None:
             ents = heat_entries(self.rt, h, w)
             if heat["heat"] is None:
@@ -880,6 +975,8 @@ class LatentSampler:
         kd = getattr(self.unet, "_kv_ds", None)
         if kd is not None:                                # key / value downsampling changes the launch sequence: a capture per (factors, mode)
             key += (("kv_downsample",) + kd,)
+        if "win" in sh:                                   # tiled diffusion: the window extents and counts; starts and weights are device memory
+            key += (("tile",) + tuple(sh["win"]["plan"][2:]),)
         graphs = getattr(self, f.graphs)
         if guided:
             key, graphs = key + (fam,), self._guided_graphs
@@ -915,7 +1012,7 @@ class LatentSampler:
         return g
 
     def _sample_fused(self, embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img=None, sampler="euler", sigmas="trailing",
-                      eta=1.0, seeds=None, guide=None, heatmap=None, hold=None):
+                      eta=1.0, seeds=None, guide=None, heatmap=None, hold=None, plan=None):
         rt, cfg, n = self.rt, self.unet.cfg, self.n
         guided = guide is not None
         if guided:
@@ -935,18 +1032,20 @@ class LatentSampler:
         dev = rt.device
         per_image = [embeds] if (n == 1 and not isinstance(embeds[0], (tuple, list))) else list(embeds)
         assert len(per_image) == n, "one (c, uc[, pc, puc]) per image"
-        cv = self.ctx.view(2 * n, CTX_PAD, -1)
-        st, sh = self._state(h, w)
+        tl = self.tiles                                   # UNet batch rows 2 j tl .. 2 (j + 1) tl - 1 are image j's: (negative, positive) per window
+        cv = self.ctx.view(n, tl, 2, CTX_PAD, -1)
+        st, sh = self._state(h, w, plan)
         for j, e in enumerate(per_image):
             c, uc, pc, puc = (tuple(e) + (None, None))[:4]
-            cv[2 * j, :77].copy_(uc[0])
-            cv[2 * j + 1, :77].copy_(c[0])
+            cv[j, :, 0, :77].copy_(uc[0])
+            cv[j, :, 1, :77].copy_(c[0])
             if cfg["addition"]:
-                self.pooled[2 * j].copy_(puc[0])
-                self.pooled[2 * j + 1].copy_(pc[0])
+                pv = self.pooled.view(n, tl, 2, -1)
+                pv[j, :, 0].copy_(puc[0])
+                pv[j, :, 1].copy_(pc[0])
         if cfg["addition"]:
             H, W = size if size is not None else (8 * h, 8 * w)
-            st["tid"].copy_(torch.tensor([float(H), float(W), 0.0, 0.0, float(H), float(W)] * (2 * n)))
+            st["tid"].copy_(torch.tensor([float(H), float(W), 0.0, 0.0, float(H), float(W)] * rt.B))
         f, start = FAMILIES[fam], 0 if img is None else img[2]
         sch = self._scheduler(sampler, steps, start, sigmas, eta)
         tab = f.table(sch, guidance_scale)

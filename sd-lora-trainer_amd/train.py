@@ -296,23 +296,24 @@ class RenderStack:
         self.text = S.TextStack(self.rt_text, self.encoders, pool_mode="argmax", arena=self.te_arena)
         self.ctx = self.rt_text.zeros(2 * M.CTX_PAD, cfg["cross_dim"])
 
-    def build_sampler(self, n_images):
-        """(Re)build the UNet, its sampler and the VAE decoder for n_images images sampled together.  Their activation buffers are allocated for
+    def build_sampler(self, n_images, tiles=1):
+        """(Re)build the UNet, its sampler and the VAE decoder for n_images images sampled together - with tiled diffusion (sampler.tile_plan) each as
+        `tiles` windows: the runtime's batch is 2 n_images tiles.  Their activation buffers are allocated for
         the first latent shape they run, so a render at another size or batch starts from fresh instances (the caller reloads the adapters).  With
         `keep_decoder` set on the stack an existing decoder stays: a tiled decode runs at the tile's shape, not the picture's (render.Loaded.prepare)."""
         from . import sampler as SM
         from . import unet as M
         config, models = self.config, self.models
         dev = models.rt.device
-        self.n_images = n_images
+        self.n_images, self.tiles = n_images, tiles
         keep = getattr(self, "keep_decoder", False) and getattr(self, "decoder", None) is not None
         self.unet = self.sampler = None
         if not keep:
             self.decoder = None
-        self.rt = M.Runtime(dev, 2 * n_images, ops=models.rt.ops)
+        self.rt = M.Runtime(dev, 2 * n_images * tiles, ops=models.rt.ops)
         kw = dict(lora_rank=config.lora_rank, lora_alpha_multiplier=config.lora_alpha_multiplier, use_dora=config.use_dora) if self.is_lora else {}
         self.unet = M.UNet(self.rt, models.cfg, models.unet_state(), **kw)
-        self.sampler = SM.LatentSampler(self.rt, self.unet)
+        self.sampler = SM.LatentSampler(self.rt, self.unet, **({} if tiles == 1 else dict(n_images=n_images)))
         if not keep:
             self.build_decoder()
 
