@@ -434,17 +434,10 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     w, h = size[0] // f, size[1] // f
     n = images_per_batch
     from . import sampler as SM
-    if sampler not in SM.SAMPLERS:
-        raise ValueError(f"sampler must be one of {SM.SAMPLERS}, got {sampler!r}")
-    if sigmas not in SM.SIGMAS:
-        raise ValueError(f"sigmas must be one of {SM.SIGMAS}, got {sigmas!r}")
-    sde = sampler in SM.SDE_KINDS
-    if eta is not None and not sde:
+    sde, eta_given = sampler in SM.SDE_KINDS, eta is not None
+    eta = SM.sampler_args(sampler, sigmas, eta)                        # (None: 1)
+    if eta_given and not sde:
         raise ValueError(f"eta scales the per-step noise of {SM.SDE_KINDS}; sampler {sampler!r} adds none")
-    if sde:
-        eta = 1.0 if eta is None else eta
-        if not eta >= 0.0:
-            raise ValueError(f"eta must be >= 0, got {eta!r}")
     if not 0.0 <= guidance_rescale <= 1.0:
         raise ValueError(f"guidance_rescale must be in [0, 1], got {guidance_rescale!r}")
     if guidance_interval is not None:
@@ -462,8 +455,7 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             raise ValueError("heatmap: this checkpoint has no trigger tokens (the job did not train any), so there is nothing to map without a word: "
                              "name the prompt's words to look at (--heatmap WORD ...)")
         for op in ("heatmap_accum", "heatmap_overlay"):
-            if not hasattr(stack.rt.ops, op):
-                raise NotImplementedError(f"this op table has no {op} kernel: the heat maps are made by that launch (ops.{op})")
+            SM.require_op(stack.rt.ops, op, f": the heat maps are made by that launch (ops.{op})")
         hm_cols = []
         for p_ in prompts:                                             # positions in the prompt as it is encoded, learned tokens in place
             lora_p = P.prompt_pair(p_, config.token_dict, (config.training_attributes or {}).get("trigger_text", "TOK"), config.name, config.concept_mode,
@@ -478,20 +470,17 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         if kv_downsample_pass == "hires" and hires is None:
             raise ValueError("kv_downsample applies to the second pass of a hires render by default and this render has none: pass "
                              "kv_downsample_pass='all' (--kv-downsample-pass all) to use it in a single-pass render")
-        if not hasattr(stack.rt.ops, "token_pool"):
-            raise NotImplementedError("this op table has no token_pool kernel (sdlt_token_pool): kv_downsample pools the keys' tokens by that launch (ops.token_pool)")
+        SM.require_op(stack.rt.ops, "token_pool", " (sdlt_token_pool): kv_downsample pools the keys' tokens by that launch (ops.token_pool)")
     kd_kw = {} if kd is None else dict(kv_downsample=kd[0], kv_downsample_mode=kd[1])
     vt = vae_tile_args(vae_tile)                                     # (raises before anything is built)
-    if vt is not None and not hasattr(stack.rt.ops, "tile_blend"):
-        raise NotImplementedError("this op table has no tile_blend kernel (sdlt_tile_blend): vae_tile puts the VAE's tiles together by that launch (ops.tile_blend)")
+    if vt is not None:
+        SM.require_op(stack.rt.ops, "tile_blend", " (sdlt_tile_blend): vae_tile puts the VAE's tiles together by that launch (ops.tile_blend)")
     td_plan = SM.tile_plan(h, w, tile_diffusion)                     # (raises before anything is built)
     td_plan2 = None
     if tile_diffusion is not None:
         if heatmap is not None:
             raise ValueError("heatmap does not combine with tile_diffusion: the hooked score sums are per window, and stitching them is not built")
-        if not hasattr(stack.rt.ops, "window_blend"):
-            raise NotImplementedError("this op table has no window_blend kernel (sdlt_window_blend): tile_diffusion cuts and fuses the windows by two "
-                                      "launches (ops.window_gather, ops.window_blend)")
+        SM.require_op(stack.rt.ops, "window_blend", " (sdlt_window_blend): tile_diffusion cuts and fuses the windows by two launches (ops.window_gather, ops.window_blend)")
     if init_image is None and (change_map_image is not None or mask_blur is not None):
         raise ValueError("change_map_image and mask_blur need init_image: the pixels to keep are taken from it")
     if change_map_image is not None and mask_image is not None:
@@ -503,8 +492,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             raise ValueError("mask_blur blurs mask_image's mask or change_map_image's map: give one of them")
         if not (isinstance(mask_blur, (int, float)) and not isinstance(mask_blur, bool) and math.isfinite(mask_blur) and mask_blur >= 0.0):
             raise ValueError(f"mask_blur must be a finite number >= 0 (latent pixels), got {mask_blur!r}")
-        if mask_blur > 0.0 and not hasattr(stack.rt.ops, "blur_planes"):
-            raise NotImplementedError("this op table has no blur_planes kernel: mask_blur blurs the map on the device by that launch (ops.blur_planes)")
+        if mask_blur > 0.0:
+            SM.require_op(stack.rt.ops, "blur_planes", ": mask_blur blurs the map on the device by that launch (ops.blur_planes)")
     hi = None
     if hires is not None:
         if mask_image is not None:
@@ -512,9 +501,7 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         hi = hires_args(hires, size, steps, f)                         # (raises before anything is built)
         td_plan2 = SM.tile_plan(hi["size"][1] // f, hi["size"][0] // f, tile_diffusion)
     for pl in (td_plan, td_plan2):
-        m = 1 if pl is None else SM.grid_multiple(cfg)
-        if pl is not None and (pl.th % m or pl.tw % m):
-            raise ValueError(f"tile_diffusion: a {pl.th} x {pl.tw} window is no multiple of {m} on both axes, which this UNet's downsampling needs")
+        SM.window_multiple(cfg, pl, "tile_diffusion")
     img_kw = {}
     if guidance_rescale != 0.0:
         img_kw.update(guidance_rescale=guidance_rescale)

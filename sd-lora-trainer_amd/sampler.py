@@ -312,6 +312,24 @@ def guidance_table(sched, guidance_scale, guidance_rescale=0.0, guidance_interva
 SAMPLERS = ("euler", "dpmpp_2m", "euler_a", "dpmpp_2m_sde")
 SIGMAS = ("trailing", "karras")
 
+
+def sampler_args(sampler, sigmas, eta):
+    """sample()'s / render()'s `sampler`, `sigmas` and `eta`, checked -> eta (None: 1).  Only the stochastic samplers read eta, so only theirs is checked."""
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
+    if sigmas not in SIGMAS:
+        raise ValueError(f"sigmas must be one of {SIGMAS}, got {sigmas!r}")
+    eta = 1.0 if eta is None else eta
+    if sampler in SDE_KINDS and not eta >= 0.0:
+        raise ValueError(f"eta must be >= 0, got {eta!r}")
+    return eta
+
+
+def require_op(ops, name, text, kernel=None):
+    """A missing kernel is an error, never a fallback: NotImplementedError unless the op table has `name` (kernel: the name the message gives it)."""
+    if not hasattr(ops, name):
+        raise NotImplementedError(f"this op table has no {kernel or name} kernel{text}")
+
 TABLE_ROWS = 2 + 1000      # rows of the device step table: two header rows + at most one step per training timestep
 MAX_GRAPHS = 4             # captured iterations kept per sampler (one per shape and adapter scale)
 
@@ -371,8 +389,7 @@ def blur_map(ops, m, sigma):
         raise ValueError(f"mask_blur must be a finite number >= 0 (latent pixels), got {sigma!r}")
     if sigma == 0.0:
         return m
-    if not hasattr(ops, "blur_planes"):
-        raise NotImplementedError("this op table has no blur_planes kernel: mask_blur blurs the map on the device by that launch (ops.blur_planes)")
+    require_op(ops, "blur_planes", ": mask_blur blurs the map on the device by that launch (ops.blur_planes)")
     m = m.to(F32).contiguous()
     return ops.blur_planes(m, torch.empty_like(m), torch.empty_like(m), ops.blur_taps(sigma).to(m.device), clamp01=True)
 
@@ -405,8 +422,7 @@ def upscale_latents(ops, lat, H, W, mode="bilinear"):
     4 latent channels, or the 3 colours of a decoded picture."""
     if mode not in RESAMPLE:
         raise ValueError(f"resample must be one of {RESAMPLE}, got {mode!r}")
-    if not hasattr(ops, "resize_planes"):
-        raise NotImplementedError("this op table has no resize_planes kernel: the hires pass resamples on the device by that launch (ops.resize_planes)")
+    require_op(ops, "resize_planes", ": the hires pass resamples on the device by that launch (ops.resize_planes)")
     lat = lat.to(F32).contiguous()
     out = torch.empty(lat.shape[0], lat.shape[1], H, W, dtype=F32, device=lat.device)
     return ops.resize_planes(lat, out, RESAMPLE.index(mode))
@@ -480,6 +496,14 @@ def grid_multiple(cfg):
     return 2 ** (len(cfg["block_out_channels"]) - 1)
 
 
+def window_multiple(cfg, plan, name="tile"):
+    """ValueError unless the windows of `plan` (a TilePlan, or None: no windows) obey grid_multiple on both axes; name: the argument the message speaks of."""
+    m = grid_multiple(cfg) if plan is not None else 1
+    if plan is not None and (plan.th % m or plan.tw % m):
+        raise ValueError(f"{name}: a {plan.th} x {plan.tw} window is no multiple of {m} on both axes, which this UNet's downsampling needs"
+                         + (" (the rule the latent size itself obeys without windows)" if name == "tile" else ""))
+
+
 HEAT_GRIDS = ("max", "min")
 
 
@@ -543,20 +567,21 @@ def step_table_ms(sched, guidance_scale):
     """The device table of ops.sampler_step_ms for a DpmSolverPP2M whose set_timesteps(n[, start]) has run: fp32 [2 + k, 8].  Columns 0..3 are
     step_table_img's (row 0 column 1 = the first USED sigma, which is init_noise_sigma when nothing is skipped); a step row continues with
     a_i, b_i, c_i, 0 - ms_coefficients in fp64 from the fp32 sigmas, rounded once.  c = 0.0f exactly on first-order rows."""
-    base = step_table_img(sched, guidance_scale)
-    tab = torch.zeros(base.shape[0], 8, dtype=torch.float32)
-    tab[:, :4] = base
-    tab[2:, 4:7] = torch.from_numpy(ms_coefficients(sched.sigmas).astype(np.float32))
-    return tab
+    return _step_table_wide(sched, guidance_scale, ms_coefficients(sched.sigmas))
 
 
 def step_table_sde(sched, guidance_scale):
     """The device table of ops.sampler_step_sde for an EulerAncestral / DpmSolverPP2MSDE whose set_timesteps(n[, start]) has run: step_table_ms with
     sde_coefficients in columns 4..7 (column 7 = d, zero in step_table_ms: the 8-float row is unchanged), rounded once."""
+    return _step_table_wide(sched, guidance_scale, sched.coeffs)
+
+
+def _step_table_wide(sched, guidance_scale, coeffs):
+    """step_table_img widened to 8-float rows: a step row continues with its row of `coeffs` (fp64 [k, 3 or 4]), rounded once; the rest stays zero."""
     base = step_table_img(sched, guidance_scale)
     tab = torch.zeros(base.shape[0], 8, dtype=torch.float32)
     tab[:, :4] = base
-    tab[2:, 4:8] = torch.from_numpy(sched.coeffs.astype(np.float32))
+    tab[2:, 4:4 + coeffs.shape[1]] = torch.from_numpy(coeffs.astype(np.float32))
     return tab
 
 
@@ -595,6 +620,16 @@ def step_family(sampler, img, held=False):
     return "sde" if sampler in SDE_KINDS else "multistep" if sampler == "dpmpp_2m" else "euler" if img is None else "img"
 
 
+class Trajectory(collections.namedtuple("Trajectory", "h w steps start sampler sigmas eta seeds guide guidance_scale img hold plan heat size family")):
+    """sample()'s arguments, checked and resolved once; both drivers (the torch loop, the fused / graph path) take it.  h, w: the latent; steps: those that
+    run, from entry `start` of the steps + start entries of the schedule; sampler, sigmas, eta, seeds: as given; guide: None, or guidance_table's
+    (scale(s), rescale, interval) - the pre-pass runs; guidance_scale: the scalar of the step itself (1 with the pre-pass: e - e = 0 takes any); img: None
+    or (x0, mask | None, start) (_img_args); hold: None or the change map's hold map; plan: None or the TilePlan; heat: None or heatmap_args' dict with
+    its weights; size: (H, W) of SDXL's size conditioning; family: the step launch (FAMILIES)."""
+    __slots__ = ()
+    masked = property(lambda self: self.img is not None and self.img[1] is not None)
+
+
 class LatentSampler:
     """`pipe(prompt_embeds=c, negative_prompt_embeds=uc, ..., num_inference_steps, guidance_scale, generator)` of the
     reference's render loop, up to the latents.  `unet` is an inference instance built for batch 2 (negative | positive, the
@@ -616,7 +651,7 @@ class LatentSampler:
         cfg = unet.cfg
         self.ctx = rt.zeros(rt.B * CTX_PAD, cfg["cross_dim"])
         self.pooled = rt.zeros(rt.B, cfg["proj_class_in"] - 6 * cfg["addition_time_embed_dim"]) if cfg["addition"] else None
-        self._fused = None                 # persistent device state of the fused / graph path, built on first use
+        self._fused = None                 # persistent device state of both drivers (the torch loop, the fused / graph path), built on first use
         self._graphs = {}                  # (h, w, n, adapter scale in effect, DoRA) -> hipGraph of one denoising iteration
         self._img_graphs = {}              # the same key + (masked,) -> hipGraph of one iteration whose step launch is ops.sampler_step_img
         self._ms_graphs = {}               # the same key + (masked, "multistep") -> hipGraph of one iteration whose step launch is ops.sampler_step_ms
@@ -692,17 +727,15 @@ class LatentSampler:
         conditioning (SDXL: the whole picture's size).  On all three paths, with every sampler; freeu and kv_downsample act per window.  Starts and
         weights are device memory: one capture per (shape, window counts) serves every overlap.  A latent that fits one window (h <= T and w <= T) is the
         plain path: the same launches and bits as without `tile`.  Not with heatmap (the hooked score sums are per window)."""
+        ops = self.rt.ops
         plan = tile_plan(h, w, tile)                        # refused before anything is built
         if plan is not None:
             if heatmap is not None:
                 raise ValueError("heatmap does not combine with tile: the hooked score sums are per window, and stitching them is not built")
-            m = grid_multiple(self.unet.cfg)
-            if plan.th % m or plan.tw % m:
-                raise ValueError(f"tile: a {plan.th} x {plan.tw} window is no multiple of {m} on both axes, which this UNet's downsampling needs "
-                                 "(the rule the latent size itself obeys without windows)")
-            if not (hasattr(self.rt.ops, "window_blend") and hasattr(self.rt.ops, "window_gather")):
-                raise NotImplementedError("this op table has no window_blend kernel (sdlt_window_blend): sample(tile=...) cuts and fuses the windows by "
-                                          "two launches (ops.window_gather, ops.window_blend), in the torch loop too")
+            window_multiple(self.unet.cfg, plan)
+            for op in ("window_blend", "window_gather"):
+                require_op(ops, op, " (sdlt_window_blend): sample(tile=...) cuts and fuses the windows by two launches (ops.window_gather, "
+                           "ops.window_blend), in the torch loop too", kernel="window_blend")
         if (1 if plan is None else plan.ty * plan.tx) != self.tiles:
             raise ValueError(f"this sampler's runtime holds {self.tiles} window(s) per image (batch {self.rt.B}, {self.n} image(s)); the call needs "
                              f"{1 if plan is None else plan.ty * plan.tx}: build it on a runtime of batch 2 n_images ty tx (LatentSampler(n_images=))")
@@ -711,112 +744,88 @@ class LatentSampler:
                 raise ValueError("change_map needs init_latents: a held pixel follows their noised trajectory")
             if mask is not None:
                 raise ValueError("change_map and mask exclude each other: the map selects per pixel and step, the mask blends after every step")
-            if (graph or fused) and not hasattr(self.rt.ops, "sampler_step_dd"):
-                raise NotImplementedError("this op table has no sampler_step_dd kernel: sample(change_map=..., graph=False, fused=False) is the torch loop")
+            if graph or fused:
+                require_op(ops, "sampler_step_dd", ": sample(change_map=..., graph=False, fused=False) is the torch loop")
         kd = self.kv_downsample
         if kv_downsample is not None or kv_downsample_mode is not None:
             kd = kv_downsample_args(kd[0] if kv_downsample is None and kd is not None else kv_downsample, kv_downsample_mode or (kd[1] if kd is not None else "nearest"))
         if kd != getattr(self.unet, "_kv_ds", None):
             self.unet.set_kv_downsample(*(kd or (None,)))      # (an op table without the kernel raises NotImplementedError here)
-        hm = heatmap_args(heatmap, n_images)
-        if hm is not None and not hasattr(self.rt.ops, "heatmap_accum"):
-            raise NotImplementedError("this op table has no heatmap_accum kernel: the heat maps are accumulated by that launch (ops.heatmap_accum), in the "
-                                      "torch loop too")
         fz = freeu_args(freeu)
         if fz is not None or getattr(self.unet, "_freeu", None) is not None:
             self.unet.set_freeu(fz)          # (None: the plain launch sequence; an op table without the kernel raises NotImplementedError here)
-        if sampler not in SAMPLERS:
-            raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
-        if sampler in SDE_KINDS and not eta >= 0.0:       # (the deterministic samplers do not read eta)
-            raise ValueError(f"eta must be >= 0, got {eta!r}")
-        if sigmas not in SIGMAS:
-            raise ValueError(f"sigmas must be one of {SIGMAS}, got {sigmas!r}")
+        eta = sampler_args(sampler, sigmas, eta)
         img = self._img_args(init_latents, strength, mask, steps, h, w, n_images, keep=change_map is not None)
-        hold = None if change_map is None else self._hold_args(change_map, steps - img[2], h, w, n_images)
+        start = 0 if img is None else img[2]
+        hold = None if change_map is None else self._hold_args(change_map, steps - start, h, w, n_images)
+        hm = heatmap_args(heatmap, n_images, steps - start)      # (the weights: one per step that runs)
+        if hm is not None:
+            require_op(ops, "heatmap_accum", ": the heat maps are accumulated by that launch (ops.heatmap_accum), in the torch loop too")
         guide = (guidance_scale, guidance_rescale, guidance_interval) if guidance_in_use(guidance_scale, guidance_rescale, guidance_interval) else None
-        if guide is not None and not hasattr(self.rt.ops, "guidance"):
-            raise NotImplementedError("this op table has no guidance kernel: a per-step guidance_scale, guidance_rescale and guidance_interval are evaluated "
-                                      "by that launch (ops.guidance), in the torch loop too")
+        if guide is not None:
+            require_op(ops, "guidance", ": a per-step guidance_scale, guidance_rescale and guidance_interval are evaluated by that launch (ops.guidance), "
+                       "in the torch loop too")
+        assert 1 <= steps <= TABLE_ROWS - 2
+        traj = Trajectory(h, w, steps - start, start, sampler, sigmas, eta, seeds, guide, guidance_scale if guide is None else 1.0, img, hold, plan, hm,
+                          size if size is not None else (8 * h, 8 * w), step_family(sampler, img, hold is not None))
         if graph or fused:
-            return self._sample_fused(embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img, sampler, sigmas, eta, seeds, guide,
-                                      heatmap, hold, plan)
+            if traj.family == "sde":
+                require_op(ops, "sampler_step_sde", f": sample(sampler={sampler!r}) draws its per-step noise inside that launch")
+            if traj.family == "multistep":
+                require_op(ops, "sampler_step_ms", ": sample(sampler='dpmpp_2m', graph=False, fused=False) is the torch loop")
+            require_op(ops, "sampler_step", ": sample(graph=False, fused=False) is the torch loop")
+            if img is not None and hold is None:
+                require_op(ops, "sampler_step_img", ": sample(init_latents=..., graph=False, fused=False) is the torch loop")
+            assert n_images == self.n, f"the runtime's batch {self.rt.B} samples {self.n} image(s) together, not {n_images}"
+            return self._sample_fused(traj, embeds, latents, generator, graph)
         assert n_images == 1 and self.n == 1, "the torch loop samples one image on a batch-2 runtime; several images together: fused=True or graph=True"
-        rt, u, cfg = self.rt, self.unet, self.unet.cfg
-        dev = rt.device
-        sde = sampler in SDE_KINDS
-        if sde and not hasattr(rt.ops, "sampler_noise"):
-            raise NotImplementedError(f"this op table has no sampler_step_sde kernel: sample(sampler={sampler!r}) takes its per-step noise from that kernel's "
-                                      "generator (ops.sampler_noise), in the torch loop too")
-        c, uc, pc, puc = (tuple(embeds) + (None, None))[:4]
-        cv = self.ctx.view(rt.B, CTX_PAD, -1)               # (with windows: every window row of the pair carries the image's conditioning)
-        cv[0::2, :77].copy_(uc[0])
-        cv[1::2, :77].copy_(c[0])
-        tid = None
-        if cfg["addition"]:
-            self.pooled[0::2].copy_(puc[0])
-            self.pooled[1::2].copy_(pc[0])
-            H, W = size if size is not None else (8 * h, 8 * w)
-            tid = torch.tensor([float(H), float(W), 0.0, 0.0, float(H), float(W)] * rt.B, device=dev)   # original_size, crop, target_size
-        x0, m, start = img if img is not None else (None, None, 0)
-        s = self._scheduler(sampler, steps, start, sigmas, eta, exact=guide is not None)
-        x = latents if latents is not None else torch.randn(1, 4, h, w, generator=generator, device=dev, dtype=F32)
-        if img is None:
-            x = x.to(dev, F32) * s.init_noise_sigma
-        else:
-            noise = x.to(dev, F32)
-            x = x0 + noise * float(s.sigmas[0])
+        if sampler in SDE_KINDS:
+            require_op(ops, "sampler_noise", f": sample(sampler={sampler!r}) takes its per-step noise from that kernel's generator (ops.sampler_noise), "
+                       "in the torch loop too", kernel="sampler_step_sde")
+        return self._sample_torch(traj, embeds, latents, generator)
+
+    def _sample_torch(self, traj, embeds, latents, generator):
+        """The torch loop: the setup and the forward stage of the fused path (_begin, _predict) on the same persistent state, then the scheduler's step,
+        the mask's blend or the hold map's select and the next model input as torch operations; the step index is written from the host."""
+        rt, h, w = self.rt, traj.h, traj.w
+        s = self._scheduler(traj, exact=traj.guide is not None)
+        st, sh, x0, noise, heat = self._begin(traj, s, embeds, latents, generator)
+        x = noise * s.init_noise_sigma if traj.img is None else x0 + noise * float(s.sigmas[0])
+        m, hold = sh["img"]["mask"] if traj.masked else None, None if traj.hold is None else sh["img"]["hold"]
+        sde, counted = traj.sampler in SDE_KINDS, heat is not None or traj.guide is not None
         if sde:
-            words, z = seed_words(seeds, 1, generator, dev), rt.zeros(1, 4, h, w, dtype=F32)
-        if guide is not None:                      # the pre-pass reads its row index from a device counter, as in the fused path
-            gtab, gctr = guidance_table(s, *guide).to(dev), torch.zeros(2, dtype=torch.int32, device=dev)
-        if hm is not None:                         # the accumulation reads its weight's index from a device counter, as in the fused path
-            hm = heatmap_args(heatmap, 1, len(s.timesteps))
-            hcols, hw_, hctr, heat = hm["cols"].to(dev), hm["weights"].to(dev), torch.zeros(2, dtype=torch.int32, device=dev), None
-        x64 = rt.zeros(2 * h * w, 64)
-        win = None if plan is None else self._window_state(dict(), h, w, plan)
+            z = rt.zeros(1, 4, h, w, dtype=F32)
+        if heat is not None and heat["heat"] is not None:
+            heat["heat"].zero_()
         for i, t in enumerate(s.timesteps):
             xin = s.scale_model_input(x, i)
-            x64[:, :4] = xin.permute(0, 2, 3, 1).reshape(h * w, 4).repeat(2, 1).to(x64.dtype)
-            tf = torch.full((2,), float(t), device=dev, dtype=F32)
-            if win is None:
-                eps = u.forward(x64, tf, self.ctx, self.pooled, tid, B=2, H=h, W=w, **self._fwd_kw())
-            else:
-                eps = self._window_forward(win, x64, tf, tid, h, w)
-            if hm is not None:
-                ents = heat_entries(rt, h, w)
-                if heat is None:
-                    heat = rt.zeros(1, hcols.shape[1], *heat_grid(ents, hm["grid"]), dtype=F32)
-                hctr[0] = i
-                rt.ops.heatmap_accum(ents, hcols, hctr, hw_, heat, row_off=1, row_stride=2)
-            if guide is not None:
-                gctr[0] = i
-                e = rt.ops.guidance(eps, gtab, gctr, 1).view(2, h, w, 4).permute(0, 3, 1, 2)[1:2]      # (both rows hold the prediction)
-            else:
-                eps = eps.view(2, h, w, 4).permute(0, 3, 1, 2)
-                e = eps[0:1] + guidance_scale * (eps[1:2] - eps[0:1])
+            sh["x64"][:, :4] = xin.permute(0, 2, 3, 1).reshape(h * w, 4).repeat(2, 1).to(sh["x64"].dtype)
+            st["tf"].fill_(float(t))
+            if counted:                            # the heat maps' weight and the pre-pass's row are read at a device counter, as in the fused path
+                st["ctr"][0] = i
+            eps = self._predict(st, sh, traj, heat).view(2, h, w, 4).permute(0, 3, 1, 2)
+            e = eps[1:2] if traj.guide is not None else eps[0:1] + traj.guidance_scale * (eps[1:2] - eps[0:1])      # (the pre-pass: both rows hold the prediction)
             if sde:                                # the kernel's own noise of step i (not drawn where the row adds none)
-                x = s.step(e, i, x, rt.ops.sampler_noise(words, i, z) if s.coeffs[i, 3] != 0.0 else None)
+                x = s.step(e, i, x, rt.ops.sampler_noise(st["seeds"], i, z) if s.coeffs[i, 3] != 0.0 else None)
             else:
                 x = s.step(e, i, x)
-            if m is not None:                      # the known region, noised to the sigma this step arrived at (0 after the last: init_latents itself)
-                k = x0 + noise * float(s.sigmas[i + 1])
-                x = k + m * (x - k)
-            if hold is not None:                   # differential diffusion: the same k, selected while the pixel is held (step row i: i + 1 < hold)
-                k = x0 + noise * float(s.sigmas[i + 1])
-                x = torch.where(hold > float(i + 1), k, x)
-        return x if hm is None else (x, heat)
+            if m is not None or hold is not None:
+                k = x0 + noise * float(s.sigmas[i + 1])      # the known region, noised to the sigma this step arrived at (0 after the last: init_latents itself)
+                # the mask blends it in; differential diffusion selects it while the pixel is held (step row i: i + 1 < hold)
+                x = k + m * (x - k) if m is not None else torch.where(hold > float(i + 1), k, x)
+        return x if heat is None else (x, heat["heat"].clone())
 
-    def _scheduler(self, sampler, steps, start, sigmas, eta, exact=False):
+    def _scheduler(self, traj, exact=False):
         """The scheduler of a trajectory, its timesteps set.  exact (the torch loop where the guidance pre-pass runs): the deterministic samplers in
         their step kernels' order."""
-        if sampler in SDE_KINDS:
-            s = self.sched_sde[sampler]
-            s.eta = eta
+        if traj.sampler in SDE_KINDS:
+            s = self.sched_sde[traj.sampler]
+            s.eta = traj.eta
         elif exact:
-            s = self.sched_exact[sampler]
+            s = self.sched_exact[traj.sampler]
         else:
-            s = self.sched_ms if sampler == "dpmpp_2m" else self.sched
-        return s.set_timesteps(steps, start, sigmas)
+            s = self.sched_ms if traj.sampler == "dpmpp_2m" else self.sched
+        return s.set_timesteps(traj.steps + traj.start, traj.start, traj.sigmas)
 
     def _hold_args(self, change_map, k, h, w, n):
         """-> hold_map of sample()'s change_map for the k steps that run, fp32 [n, 1, h, w] on the device."""
@@ -851,7 +860,7 @@ class LatentSampler:
             return None
         return x0, mask, start
 
-    # ---- fused / graph path ---------------------------------------------------------------------------------------------------
+    # ---- the persistent state, setup and forward stage of both drivers; the fused / graph path ---------------------------------
     def _scope(self):
         """This sampler's own split-K / norm scratch (ops.workspace_owner), as the training step keeps its own: a captured launch holds the pointers."""
         own = getattr(self.rt.ops, "workspace_owner", None)
@@ -899,24 +908,65 @@ class LatentSampler:
         e = self.unet.forward(win["x64_tiles"], win["tf_tiles"], self.ctx, self.pooled, tid, B=rt.B, H=plan.th, W=plan.tw, **self._fwd_kw())
         return rt.ops.window_blend(win["tabs"], e, win["eps_full"], n=self.n, H=h, W=w)
 
-    def _load_image_state(self, sh, h, w, img, noise, hold=None):
-        """-> (x0, noise, masked) of the init launch.  hold (a change map's hold map): copied into its persistent buffer beside them.  From init latents: x0, the noise and the mask are copied into the persistent buffers of the shape
-        (a captured step launch holds their pointers) and those are returned; txt2img: (None, the noise as given, None)."""
-        if img is None:
-            return None, noise, None
-        if "img" not in sh:
-            rt, n = self.rt, self.n
-            sh["img"] = dict(x0=rt.zeros(n, 4, h, w, dtype=F32), noise=rt.zeros(n, 4, h, w, dtype=F32), mask=rt.zeros(n, 1, h, w, dtype=F32))
-        im, masked = sh["img"], img[1] is not None
-        im["x0"].copy_(img[0])
-        im["noise"].copy_(noise)
-        if masked:
-            im["mask"].copy_(img[1])
-        if hold is not None:
-            if "hold" not in im:
-                im["hold"] = self.rt.zeros(self.n, 1, h, w, dtype=F32)
-            im["hold"].copy_(hold)
-        return im["x0"], im["noise"], masked
+    def _load_conditioning(self, st, embeds, size):
+        """embeds: one (c, uc[, pc, puc]) per image (one image: the tuple itself) -> ctx, pooled and SDXL's size conditioning st["tid"].  UNet batch rows
+        2 j tl .. 2 (j + 1) tl - 1 are image j's, (negative, positive) per window: every window row carries the image's conditioning."""
+        rt, cfg, n, tl = self.rt, self.unet.cfg, self.n, self.tiles
+        per_image = [embeds] if (n == 1 and not isinstance(embeds[0], (tuple, list))) else list(embeds)
+        assert len(per_image) == n, "one (c, uc[, pc, puc]) per image"
+        cv = self.ctx.view(n, tl, 2, CTX_PAD, -1)
+        for j, e in enumerate(per_image):
+            c, uc, pc, puc = (tuple(e) + (None, None))[:4]
+            cv[j, :, 0, :77].copy_(uc[0])
+            cv[j, :, 1, :77].copy_(c[0])
+            if cfg["addition"]:
+                pv = self.pooled.view(n, tl, 2, -1)
+                pv[j, :, 0].copy_(puc[0])
+                pv[j, :, 1].copy_(pc[0])
+        if cfg["addition"]:
+            H, W = size
+            st["tid"].copy_(torch.tensor([float(H), float(W), 0.0, 0.0, float(H), float(W)] * rt.B))      # original_size, crop, target_size
+
+    def _begin(self, traj, sch, embeds, latents, generator):
+        """A trajectory starts, on either driver: the conditioning, the guidance table, the initial noise (`latents`, or drawn from `generator`), the seed
+        words - drawn after it - the init latents, mask and hold map, and the heat maps' columns and weights go into the persistent state of the shape
+        (_state: a captured launch holds its pointers; the window tables are refilled there).  Only ops the trajectory uses are touched.
+        -> (st, sh, x0 | None, noise, heat | None): x0 and noise as the init launch takes them, heat the dict of sh["heat"] for these columns."""
+        rt, n, h, w = self.rt, self.n, traj.h, traj.w
+        dev = rt.device
+        st, sh = self._state(h, w, traj.plan)
+        self._load_conditioning(st, embeds, traj.size)
+        if traj.guide is not None:                        # a persistent buffer, rewritten per trajectory: a captured pre-pass holds its pointer
+            gtab = guidance_table(sch, *traj.guide)
+            if "gtab" not in st:
+                st["gtab"] = rt.zeros(TABLE_ROWS - 1, 4, dtype=F32)
+            st["gtab"][: gtab.shape[0]].copy_(gtab)
+        noise = latents if latents is not None else torch.randn(n, 4, h, w, generator=generator, device=dev, dtype=F32)
+        noise = noise.to(dev, F32).contiguous()
+        assert tuple(noise.shape) == (n, 4, h, w)
+        if traj.sampler in SDE_KINDS:                     # after the initial latents; a captured launch holds the buffer
+            if "seeds" not in st:
+                st["seeds"] = torch.zeros(n, 2, dtype=torch.int32, device=dev)
+            st["seeds"].copy_(seed_words(traj.seeds, n, generator, dev))
+        x0 = None
+        if traj.img is not None:                          # init latents, noise, mask and hold map: persistent too; the init launch takes the copies
+            im = sh.setdefault("img", {})
+            for k, v in (("x0", traj.img[0]), ("noise", noise), ("mask", traj.img[1]), ("hold", traj.hold)):
+                if v is not None:
+                    if k not in im:
+                        im[k] = torch.zeros_like(v)
+                    im[k].copy_(v)
+            x0, noise = im["x0"], im["noise"]
+        heat = None
+        if traj.heat is not None:                         # persistent buffers, rewritten per trajectory: a captured launch holds their pointers
+            hm = traj.heat
+            if "hw" not in st:
+                st["hw"] = rt.zeros(TABLE_ROWS, dtype=F32)
+            st["hw"][: traj.steps].copy_(hm["weights"])
+            hkey = (hm["grid"],) + tuple(hm["cols"].shape[1:])
+            heat = sh.setdefault("heat", {}).setdefault(hkey, dict(grid=hm["grid"], cols=torch.zeros_like(hm["cols"], device=dev), heat=None))
+            heat["cols"].copy_(hm["cols"])
+        return st, sh, x0, noise, heat
 
     def _step_launch(self, fam, st, sh, eps, x0=None, noise=None, mask=None):
         """The launch of family `fam` (FAMILIES) on the persistent state; eps None: its init entry."""
@@ -930,15 +980,14 @@ class LatentSampler:
             kw["seeds"] = st["seeds"]
         getattr(self.rt.ops, f.op)(eps, sh["x"], sh["x64"], st["tf"], st[f.tab], st["ctr"], **kw)
 
-    def _iteration(self, st, sh, h, w, fam="euler", masked=None, guided=False, heat=None):
-        """fam: the step launch (FAMILIES).  masked None: txt2img; False / True: from init latents, without / with the mask (sh["img"] holds them).
-        The Euler launch from init latents takes them at every step; the multistep and stochastic launches read neither the init latents nor the
-        noise without a mask, whatever the trajectory started from.  guided: ops.guidance rewrites eps first (row ctr[0] of st["gtab"]); the step
-        launch is the same.  heat (a dict of sh["heat"]): ops.heatmap_accum reads the forward's score sums first, with the weight of row ctr[0] of
-        st["hw"]; its maps are allocated at the first iteration (the eager warm-up of a capture), when the forward has told the resolutions."""
-        u = self.unet
+    def _predict(self, st, sh, traj, heat):
+        """The forward stage of one iteration, on either driver: the UNet on sh["x64"] at st["tf"] - with a tile plan: gather, the forward on the windows,
+        blend - then ops.heatmap_accum on the forward's score sums (heat, a dict of sh["heat"]: the weight of row ctr[0] of st["hw"]; the maps are
+        allocated at the first iteration, when the forward has told the resolutions), then ops.guidance (row ctr[0] of st["gtab"]) where the pre-pass
+        runs -> eps fp32 [2 n h w, 4]."""
+        u, h, w = self.unet, traj.h, traj.w
         tid = st["tid"] if u.cfg["addition"] else None
-        if "win" in sh:                                   # tiled diffusion: gather, the forward on the windows, blend (sh is the state of a tile plan)
+        if traj.plan is not None:
             eps = self._window_forward(sh["win"], sh["x64"], st["tf"], tid, h, w)
         else:
             eps = u.forward(sh["x64"], st["tf"], self.ctx, self.pooled, tid, B=2 * self.n, H=h, W=w, **self._fwd_kw())
@@ -947,12 +996,19 @@ class LatentSampler:
             if heat["heat"] is None:
                 heat["heat"] = self.rt.zeros(self.n, heat["cols"].shape[1], *heat_grid(ents, heat["grid"]), dtype=F32)
             self.rt.ops.heatmap_accum(ents, heat["cols"], st["ctr"], st["hw"], heat["heat"], row_off=1, row_stride=2)
-        if guided:
+        if traj.guide is not None:
             self.rt.ops.guidance(eps, st["gtab"], st["ctr"], self.n)
-        im = sh["img"] if masked or fam == "img" or FAMILIES[fam].form is not None else dict(x0=None, noise=None, mask=None)
-        self._step_launch(fam, st, sh, eps, im["x0"], im["noise"], im["mask"] if masked else None)
+        return eps
 
-    def _graph(self, st, sh, h, w, fam="euler", masked=None, guided=False, heat=None):
+    def _iteration(self, st, sh, traj, heat):
+        """_predict, then the step launch of the trajectory's family.  The Euler launch from init latents takes them (sh["img"]) at every step, as the
+        launch with a hold map does; the multistep and stochastic launches read neither the init latents nor the noise without a mask, whatever the
+        trajectory started from."""
+        eps = self._predict(st, sh, traj, heat)
+        im = sh["img"] if traj.masked or traj.family == "img" or traj.hold is not None else dict(x0=None, noise=None, mask=None)
+        self._step_launch(traj.family, st, sh, eps, im["x0"], im["noise"], im["mask"] if traj.masked else None)
+
+    def _graph(self, st, sh, traj, heat):
         """The hipGraph of one iteration for this shape and the adapter scale in effect.  The scale is a launch argument of every adapted GEMM
         (baked by capture), hence part of the key; adapters, DoRA factors, token rows, conditioning, table and counter are device memory.
         Each family's step launch is another kernel: its captures live in a dict of their own (FAMILIES), keyed - txt2img Euler apart - by the mask
@@ -963,6 +1019,7 @@ class LatentSampler:
         neither collide with those captures nor evict them; the scales, phi and the interval are in st["gtab"]: one capture per family serves all.
         heat: the captures with ops.heatmap_accum in them are keyed by ("heat", grid, T, P) as well - the launch's shape; which columns and which
         step weights are device memory."""
+        h, w, fam, masked, guided = traj.h, traj.w, traj.family, traj.masked, traj.guide is not None
         a, f = self.unet.arena, FAMILIES[fam]
         key = (h, w, self.n, None if a is None else float(a.scale), bool(a is not None and a.dora))
         if f.suffix is not None:
@@ -991,11 +1048,11 @@ class LatentSampler:
         side.wait_stream(torch.cuda.current_stream())
         seq = None
         with torch.cuda.stream(side):
-            self._iteration(st, sh, h, w, fam, masked, guided, heat)     # eager warm-up: every persistent buffer and packed-weight copy exists before the capture
+            self._iteration(st, sh, traj, heat)     # eager warm-up: every persistent buffer and packed-weight copy exists before the capture
             if prefetch:                                  # next-weight hints of the wave-split-K products, recorded from one eager pass (step.TrainStep.capture)
                 ops.pf_record_begin()
                 try:
-                    self._iteration(st, sh, h, w, fam, masked, guided, heat)
+                    self._iteration(st, sh, traj, heat)
                 finally:
                     seq = ops.pf_record_end()
         torch.cuda.current_stream().wait_stream(side)
@@ -1004,93 +1061,37 @@ class LatentSampler:
             if seq:
                 ops.pf_replay_begin(seq)
             try:
-                self._iteration(st, sh, h, w, fam, masked, guided, heat)
+                self._iteration(st, sh, traj, heat)
             finally:
                 if seq:
                     ops.pf_replay_end()
         graphs[key] = g
         return g
 
-    def _sample_fused(self, embeds, h, w, steps, guidance_scale, generator, size, latents, graph, n_images, img=None, sampler="euler", sigmas="trailing",
-                      eta=1.0, seeds=None, guide=None, heatmap=None, hold=None, plan=None):
-        rt, cfg, n = self.rt, self.unet.cfg, self.n
-        guided = guide is not None
-        if guided:
-            guidance_scale = 1.0                          # the step launch's own scale multiplies e - e = 0: any value gives the same bits
-        fam = step_family(sampler, img, hold is not None)
-        ms, sde = fam == "multistep", fam == "sde"
-        if sde and not hasattr(rt.ops, "sampler_step_sde"):
-            raise NotImplementedError(f"this op table has no sampler_step_sde kernel: sample(sampler={sampler!r}) draws its per-step noise inside that launch")
-        if ms and not hasattr(rt.ops, "sampler_step_ms"):
-            raise NotImplementedError("this op table has no sampler_step_ms kernel: sample(sampler='dpmpp_2m', graph=False, fused=False) is the torch loop")
-        if not hasattr(rt.ops, "sampler_step"):
-            raise NotImplementedError("this op table has no sampler_step kernel: sample(graph=False, fused=False) is the torch loop")
-        if img is not None and hold is None and not hasattr(rt.ops, "sampler_step_img"):
-            raise NotImplementedError("this op table has no sampler_step_img kernel: sample(init_latents=..., graph=False, fused=False) is the torch loop")
-        assert n_images == n, f"the runtime's batch {rt.B} samples {n} image(s) together, not {n_images}"
-        assert 1 <= steps <= TABLE_ROWS - 2
-        dev = rt.device
-        per_image = [embeds] if (n == 1 and not isinstance(embeds[0], (tuple, list))) else list(embeds)
-        assert len(per_image) == n, "one (c, uc[, pc, puc]) per image"
-        tl = self.tiles                                   # UNet batch rows 2 j tl .. 2 (j + 1) tl - 1 are image j's: (negative, positive) per window
-        cv = self.ctx.view(n, tl, 2, CTX_PAD, -1)
-        st, sh = self._state(h, w, plan)
-        for j, e in enumerate(per_image):
-            c, uc, pc, puc = (tuple(e) + (None, None))[:4]
-            cv[j, :, 0, :77].copy_(uc[0])
-            cv[j, :, 1, :77].copy_(c[0])
-            if cfg["addition"]:
-                pv = self.pooled.view(n, tl, 2, -1)
-                pv[j, :, 0].copy_(puc[0])
-                pv[j, :, 1].copy_(pc[0])
-        if cfg["addition"]:
-            H, W = size if size is not None else (8 * h, 8 * w)
-            st["tid"].copy_(torch.tensor([float(H), float(W), 0.0, 0.0, float(H), float(W)] * rt.B))
-        f, start = FAMILIES[fam], 0 if img is None else img[2]
-        sch = self._scheduler(sampler, steps, start, sigmas, eta)
-        tab = f.table(sch, guidance_scale)
-        steps -= start                                    # the steps that run: the table holds their rows only
+    def _sample_fused(self, traj, embeds, latents, generator, graph):
+        rt, f = self.rt, FAMILIES[traj.family]
+        sch = self._scheduler(traj)
+        st, sh, x0, noise, heat = self._begin(traj, sch, embeds, latents, generator)
+        tab = f.table(sch, traj.guidance_scale)          # the rows of the steps that run
         if f.tab not in st:                               # (the multistep and stochastic launches share the 8-column table and the history buffer: both are rewritten per trajectory)
             st[f.tab] = rt.zeros(TABLE_ROWS, f.width, dtype=F32)
         if f.dprev and "dprev" not in sh:
-            sh["dprev"] = rt.zeros(n, 4, h, w, dtype=F32)
-        if f.seeds and "seeds" not in st:
-            st["seeds"] = torch.zeros(n, 2, dtype=torch.int32, device=rt.device)
+            sh["dprev"] = rt.zeros(self.n, 4, traj.h, traj.w, dtype=F32)
         st[f.tab][: tab.shape[0]].copy_(tab)
-        if guided:                                        # a persistent buffer, rewritten per trajectory: a captured pre-pass holds its pointer
-            gtab = guidance_table(sch, *guide)
-            if "gtab" not in st:
-                st["gtab"] = rt.zeros(TABLE_ROWS - 1, 4, dtype=F32)
-            st["gtab"][: gtab.shape[0]].copy_(gtab)
-        noise = latents if latents is not None else torch.randn(n, 4, h, w, generator=generator, device=dev, dtype=F32)
-        noise = noise.to(dev, F32).contiguous()
-        assert tuple(noise.shape) == (n, 4, h, w)
-        if f.seeds:                                       # after the initial latents, as in the torch loop; a captured launch holds the buffer
-            st["seeds"].copy_(seed_words(seeds, n, generator, dev))
-        x0, noise, masked = self._load_image_state(sh, h, w, img, noise, hold)
-        heat = None
-        if heatmap is not None:                           # persistent buffers, rewritten per trajectory: a captured launch holds their pointers
-            hm = heatmap_args(heatmap, n, steps)
-            if "hw" not in st:
-                st["hw"] = rt.zeros(TABLE_ROWS, dtype=F32)
-            st["hw"][:steps].copy_(hm["weights"])
-            hkey = (hm["grid"],) + tuple(hm["cols"].shape[1:])
-            heat = sh.setdefault("heat", {}).setdefault(hkey, dict(grid=hm["grid"], cols=torch.zeros_like(hm["cols"], device=dev), heat=None))
-            heat["cols"].copy_(hm["cols"])
-        init = lambda: self._step_launch(fam, st, sh, None, x0=x0, noise=noise)  # noqa: E731
+        init = lambda: self._step_launch(traj.family, st, sh, None, x0=x0, noise=noise)  # noqa: E731
         with self._scope():
             g = None
             if graph:
                 init()                                    # (a defined state for the warm-up passes)
-                g = self._graph(st, sh, h, w, fam, masked, guided, heat)
+                g = self._graph(st, sh, traj, heat)
             init()
             if heat is not None and heat["heat"] is not None:      # (the warm-up passes of a capture accumulated into it)
                 heat["heat"].zero_()
-            for _ in range(steps):                        # no host read in here: the step index lives in ctr, its scalars in the table
+            for _ in range(traj.steps):                   # no host read in here: the step index lives in ctr, its scalars in the table
                 if g is not None:
                     g.replay()
                 else:
-                    self._iteration(st, sh, h, w, fam, masked, guided, heat)
+                    self._iteration(st, sh, traj, heat)
         return sh["x"].clone() if heat is None else (sh["x"].clone(), heat["heat"].clone())
 
 
