@@ -1206,6 +1206,7 @@ int attn_plan_bwd(const sdlt_attn_params& p, const AttnSwitches& sw, AttnPlan& p
   pl = AttnPlan{};
   pl.dp = attn_dp(p.d);
   const int tq = (p.Nq + 63) / 64, tk = (p.Nk + 63) / 64;
+  const int tkp = (p.Nkp + 63) / 64;      // key tiles launched: pad keys behind the last live tile get their zero dK / dV rows from a tile of their own (no model shape has one)
   if (p.qsplit > 1 && !p.causal && p.Nk <= 128 && p.Nkp <= 128 && pl.dp <= 96) {
     // cross-attention: prep + dQ + dK/dV in one kernel (see attn_bwd_cross_kernel); qsplit = workgroups along the queries,
     // dK32 / dV32 = [qsplit][B*Nkp][ld32] partial slabs (any contents)
@@ -1223,12 +1224,14 @@ int attn_plan_bwd(const sdlt_attn_params& p, const AttnSwitches& sw, AttnPlan& p
     const int64_t groups = (int64_t)p.B * p.Nqp * p.H;
     if (groups >= (1 << 22)) SDLT_FAIL(SDLT_ERR_UNSUPPORTED, "sdlt_attn_bwd: B * Nq * H = %lld rows (the D pre-pass indexes < 2^22)", (long long)groups);
     pl.prep = !p.d_ready;      // (d_ready: sdlt_wsk_gemm_rowdot left D while it produced dO)
-    pl.grid = dim3(tq + tk, p.H, p.B);
-    if (sw.r32 && sdlt_attn32_ok(p) && ((uintptr_t)p.L % 16) == 0 && ((uintptr_t)p.D % 16) == 0 &&
+    pl.grid = dim3(tq + tkp, p.H, p.B);
+    // (Nkp == Nk: attn32_bwd_both_kernel stores the rows of its key tiles only - pad keys behind a whole number of tiles get their zeros from the 16-row kernel)
+    if (sw.r32 && sdlt_attn32_ok(p) && p.Nkp == p.Nk && ((uintptr_t)p.L % 16) == 0 && ((uintptr_t)p.D % 16) == 0 &&
         (((uintptr_t)p.dQ | (uintptr_t)p.dK | (uintptr_t)p.dV) % 16) == 0 && ((p.lddq | p.lddk | p.lddv) % 8) == 0) {      // (16-byte epilogue stores)
       pl.route = SDLT_ATTN_ROUTE_BWD_BOTH32;
       // (1 / 2 / 4 groups: 1024 x 20 44.0 / 38.1 / 46.4 us, 4096 x 10 219.9 / 203.3 / 201.5, 4 x 1024 x 10 72.0 / 60.1 / 75.1)
       pl.ks = attn32_ks(sw.ks32_bwd, p.Nk >= 128 && p.Nq >= 128);
+      pl.grid = dim3(tq + tk, p.H, p.B);
       pl.block = 128 * pl.ks;
       pl.smem = sdlt_attn32_bwd_both(pl.ks).smem;
     } else {
@@ -1243,7 +1246,7 @@ int attn_plan_bwd(const sdlt_attn_params& p, const AttnSwitches& sw, AttnPlan& p
   pl.route = SDLT_ATTN_ROUTE_BWD_SPLIT;
   pl.dv48 = sw.dv48 && pl.dp == 64 && p.d <= 48;
   pl.grid = dim3(tq, p.H, p.B);
-  pl.grid2 = dim3(tk * p.qsplit, p.H, p.B);
+  pl.grid2 = dim3(tkp * p.qsplit, p.H, p.B);
   pl.smem = smem_fwd(pl.dp);
   pl.smem2 = smem_both(pl.dp);
   pl.splitsum = p.qsplit > 1;      // [qsplit][B * Nkp][ld32] partial slabs -> bf16 dK / dV, summed in slab order (bitwise reproducible)

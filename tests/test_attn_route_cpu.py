@@ -86,6 +86,9 @@ def test_threshold_edges():
     assert route(c1, 1, dK=0x100008) == R("BWD_BOTH16", prep=True)
     assert route(c1, 1, d_ready=1) == R("BWD_BOTH32", ks=2)
     assert route(c2, 1, defer_splitsum=1) == R("BWD_CROSS_ROLES", five=True)
+    # the 32-row backward stores the rows of its key tiles only: pad keys behind whole tiles keep the backward on the 16-row kernel (which zeroes their dK / dV rows)
+    x = dict(B=1, H=2, Nq=192, Nk=64, Nkp=72, d=64, causal=False, qsplit=1)
+    assert route(x, 0) == R("FWD32", ks=1) and route(x, 1) == R("BWD_BOTH16", prep=True)
     # five 16-key blocks: 64 < Nk <= 80
     for Nk, five in ((64, False), (65, True), (80, True), (81, False)):
         x = dict(B=1, H=2, Nq=128, Nk=Nk, Nkp=128, d=64, causal=False, qsplit=2)

@@ -1835,9 +1835,16 @@ def _count_paired(ops, gens, prefer):
                                         (dict(SDLT_ATTN32_KS_FWD="1", SDLT_ATTN32_KS_BWD="1"), "test_attention_fwd_bwd"),
                                         (dict(SDLT_WSK_STAGGER="0", SDLT_STRIP_WIDE_MIN="4096"), "test_wsk or test_strip"),
                                         (dict(SDLT_LN_FOLD="7", SDLT_LN_FOLD_WIDTH="64", SDLT_LN_PARTS="0"), "file:test_ti_step_gpu.py:trajectory or step"),
-                                        (dict(SDLT_LN_FOLD="0"), "file:test_ti_step_gpu.py:trajectory or step")],
+                                        (dict(SDLT_LN_FOLD="0"), "file:test_ti_step_gpu.py:trajectory or step"),
+                                        # the same attention switch sets on the bit-exact file (tests/test_attn_exact_gpu.py: under switches it takes the planner's route as it comes)
+                                        (dict(SDLT_XATTN_ROLES="0"), "file:test_attn_exact_gpu.py:test_"),
+                                        (dict(SDLT_XATTN_ROLES="0", SDLT_XATTN_FIVE="0"), "file:test_attn_exact_gpu.py:test_"),
+                                        (dict(SDLT_ATTN_XCD="0", SDLT_ATTN_KS="1", SDLT_ATTN_R32="0"), "file:test_attn_exact_gpu.py:test_"),
+                                        (dict(SDLT_ATTN32_KS_FWD="4", SDLT_ATTN32_KS_BWD="4"), "file:test_attn_exact_gpu.py:test_"),
+                                        (dict(SDLT_ATTN32_KS_FWD="1", SDLT_ATTN32_KS_BWD="1"), "file:test_attn_exact_gpu.py:test_")],
                          ids=["single-role", "single-role-128-keys", "plain-order-unsplit-16-rows", "attn32-four-groups", "attn32-one-group", "unstaggered-narrow-strips",
-                              "layernorm-fold-every-width-k-walk-statistics", "layernorm-launches"])
+                              "layernorm-fold-every-width-k-walk-statistics", "layernorm-launches", "exact-single-role", "exact-single-role-128-keys",
+                              "exact-plain-order-unsplit-16-rows", "exact-attn32-four-groups", "exact-attn32-one-group"])
 def test_fallback_kernel_paths_in_a_subprocess(env, select):
     """The A/B switches are read once per process, so the non-default kernels behind them (single-role / 128-key cross-attention backward,
     plain workgroup order, unsplit attention forward, unstaggered wave-split-K refills, 16-column strips; step level: the LayerNorm fold at every
