@@ -904,6 +904,47 @@ typedef struct {
 int sdlt_window_gather(const sdlt_window_params* p, const void* x_full, void* x_tiles, int64_t ld, const float* tf_full, float* tf_tiles, void* stream);
 int sdlt_window_blend(const sdlt_window_params* p, const float* eps_tiles, float* eps_full, void* stream);
 
+/* sdlt_region_gather / sdlt_region_blend / sdlt_region_noise : the launches regional prompts add to a denoising iteration (MultiDiffusion, Bar-Tal et al.
+ * 2023, section 4.2; sampler.py: sample(regions=); inference only).  The UNet runs the whole H x W latent once per region, each with its own prompt, as one
+ * batch of 2 n R rows; the step launches and sdlt_guidance stay at full size.  Region 0 is the background (the main prompt).  Every table is DEVICE
+ * memory: a captured graph serves every mask set, background and bootstrap length with the same R.
+ *   full-size rows   ((2 j + s) H + y) W + x                  image j, s = 0 negative | 1 positive (what the step launches read and write)
+ *   region batch     b = 2 (j R + r) + s ; pixel row (b H + y) W + x
+ * sdlt_region_gather: x_regions[b, y, x, 0 .. ld) = x_full[2 j + s, y, x, 0 .. ld) - whole bf16 model-input rows of ld elements, 16-byte pieces, eight
+ *   lanes per row - and tf_regions[b] = tf_full[2 j + s].  wn is not read and may be null.  Bootstrap: with wraw, bg, rtab, ctr and seeds given (all five,
+ *   or none: a pure copy), at step row i = ctr[0] (clamped to 0 .. SDLT_REGION_TABLE_ROWS - 1; ctr is read, never written) with sigma_i = rtab[i, 0] >= 0
+ *   and inv_i = rtab[i, 1], columns 0 .. 3 of every row of a region r >= 1 whose wraw[r, y, x] < 0.5 become, for both s,
+ *   bf16((bg[j, r, c] + sigma_i * z_c) * inv_i): t = sigma_i * z_c, u = bg + t, v = u * inv_i, one fp32 rounding each, no contraction, then the
+ *   round-to-nearest-even conversion of the step launches' repack.  Columns 4 and up are copied.  z = the project's Philox4x32-10 / Box-Muller normals
+ *   (sdlt_sampler_step_sde) with key = image j's seed words and counter = (pixel y W + x, i, r, 0x52474E31) - seed, step, region and pixel only, and never
+ *   the stochastic samplers' draws (their tag is 0x53444531).  rtab holds SDLT_REGION_TABLE_ROWS rows whatever the step count; sigma_i < 0: no
+ *   bootstrap at that step (uniform over the launch).
+ * sdlt_region_blend: eps_full[2 j + s, y, x, 0 .. 4) = the sum over r ascending of  u = wn[r, y, x] * eps_regions[b, y, x, c] rounded, acc = acc + u
+ *   rounded, from +0.0 - two fp32 operations per term, no contraction, which a torch fp32 restatement reproduces exactly.  wn fp32 [R, H, W]: normalised
+ *   weights, summing to 1 over r at every pixel.  A gather: one thread per full-size row, one 16-byte store; every row of eps_full is written exactly
+ *   once - no zeroing launch, no atomics, bit-reproducible.  The bootstrap pointers are not read.
+ * sdlt_region_noise: out fp32 [n, 4, hw] = the z of sdlt_region_gather at step row `step` for region `region` (the same device function).
+ * 64-bit row offsets, vector stores only.  A null block or required pointer, a non-positive extent, R above 16, H or W above 16384, n above 32767, more
+ * than 2^40 region rows, ld below 8 or above 4096, x_regions overlapping x_full or eps_full overlapping eps_regions, some but not all of the five
+ * bootstrap pointers (-1); x_full, x_regions, eps_regions or eps_full not 16-byte aligned, a table or timestep pointer not 4-byte aligned, ld no multiple
+ * of 8 (-2): the code is returned, sdlt_last_error names the entry point and nothing is launched.  Whatever the tables hold, neither kernel reads or
+ * writes out of bounds.
+ * The block is declared without a struct tag and has no index in sdlt_struct_size(), like sdlt_window_params: it is 64 bytes - six pointers and four
+ * int32 - with no padding between fields. */
+#define SDLT_REGION_TABLE_ROWS 1000
+typedef struct {
+  const float* wn;                           /* fp32 [R, H, W]: normalised weights (blend only) */
+  const float* wraw;                         /* fp32 [R, H, W]: raw masks in [0, 1]; bootstrap keeps a pixel of region r where wraw >= 0.5 (gather; NULL: no bootstrap) */
+  const float* bg;                           /* fp32 [n, R, 4]: a constant background latent per image and region (gather; NULL: no bootstrap) */
+  const float* rtab;                         /* fp32 [SDLT_REGION_TABLE_ROWS, 2]: (sigma_i, inv_i) per step row; sigma_i < 0: no bootstrap at that step (gather; NULL: no bootstrap) */
+  const int32_t* ctr;                        /* the sampler's step counter: ctr[0] = i is read and never written (gather with bootstrap) */
+  const uint32_t* seeds;                     /* uint32 [n, 2]: the stochastic samplers' seed words (gather with bootstrap) */
+  int32_t n, R, H, W;
+} sdlt_region_params;
+int sdlt_region_gather(const sdlt_region_params* p, const void* x_full, void* x_regions, int64_t ld, const float* tf_full, float* tf_regions, void* stream);
+int sdlt_region_blend(const sdlt_region_params* p, const float* eps_regions, float* eps_full, void* stream);
+int sdlt_region_noise(const uint32_t* seeds, int32_t step, int32_t region, int32_t n, int32_t hw, float* out, void* stream);
+
 /* out[M,C] = a + b on strided 2-D bf16 views (gradient fan-in of the UNet skip connections). */
 int sdlt_add2d(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int32_t M, int32_t C, void* stream);
 

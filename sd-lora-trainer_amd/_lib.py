@@ -242,6 +242,11 @@ class WindowParams(C.Structure):
                 ("pad_", i32)]
 
 
+class RegionParams(C.Structure):
+    # sdlt_region_params: 64 bytes by the header's text (tagless, like sdlt_window_params)
+    _fields_ = [("wn", vp), ("wraw", vp), ("bg", vp), ("rtab", vp), ("ctr", vp), ("seeds", vp), ("n", i32), ("R", i32), ("H", i32), ("W", i32)]
+
+
 class ShadowDesc(C.Structure):
     _fields_ = [("offset", i64), ("src_ld", i64), ("rows", i32), ("cols", i32), ("dst", vp), ("ld", i64), ("dstT", vp), ("ldT", i64)]
 
@@ -311,6 +316,9 @@ SYMBOLS = {
     "sdlt_tile_blend": (i32, [vp, i64, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
     "sdlt_window_gather": (i32, [C.POINTER(WindowParams), vp, vp, i64, vp, vp, vp]),
     "sdlt_window_blend": (i32, [C.POINTER(WindowParams), vp, vp, vp]),
+    "sdlt_region_gather": (i32, [C.POINTER(RegionParams), vp, vp, i64, vp, vp, vp]),
+    "sdlt_region_blend": (i32, [C.POINTER(RegionParams), vp, vp, vp]),
+    "sdlt_region_noise": (i32, [vp, i32, i32, i32, i32, vp, vp]),
     "sdlt_strip_gemm": (i32, [C.POINTER(StripParams), vp]),
     "sdlt_strip_gemm_pair": (i32, [C.POINTER(StripParams), C.POINTER(StripParams), vp]),
     "sdlt_attn_pair_ok": (i32, [C.POINTER(AttnParams), C.POINTER(AttnParams)]),
@@ -362,7 +370,7 @@ def load():
             raise KernelLibraryError(f"struct layout mismatch for {name}: C {lib.sdlt_struct_size(which)} vs binding {size}")
     if C.sizeof(ResizeParams) != 48:
         raise KernelLibraryError(f"struct layout mismatch for ResizeParams: header 48 vs binding {C.sizeof(ResizeParams)}")
-    for cls, size in ((HeatAccumParams, 152), (HeatOverlayParams, 80), (GemmPlan, 64), (SamplerDdParams, 128), (WindowParams, 64)):
+    for cls, size in ((HeatAccumParams, 152), (HeatOverlayParams, 80), (GemmPlan, 64), (SamplerDdParams, 128), (WindowParams, 64), (RegionParams, 64)):
         if C.sizeof(cls) != size:
             raise KernelLibraryError(f"struct layout mismatch for {cls.__name__}: header {size} vs binding {C.sizeof(cls)}")
     _lib = lib

@@ -21,6 +21,7 @@ extern "C" int sdlt_abi_version(void) { return 1; }
 static_assert(sizeof(sdlt_resize_params) == 48, "sdlt_resize_params has no index below: its size is part of the header's text");
 static_assert(sizeof(sdlt_sampler_dd_params) == 128, "sdlt_sampler_dd_params has no index below: its size is part of the header's text");
 static_assert(sizeof(sdlt_window_params) == 64, "sdlt_window_params has no index below: its size is part of the header's text");
+static_assert(sizeof(sdlt_region_params) == 64, "sdlt_region_params has no index below: its size is part of the header's text");
 
 extern "C" int sdlt_struct_size(int which) {
   switch (which) {

@@ -57,6 +57,7 @@
 // `d != 0` are uniform over the launch, so no load sits under a per-thread condition (the hold select is per thread, on values already loaded).  Vector stores only.  All arithmetic in fp32, each operation
 // rounded once (no contraction: the tests compare bits).
 #include "common.h"
+#include "philox.h"
 #include "../../include/sdlt_kernels.h"
 
 #pragma clang fp contract(off)
@@ -82,39 +83,9 @@ struct step_args {
   const float* hold;
 };
 
-constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u, PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
-constexpr uint32_t NOISE_TAG = 0x53444531u;             // counter word 3: keeps these draws apart from any other use of the same seed
-
-// Philox4x32-10 (Salmon et al. 2011, Random123): ten rounds, the key bumped by the Weyl constants between them.
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t w[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(PHILOX_M0, c0), lo0 = PHILOX_M0 * c0;
-    const uint32_t hi1 = __umulhi(PHILOX_M1, c2), lo1 = PHILOX_M1 * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += PHILOX_W0;
-    k1 += PHILOX_W1;
-  }
-  w[0] = c0, w[1] = c1, w[2] = c2, w[3] = c3;
-}
-
-// The four channel normals of pixel `px` of an image with key (k0, k1) at step row `step`.
+// The four channel normals of pixel `px` of an image with key (k0, k1) at step row `step` (philox.h: the generator region.hip shares).
 __device__ __forceinline__ void sde_noise4(uint32_t k0, uint32_t k1, uint32_t px, uint32_t step, float z[4]) {
-  uint32_t w[4];
-  philox4x32_10(px, step, 0u, NOISE_TAG, k0, k1, w);
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const float u0 = ((float)(w[2 * h] >> 9) + 0.5f) * 0x1p-23f;
-    const float u1 = ((float)(w[2 * h + 1] >> 9) + 0.5f) * 0x1p-23f;
-    const float r = sqrtf(-2.f * logf(u0));
-    float sn, cs;
-    sincospif(2.f * u1, &sn, &cs);
-    z[2 * h] = r * cs;
-    z[2 * h + 1] = r * sn;
-  }
+  philox_normal4(px, step, 0u, NOISE_TAG, k0, k1, z);
 }
 
 __global__ __launch_bounds__(256) void sampler_noise_kernel(const uint32_t* seeds, int step, int n, int hw, float* out) {

@@ -1563,6 +1563,99 @@ def window_blend(tabs, eps_tiles, eps_full, *, n, H, W):
     return eps_full
 
 
+REGION_MAX = 16            # regions of sdlt_region_gather / sdlt_region_blend (sampler.region_plan takes at most 8: the UNet batch is 2 n R)
+REGION_TABLE_ROWS = 1000   # rows of the bootstrap table rtab (SDLT_REGION_TABLE_ROWS): one per step of the longest schedule
+
+RegionTables = collections.namedtuple("RegionTables", "wn wraw R")
+
+
+def region_tables(h, w, masks, base=0.0, device=None):
+    """The tables of region_gather / region_blend for an h x w latent with foreground masks [R - 1, h, w] in [0, 1] (None or empty: R = 1) ->
+    RegionTables: wraw fp32 [R, h, w] - row 0 the background's raw weight clamp(1 - sum of the foregrounds, 0, 1) + base, rows 1.. the masks - and wn
+    fp32 [R, h, w] = wraw / its sum over r, formed in fp64 from the fp32 masks and rounded once - on `device` (None: the CPU) - and R.  The total is
+    positive at every pixel by construction: where no foreground has weight the background has 1 + base.  ValueError for a wrong shape, values outside
+    [0, 1] or not finite, more than REGION_MAX regions, or base < 0."""
+    if not (isinstance(base, (int, float)) and not isinstance(base, bool) and math.isfinite(base) and base >= 0.0):
+        raise ValueError(f"regions: base must be a finite number >= 0 (the main prompt's extra weight), got {base!r}")
+    if h < 1 or w < 1:
+        raise ValueError(f"regions: a {h} x {w} latent")
+    fg = torch.zeros(0, h, w, dtype=torch.float64) if masks is None else torch.as_tensor(masks).detach().to("cpu", torch.float32).double()
+    if fg.dim() != 3 or tuple(fg.shape[1:]) != (h, w):
+        raise ValueError(f"regions: masks {tuple(fg.shape)}: expected [R - 1, {h}, {w}], one per foreground region")
+    if fg.shape[0] + 1 > REGION_MAX:
+        raise ValueError(f"regions: {fg.shape[0] + 1} regions with the background (at most {REGION_MAX})")
+    if fg.numel() and (not bool(torch.isfinite(fg).all()) or float(fg.min()) < 0.0 or float(fg.max()) > 1.0):
+        raise ValueError("regions: mask values must be finite and lie in [0, 1]")
+    raw = torch.cat([((1.0 - fg.sum(0)).clamp_(0.0, 1.0) + float(base))[None], fg])
+    total = raw.sum(0)
+    assert float(total.min()) > 0.0, "a pixel without any weight: the background has 1 + base where no foreground has any"
+    tabs = ((raw / total).to(F32).contiguous(), raw.to(F32).contiguous())
+    if device is not None:
+        tabs = tuple(t.to(device) for t in tabs)
+    return RegionTables(*tabs, int(raw.shape[0]))
+
+
+def _region_params(tabs, n, H, W, weights, boot=None):
+    R = tabs.R
+    assert 1 <= R <= REGION_MAX, R
+    kw = dict(wn=None, wraw=None, bg=None, rtab=None, ctr=None, seeds=None)
+    if weights:
+        _chk2(tabs.wn, F32)
+        assert tuple(tabs.wn.shape) == (R, H, W) and tabs.wn.is_contiguous(), "wn [R, H, W]"
+        kw["wn"] = tabs.wn.data_ptr()
+    if boot is not None:
+        bg, rtab, ctr, seeds = boot["bg"], boot["rtab"], boot["ctr"], boot["seeds"]
+        _chk2(tabs.wraw, F32), _chk2(bg, F32), _chk2(rtab, F32), _chk2(ctr, torch.int32), _chk2(seeds, torch.int32)
+        assert tuple(tabs.wraw.shape) == (R, H, W) and tabs.wraw.is_contiguous(), "wraw [R, H, W]"
+        assert tuple(bg.shape) == (n, R, 4) and bg.is_contiguous(), f"bg {tuple(bg.shape)}: expected [{n}, {R}, 4]"
+        assert tuple(rtab.shape) == (REGION_TABLE_ROWS, 2) and rtab.is_contiguous(), f"rtab {tuple(rtab.shape)}: expected [{REGION_TABLE_ROWS}, 2]"
+        assert ctr.numel() >= 1 and ctr.is_contiguous() and tuple(seeds.shape) == (n, 2) and seeds.is_contiguous(), "ctr int32 [>= 1], seeds int32 [n, 2]"
+        kw.update(wraw=tabs.wraw.data_ptr(), bg=bg.data_ptr(), rtab=rtab.data_ptr(), ctr=ctr.data_ptr(), seeds=seeds.data_ptr())
+    return _lib.RegionParams(n=int(n), R=R, H=int(H), W=int(W), **kw)
+
+
+def region_gather(tabs, x_full, x_regions, tf_full, tf_regions, *, n, H, W, boot=None):
+    """sdlt_region_gather: the model input of regional prompts.  x_full bf16 [2n H W, ld] (row ((2 j + s) H + y) W + x, as the step launch left it) ->
+    x_regions bf16 [2n R H W, ld], batch row b = 2 (j R + r) + s: whole rows, every column; tf_full fp32 [2n] -> tf_regions fp32 [2n R].  tabs:
+    region_tables' (on the device).  boot: None (a pure copy), or dict(bg fp32 [n, R, 4], rtab fp32 [REGION_TABLE_ROWS, 2], ctr int32 (read only),
+    seeds int32 [n, 2]): at step row i = ctr[0] with rtab[i, 0] = sigma_i >= 0, columns 0 .. 3 of the rows of a region r >= 1 where tabs.wraw[r] < 0.5
+    become bf16((bg[j, r] + sigma_i z) rtab[i, 1]), z = region_noise(seeds, i, r)."""
+    lib = _lib.load()
+    p = _region_params(tabs, n, H, W, False, boot)
+    _chk2(x_full), _chk2(x_regions), _chk2(tf_full, F32), _chk2(tf_regions, F32)
+    B = 2 * n * tabs.R
+    assert x_full.dim() == 2 and x_regions.dim() == 2 and x_full.shape[0] == 2 * n * H * W and x_regions.shape[0] == B * H * W, \
+        f"x_full {tuple(x_full.shape)} / x_regions {tuple(x_regions.shape)} for n={n} H={H} W={W} and {tabs.R} regions"
+    assert _ld(x_full) == _ld(x_regions) == x_full.shape[1] == x_regions.shape[1], "whole rows are copied: both sides contiguous with the same width"
+    assert tf_full.numel() >= 2 * n and tf_regions.numel() >= B and tf_full.is_contiguous() and tf_regions.is_contiguous()
+    _lib.check(lib.sdlt_region_gather(C.byref(p), _p(x_full), _p(x_regions), _ld(x_full), _p(tf_full), _p(tf_regions), _stream()), "sdlt_region_gather")
+    return x_regions
+
+
+def region_blend(tabs, eps_regions, eps_full, *, n, H, W):
+    """sdlt_region_blend: the regions' predictions fused into one for the whole latent.  eps_regions fp32 [2n R H W, 4] (UNet.forward's output on
+    region_gather's batch) -> eps_full fp32 [2n H W, 4], every row written once: the sum over r ascending of wn[r] * v - u = w v, acc + u, two fp32
+    roundings per term from +0.0 (tests/region_ref.py: blend32 gives the same bits)."""
+    lib = _lib.load()
+    p = _region_params(tabs, n, H, W, True)
+    _chk2(eps_regions, F32), _chk2(eps_full, F32)
+    assert eps_regions.is_contiguous() and tuple(eps_regions.shape) == (2 * n * tabs.R * H * W, 4), tuple(eps_regions.shape)
+    assert eps_full.is_contiguous() and tuple(eps_full.shape) == (2 * n * H * W, 4), tuple(eps_full.shape)
+    _lib.check(lib.sdlt_region_blend(C.byref(p), _p(eps_regions), _p(eps_full), _stream()), "sdlt_region_blend")
+    return eps_full
+
+
+def region_noise(seeds, step, region, out):
+    """sdlt_region_noise: out fp32 [n, 4, h, w] = the noise sdlt_region_gather's bootstrap uses at step row `step` for region `region` and seeds int32
+    [n, 2]."""
+    lib = _lib.load()
+    n, c4, h, w = out.shape
+    _chk2(out, F32), _chk2(seeds, torch.int32)
+    assert c4 == 4 and out.is_contiguous() and tuple(seeds.shape) == (n, 2) and seeds.is_contiguous() and step >= 0 and region >= 0
+    _lib.check(lib.sdlt_region_noise(seeds.data_ptr(), int(step), int(region), n, h * w, out.data_ptr(), _stream()), "sdlt_region_noise")
+    return out
+
+
 def masked_mse_fwd_bwd(pred, noise, noisy, mask, timesteps, alphas_cumprod, sums, loss_out, dpred, *, snr_gamma, v_prediction=False,
                        loss_scale=1.0):
     lib = _lib.load()

@@ -11,6 +11,7 @@ scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-squ
                                          [--hires-resample nearest|bilinear|bicubic] [--heatmap [WORD ...]] [--heatmap-grid max|min]
                                          [--kv-downsample F [F2 ...]] [--kv-downsample-mode nearest|area] [--kv-downsample-pass hires|all]
                                          [--vae-tile [T]] [--vae-tile-overlap O] [--tile-diffusion [T]] [--tile-diffusion-overlap O]
+                                         [--region MASK.png|x0,y0,x1,y1 PROMPT ...] [--region-feather SIGMA] [--region-base F] [--region-bootstrap SHARE]
                                          [--unet F] [--text-encoder F] [--text-encoder-2 F] [--vae F] [--tokenizer DIR]
 
 DIR is a checkpoint directory of train(): training_args.json (the job's TrainingConfig), adapter_config.json + the kohya adapter file
@@ -88,6 +89,16 @@ exceeds T x T latent units (default: the job's resolution // 8) the UNet runs on
 latent by sdlt_window_blend at every step; guidance and the step launch run on the whole latent as before (sampler.LatentSampler.sample(tile=)).  One
 UNet shape at any picture size, attention cost linear in the picture's area, every window at the size the adapters were trained at.  A pass that fits one
 window - the first pass of a hires render at the model's size - stays plain.  Not with --heatmap.  Without the flag nothing changes.
+
+--region MASK.png|x0,y0,x1,y1 PROMPT (repeatable; "Region Prompt Control" of A1111 / ComfyUI Tiled Diffusion; MultiDiffusion section 4.2) says where
+things go: "--prompt 'a stormy sky' --region 0,0.5,0.5,1 '<concept>' --region 0.5,0.5,1,1 'a red barn'".  A region is a mask picture (white: the region;
+brought to the latent grid the way --mask is) or a box in fractions of the picture, with a prompt of its own - <concept> is allowed, and the prompt takes
+the route the main prompt takes.  --prompt is the background: it rules wherever no region has weight.  The UNet runs the whole latent once per region
+as one batch of 2 N R rows, copied by sdlt_region_gather and fused by sdlt_region_blend with per-pixel weights at every step, inside the replayed graph
+(sampler.LatentSampler.sample(regions=)).  --region-feather SIGMA blurs each mask by a Gaussian of SIGMA latent pixels (sdlt_blur_planes);
+--region-base F gives the main prompt the extra weight F everywhere (default 0); --region-bootstrap SHARE (default 0.2, the paper's; 0: off) is the share
+of the steps at which a region sees a solid colour noised to the step's level outside its mask, so that its object forms inside.  Not with
+--tile-diffusion, --heatmap or --hires-*.  Without the flag nothing changes.
 """
 import argparse
 import json
@@ -119,13 +130,16 @@ class Loaded:
         if self.lora is not None:
             self.stack.unet.arena.load(self.lora)
 
-    def prepare(self, n_images, h, w, keep_decoder=False, plan=None):
+    def prepare(self, n_images, h, w, keep_decoder=False, plan=None, regions=1):
         """The UNet's activation buffers belong to the first latent shape it runs: another batch or size starts from fresh instances.  keep_decoder: the
         VAE decoder is not rebuilt with them (a tiled decode runs at the tile's shape whatever the picture's: prepare_decoder).  plan (a
         sampler.TilePlan): tiled diffusion - the UNet runs at the window's shape on 2 n_images ty tx rows whatever the picture's size, so the shape
-        is the windows' extents and counts: another picture size with the same ones keeps the instances."""
+        is the windows' extents and counts: another picture size with the same ones keeps the instances.  regions (R > 1): regional prompts - the UNet
+        runs at the picture's shape on 2 n_images R rows."""
         shape = (n_images, h, w) if plan is None else (n_images,) + tuple(plan[2:])
         tiles = 1 if plan is None else plan.ty * plan.tx
+        if regions > 1:
+            shape, tiles = (n_images, h, w, "region", regions), regions
         if self.shape is not None and self.shape != shape or n_images != self.stack.n_images or tiles != getattr(self.stack, "tiles", 1):
             self.stack.keep_decoder = keep_decoder
             try:
@@ -376,11 +390,99 @@ def hires_args(hires, size, steps, f=8):
     return dict(size=target, base_size=(int(size[0]), int(size[1])), strength=strength, steps=int(steps2), upscaler=upscaler, resample=resample)
 
 
+REGION_BOOTSTRAP = 0.2      # --region-bootstrap's default: the share of the steps that bootstrap (MultiDiffusion section 4.2)
+REGION_BG_SIZE = 8          # latent units of the solid-colour picture whose encoding is a region's bootstrap background
+
+
+def region_spec(text):
+    """--region's first value -> a box (x0, y0, x1, y1) where it reads as four comma-separated numbers, else the text: a mask picture's path."""
+    parts = text.split(",")
+    if len(parts) == 4:
+        try:
+            return tuple(float(v) for v in parts)
+        except ValueError:
+            pass
+    return text
+
+
+def region_args(regions, region_feather=None, region_base=None, region_bootstrap=None):
+    """render()'s `regions`, `region_feather`, `region_base` and `region_bootstrap`, checked -> None | dict(regions [(mask image | box, prompt)], feather,
+    base, bootstrap).  regions: None, or a non-empty list of (mask image - a path or PIL image - | box (x0, y0, x1, y1) in fractions of the picture with
+    0 <= x0 < x1 <= 1 and 0 <= y0 < y1 <= 1, prompt); at most 7 (sampler.region_plan: 8 with the background).  feather: a Gaussian sigma in latent
+    pixels >= 0 (default 0); base >= 0 (default 0); bootstrap: a share of the steps in [0, 1] (default REGION_BOOTSTRAP).  ValueError otherwise, and
+    for any of the three without regions."""
+    from . import sampler as SM
+    num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)  # noqa: E731
+    if regions is None:
+        if region_feather is not None or region_base is not None or region_bootstrap is not None:
+            raise ValueError("region_feather, region_base and region_bootstrap need regions")
+        return None
+    regions = list(regions)
+    if not regions or len(regions) + 1 > SM.REGION_PLAN_MAX:
+        raise ValueError(f"regions: {len(regions)} region(s); 1 .. {SM.REGION_PLAN_MAX - 1} beside the main prompt's")
+    out = []
+    for item in regions:
+        if not (isinstance(item, (tuple, list)) and len(item) == 2 and isinstance(item[1], str) and item[1].strip()):
+            raise ValueError(f"regions: each entry is (mask image | box, prompt), got {item!r}")
+        where, prompt = item
+        if isinstance(where, (tuple, list)):
+            if not (len(where) == 4 and all(num(v) for v in where) and 0.0 <= where[0] < where[2] <= 1.0 and 0.0 <= where[1] < where[3] <= 1.0):
+                raise ValueError(f"regions: a box is (x0, y0, x1, y1) in fractions of the picture with 0 <= x0 < x1 <= 1 and 0 <= y0 < y1 <= 1, got {where!r}")
+            where = tuple(float(v) for v in where)
+        out.append((where, prompt))
+    feather = 0.0 if region_feather is None else region_feather
+    if not (num(feather) and feather >= 0.0):
+        raise ValueError(f"region_feather must be a finite number >= 0 (latent pixels), got {region_feather!r}")
+    base = 0.0 if region_base is None else region_base
+    if not (num(base) and base >= 0.0):
+        raise ValueError(f"region_base must be a finite number >= 0, got {region_base!r}")
+    boot = REGION_BOOTSTRAP if region_bootstrap is None else region_bootstrap
+    if not (num(boot) and 0.0 <= boot <= 1.0):
+        raise ValueError(f"region_bootstrap must be a share of the steps in [0, 1], got {region_bootstrap!r}")
+    return dict(regions=out, feather=float(feather), base=float(base), bootstrap=float(boot))
+
+
+def region_masks(loaded, rg, size, latent_hw):
+    """The foreground masks of region_args' dict on the latent grid -> fp32 [R - 1, h, w] in [0, 1] on the device: a mask picture by dataset.latent_mask
+    (the way --mask is resized), a box filled between round(x0 w) and round(x1 w) (at least one latent pixel), then each blurred by `feather`
+    (sampler.blur_map)."""
+    from . import dataset as D
+    from . import sampler as SM
+    h, w = latent_hw
+    planes = []
+    for where, _ in rg["regions"]:
+        if isinstance(where, tuple):
+            m = torch.zeros(h, w)
+            x0, y0 = min(int(round(where[0] * w)), w - 1), min(int(round(where[1] * h)), h - 1)
+            m[y0:max(int(round(where[3] * h)), y0 + 1), x0:max(int(round(where[2] * w)), x0 + 1)] = 1.0
+        else:
+            m = D.latent_mask(_open(where), size, (h, w), channels=1).reshape(h, w).float()
+        planes.append(m)
+    masks = torch.stack(planes)[:, None].to(loaded.stack.rt.device)
+    return SM.blur_map(loaded.stack.rt.ops, masks, rg["feather"]).reshape(len(planes), h, w).contiguous()
+
+
+@torch.no_grad()
+def region_backgrounds(loaded, R, seed):
+    """The bootstrap backgrounds -> fp32 [R, 4] on the device: per region one solid colour drawn from `seed`, encoded once by the VAE encoder at a small
+    size (REGION_BG_SIZE latent units), its latent mean over the picture times the scaling factor."""
+    enc = _vae_encoder(loaded)
+    f = 2 ** (len(enc.downs) - 1)
+    colours = torch.rand(R, 3, generator=torch.Generator().manual_seed(seed)) * 2.0 - 1.0
+    dev = loaded.stack.rt.device
+    out = []
+    for r in range(R):
+        img = colours[r].view(1, 3, 1, 1).expand(1, 3, f * REGION_BG_SIZE, f * REGION_BG_SIZE).contiguous().to(dev)
+        out.append(encode_image(loaded, img, enc).float().mean(dim=(0, 2, 3)))
+    return torch.stack(out)
+
+
 @torch.no_grad()
 def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, guidance_scale=8.0, seed=None, images_per_batch=1, token_scale=None,
            graph=True, n_validation=4, init_image=None, strength=None, mask_image=None, sampler="euler", sigmas="trailing", eta=None,
            guidance_rescale=0.0, guidance_interval=None, negative_prompt=None, hires=None, freeu=None, heatmap=None, heatmap_grid="max",
-           kv_downsample=None, kv_downsample_mode="nearest", kv_downsample_pass="hires", vae_tile=None, change_map_image=None, mask_blur=None, tile_diffusion=None):
+           kv_downsample=None, kv_downsample_mode="nearest", kv_downsample_pass="hires", vae_tile=None, change_map_image=None, mask_blur=None, tile_diffusion=None, regions=None, region_feather=None,
+           region_base=None, region_bootstrap=None):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
     seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
@@ -413,6 +515,12 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     tile_diffusion: None, a window length T or (T, overlap) in latent units (sampler.tile_plan; the overlap defaults to T // 4): tiled diffusion -
     LatentSampler.sample's `tile` - in every pass whose latent exceeds T on an axis: the UNet then runs at the window's shape on 2 images_per_batch ty tx
     rows.  A pass that fits one window - the first pass of a hires render at the model's size - stays plain.  Not with heatmap.
+    regions: None, or [(mask image | box (x0, y0, x1, y1) in fractions of the picture, prompt), ...] (region_args): regional prompts -
+    LatentSampler.sample's `regions`.  Every prompt of `prompts` is the background of its picture; each region's prompt is encoded by the route the main
+    prompt takes (trigger substitution, blend_conditions) and rules where its mask has weight: the UNet then runs on 2 images_per_batch R rows.
+    region_feather: a Gaussian sigma in latent pixels that blurs each mask first; region_base: the main prompt's extra weight everywhere;
+    region_bootstrap: the share of the steps that run at which a region sees a solid colour (region_backgrounds, from `seed`) noised to the step's
+    level outside its mask (default 0.2; 0: off).  Not with tile_diffusion, heatmap or hires.
     -> {scale: [paths]}."""
     from . import train as T
     from . import vae as _vae
@@ -444,6 +552,15 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         guidance_interval = tuple(float(v) for v in guidance_interval)
         if len(guidance_interval) != 2 or not guidance_interval[0] < guidance_interval[1]:
             raise ValueError(f"guidance_interval must be (sigma_lo, sigma_hi) with sigma_lo < sigma_hi, got {guidance_interval!r}")
+    rg = region_args(regions, region_feather, region_base, region_bootstrap)      # (raises before anything is built)
+    if rg is not None:
+        for other, name in ((tile_diffusion, "tile_diffusion: windows of regions are not built"), (hires, "hires: the masks would need a second grid"),
+                            (heatmap, "heatmap: the hooked score sums are per region row, and fusing them is not built")):
+            if other is not None:
+                raise ValueError(f"regions do not combine with {name}")
+        SM.require_op(stack.rt.ops, "region_blend", " (sdlt_region_blend): regions copy the model input and fuse the predictions by two launches (ops.region_gather, ops.region_blend)")
+        if rg["feather"] > 0.0:
+            SM.require_op(stack.rt.ops, "blur_planes", ": region_feather blurs the masks on the device by that launch (ops.blur_planes)")
     fz = SM.freeu_args(freeu)                                          # (raises before anything is built)
     hm_names = hm_cols = None
     if heatmap is not None:
@@ -533,7 +650,14 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             img_kw.update(change_map=SM.blur_map(stack.rt.ops, cmap, mask_blur or 0.0))
     td_kw = lambda pl: {} if pl is None else dict(plan=pl)  # noqa: E731
     tile_kw = lambda pl: {} if pl is None else dict(tile=(pl.T, pl.O))  # noqa: E731
-    loaded.prepare(n, h, w, **({} if vt is None else dict(keep_decoder=True)), **td_kw(td_plan))
+    R_ = 1 if rg is None else len(rg["regions"]) + 1
+    reg_kw = None
+    if rg is not None:                                  # masks, backgrounds and the bootstrap's step count: the same for every picture of the render
+        k_run = steps if init_image is None else SM.img2img_steps(steps, strength)[0]
+        k_boot = int(round(rg["bootstrap"] * k_run))
+        reg_kw = dict(masks=region_masks(loaded, rg, size, (h, w)), base=rg["base"], bootstrap=k_boot,
+                      bg=None if k_boot == 0 else region_backgrounds(loaded, R_, seed)[None].expand(n, R_, 4).contiguous())
+    loaded.prepare(n, h, w, **({} if vt is None else dict(keep_decoder=True)), **td_kw(td_plan), **({} if rg is None else dict(regions=R_)))
     fused = hasattr(stack.rt.ops, "sampler_step_dd" if change_map_image is not None else "sampler_step_sde" if sde else "sampler_step_ms" if sampler == "dpmpp_2m"
                     else "sampler_step")
     graph = graph and dev.type == "cuda"
@@ -544,15 +668,17 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         """One batch: latents [n, 4, lh, lw].  px = (width, height) of the size conditioning; seed0 + i keys image i's per-step noise.  heat: with the
         batch's heat maps -> (latents, maps [n, T, gh, gw])."""
         smp = stack.sampler
-        sd = (lambda js: dict(seeds=[seed0 + idx[j] for j in js])) if sde else (lambda js: {})
+        # regional prompts: the same region conditioning for every image of the batch (m images: one list per image; one image: the list itself)
+        rk = lambda m: {} if reg_kw is None else dict(regions=dict(reg_kw, embeds=[reg_embeds] * m if m > 1 else reg_embeds, bg=None if reg_kw["bg"] is None else reg_kw["bg"][:m]))  # noqa: E731
+        sd = (lambda js: dict(seeds=[seed0 + idx[j] for j in js])) if sde or reg_kw is not None else (lambda js: {})      # (regions: the bootstrap's key)
         hm = (lambda js: dict(heatmap=dict(cols=hm_cols[[idx[j] for j in js]], grid=heatmap_grid))) if heat else (lambda js: {})
         if fused:
             return smp.sample([embeds[i] for i in idx] if n > 1 else embeds[idx[0]], lh, lw, steps=steps, guidance_scale=guidance_scale,
-                              size=(px[1], px[0]), latents=noise, graph=graph, fused=True, n_images=n, **kw, **sd(range(n)), **hm(range(n)))
+                              size=(px[1], px[0]), latents=noise, graph=graph, fused=True, n_images=n, **kw, **sd(range(n)), **hm(range(n)), **rk(n))
         # an op table without the fused kernel: the torch loop, image by image
         one = lambda v, j: v[j:j + 1] if torch.is_tensor(v) and v.shape[0] == n and n > 1 else v  # noqa: E731
         outs = [smp.sample(embeds[i], lh, lw, steps=steps, guidance_scale=guidance_scale, size=(px[1], px[0]), latents=noise[j:j + 1],
-                           **{k: one(v, j) for k, v in kw.items()}, **sd([j]), **hm([j])) for j, i in enumerate(idx)]
+                           **{k: one(v, j) for k, v in kw.items()}, **sd([j]), **hm([j]), **rk(1)) for j, i in enumerate(idx)]
         return (torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])) if heat else torch.cat(outs)
 
     def decode(z):
@@ -608,6 +734,7 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         for k, scale in enumerate(lora_scales):
             stack.sampler.set_lora_scale(scale)
             embeds = [stack.conditioning(p, scale, token_scale, negative_prompt)[0] for p in prompts]
+            reg_embeds = [] if rg is None else [stack.conditioning(p, scale, token_scale, negative_prompt)[0] for _, p in rg["regions"]]
             paths = []
             for s0 in range(0, len(prompts), n):
                 idx = [min(s0 + j, len(prompts) - 1) for j in range(n)]          # a short last batch repeats its last prompt
@@ -668,6 +795,9 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             T_, O_ = (tile_diffusion, tile_diffusion // 4) if isinstance(tile_diffusion, int) else tile_diffusion
             pl = td_plan2 if hi is not None else td_plan
             meta.update(tile_diffusion=dict(tile=T_, overlap=O_, tiles=[1, 1] if pl is None else [pl.ty, pl.tx]))
+        if rg is not None:
+            meta.update(regions=[dict(prompt=p, **(dict(box=list(wh)) if isinstance(wh, tuple) else dict(mask=wh if isinstance(wh, str) else None))) for wh, p in rg["regions"]],
+                        region_base=rg["base"], region_bootstrap=rg["bootstrap"], region_feather=rg["feather"])
         json.dump(meta, fh, indent=2)
     return result
 
@@ -729,6 +859,13 @@ def main(argv=None, runtime=None):
                     "on the device at every step - one UNet shape at any picture size (default T: the job's resolution // 8)")
     ap.add_argument("--tile-diffusion-overlap", type=int, default=None, metavar="O",
                     help="with --tile-diffusion: least overlap of neighbouring windows in latent units, 0 <= 2 O <= T (default T // 4)")
+    ap.add_argument("--region", nargs=2, action="append", default=None, metavar=("MASK.png|x0,y0,x1,y1", "PROMPT"),
+                    help="a region with a prompt of its own (repeatable): a mask picture (white: the region) or a box in fractions of the picture; <concept> is "
+                    "allowed in PROMPT; --prompt rules wherever no region has weight")
+    ap.add_argument("--region-feather", type=float, default=None, metavar="SIGMA", help="with --region: blur each mask by a Gaussian of SIGMA latent pixels")
+    ap.add_argument("--region-base", type=float, default=None, metavar="F", help="with --region: extra weight of the main prompt everywhere (default 0)")
+    ap.add_argument("--region-bootstrap", type=float, default=None, metavar="SHARE",
+                    help=f"with --region: share of the steps at which a region sees a noised solid colour outside its mask (default {REGION_BOOTSTRAP}; 0: off)")
     ap.add_argument("--device", default="cuda:0")
     for flag, key, what in (("--unet", "path", "base UNet weights or synthetic:<version>"), ("--text-encoder", "text_encoder_path", "text encoder state dict"),
                             ("--text-encoder-2", "text_encoder_2_path", "SDXL's second text encoder"), ("--vae", "vae_path", "AutoencoderKL state dict"),
@@ -791,6 +928,24 @@ def main(argv=None, runtime=None):
             ap.error(f"--tile-diffusion / --tile-diffusion-overlap: {e}")
     if a.tile_diffusion is not None and a.heatmap is not None:
         ap.error("--tile-diffusion does not combine with --heatmap")
+    regs = {}
+    if a.region is None:
+        if a.region_feather is not None or a.region_base is not None or a.region_bootstrap is not None:
+            ap.error("--region-feather, --region-base and --region-bootstrap need --region")
+    else:
+        for flag, on in (("--tile-diffusion", a.tile_diffusion is not None), ("--heatmap", a.heatmap is not None),
+                         ("--hires-scale / --hires-size", any(v is not None for v in (a.hires_scale, a.hires_size, a.hires_strength, a.hires_steps, a.hires_upscaler, a.hires_resample)))):
+            if on:
+                ap.error(f"--region does not combine with {flag}")
+        regs = dict(regions=[(region_spec(where), prompt) for where, prompt in a.region],
+                    **{k: v for k, v in dict(region_feather=a.region_feather, region_base=a.region_base, region_bootstrap=a.region_bootstrap).items() if v is not None})
+        try:
+            region_args(**regs)
+        except ValueError as e:
+            ap.error(f"--region / --region-feather / --region-base / --region-bootstrap: {e}")
+        for where, _ in regs["regions"]:
+            if isinstance(where, str) and not os.path.exists(where):
+                ap.error(f"--region: {where!r} is neither a box x0,y0,x1,y1 nor a mask picture that exists")
     freeu = None if a.freeu is None else dict(zip(("b1", "b2", "s1", "s2"), a.freeu), version=2 if a.freeu_v2 else 1)
     hires = None
     if a.hires_scale is not None and a.hires_size is not None:
@@ -823,7 +978,7 @@ def main(argv=None, runtime=None):
                  images_per_batch=a.images_per_batch, graph=not a.eager, n_validation=a.n_validation, init_image=a.init_image, strength=a.strength,
                  mask_image=a.mask, sampler=a.sampler, sigmas=a.sigmas, eta=a.eta, guidance_rescale=a.guidance_rescale,
                  guidance_interval=a.guidance_interval, negative_prompt=a.negative_prompt, **({} if hires is None else dict(hires=hires)),
-                 **({} if freeu is None else dict(freeu=freeu)), **kvd, **vtile, **tdiff,
+                 **({} if freeu is None else dict(freeu=freeu)), **kvd, **vtile, **tdiff, **regs,
                  **({} if a.change_map is None else dict(change_map_image=a.change_map)), **({} if a.mask_blur is None else dict(mask_blur=a.mask_blur)),
                  **({} if a.heatmap is None else dict(heatmap=a.heatmap, heatmap_grid=a.heatmap_grid or "max")))
     for scale, paths in res.items():

@@ -504,6 +504,66 @@ def window_multiple(cfg, plan, name="tile"):
                          + (" (the rule the latent size itself obeys without windows)" if name == "tile" else ""))
 
 
+REGION_PLAN_MAX = 8        # regions of sample(regions=) with the background: the UNet batch is 2 n R (the kernels take 16)
+REGION_KEYS = ("masks", "embeds", "base", "bootstrap", "bg")
+
+
+def region_plan(h, w, masks, base=0.0):
+    """The tables of regional prompts for an h x w latent -> ops.RegionTables(wn, wraw, R) on the CPU.  masks [R - 1, h, w] in [0, 1]: the foreground
+    regions (None or empty: R = 1, the background alone); the background's raw weight is clamp(1 - sum of the foregrounds, 0, 1) + base, base >= 0 the
+    main prompt's extra weight everywhere; wn = raw / sum over r, formed in fp64 and rounded once to fp32 - over r it sums to 1 at every pixel, and a
+    pixel whose total raw weight is 0 cannot occur (asserted).  ValueError for masks outside [0, 1], a wrong shape, R > 8, or base < 0."""
+    from . import ops as _ops
+    if masks is not None and torch.is_tensor(masks) and masks.dim() == 3 and masks.shape[0] + 1 > REGION_PLAN_MAX:
+        raise ValueError(f"regions: {masks.shape[0] + 1} regions with the background (at most {REGION_PLAN_MAX}: the UNet batch is 2 n R)")
+    return _ops.region_tables(h, w, masks, base)
+
+
+def region_args(regions, h, w, n, k):
+    """sample()'s `regions`, checked -> None | dict(tabs, embeds, bootstrap, bg).  regions: None, or dict(masks=, embeds=, base=0.0, bootstrap=0,
+    bg=None) - masks [R - 1, h, w] (region_plan), embeds one (c, uc[, pc, puc]) per foreground region per image (one image: the list of R - 1 tuples
+    itself), bootstrap the number of steps that bootstrap (an int >= 0; at most the k that run count), bg fp32 [n, R, 4] or None: zeros.  No foreground
+    mask (R = 1): None - the plain path."""
+    if regions is None:
+        return None
+    unknown = sorted(set(regions) - set(REGION_KEYS))
+    if unknown or "masks" not in regions or "embeds" not in regions:
+        raise ValueError(f"regions: keys masks, embeds and optionally base, bootstrap, bg; unknown {unknown}")
+    masks = regions["masks"]
+    if masks is not None and not torch.is_tensor(masks):
+        masks = torch.as_tensor(np.asarray(masks, dtype=np.float32))
+    tabs = region_plan(h, w, masks, regions.get("base", 0.0))
+    boot = regions.get("bootstrap", 0)
+    if not (isinstance(boot, int) and not isinstance(boot, bool) and boot >= 0):
+        raise ValueError(f"regions: bootstrap must be a step count >= 0, got {boot!r}")
+    R = tabs.R
+    em = regions["embeds"]
+    em = [] if em is None else list(em)
+    per_image = [em] if n == 1 and (not em or torch.is_tensor(em[0][0])) else [list(e) for e in em]
+    if len(per_image) != n or any(len(e) != R - 1 for e in per_image):
+        raise ValueError(f"regions: embeds must hold one (c, uc[, pc, puc]) per foreground region per image: {n} image(s) x {R - 1} region(s)")
+    if R == 1:
+        return None
+    bg = regions.get("bg")
+    if bg is None:
+        bg = torch.zeros(n, R, 4, dtype=F32)
+    bg = torch.as_tensor(bg)
+    if tuple(bg.shape) != (n, R, 4) or not bool(torch.isfinite(bg).all()):
+        raise ValueError(f"regions: bg {tuple(bg.shape)}: expected finite fp32 [{n}, {R}, 4], a background latent per image and region")
+    return dict(tabs=tabs, embeds=per_image, bootstrap=min(boot, k), bg=bg.to(F32).contiguous())
+
+
+def region_rtab(sched, k_boot):
+    """The bootstrap table of ops.region_gather for a scheduler whose set_timesteps has run: fp32 [ops.REGION_TABLE_ROWS, 2], row i < k_boot
+    (sigma_i, 1 / sqrt(sigma_i^2 + 1)) - step_table's factor: fp64 from the fp32 sigma, rounded once - every later row (-1, 0): no bootstrap."""
+    from . import ops as _ops
+    tab = np.zeros((_ops.REGION_TABLE_ROWS, 2), dtype=np.float32)
+    tab[:, 0] = -1.0
+    sig = np.asarray(sched.sigmas[:k_boot], dtype=np.float64)
+    tab[:k_boot, 0], tab[:k_boot, 1] = sig, 1.0 / np.sqrt(sig ** 2 + 1.0)
+    return torch.from_numpy(tab)
+
+
 HEAT_GRIDS = ("max", "min")
 
 
@@ -620,12 +680,12 @@ def step_family(sampler, img, held=False):
     return "sde" if sampler in SDE_KINDS else "multistep" if sampler == "dpmpp_2m" else "euler" if img is None else "img"
 
 
-class Trajectory(collections.namedtuple("Trajectory", "h w steps start sampler sigmas eta seeds guide guidance_scale img hold plan heat size family")):
+class Trajectory(collections.namedtuple("Trajectory", "h w steps start sampler sigmas eta seeds guide guidance_scale img hold plan heat size family reg", defaults=(None,))):
     """sample()'s arguments, checked and resolved once; both drivers (the torch loop, the fused / graph path) take it.  h, w: the latent; steps: those that
     run, from entry `start` of the steps + start entries of the schedule; sampler, sigmas, eta, seeds: as given; guide: None, or guidance_table's
     (scale(s), rescale, interval) - the pre-pass runs; guidance_scale: the scalar of the step itself (1 with the pre-pass: e - e = 0 takes any); img: None
     or (x0, mask | None, start) (_img_args); hold: None or the change map's hold map; plan: None or the TilePlan; heat: None or heatmap_args' dict with
-    its weights; size: (H, W) of SDXL's size conditioning; family: the step launch (FAMILIES)."""
+    its weights; size: (H, W) of SDXL's size conditioning; family: the step launch (FAMILIES); reg: None or region_args' dict (regional prompts)."""
     __slots__ = ()
     masked = property(lambda self: self.img is not None and self.img[1] is not None)
 
@@ -678,7 +738,7 @@ class LatentSampler:
     @torch.no_grad()
     def sample(self, embeds, h, w, *, steps=25, guidance_scale=8.0, generator=None, size=None, latents=None, graph=False, fused=False, n_images=1,
                init_latents=None, strength=1.0, mask=None, sampler="euler", sigmas="trailing", eta=1.0, seeds=None, guidance_rescale=0.0,
-               guidance_interval=None, freeu=None, heatmap=None, kv_downsample=None, kv_downsample_mode=None, change_map=None, tile=None):
+               guidance_interval=None, freeu=None, heatmap=None, kv_downsample=None, kv_downsample_mode=None, change_map=None, tile=None, regions=None):
         """embeds = (c [1,77,D], uc [1,77,D], pc [1,P] | None, puc | None); h, w latent size.  Returns latents [1,4,h,w] fp32
         (still multiplied by the VAE scaling factor, as the pipeline holds them before `vae.decode(latents / scaling_factor)`).
         fused: guidance, the Euler update and the next model input are ONE kernel between two forwards (ops.sampler_step) instead of torch
@@ -726,8 +786,24 @@ class LatentSampler:
         stepping once on the fused prediction equals stepping every window and averaging.  Every window row of an image carries that image's
         conditioning (SDXL: the whole picture's size).  On all three paths, with every sampler; freeu and kv_downsample act per window.  Starts and
         weights are device memory: one capture per (shape, window counts) serves every overlap.  A latent that fits one window (h <= T and w <= T) is the
-        plain path: the same launches and bits as without `tile`.  Not with heatmap (the hooked score sums are per window)."""
+        plain path: the same launches and bits as without `tile`.  Not with heatmap (the hooked score sums are per window).
+        regions: None, or dict(masks=, embeds=, base=0.0, bootstrap=0, bg=None) (region_args): regional prompts (MultiDiffusion section 4.2).  masks
+        [R - 1, h, w] in [0, 1] are the foreground regions, embeds one (c, uc[, pc, puc]) per foreground region per image; the call's own `embeds` is
+        region 0, the background.  The UNet runs the whole latent once per region as ONE batch of 2 n_images R rows - the sampler is built on a
+        runtime of that batch (LatentSampler(n_images=)) - between two launches: ops.region_gather copies the model input to every region's rows,
+        ops.region_blend fuses their predictions with the normalised per-pixel weights (region_plan; base: the main prompt's extra weight
+        everywhere).  Batch row 2 (j R + r) + 1 carries region r's positive conditioning, every even row the call's negative one; SDXL's size
+        conditioning stays the whole picture's.  bootstrap = k: at the first min(k, steps that run) steps a foreground region's model input is
+        replaced, outside its mask (raw weight < 0.5), by a constant background bg [n_images, R, 4] (None: zeros) noised to the step's level - made
+        inside the gather launch from the image's seed (`seeds`, as the stochastic samplers; None: drawn from `generator`), the step, the region and
+        the pixel - so that the region's object forms inside its mask.  Guidance, the step launch, init latents, mask, change map and the per-step
+        noise stay at full size and unchanged; freeu and kv_downsample act per row.  On all three paths, with every sampler.  Masks, weights, bg and
+        the bootstrap length are device memory: one capture per (shape, R) serves all of them.  No foreground mask (R = 1) is the plain path: the
+        same launches, bits and capture key as without `regions`.  Not with tile or heatmap."""
         ops = self.rt.ops
+        if regions is not None and (tile is not None or heatmap is not None):      # refused before anything is built
+            raise ValueError("regions do not combine with " + ("tile: windows of regions are not built" if tile is not None else
+                                                               "heatmap: the hooked score sums are per region row, and fusing them is not built"))
         plan = tile_plan(h, w, tile)                        # refused before anything is built
         if plan is not None:
             if heatmap is not None:
@@ -736,9 +812,17 @@ class LatentSampler:
             for op in ("window_blend", "window_gather"):
                 require_op(ops, op, " (sdlt_window_blend): sample(tile=...) cuts and fuses the windows by two launches (ops.window_gather, "
                            "ops.window_blend), in the torch loop too", kernel="window_blend")
-        if (1 if plan is None else plan.ty * plan.tx) != self.tiles:
+        reg = None
+        if regions is not None:                            # (the step count of the bootstrap is cut to the steps that run below)
+            reg = region_args(regions, h, w, n_images, TABLE_ROWS)
+        if reg is not None:
+            for op in ("region_blend", "region_gather"):
+                require_op(ops, op, " (sdlt_region_blend): sample(regions=...) copies the model input to the regions' rows and fuses their predictions "
+                           "by two launches (ops.region_gather, ops.region_blend), in the torch loop too", kernel="region_blend")
+        rows = reg["tabs"].R if reg is not None else 1 if plan is None else plan.ty * plan.tx
+        if rows != self.tiles:
             raise ValueError(f"this sampler's runtime holds {self.tiles} window(s) per image (batch {self.rt.B}, {self.n} image(s)); the call needs "
-                             f"{1 if plan is None else plan.ty * plan.tx}: build it on a runtime of batch 2 n_images ty tx (LatentSampler(n_images=))")
+                             f"{rows}: build it on a runtime of batch 2 n_images ty tx (LatentSampler(n_images=))")
         if change_map is not None:                         # refused before anything is built
             if init_latents is None:
                 raise ValueError("change_map needs init_latents: a held pixel follows their noised trajectory")
@@ -767,7 +851,8 @@ class LatentSampler:
                        "in the torch loop too")
         assert 1 <= steps <= TABLE_ROWS - 2
         traj = Trajectory(h, w, steps - start, start, sampler, sigmas, eta, seeds, guide, guidance_scale if guide is None else 1.0, img, hold, plan, hm,
-                          size if size is not None else (8 * h, 8 * w), step_family(sampler, img, hold is not None))
+                          size if size is not None else (8 * h, 8 * w), step_family(sampler, img, hold is not None),
+                          None if reg is None else dict(reg, bootstrap=min(reg["bootstrap"], steps - start)))
         if graph or fused:
             if traj.family == "sde":
                 require_op(ops, "sampler_step_sde", f": sample(sampler={sampler!r}) draws its per-step noise inside that launch")
@@ -792,7 +877,7 @@ class LatentSampler:
         st, sh, x0, noise, heat = self._begin(traj, s, embeds, latents, generator)
         x = noise * s.init_noise_sigma if traj.img is None else x0 + noise * float(s.sigmas[0])
         m, hold = sh["img"]["mask"] if traj.masked else None, None if traj.hold is None else sh["img"]["hold"]
-        sde, counted = traj.sampler in SDE_KINDS, heat is not None or traj.guide is not None
+        sde, counted = traj.sampler in SDE_KINDS, heat is not None or traj.guide is not None or traj.reg is not None      # (the gather reads the bootstrap's row)
         if sde:
             z = rt.zeros(1, 4, h, w, dtype=F32)
         if heat is not None and heat["heat"] is not None:
@@ -869,19 +954,49 @@ class LatentSampler:
             return contextlib.nullcontext()
         return own(id(self))
 
-    def _state(self, h, w, plan=None):
-        """plan (a TilePlan): the shape's state is keyed by the window extents and counts as well, and holds the windows' buffers (_window_state)."""
+    def _state(self, h, w, plan=None, reg=None):
+        """plan (a TilePlan): the shape's state is keyed by the window extents and counts as well, and holds the windows' buffers (_window_state); reg
+        (region_args' dict): by the region count, and holds the regions' buffers (_region_state)."""
         rt, n = self.rt, self.n
         if self._fused is None:      # (tid: one row of six per UNET batch row - 2 n without windows)
             self._fused = dict(tf=rt.zeros(2 * n, dtype=F32), tid=rt.zeros(rt.B * 6, dtype=F32), table=rt.zeros(TABLE_ROWS, 4, dtype=F32),
                                ctr=torch.zeros(2, dtype=torch.int32, device=rt.device), shapes={})
         st = self._fused
-        key = (h, w) if plan is None else (h, w) + tuple(plan[2:])
+        key = (h, w, "region", reg["tabs"].R) if reg is not None else (h, w) if plan is None else (h, w) + tuple(plan[2:])
         if key not in st["shapes"]:
             st["shapes"][key] = dict(x=rt.zeros(n, 4, h, w, dtype=F32), x64=rt.zeros(2 * n * h * w, 64))
         if plan is not None:
             self._window_state(st["shapes"][key], h, w, plan)
+        if reg is not None:
+            self._region_state(st["shapes"][key], h, w, reg)
         return st, st["shapes"][key]
+
+    def _region_state(self, sh, h, w, reg):
+        """-> sh["reg"]: the persistent buffers of regional prompts for this shape - the regions' model input x64_regions and timesteps tf_regions, the
+        fused prediction eps_full fp32 [2 n h w, 4], the tables wn and wraw, the backgrounds bg and the bootstrap table rtab - allocated once (a
+        captured launch holds their pointers); weights, masks and backgrounds are rewritten per call (rtab: by _begin, which knows the schedule):
+        another mask set with the same region count is the same buffers and the same capture."""
+        rt, n, fresh = self.rt, self.n, reg["tabs"]
+        rs = sh.get("reg")
+        if rs is None:
+            from . import ops as _ops
+            tabs = fresh._replace(wn=torch.zeros_like(fresh.wn, device=rt.device), wraw=torch.zeros_like(fresh.wraw, device=rt.device))
+            rs = sh["reg"] = dict(tabs=tabs, x64_regions=rt.zeros(rt.B * h * w, 64), tf_regions=rt.zeros(rt.B, dtype=F32),
+                                  eps_full=rt.zeros(2 * n * h * w, 4, dtype=F32), bg=rt.zeros(n, fresh.R, 4, dtype=F32),
+                                  rtab=rt.zeros(_ops.REGION_TABLE_ROWS, 2, dtype=F32))
+        rs["tabs"].wn.copy_(fresh.wn)
+        rs["tabs"].wraw.copy_(fresh.wraw)
+        rs["bg"].copy_(reg["bg"])
+        return rs
+
+    def _region_forward(self, rs, st, x64, tf, tid, h, w):
+        """The forward of regional prompts: copy the model input to every region's rows (bootstrap: with the background outside a foreground's mask),
+        run the UNet on them as one batch, fuse the predictions -> eps fp32 [2 n h w, 4], the prediction for the whole latent."""
+        rt = self.rt
+        boot = dict(bg=rs["bg"], rtab=rs["rtab"], ctr=st["ctr"], seeds=st["seeds"])
+        rt.ops.region_gather(rs["tabs"], x64, rs["x64_regions"], tf, rs["tf_regions"], n=self.n, H=h, W=w, boot=boot)
+        e = self.unet.forward(rs["x64_regions"], rs["tf_regions"], self.ctx, self.pooled, tid, B=rt.B, H=h, W=w, **self._fwd_kw())
+        return rt.ops.region_blend(rs["tabs"], e, rs["eps_full"], n=self.n, H=h, W=w)
 
     def _window_state(self, sh, h, w, plan):
         """-> sh["win"]: the persistent buffers of tiled diffusion for this shape - the windows' model input x64_tiles and timesteps tf_tiles, the fused
@@ -908,9 +1023,11 @@ class LatentSampler:
         e = self.unet.forward(win["x64_tiles"], win["tf_tiles"], self.ctx, self.pooled, tid, B=rt.B, H=plan.th, W=plan.tw, **self._fwd_kw())
         return rt.ops.window_blend(win["tabs"], e, win["eps_full"], n=self.n, H=h, W=w)
 
-    def _load_conditioning(self, st, embeds, size):
+    def _load_conditioning(self, st, embeds, size, reg=None):
         """embeds: one (c, uc[, pc, puc]) per image (one image: the tuple itself) -> ctx, pooled and SDXL's size conditioning st["tid"].  UNet batch rows
-        2 j tl .. 2 (j + 1) tl - 1 are image j's, (negative, positive) per window: every window row carries the image's conditioning."""
+        2 j tl .. 2 (j + 1) tl - 1 are image j's, (negative, positive) per window: every window row carries the image's conditioning.  reg (regional
+        prompts: tl = R): row 2 (j R + r) + 1 then takes region r's positive context and pooled vector for r >= 1; every even row keeps the call's
+        negative ones."""
         rt, cfg, n, tl = self.rt, self.unet.cfg, self.n, self.tiles
         per_image = [embeds] if (n == 1 and not isinstance(embeds[0], (tuple, list))) else list(embeds)
         assert len(per_image) == n, "one (c, uc[, pc, puc]) per image"
@@ -923,6 +1040,11 @@ class LatentSampler:
                 pv = self.pooled.view(n, tl, 2, -1)
                 pv[j, :, 0].copy_(puc[0])
                 pv[j, :, 1].copy_(pc[0])
+            for r, er in enumerate(reg["embeds"][j] if reg is not None else (), start=1):
+                cr, _, pcr, _ = (tuple(er) + (None, None))[:4]
+                cv[j, r, 1, :77].copy_(cr[0])
+                if cfg["addition"]:
+                    pv[j, r, 1].copy_(pcr[0])
         if cfg["addition"]:
             H, W = size
             st["tid"].copy_(torch.tensor([float(H), float(W), 0.0, 0.0, float(H), float(W)] * rt.B))      # original_size, crop, target_size
@@ -934,8 +1056,10 @@ class LatentSampler:
         -> (st, sh, x0 | None, noise, heat | None): x0 and noise as the init launch takes them, heat the dict of sh["heat"] for these columns."""
         rt, n, h, w = self.rt, self.n, traj.h, traj.w
         dev = rt.device
-        st, sh = self._state(h, w, traj.plan)
-        self._load_conditioning(st, embeds, traj.size)
+        st, sh = self._state(h, w, traj.plan, traj.reg)
+        self._load_conditioning(st, embeds, traj.size, traj.reg)
+        if traj.reg is not None:                          # the bootstrap's rows of the steps that run; a captured gather holds the buffer
+            sh["reg"]["rtab"].copy_(region_rtab(sch, traj.reg["bootstrap"]))
         if traj.guide is not None:                        # a persistent buffer, rewritten per trajectory: a captured pre-pass holds its pointer
             gtab = guidance_table(sch, *traj.guide)
             if "gtab" not in st:
@@ -944,7 +1068,7 @@ class LatentSampler:
         noise = latents if latents is not None else torch.randn(n, 4, h, w, generator=generator, device=dev, dtype=F32)
         noise = noise.to(dev, F32).contiguous()
         assert tuple(noise.shape) == (n, 4, h, w)
-        if traj.sampler in SDE_KINDS:                     # after the initial latents; a captured launch holds the buffer
+        if traj.sampler in SDE_KINDS or traj.reg is not None:      # after the initial latents; a captured launch holds the buffer (regions: the bootstrap's key)
             if "seeds" not in st:
                 st["seeds"] = torch.zeros(n, 2, dtype=torch.int32, device=dev)
             st["seeds"].copy_(seed_words(traj.seeds, n, generator, dev))
@@ -982,13 +1106,15 @@ class LatentSampler:
 
     def _predict(self, st, sh, traj, heat):
         """The forward stage of one iteration, on either driver: the UNet on sh["x64"] at st["tf"] - with a tile plan: gather, the forward on the windows,
-        blend - then ops.heatmap_accum on the forward's score sums (heat, a dict of sh["heat"]: the weight of row ctr[0] of st["hw"]; the maps are
+        blend; with regions: gather, the forward on every region's rows, blend - then ops.heatmap_accum on the forward's score sums (heat, a dict of sh["heat"]: the weight of row ctr[0] of st["hw"]; the maps are
         allocated at the first iteration, when the forward has told the resolutions), then ops.guidance (row ctr[0] of st["gtab"]) where the pre-pass
         runs -> eps fp32 [2 n h w, 4]."""
         u, h, w = self.unet, traj.h, traj.w
         tid = st["tid"] if u.cfg["addition"] else None
         if traj.plan is not None:
             eps = self._window_forward(sh["win"], sh["x64"], st["tf"], tid, h, w)
+        elif traj.reg is not None:
+            eps = self._region_forward(sh["reg"], st, sh["x64"], st["tf"], tid, h, w)
         else:
             eps = u.forward(sh["x64"], st["tf"], self.ctx, self.pooled, tid, B=2 * self.n, H=h, W=w, **self._fwd_kw())
         if heat is not None:
@@ -1034,6 +1160,8 @@ class LatentSampler:
             key += (("kv_downsample",) + kd,)
         if "win" in sh:                                   # tiled diffusion: the window extents and counts; starts and weights are device memory
             key += (("tile",) + tuple(sh["win"]["plan"][2:]),)
+        if traj.reg is not None:                          # regional prompts: the region count; masks, weights, backgrounds and the bootstrap table are device memory
+            key += (("region", traj.reg["tabs"].R),)
         graphs = getattr(self, f.graphs)
         if guided:
             key, graphs = key + (fam,), self._guided_graphs
