@@ -1841,10 +1841,12 @@ def _count_paired(ops, gens, prefer):
                                         (dict(SDLT_XATTN_ROLES="0", SDLT_XATTN_FIVE="0"), "file:test_attn_exact_gpu.py:test_"),
                                         (dict(SDLT_ATTN_XCD="0", SDLT_ATTN_KS="1", SDLT_ATTN_R32="0"), "file:test_attn_exact_gpu.py:test_"),
                                         (dict(SDLT_ATTN32_KS_FWD="4", SDLT_ATTN32_KS_BWD="4"), "file:test_attn_exact_gpu.py:test_"),
-                                        (dict(SDLT_ATTN32_KS_FWD="1", SDLT_ATTN32_KS_BWD="1"), "file:test_attn_exact_gpu.py:test_")],
+                                        (dict(SDLT_ATTN32_KS_FWD="1", SDLT_ATTN32_KS_BWD="1"), "file:test_attn_exact_gpu.py:test_"),
+                                        # the bit-exact wave-split-K / row-strip file: unstaggered refills, N = 2304 on the 16-column strips
+                                        (dict(SDLT_WSK_STAGGER="0", SDLT_STRIP_WIDE_MIN="4096"), "file:test_wsk_exact_gpu.py:test_")],
                          ids=["single-role", "single-role-128-keys", "plain-order-unsplit-16-rows", "attn32-four-groups", "attn32-one-group", "unstaggered-narrow-strips",
                               "layernorm-fold-every-width-k-walk-statistics", "layernorm-launches", "exact-single-role", "exact-single-role-128-keys",
-                              "exact-plain-order-unsplit-16-rows", "exact-attn32-four-groups", "exact-attn32-one-group"])
+                              "exact-plain-order-unsplit-16-rows", "exact-attn32-four-groups", "exact-attn32-one-group", "exact-unstaggered-narrow-strips"])
 def test_fallback_kernel_paths_in_a_subprocess(env, select):
     """The A/B switches are read once per process, so the non-default kernels behind them (single-role / 128-key cross-attention backward,
     plain workgroup order, unsplit attention forward, unstaggered wave-split-K refills, 16-column strips; step level: the LayerNorm fold at every
