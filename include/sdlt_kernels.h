@@ -732,6 +732,45 @@ typedef struct sdlt_guidance_params {
 } sdlt_guidance_params;
 int sdlt_guidance(const sdlt_guidance_params* p, void* stream);
 
+/* sdlt_guidance_apg : adaptive projected guidance (Sadat et al. 2024, "Eliminating Oversaturation and Artifacts of High Guidance Scales") as the
+ * guidance pre-pass, issued where sdlt_guidance would be: it rewrites eps in place so that both row blocks of image j hold the final prediction e.
+ * eps, gtab, ctr, n, hw, gtab_rows as in sdlt_guidance_params.  atab fp32 [gtab_rows, 4]: row 1 + i = (eta_i, tau_i, beta_i, 0) (row 0 is not read).
+ * mom fp32 [n * hw, 4]: the running average of the update, one row per pixel of image j at rows j hw ..; may be null, and then no momentum is applied
+ * whatever atab holds.  With i = ctr[0] clamped to 0 .. k - 1 (read, never written), (g, phi) from gtab and (eta, tau, beta) from atab, per image, fp32,
+ * one rounding per operation, in the order written:
+ *     g == 1:          e = e_pos exactly; mom is neither read nor written
+ *     otherwise        d = e_pos - e_neg
+ *     beta != 0:       m = d + beta m_prev, with m_prev = +0 at i == 0 (the buffer is NOT read there: whatever it holds, a NaN included, changes no
+ *     (and mom given)  bit of row 0 - this is the reset between two trajectories, inside the launch);  m is stored to mom;  d = m
+ *     sums             S_dd = sum d d ;  S_dp = sum d e_pos ;  S_pp = sum e_pos e_pos   over the image's 4 hw values, in ONE pass, all of the
+ *                      UNCLIPPED d: the clipped update's dot product is c S_dp, and its norm is not needed again
+ *     norm clip        c = min(1, tau / sqrt(S_dd)) where tau > 0 and S_dd != 0, else c = 1 ;  d = c d   (c = 1 multiplies too: no bit changes)
+ *     projection       a = (c S_dp) / S_pp, and a = 0 where S_pp == 0
+ *                      par = a e_pos ;  orth = d - par ;  e_c = e_pos + (g - 1) (orth + eta par)
+ *     phi == 0:        e = e_c
+ *     otherwise        sdlt_guidance's rescale on e_c, the same definitions: s_pos, s_c unbiased standard deviations about the mean, r = s_pos / s_c
+ *                      (r = 1 where s_c == 0), e = phi (e_c r) + (1 - phi) e_c
+ * This is diffusers' normalized_guidance(pred_cond = e_pos, pred_uncond = e_neg, guidance_scale = g, momentum_buffer, eta, norm_threshold = tau)
+ * with MomentumBuffer(momentum = beta): there the buffer starts at 0 and update() forms running_average = diff + momentum * running_average - m above;
+ * the clip is diff * min(1, norm_threshold / ||diff||) - c above (the published code divides by a zero norm; here c = 1); with v1 = e_pos / ||e_pos||
+ * its parallel part (diff . v1) v1 is ((diff . e_pos) / (e_pos . e_pos)) e_pos = a e_pos (the published normalize() clamps the norm at 1e-12; here
+ * a = 0 at e_pos = 0, the same result); pred_guided = pred_cond + (g - 1) (orthogonal + eta parallel).  The published function projects in fp64; this
+ * one in fp32.  (eta, tau, beta) = (1, 0, 0) is classifier-free guidance mathematically (e_pos + (g - 1) d), not bit for bit: sdlt_guidance forms
+ * e_neg + g d.  One workgroup per image and a fixed summation order (sdlt_guidance's): image j's result depends on neither n nor j and repeats bit for bit.
+ * Table contents are only values: whatever they hold, every access stays inside eps, mom and the rows of the tables.
+ * Null eps, gtab, atab or ctr, n < 1, hw < 1, gtab_rows < 2, mom overlapping eps (-1); eps or mom not 16-byte aligned, a table or ctr not 4-byte aligned
+ * (-2): the code is returned, sdlt_last_error names the entry point and nothing is launched.  The block is declared without a struct tag, like
+ * sdlt_resize_params, and has no index in sdlt_struct_size(): 56 bytes, five pointers and four int32, no padding between fields. */
+typedef struct {
+  float* eps;                        /* fp32 [2n * hw, 4]: UNet.forward's output, rewritten in place */
+  const float* gtab;                 /* fp32 [gtab_rows, 4] */
+  const float* atab;                 /* fp32 [gtab_rows, 4] */
+  float* mom;                        /* fp32 [n * hw, 4] or null */
+  const int32_t* ctr;                /* int32 [>= 1]: ctr[0] = step row, read only */
+  int32_t n, hw, gtab_rows, pad_;
+} sdlt_guidance_apg_params;
+int sdlt_guidance_apg(const sdlt_guidance_apg_params* p, void* stream);
+
 /* sdlt_resize_planes : out fp32 [planes, H, W] = in fp32 [planes, h, w] resampled, both contiguous, out not overlapping in.  The step between the two
  * passes of a hires render (render.py: `hires`): the first pass's latents [n, 4, h, w] (planes = 4 n, planes_per_image = 4) or the decoder's image
  * [n, 3, 8h, 8w] (planes_per_image = 3) enlarged before the second pass re-noises them.  planes_per_image consecutive planes are one image: its

@@ -1348,6 +1348,25 @@ def guidance(eps, gtab, ctr, n):
     return eps
 
 
+def guidance_apg(eps, gtab, atab, mom, ctr, n):
+    """sdlt_guidance_apg: adaptive projected guidance (Sadat et al. 2024; diffusers' normalized_guidance) as the pre-pass, in ops.guidance's place.
+    eps, gtab, ctr, n as there; atab fp32 [gtab's rows, 4] (sampler.apg_table: row 1 + i = (eta_i, tau_i, beta_i, 0)); mom fp32 [n hw, 4], the running
+    average of the update - written at every step with beta_i != 0, read at every such step but step row 0, so a trajectory needs no reset - or None:
+    no momentum.  The order of operations: include/sdlt_kernels.h."""
+    lib = _lib.load()
+    _chk2(eps, F32), _chk2(gtab, F32), _chk2(atab, F32), _chk2(ctr, torch.int32)
+    assert eps.dim() == 2 and eps.shape[1] == 4 and eps.is_contiguous() and n >= 1 and eps.shape[0] % (2 * n) == 0 and eps.shape[0] >= 2 * n
+    assert gtab.dim() == 2 and gtab.shape[1] == 4 and gtab.shape[0] >= 2 and gtab.is_contiguous() and ctr.numel() >= 1
+    assert tuple(atab.shape) == tuple(gtab.shape) and atab.is_contiguous(), "atab: one row per row of gtab"
+    if mom is not None:
+        _chk2(mom, F32)
+        assert tuple(mom.shape) == (eps.shape[0] // 2, 4) and mom.is_contiguous(), "mom: fp32 [n hw, 4]"
+    p = _lib.GuidanceApgParams(eps=eps.data_ptr(), gtab=gtab.data_ptr(), atab=atab.data_ptr(), mom=None if mom is None else mom.data_ptr(), ctr=ctr.data_ptr(),
+                               n=n, hw=eps.shape[0] // (2 * n), gtab_rows=gtab.shape[0])
+    _lib.check(lib.sdlt_guidance_apg(C.byref(p), _stream()), "sdlt_guidance_apg")
+    return eps
+
+
 def resize_planes(src, out, mode):
     """sdlt_resize_planes: out fp32 [n, c, H, W] = src fp32 [n, c, h, w] resampled with PyTorch's align_corners=False conventions - mode 0 nearest-exact,
     1 bilinear, 2 bicubic (Keys, A = -0.75), the arithmetic in the order include/sdlt_kernels.h writes down (tests/hires_ref.py gives the same bits).

@@ -6,6 +6,7 @@ scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-squ
                                          [--steps N] [--guidance G] [--seed S] [--images-per-batch N] [--eager]
                                          [--init-image PATH [--strength S] [--mask PATH | --change-map PATH] [--mask-blur SIGMA]] [--sampler euler|dpmpp_2m|euler_a|dpmpp_2m_sde] [--eta F]
                                          [--sigmas trailing|karras] [--guidance-rescale F] [--guidance-interval SIGMA_LO SIGMA_HI]
+                                         [--apg [--apg-eta F] [--apg-norm-threshold F] [--apg-momentum F]]
                                          [--negative-prompt TEXT] [--freeu B1 B2 S1 S2 [--freeu-v2]]
                                          [--hires-scale F | --hires-size W H] [--hires-strength F] [--hires-steps N] [--hires-upscaler latent|pixel]
                                          [--hires-resample nearest|bilinear|bicubic] [--heatmap [WORD ...]] [--heatmap-grid max|min]
@@ -46,6 +47,16 @@ F (Lin et al. 2024, section 3.4; diffusers' guidance_rescale): it takes the over
 it.  --guidance-interval SIGMA_LO SIGMA_HI applies guidance only at the steps whose noise level lies in (SIGMA_LO, SIGMA_HI] (Kynkaanniemi et al.
 2024).  Both are evaluated by one more launch per iteration (sdlt_guidance) inside the replayed graph; without them nothing changes.
 --negative-prompt TEXT replaces the fixed negative prompt of the training-time renders.
+
+--apg is adaptive projected guidance (Sadat et al. 2024, "Eliminating Oversaturation and Artifacts of High Guidance Scales"; diffusers'
+normalized_guidance, ComfyUI's APG node), the fix for the burnt contrast of a strong --guidance that works before the damage is done: the guidance update
+e_pos - e_neg is averaged over the steps with a negative momentum, its norm over the image is clipped, and its part parallel to the positive prediction -
+the part that drives saturation - is scaled down.  The defaults are the paper's SDXL settings: --apg-eta 0 (the parallel part is dropped; 1 keeps it),
+--apg-norm-threshold 15 (0: no clip), --apg-momentum -0.5 (0: none); the three flags are errors without --apg.  One launch (sdlt_guidance_apg) in
+sdlt_guidance's place inside the replayed graph, the running average in a device buffer the launch restarts at the first step, so it needs no weights and
+no host work.  It works on the noise prediction (the paper and ComfyUI project the denoised value).  With every sampler, noise schedule,
+--guidance-rescale, --guidance-interval, --init-image / --mask / --change-map, --tile-diffusion, --region and --heatmap; both passes of a hires render
+use it, each with a running average of its own.  Without the flag nothing changes.
 
 --hires-scale F / --hires-size W H render in two passes (the "hires fix"): a picture much larger than the model was trained for falls apart when it is
 sampled in one go (doubled subjects, tiled compositions), so the first pass samples at --size, the result is enlarged on the device
@@ -250,6 +261,30 @@ def load_for_inference(checkpoint_dir, pretrained_model=None, device="cuda:0", r
     loaded = Loaded(config, models, stack, checkpoint_dir, lora, te_lora or None, rows)
     loaded.load_adapters()
     return loaded
+
+
+APG_DEFAULT = (0.0, 15.0, -0.5)      # eta, norm threshold, momentum: the SDXL settings of Sadat et al. 2024 (quoted from memory)
+APG_KEYS = ("eta", "norm_threshold", "momentum")
+
+
+def apg_args(apg):
+    """render()'s `apg`, checked -> None | (eta, norm_threshold, momentum).  None or False: off; True: APG_DEFAULT; three numbers in that order, or a dict
+    with any of the keys eta, norm_threshold, momentum (the others: APG_DEFAULT's).  The ranges are sampler.apg_table's."""
+    from . import sampler as SM
+    if apg is None or apg is False:
+        return None
+    if apg is True:
+        apg = APG_DEFAULT
+    elif isinstance(apg, dict):
+        unknown = sorted(set(apg) - set(APG_KEYS))
+        if unknown:
+            raise ValueError(f"apg: keys {', '.join(APG_KEYS)}; unknown {unknown}")
+        apg = tuple(apg.get(k, d) for k, d in zip(APG_KEYS, APG_DEFAULT))
+    if not (isinstance(apg, (tuple, list)) and len(apg) == 3 and all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in apg)):
+        raise ValueError(f"apg takes True, (eta, norm_threshold, momentum) or a dict of them, got {apg!r}")
+    apg = tuple(float(v) for v in apg)
+    SM.apg_table(None, apg, 1)                          # (the ranges)
+    return apg
 
 
 def _scale_tag(s):
@@ -482,7 +517,7 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
            graph=True, n_validation=4, init_image=None, strength=None, mask_image=None, sampler="euler", sigmas="trailing", eta=None,
            guidance_rescale=0.0, guidance_interval=None, negative_prompt=None, hires=None, freeu=None, heatmap=None, heatmap_grid="max",
            kv_downsample=None, kv_downsample_mode="nearest", kv_downsample_pass="hires", vae_tile=None, change_map_image=None, mask_blur=None, tile_diffusion=None, regions=None, region_feather=None,
-           region_base=None, region_bootstrap=None):
+           region_base=None, region_bootstrap=None, apg=None):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
     seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
@@ -491,6 +526,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     "dpmpp_2m" | "euler_a" | "dpmpp_2m_sde", sigmas "trailing" | "karras", eta (stochastic samplers only; default 1): LatentSampler.sample's; the
     per-step noise of image i is keyed by seed + i, like its initial latents.  guidance_rescale in [0, 1], guidance_interval (sigma_lo, sigma_hi):
     LatentSampler.sample's; negative_prompt: the negative row's text (None: prompts.NEGATIVE_PROMPT).
+    apg: None, True (APG_DEFAULT), (eta, norm_threshold, momentum) or a dict of them (apg_args): adaptive projected guidance - LatentSampler.sample's
+    `apg` - in every pass, of a hires render too (each pass is a trajectory of its own: the running average restarts); with everything else.
     hires (a dict, hires_args: scale | size, strength, steps, upscaler, resample): two passes - every image is first sampled at `size`, for all adapter
     scales and prompt batches, its latents staying on the device; they are enlarged (sampler.upscale_latents: the latents, or with upscaler "pixel"
     the decoded picture, encoded again); then the UNet is rebuilt ONCE for the large shape and every second pass runs: sample(init_latents=the
@@ -552,6 +589,9 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         guidance_interval = tuple(float(v) for v in guidance_interval)
         if len(guidance_interval) != 2 or not guidance_interval[0] < guidance_interval[1]:
             raise ValueError(f"guidance_interval must be (sigma_lo, sigma_hi) with sigma_lo < sigma_hi, got {guidance_interval!r}")
+    ag = apg_args(apg)                                                 # (raises before anything is built)
+    if ag is not None:
+        SM.require_op(stack.rt.ops, "guidance_apg", " (sdlt_guidance_apg): apg forms the projected prediction by that launch (ops.guidance_apg)", kernel="sdlt_guidance_apg")
     rg = region_args(regions, region_feather, region_base, region_bootstrap)      # (raises before anything is built)
     if rg is not None:
         for other, name in ((tile_diffusion, "tile_diffusion: windows of regions are not built"), (hires, "hires: the masks would need a second grid"),
@@ -624,6 +664,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         img_kw.update(guidance_rescale=guidance_rescale)
     if guidance_interval is not None:
         img_kw.update(guidance_interval=guidance_interval)
+    if ag is not None:
+        img_kw.update(apg=ag)
     if (sampler, sigmas) != ("euler", "trailing"):
         img_kw.update(sampler=sampler, sigmas=sigmas)
     if sde:
@@ -779,6 +821,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             meta.update(guidance_rescale=guidance_rescale)
         if guidance_interval is not None:
             meta.update(guidance_interval=list(guidance_interval))
+        if ag is not None:
+            meta.update(apg=dict(zip(APG_KEYS, ag)))
         if negative_prompt is not None:
             meta.update(negative_prompt=negative_prompt)
         if hi is not None:
@@ -829,6 +873,11 @@ def main(argv=None, runtime=None):
     ap.add_argument("--guidance-rescale", type=float, default=0.0, help="rescale the guided prediction to the positive one's standard deviation, blended with this weight in [0, 1] (default 0: off)")
     ap.add_argument("--guidance-interval", type=float, nargs=2, metavar=("SIGMA_LO", "SIGMA_HI"), default=None,
                     help="apply guidance only at the steps whose noise level lies in (SIGMA_LO, SIGMA_HI]")
+    ap.add_argument("--apg", action="store_true", help="adaptive projected guidance (Sadat et al. 2024): project, clip and average the guidance update; "
+                    f"defaults eta {APG_DEFAULT[0]:g}, norm threshold {APG_DEFAULT[1]:g}, momentum {APG_DEFAULT[2]:g}")
+    ap.add_argument("--apg-eta", type=float, default=None, metavar="F", help="with --apg: weight of the update's part parallel to the positive prediction, in [0, 1]")
+    ap.add_argument("--apg-norm-threshold", type=float, default=None, metavar="F", help="with --apg: bound of the update's norm over the image, >= 0 (0: no clip)")
+    ap.add_argument("--apg-momentum", type=float, default=None, metavar="F", help="with --apg: weight of the previous steps' running average, in (-1, 1) (0: none)")
     ap.add_argument("--negative-prompt", default=None, help="the negative prompt; default: the fixed one of the training-time renders")
     ap.add_argument("--hires-scale", type=float, default=None, help="two passes: sample at --size, enlarge by this factor (each axis rounded to the VAE's multiple), finish at the large size")
     ap.add_argument("--hires-size", type=int, nargs=2, metavar=("W", "H"), default=None, help="two passes with the final size given in pixels instead of a factor")
@@ -890,6 +939,15 @@ def main(argv=None, runtime=None):
         ap.error(f"--guidance-rescale must be in [0, 1], got {a.guidance_rescale}")
     if a.guidance_interval is not None and not a.guidance_interval[0] < a.guidance_interval[1]:
         ap.error(f"--guidance-interval needs SIGMA_LO < SIGMA_HI, got {a.guidance_interval[0]} {a.guidance_interval[1]}")
+    apg = {}
+    given = {k: v for k, v in zip(APG_KEYS, (a.apg_eta, a.apg_norm_threshold, a.apg_momentum)) if v is not None}
+    if given and not a.apg:
+        ap.error("--apg-eta, --apg-norm-threshold and --apg-momentum need --apg")
+    if a.apg:
+        try:
+            apg = dict(apg=apg_args(given or True))
+        except ValueError as e:
+            ap.error(f"--apg-eta / --apg-norm-threshold / --apg-momentum: {e}")
     if a.strength is not None and not 0.0 < a.strength <= 1.0:
         ap.error(f"--strength must be in (0, 1], got {a.strength}")
     if a.heatmap_grid is not None and a.heatmap is None:
@@ -978,7 +1036,7 @@ def main(argv=None, runtime=None):
                  images_per_batch=a.images_per_batch, graph=not a.eager, n_validation=a.n_validation, init_image=a.init_image, strength=a.strength,
                  mask_image=a.mask, sampler=a.sampler, sigmas=a.sigmas, eta=a.eta, guidance_rescale=a.guidance_rescale,
                  guidance_interval=a.guidance_interval, negative_prompt=a.negative_prompt, **({} if hires is None else dict(hires=hires)),
-                 **({} if freeu is None else dict(freeu=freeu)), **kvd, **vtile, **tdiff, **regs,
+                 **({} if freeu is None else dict(freeu=freeu)), **kvd, **vtile, **tdiff, **regs, **apg,
                  **({} if a.change_map is None else dict(change_map_image=a.change_map)), **({} if a.mask_blur is None else dict(mask_blur=a.mask_blur)),
                  **({} if a.heatmap is None else dict(heatmap=a.heatmap, heatmap_grid=a.heatmap_grid or "max")))
     for scale, paths in res.items():

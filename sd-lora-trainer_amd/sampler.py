@@ -25,6 +25,12 @@ sigma_i lies in (sigma_lo, sigma_hi] (Kynkaanniemi et al. 2024, "Applying Guidan
 al. 2024, section 3.4 (diffusers' rescale_noise_cfg: the guided prediction is scaled to the standard deviation of the positive one, per image, and
 blended with weight phi).  `guidance_table` holds (g_i, phi_i) per step; ops.guidance evaluates it on the device between the forward and the step
 launch, on all three paths.
+
+Adaptive projected guidance (`sample(apg=(eta, norm_threshold, momentum))`; Sadat et al. 2024, "Eliminating Oversaturation and Artifacts of High
+Guidance Scales"; diffusers' normalized_guidance): the guidance update e_pos - e_neg is averaged over the steps with a (negative) momentum, its norm
+clipped to norm_threshold, and its part parallel to the positive prediction - the part that drives saturation - scaled by eta.  `apg_table` holds
+(eta_i, tau_i, beta_i) per step; ops.guidance_apg evaluates it in ops.guidance's place, the running average in a device buffer that the launch itself
+restarts at step row 0.
 """
 import collections
 import math
@@ -306,6 +312,32 @@ def guidance_table(sched, guidance_scale, guidance_rescale=0.0, guidance_interva
     tab[0, 0] = k
     tab[1:, 0] = g
     tab[1:, 1] = np.where(tab[1:, 0] != 1.0, np.float32(phi), np.float32(0.0))
+    return torch.from_numpy(tab)
+
+
+def apg_table(sched, apg, k=None):
+    """The device table of ops.guidance_apg beside guidance_table's, for a scheduler whose set_timesteps(n[, start]) has run: fp32 [1 + k, 4] for the k
+    steps that run (None: all of the scheduler's), row 0 (k, 0, 0, 0), row 1 + i (eta_i, tau_i, beta_i, 0).  apg: (eta, norm_threshold, momentum) as
+    numbers, or one such tuple per step that runs.  eta in [0, 1] scales the update's part parallel to the positive prediction (1: keep it, 0: drop it),
+    norm_threshold >= 0 bounds the update's norm over the image (0: no clip), |momentum| < 1 is the weight of the previous steps' running average
+    (0: none; the paper's are negative).  ValueError otherwise."""
+    k = len(sched.timesteps) if k is None else k
+    rows = list(apg) if isinstance(apg, (tuple, list)) else None
+    if rows is not None and len(rows) == 3 and all(isinstance(v, numbers.Real) and not isinstance(v, bool) for v in rows):
+        rows = [tuple(rows)] * k
+    elif rows is None or len(rows) != k or not all(isinstance(r, (tuple, list)) and len(r) == 3 and
+                                                   all(isinstance(v, numbers.Real) and not isinstance(v, bool) for v in r) for r in rows):
+        raise ValueError(f"apg takes (eta, norm_threshold, momentum) as three numbers, or one such tuple for each of the {k} step(s) that run, got {apg!r}")
+    tab = np.zeros((1 + k, 4), dtype=np.float32)
+    tab[0, 0] = k
+    for i, (eta, tau, beta) in enumerate(rows):
+        if not 0.0 <= eta <= 1.0:
+            raise ValueError(f"apg: eta must be in [0, 1], got {eta!r}")
+        if not (tau >= 0.0 and math.isfinite(tau)):
+            raise ValueError(f"apg: norm_threshold must be a finite number >= 0 (0: no clip), got {tau!r}")
+        if not abs(beta) < 1.0:
+            raise ValueError(f"apg: momentum must lie in (-1, 1), got {beta!r}")
+        tab[1 + i, :3] = (eta, tau, beta)
     return torch.from_numpy(tab)
 
 
@@ -680,12 +712,13 @@ def step_family(sampler, img, held=False):
     return "sde" if sampler in SDE_KINDS else "multistep" if sampler == "dpmpp_2m" else "euler" if img is None else "img"
 
 
-class Trajectory(collections.namedtuple("Trajectory", "h w steps start sampler sigmas eta seeds guide guidance_scale img hold plan heat size family reg", defaults=(None,))):
+class Trajectory(collections.namedtuple("Trajectory", "h w steps start sampler sigmas eta seeds guide guidance_scale img hold plan heat size family reg apg", defaults=(None, None))):
     """sample()'s arguments, checked and resolved once; both drivers (the torch loop, the fused / graph path) take it.  h, w: the latent; steps: those that
     run, from entry `start` of the steps + start entries of the schedule; sampler, sigmas, eta, seeds: as given; guide: None, or guidance_table's
     (scale(s), rescale, interval) - the pre-pass runs; guidance_scale: the scalar of the step itself (1 with the pre-pass: e - e = 0 takes any); img: None
     or (x0, mask | None, start) (_img_args); hold: None or the change map's hold map; plan: None or the TilePlan; heat: None or heatmap_args' dict with
-    its weights; size: (H, W) of SDXL's size conditioning; family: the step launch (FAMILIES); reg: None or region_args' dict (regional prompts)."""
+    its weights; size: (H, W) of SDXL's size conditioning; family: the step launch (FAMILIES); reg: None or region_args' dict (regional prompts); apg: None or apg_table's argument - the pre-pass
+    is then ops.guidance_apg (guide is set with it)."""
     __slots__ = ()
     masked = property(lambda self: self.img is not None and self.img[1] is not None)
 
@@ -718,6 +751,7 @@ class LatentSampler:
         self._sde_graphs = {}              # the same key + (masked, "sde") -> hipGraph of one iteration whose step launch is ops.sampler_step_sde
         self._dd_graphs = {}               # the same key + (False, "dd", form) -> hipGraph of one iteration whose step launch is ops.sampler_step_dd
         self._guided_graphs = {}           # any of the four keys above + (its family,) -> hipGraph of that iteration with ops.guidance before the step launch
+        self._apg_graphs = {}              # the same + ("apg",) -> hipGraph of that iteration with ops.guidance_apg there instead: a dict of their own, so they evict no other
         # the torch loop where the pre-pass runs: the deterministic samplers in their step kernels' order (dpmpp_2m: the SDE form's eta = 0 rows are
         # ms_coefficients with d = 0)
         self.sched_exact = dict(euler=EulerStepOrder(prediction_type=prediction_type), dpmpp_2m=DpmSolverPP2MSDE(prediction_type=prediction_type, eta=0.0))
@@ -738,7 +772,7 @@ class LatentSampler:
     @torch.no_grad()
     def sample(self, embeds, h, w, *, steps=25, guidance_scale=8.0, generator=None, size=None, latents=None, graph=False, fused=False, n_images=1,
                init_latents=None, strength=1.0, mask=None, sampler="euler", sigmas="trailing", eta=1.0, seeds=None, guidance_rescale=0.0,
-               guidance_interval=None, freeu=None, heatmap=None, kv_downsample=None, kv_downsample_mode=None, change_map=None, tile=None, regions=None):
+               guidance_interval=None, freeu=None, heatmap=None, kv_downsample=None, kv_downsample_mode=None, change_map=None, tile=None, regions=None, apg=None):
         """embeds = (c [1,77,D], uc [1,77,D], pc [1,P] | None, puc | None); h, w latent size.  Returns latents [1,4,h,w] fp32
         (still multiplied by the VAE scaling factor, as the pipeline holds them before `vae.decode(latents / scaling_factor)`).
         fused: guidance, the Euler update and the next model input are ONE kernel between two forwards (ops.sampler_step) instead of torch
@@ -799,7 +833,15 @@ class LatentSampler:
         the pixel - so that the region's object forms inside its mask.  Guidance, the step launch, init latents, mask, change map and the per-step
         noise stay at full size and unchanged; freeu and kv_downsample act per row.  On all three paths, with every sampler.  Masks, weights, bg and
         the bootstrap length are device memory: one capture per (shape, R) serves all of them.  No foreground mask (R = 1) is the plain path: the
-        same launches, bits and capture key as without `regions`.  Not with tile or heatmap."""
+        same launches, bits and capture key as without `regions`.  Not with tile or heatmap.
+        apg: None, or (eta, norm_threshold, momentum) - numbers, or one tuple per step that runs (apg_table): adaptive projected guidance.  The
+        pre-pass is then ops.guidance_apg where it would be ops.guidance - with apg alone too: it counts as guidance in use - on all three paths, with
+        every sampler, init latents, mask, change map, and with tile / regions on the fused full-size prediction; guidance_scale, guidance_interval
+        and guidance_rescale act as before (g_i = 1 steps pass e_pos through and leave the running average alone).  The three values per step are
+        device memory and the running average is a persistent buffer per shape that the launch restarts at step row 0 by itself: one capture (in a
+        dict of its own, the key ending in "apg") serves every setting and every picture.  apg=None is the path without it: the same launches,
+        capture keys and bits.  The neutral values (1, 0, 0) are still the new launch: e_pos + (g - 1) d equals classifier-free guidance's
+        e_neg + g d mathematically, not bit for bit."""
         ops = self.rt.ops
         if regions is not None and (tile is not None or heatmap is not None):      # refused before anything is built
             raise ValueError("regions do not combine with " + ("tile: windows of regions are not built" if tile is not None else
@@ -845,14 +887,18 @@ class LatentSampler:
         hm = heatmap_args(heatmap, n_images, steps - start)      # (the weights: one per step that runs)
         if hm is not None:
             require_op(ops, "heatmap_accum", ": the heat maps are accumulated by that launch (ops.heatmap_accum), in the torch loop too")
-        guide = (guidance_scale, guidance_rescale, guidance_interval) if guidance_in_use(guidance_scale, guidance_rescale, guidance_interval) else None
-        if guide is not None:
+        guide = (guidance_scale, guidance_rescale, guidance_interval) if apg is not None or guidance_in_use(guidance_scale, guidance_rescale, guidance_interval) else None
+        if apg is not None:
+            apg_table(None, apg, steps - start)            # refused before anything is built
+            require_op(ops, "guidance_apg", " (sdlt_guidance_apg): sample(apg=...) forms the projected prediction by that launch (ops.guidance_apg), in "
+                       "the torch loop too", kernel="sdlt_guidance_apg")
+        elif guide is not None:
             require_op(ops, "guidance", ": a per-step guidance_scale, guidance_rescale and guidance_interval are evaluated by that launch (ops.guidance), "
                        "in the torch loop too")
         assert 1 <= steps <= TABLE_ROWS - 2
         traj = Trajectory(h, w, steps - start, start, sampler, sigmas, eta, seeds, guide, guidance_scale if guide is None else 1.0, img, hold, plan, hm,
                           size if size is not None else (8 * h, 8 * w), step_family(sampler, img, hold is not None),
-                          None if reg is None else dict(reg, bootstrap=min(reg["bootstrap"], steps - start)))
+                          None if reg is None else dict(reg, bootstrap=min(reg["bootstrap"], steps - start)), apg)
         if graph or fused:
             if traj.family == "sde":
                 require_op(ops, "sampler_step_sde", f": sample(sampler={sampler!r}) draws its per-step noise inside that launch")
@@ -1065,6 +1111,13 @@ class LatentSampler:
             if "gtab" not in st:
                 st["gtab"] = rt.zeros(TABLE_ROWS - 1, 4, dtype=F32)
             st["gtab"][: gtab.shape[0]].copy_(gtab)
+        if traj.apg is not None:                          # the table beside gtab, rewritten per trajectory; the running average of the shape's full-size prediction,
+            atab = apg_table(sch, traj.apg, traj.steps)   # which the launch restarts at step row 0 itself: nothing to clear here
+            if "atab" not in st:
+                st["atab"] = rt.zeros(TABLE_ROWS - 1, 4, dtype=F32)
+            st["atab"][: atab.shape[0]].copy_(atab)
+            if "mom" not in sh:
+                sh["mom"] = rt.zeros(n * h * w, 4, dtype=F32)
         noise = latents if latents is not None else torch.randn(n, 4, h, w, generator=generator, device=dev, dtype=F32)
         noise = noise.to(dev, F32).contiguous()
         assert tuple(noise.shape) == (n, 4, h, w)
@@ -1108,7 +1161,7 @@ class LatentSampler:
         """The forward stage of one iteration, on either driver: the UNet on sh["x64"] at st["tf"] - with a tile plan: gather, the forward on the windows,
         blend; with regions: gather, the forward on every region's rows, blend - then ops.heatmap_accum on the forward's score sums (heat, a dict of sh["heat"]: the weight of row ctr[0] of st["hw"]; the maps are
         allocated at the first iteration, when the forward has told the resolutions), then ops.guidance (row ctr[0] of st["gtab"]) where the pre-pass
-        runs -> eps fp32 [2 n h w, 4]."""
+        runs - with apg: ops.guidance_apg (the same row of st["atab"] as well, the running average in sh["mom"]) -> eps fp32 [2 n h w, 4]."""
         u, h, w = self.unet, traj.h, traj.w
         tid = st["tid"] if u.cfg["addition"] else None
         if traj.plan is not None:
@@ -1122,7 +1175,9 @@ class LatentSampler:
             if heat["heat"] is None:
                 heat["heat"] = self.rt.zeros(self.n, heat["cols"].shape[1], *heat_grid(ents, heat["grid"]), dtype=F32)
             self.rt.ops.heatmap_accum(ents, heat["cols"], st["ctr"], st["hw"], heat["heat"], row_off=1, row_stride=2)
-        if traj.guide is not None:
+        if traj.apg is not None:
+            self.rt.ops.guidance_apg(eps, st["gtab"], st["atab"], sh["mom"], st["ctr"], self.n)
+        elif traj.guide is not None:
             self.rt.ops.guidance(eps, st["gtab"], st["ctr"], self.n)
         return eps
 
@@ -1143,6 +1198,7 @@ class LatentSampler:
         denoised value and the seeds in persistent buffers: one capture serves all of them.
         guided: the captures with the guidance pre-pass in them, in a fifth dict, keyed by the key the iteration has above plus its family, so they
         neither collide with those captures nor evict them; the scales, phi and the interval are in st["gtab"]: one capture per family serves all.
+        apg: the captures with ops.guidance_apg instead, in a sixth dict, that key plus "apg"; eta, threshold and momentum are in st["atab"].
         heat: the captures with ops.heatmap_accum in them are keyed by ("heat", grid, T, P) as well - the launch's shape; which columns and which
         step weights are device memory."""
         h, w, fam, masked, guided = traj.h, traj.w, traj.family, traj.masked, traj.guide is not None
@@ -1165,6 +1221,8 @@ class LatentSampler:
         graphs = getattr(self, f.graphs)
         if guided:
             key, graphs = key + (fam,), self._guided_graphs
+        if traj.apg is not None:                          # ops.guidance_apg is another launch: captures of their own; eta, threshold and momentum are in st["atab"]
+            key, graphs = key + ("apg",), self._apg_graphs
         g = graphs.get(key)
         if g is not None:
             return g

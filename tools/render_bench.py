@@ -7,13 +7,16 @@ strength 1 (all 25, the mask blend in every one); their time is divided by the i
 each named combination other than the default one - e.g. `--sampler dpmpp_2m` times (f) the iteration whose step launch is sdlt_sampler_step_ms
 against (c) - and, with --img2img, its masked variant (`inp`).  The stochastic samplers (`euler_a`, `dpmpp_2m_sde`: step launch sdlt_sampler_step_sde)
 are timed at eta = 1 with fixed seeds.  --guidance-rescale F adds (r) the default iteration with the sdlt_guidance pre-pass in it (phi = F) against (c).
+--apg adds the default iteration with adaptive projected guidance - (p) sdlt_guidance_apg at eta 0, norm threshold 15, momentum -0.5; (q) the same with
+--guidance-rescale's phi (0.7 when not given) - against (c) and (r), and, after the table, the device-event time of 50 back-to-back launches of
+sdlt_guidance_apg (momentum and clip on, with and without phi) and of sdlt_guidance (phi) on one image of the latent's size.
 --freeu B1 B2 S1 S2 adds the default iteration with FreeU in its forward - (u) version 1, (v) version 2: six sdlt_freeu calls per forward on SDXL - against
 (c); with --trace-iteration the traced loop runs it (version 2 with --freeu-v2).
 --kv-downsample SPEC [SPEC ...] adds (k, l, m, ...) the default iteration with key / value token downsampling - SPEC = factors, largest grid first, and
 optionally a mode: `2`, `2:area`, `4,2` - against (c); with --trace-iteration the traced loop runs the first SPEC.  --graph-only drops (a) and (b), which
 take long at large latents.  --dump FILE saves the final latents of (c), for a bit comparison between two builds.
 
-    python tools/render_bench.py [--out FILE] [--rounds 5] [--version sdxl] [--latent 128] [--n 1 2] [--img2img] [--sampler dpmpp_2m] [--sigmas karras] [--guidance-rescale 0.7] [--freeu 1.3 1.4 0.9 0.2]
+    python tools/render_bench.py [--out FILE] [--rounds 5] [--version sdxl] [--latent 128] [--n 1 2] [--img2img] [--sampler dpmpp_2m] [--sigmas karras] [--guidance-rescale 0.7] [--apg] [--freeu 1.3 1.4 0.9 0.2]
                                   [--kv-downsample 2 2:area 4,2] [--graph-only] [--dump FILE]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/render_bench.py --trace-iteration --n 1      # kernel time of one iteration: sum the stats
 
@@ -64,6 +67,40 @@ def timed(fn):
     return time.perf_counter() - t0
 
 
+def launch_times(h, phi, launches=50, rounds=5):
+    """Device-event microseconds per launch of the two guidance pre-passes on ONE image of h x h latent pixels (n = 1: one workgroup), `launches` of them
+    back to back between two events, median (min .. max) of `rounds` alternated rounds after a warm-up.  The table row has momentum and clip on."""
+    from sd_lora_trainer_amd import ops
+    g = torch.Generator(device="cuda").manual_seed(5)
+    hw = h * h
+    src = torch.randn(2 * hw, 4, device="cuda", generator=g)
+    src[hw:] = src[:hw] + 0.12 * torch.randn(hw, 4, device="cuda", generator=g)
+    eps, mom = src.clone(), torch.zeros(hw, 4, device="cuda")
+    ctr = torch.tensor([1, 0], dtype=torch.int32, device="cuda")
+    tabs = {p: torch.tensor([[2.0, 0, 0, 0], [8.0, p, 0, 0], [8.0, p, 0, 0]], device="cuda") for p in (0.0, phi)}
+    atab = torch.tensor([[2.0, 0, 0, 0], [0.0, 15.0, -0.5, 0], [0.0, 15.0, -0.5, 0]], device="cuda")
+    kinds = {"sdlt_guidance_apg, phi 0": lambda: ops.guidance_apg(eps, tabs[0.0], atab, mom, ctr, 1),
+             f"sdlt_guidance_apg, phi {phi:g}": lambda: ops.guidance_apg(eps, tabs[phi], atab, mom, ctr, 1),
+             f"sdlt_guidance, phi {phi:g}": lambda: ops.guidance(eps, tabs[phi], ctr, 1)}
+    times = {k: [] for k in kinds}
+    for r in range(rounds + 1):
+        for k, fn in kinds.items():
+            eps.copy_(src)
+            mom.zero_()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(launches):                       # (in place: later launches see a guided prediction in both row blocks - the same traffic and arithmetic)
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if r:
+                times[k].append(e0.elapsed_time(e1) * 1e3 / launches)
+    lines = [f"# device-event us per launch, n = 1, hw = {hw}, {launches} launches back to back: median (min .. max) of {rounds} rounds, alternated"]
+    for k, t in times.items():
+        lines.append(f"   {k:<28} {statistics.median(t):>16.2f} {min(t):>8.2f} {max(t):>8.2f}")
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -79,6 +116,7 @@ def main():
     ap.add_argument("--sampler", nargs="+", choices=("euler", "dpmpp_2m", "euler_a", "dpmpp_2m_sde"), default=["euler"], help="also time the graph sampler with these integrators")
     ap.add_argument("--sigmas", nargs="+", choices=("trailing", "karras"), default=["trailing"], help="... on these noise levels")
     ap.add_argument("--guidance-rescale", type=float, default=0.0, help="also time the default graph sampler with the guidance pre-pass at this rescale weight")
+    ap.add_argument("--apg", action="store_true", help="also time the default graph sampler with adaptive projected guidance (with and without the rescale), and the pre-pass launches alone")
     ap.add_argument("--freeu", type=float, nargs=4, metavar=("B1", "B2", "S1", "S2"), default=None, help="also time the default graph sampler with FreeU, versions 1 and 2")
     ap.add_argument("--freeu-v2", action="store_true", help="with --trace-iteration --freeu: trace version 2")
     ap.add_argument("--kv-downsample", nargs="+", metavar="SPEC", default=[], help="also time the default graph sampler with key / value token downsampling: "
@@ -115,6 +153,10 @@ def main():
             ran["d graph, init latents 0.6"], ran["e graph, inpaint 1.0"] = min(int(a.steps * 0.6), a.steps), a.steps
         if a.guidance_rescale:
             variants["r graph, guidance rescale"], ran["r graph, guidance rescale"] = (lambda: one(graph=True, guidance_rescale=a.guidance_rescale)), a.steps
+        if a.apg:
+            phi = a.guidance_rescale or 0.7
+            variants["p graph, APG"], ran["p graph, APG"] = (lambda: one(graph=True, apg=(0.0, 15.0, -0.5))), a.steps
+            variants["q graph, APG + rescale"], ran["q graph, APG + rescale"] = (lambda: one(graph=True, apg=(0.0, 15.0, -0.5), guidance_rescale=phi)), a.steps
         if a.freeu:
             for tag, ver in (("u", 1), ("v", 2)):
                 fz = dict(zip(("b1", "b2", "s1", "s2"), a.freeu), version=ver)
@@ -150,6 +192,8 @@ def main():
         if n != 1:
             del smp
             torch.cuda.empty_cache()
+    if a.apg:
+        lines += launch_times(h, a.guidance_rescale or 0.7)
     text = "\n".join(lines) + "\n"
     print(text, end="")
     if a.out:
