@@ -771,6 +771,38 @@ typedef struct {
 } sdlt_guidance_apg_params;
 int sdlt_guidance_apg(const sdlt_guidance_apg_params* p, void* stream);
 
+/* sdlt_guidance_dyn : dynamic thresholding (the "Dynamic Thresholding (CFG scale fix)" extension of A1111 / ComfyUI / SwarmUI, a latent-space form of
+ * Imagen's dynamic thresholding) as the guidance pre-pass, issued where sdlt_guidance would be: it rewrites eps in place so that both row blocks of image j
+ * hold the final prediction e.  eps, gtab, ctr, n, hw, gtab_rows as in sdlt_guidance_params (phi of gtab is not read).  dtab fp32 [gtab_rows, 4]: row 0 is
+ * the header (not read), row 1 + i = (mimic_i, q_i, psi_i, 0).  With i = ctr[0] clamped to 0 .. k - 1 (read, never written), g from gtab and
+ * (mimic, q, psi) from dtab, per image j and per channel c of the 4, over that channel's hw values, fp32, one rounding per operation, no contraction, IEEE
+ * division, in the order written:
+ *     g == 1:    e = e_pos exactly (guidance off: outside the interval); nothing else is computed
+ *     d = e_pos - e_neg ;  e_g = e_neg + g d ;  e_m = e_neg + mimic d
+ *     mu_g[c] = (sum e_g[:, c]) / hw ;  mu_m[c] = (sum e_m[:, c]) / hw        the sums in sdlt_guidance's fixed order, per channel
+ *     c_g = e_g - mu_g[c] ;  c_m = e_m - mu_m[c]
+ *     A[c] = max |c_m|                                                         exact
+ *     pos = q (float)(hw - 1) ;  lo = min((int)floorf(pos), hw - 1) ;  hi = min(lo + 1, hw - 1) ;  w = pos - (float)lo
+ *     v_lo, v_hi = the lo-th and hi-th smallest of |c_g[:, c]|                 0-based, EXACT order statistics, ties included
+ *     Q[c] = v_lo + w (v_hi - v_lo) ;  S[c] = max(A[c], Q[c])
+ *     S[c] == 0: e_d = e_g ;  otherwise e_d = ((min(max(c_g, -S), S) / S) A) + mu_g[c]
+ *     psi == 1:  e = e_d ;  otherwise e = psi e_d + (1 - psi) e_g
+ * This is the extension's default mode - per channel, "AD" variability measure, "MEAN" start point - restated from memory; the text above governs, not the
+ * extension.  Its only deliberate difference: at S == 0 (a constant channel) the extension divides by zero, here e_d = e_g.  The order statistics come
+ * from a radix select on the bit patterns of |c_g| with integer histograms: image j's result depends on neither n nor j and repeats bit for bit.
+ * Table contents are only values: whatever they hold, every access stays inside eps and the rows of the tables.
+ * Null eps, gtab, dtab or ctr, n < 1, hw < 1, n hw > 2^28, hw > 2^24 (pos must hold hw - 1 exactly), gtab_rows < 2 (-1); eps not 16-byte aligned, a table
+ * or ctr not 4-byte aligned (-2): the code is returned, sdlt_last_error names the entry point and nothing is launched.  The block is declared without a
+ * struct tag, like sdlt_guidance_apg_params, and has no index in sdlt_struct_size(): 48 bytes, four pointers and four int32, no padding between fields. */
+typedef struct {
+  float* eps;                        /* fp32 [2n * hw, 4]: UNet.forward's output, rewritten in place */
+  const float* gtab;                 /* fp32 [gtab_rows, 4] */
+  const float* dtab;                 /* fp32 [gtab_rows, 4] */
+  const int32_t* ctr;                /* int32 [>= 1]: ctr[0] = step row, read only */
+  int32_t n, hw, gtab_rows, pad_;
+} sdlt_guidance_dyn_params;
+int sdlt_guidance_dyn(const sdlt_guidance_dyn_params* p, void* stream);
+
 /* sdlt_resize_planes : out fp32 [planes, H, W] = in fp32 [planes, h, w] resampled, both contiguous, out not overlapping in.  The step between the two
  * passes of a hires render (render.py: `hires`): the first pass's latents [n, 4, h, w] (planes = 4 n, planes_per_image = 4) or the decoder's image
  * [n, 3, 8h, 8w] (planes_per_image = 3) enlarged before the second pass re-noises them.  planes_per_image consecutive planes are one image: its

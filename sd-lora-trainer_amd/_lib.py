@@ -224,6 +224,11 @@ class GuidanceApgParams(C.Structure):
     _fields_ = [("eps", vp), ("gtab", vp), ("atab", vp), ("mom", vp), ("ctr", vp), ("n", i32), ("hw", i32), ("gtab_rows", i32), ("pad_", i32)]
 
 
+class GuidanceDynParams(C.Structure):
+    # sdlt_guidance_dyn_params: 48 bytes by the header's text (tagless, like sdlt_guidance_apg_params)
+    _fields_ = [("eps", vp), ("gtab", vp), ("dtab", vp), ("ctr", vp), ("n", i32), ("hw", i32), ("gtab_rows", i32), ("pad_", i32)]
+
+
 class ResizeParams(C.Structure):
     # sdlt_resize_params: 48 bytes by the header's text (it has no index in sdlt_struct_size, whose table ends with GuidanceParams)
     _fields_ = [("in_", vp), ("out", vp), ("planes", i32), ("planes_per_image", i32), ("h", i32), ("w", i32), ("H", i32), ("W", i32), ("mode", i32), ("pad_", i32)]
@@ -312,6 +317,7 @@ SYMBOLS = {
     "sdlt_sampler_noise": (i32, [vp, i32, i32, i32, vp, vp]),
     "sdlt_guidance": (i32, [C.POINTER(GuidanceParams), vp]),
     "sdlt_guidance_apg": (i32, [C.POINTER(GuidanceApgParams), vp]),
+    "sdlt_guidance_dyn": (i32, [C.POINTER(GuidanceDynParams), vp]),
     "sdlt_resize_planes": (i32, [C.POINTER(ResizeParams), vp]),
     "sdlt_blur_planes": (i32, [vp, vp, vp, i32, i32, i32, vp, i32, i32, vp]),
     "sdlt_freeu_ws_floats": (i64, [i32, i32, i32, i32, i32]),
@@ -377,7 +383,7 @@ def load():
     if C.sizeof(ResizeParams) != 48:
         raise KernelLibraryError(f"struct layout mismatch for ResizeParams: header 48 vs binding {C.sizeof(ResizeParams)}")
     for cls, size in ((HeatAccumParams, 152), (HeatOverlayParams, 80), (GemmPlan, 64), (SamplerDdParams, 128), (WindowParams, 64), (RegionParams, 64),
-                      (GuidanceApgParams, 56)):
+                      (GuidanceApgParams, 56), (GuidanceDynParams, 48)):
         if C.sizeof(cls) != size:
             raise KernelLibraryError(f"struct layout mismatch for {cls.__name__}: header {size} vs binding {C.sizeof(cls)}")
     _lib = lib

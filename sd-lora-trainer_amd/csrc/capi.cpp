@@ -23,6 +23,7 @@ static_assert(sizeof(sdlt_sampler_dd_params) == 128, "sdlt_sampler_dd_params has
 static_assert(sizeof(sdlt_window_params) == 64, "sdlt_window_params has no index below: its size is part of the header's text");
 static_assert(sizeof(sdlt_region_params) == 64, "sdlt_region_params has no index below: its size is part of the header's text");
 static_assert(sizeof(sdlt_guidance_apg_params) == 56, "sdlt_guidance_apg_params has no index below: its size is part of the header's text");
+static_assert(sizeof(sdlt_guidance_dyn_params) == 48, "sdlt_guidance_dyn_params has no index below: its size is part of the header's text");
 
 extern "C" int sdlt_struct_size(int which) {
   switch (which) {

@@ -1367,6 +1367,22 @@ def guidance_apg(eps, gtab, atab, mom, ctr, n):
     return eps
 
 
+def guidance_dyn(eps, gtab, dtab, ctr, n):
+    """sdlt_guidance_dyn: dynamic thresholding (the "Dynamic Thresholding (CFG scale fix)" extension of the common front ends) as the pre-pass, in
+    ops.guidance's place.  eps, gtab, ctr, n as there; dtab fp32 [gtab's rows, 4] (sampler.dyn_table: row 1 + i = (mimic_i, percentile_i,
+    interpolate_i, 0)).  Per image and latent channel the guided prediction is centred, clamped to max(the mimic prediction's largest deviation, the
+    percentile of its own) and scaled to the mimic prediction's range.  The order of operations: include/sdlt_kernels.h."""
+    lib = _lib.load()
+    _chk2(eps, F32), _chk2(gtab, F32), _chk2(dtab, F32), _chk2(ctr, torch.int32)
+    assert eps.dim() == 2 and eps.shape[1] == 4 and eps.is_contiguous() and n >= 1 and eps.shape[0] % (2 * n) == 0 and eps.shape[0] >= 2 * n
+    assert gtab.dim() == 2 and gtab.shape[1] == 4 and gtab.shape[0] >= 2 and gtab.is_contiguous() and ctr.numel() >= 1
+    assert tuple(dtab.shape) == tuple(gtab.shape) and dtab.is_contiguous(), "dtab: one row per row of gtab"
+    p = _lib.GuidanceDynParams(eps=eps.data_ptr(), gtab=gtab.data_ptr(), dtab=dtab.data_ptr(), ctr=ctr.data_ptr(), n=n, hw=eps.shape[0] // (2 * n),
+                               gtab_rows=gtab.shape[0])
+    _lib.check(lib.sdlt_guidance_dyn(C.byref(p), _stream()), "sdlt_guidance_dyn")
+    return eps
+
+
 def resize_planes(src, out, mode):
     """sdlt_resize_planes: out fp32 [n, c, H, W] = src fp32 [n, c, h, w] resampled with PyTorch's align_corners=False conventions - mode 0 nearest-exact,
     1 bilinear, 2 bicubic (Keys, A = -0.75), the arithmetic in the order include/sdlt_kernels.h writes down (tests/hires_ref.py gives the same bits).

@@ -7,6 +7,7 @@ scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-squ
                                          [--init-image PATH [--strength S] [--mask PATH | --change-map PATH] [--mask-blur SIGMA]] [--sampler euler|dpmpp_2m|euler_a|dpmpp_2m_sde] [--eta F]
                                          [--sigmas trailing|karras] [--guidance-rescale F] [--guidance-interval SIGMA_LO SIGMA_HI]
                                          [--apg [--apg-eta F] [--apg-norm-threshold F] [--apg-momentum F]]
+                                         [--dynthresh [MIMIC] [--dynthresh-percentile F] [--dynthresh-interpolate F]]
                                          [--negative-prompt TEXT] [--freeu B1 B2 S1 S2 [--freeu-v2]]
                                          [--hires-scale F | --hires-size W H] [--hires-strength F] [--hires-steps N] [--hires-upscaler latent|pixel]
                                          [--hires-resample nearest|bilinear|bicubic] [--heatmap [WORD ...]] [--heatmap-grid max|min]
@@ -57,6 +58,16 @@ sdlt_guidance's place inside the replayed graph, the running average in a device
 no host work.  It works on the noise prediction (the paper and ComfyUI project the denoised value).  With every sampler, noise schedule,
 --guidance-rescale, --guidance-interval, --init-image / --mask / --change-map, --tile-diffusion, --region and --heatmap; both passes of a hires render
 use it, each with a running average of its own.  Without the flag nothing changes.
+
+--dynthresh [MIMIC] is dynamic thresholding (the "Dynamic Thresholding (CFG scale fix)" extension of A1111 / ComfyUI / SwarmUI, a latent-space form of
+Imagen's dynamic thresholding): sample at --guidance 12-20 for its prompt adherence, but give every latent channel of the prediction the value range it
+would have had at the mild scale MIMIC (default 7).  Per image and channel the guided prediction is centred on its mean, clamped to max(the largest
+deviation of the MIMIC-scale prediction, the --dynthresh-percentile quantile of its own deviations; default 0.999, 1: the maximum) and scaled back to the
+MIMIC prediction's range; --dynthresh-interpolate F (default 1) blends the result with the plain guided prediction.  The defaults are this project's
+choice; the two sub-flags are errors without --dynthresh.  One launch (sdlt_guidance_dyn) in sdlt_guidance's place inside the replayed graph; the
+quantile is an exact order statistic from a radix select inside the launch, so it needs no host work and repeats bit for bit.  With every sampler, noise
+schedule, --guidance-interval, --init-image / --mask / --change-map, --tile-diffusion, --region and --heatmap; both passes of a hires render use it.  Not
+with --guidance-rescale or --apg: they are alternative answers to the same fault.  Without the flag nothing changes.
 
 --hires-scale F / --hires-size W H render in two passes (the "hires fix"): a picture much larger than the model was trained for falls apart when it is
 sampled in one go (doubled subjects, tiled compositions), so the first pass samples at --size, the result is enlarged on the device
@@ -285,6 +296,31 @@ def apg_args(apg):
     apg = tuple(float(v) for v in apg)
     SM.apg_table(None, apg, 1)                          # (the ranges)
     return apg
+
+
+DYN_DEFAULT = (7.0, 0.999, 1.0)      # mimic scale, percentile, interpolate: this project's choice
+DYN_KEYS = ("mimic", "percentile", "interpolate")
+
+
+def dynthresh_args(dynthresh):
+    """render()'s `dynthresh`, checked -> None | (mimic, percentile, interpolate).  None or False: off; True: DYN_DEFAULT; three numbers in that order, or a
+    dict with any of the keys mimic, percentile, interpolate (the others: DYN_DEFAULT's).  The ranges are sampler.dyn_table's."""
+    from . import sampler as SM
+    dt = dynthresh
+    if dt is None or dt is False:
+        return None
+    if dt is True:
+        dt = DYN_DEFAULT
+    elif isinstance(dt, dict):
+        unknown = sorted(set(dt) - set(DYN_KEYS))
+        if unknown:
+            raise ValueError(f"dynthresh: keys {', '.join(DYN_KEYS)}; unknown {unknown}")
+        dt = tuple(dt.get(k, d) for k, d in zip(DYN_KEYS, DYN_DEFAULT))
+    if not (isinstance(dt, (tuple, list)) and len(dt) == 3 and all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in dt)):
+        raise ValueError(f"dynthresh takes True, (mimic, percentile, interpolate) or a dict of them, got {dynthresh!r}")
+    dt = tuple(float(v) for v in dt)
+    SM.dyn_table(None, dt, 1)                           # (the ranges)
+    return dt
 
 
 def _scale_tag(s):
@@ -517,7 +553,7 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
            graph=True, n_validation=4, init_image=None, strength=None, mask_image=None, sampler="euler", sigmas="trailing", eta=None,
            guidance_rescale=0.0, guidance_interval=None, negative_prompt=None, hires=None, freeu=None, heatmap=None, heatmap_grid="max",
            kv_downsample=None, kv_downsample_mode="nearest", kv_downsample_pass="hires", vae_tile=None, change_map_image=None, mask_blur=None, tile_diffusion=None, regions=None, region_feather=None,
-           region_base=None, region_bootstrap=None, apg=None):
+           region_base=None, region_bootstrap=None, apg=None, dynthresh=None):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
     seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
@@ -528,6 +564,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     LatentSampler.sample's; negative_prompt: the negative row's text (None: prompts.NEGATIVE_PROMPT).
     apg: None, True (APG_DEFAULT), (eta, norm_threshold, momentum) or a dict of them (apg_args): adaptive projected guidance - LatentSampler.sample's
     `apg` - in every pass, of a hires render too (each pass is a trajectory of its own: the running average restarts); with everything else.
+    dynthresh: None, True (DYN_DEFAULT), (mimic, percentile, interpolate) or a dict of them (dynthresh_args): dynamic thresholding - LatentSampler.sample's
+    `dynthresh` - in every pass, of a hires render too; not with apg or guidance_rescale > 0 (ValueError).
     hires (a dict, hires_args: scale | size, strength, steps, upscaler, resample): two passes - every image is first sampled at `size`, for all adapter
     scales and prompt batches, its latents staying on the device; they are enlarged (sampler.upscale_latents: the latents, or with upscaler "pixel"
     the decoded picture, encoded again); then the UNet is rebuilt ONCE for the large shape and every second pass runs: sample(init_latents=the
@@ -590,8 +628,14 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         if len(guidance_interval) != 2 or not guidance_interval[0] < guidance_interval[1]:
             raise ValueError(f"guidance_interval must be (sigma_lo, sigma_hi) with sigma_lo < sigma_hi, got {guidance_interval!r}")
     ag = apg_args(apg)                                                 # (raises before anything is built)
+    dt = dynthresh_args(dynthresh)
+    if dt is not None and (ag is not None or guidance_rescale):
+        raise ValueError("dynthresh does not combine with " + ("apg" if ag is not None else "guidance_rescale") + ": they are alternative answers to the burnt "
+                         "contrast of a strong guidance scale")
     if ag is not None:
         SM.require_op(stack.rt.ops, "guidance_apg", " (sdlt_guidance_apg): apg forms the projected prediction by that launch (ops.guidance_apg)", kernel="sdlt_guidance_apg")
+    if dt is not None:
+        SM.require_op(stack.rt.ops, "guidance_dyn", " (sdlt_guidance_dyn): dynthresh forms the thresholded prediction by that launch (ops.guidance_dyn)", kernel="sdlt_guidance_dyn")
     rg = region_args(regions, region_feather, region_base, region_bootstrap)      # (raises before anything is built)
     if rg is not None:
         for other, name in ((tile_diffusion, "tile_diffusion: windows of regions are not built"), (hires, "hires: the masks would need a second grid"),
@@ -666,6 +710,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         img_kw.update(guidance_interval=guidance_interval)
     if ag is not None:
         img_kw.update(apg=ag)
+    if dt is not None:
+        img_kw.update(dynthresh=dt)
     if (sampler, sigmas) != ("euler", "trailing"):
         img_kw.update(sampler=sampler, sigmas=sigmas)
     if sde:
@@ -823,6 +869,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             meta.update(guidance_interval=list(guidance_interval))
         if ag is not None:
             meta.update(apg=dict(zip(APG_KEYS, ag)))
+        if dt is not None:
+            meta.update(dynthresh=dict(zip(DYN_KEYS, dt)))
         if negative_prompt is not None:
             meta.update(negative_prompt=negative_prompt)
         if hi is not None:
@@ -878,6 +926,10 @@ def main(argv=None, runtime=None):
     ap.add_argument("--apg-eta", type=float, default=None, metavar="F", help="with --apg: weight of the update's part parallel to the positive prediction, in [0, 1]")
     ap.add_argument("--apg-norm-threshold", type=float, default=None, metavar="F", help="with --apg: bound of the update's norm over the image, >= 0 (0: no clip)")
     ap.add_argument("--apg-momentum", type=float, default=None, metavar="F", help="with --apg: weight of the previous steps' running average, in (-1, 1) (0: none)")
+    ap.add_argument("--dynthresh", type=float, nargs="?", const=DYN_DEFAULT[0], default=None, metavar="MIMIC",
+                    help=f"dynamic thresholding: every latent channel of the guided prediction gets the value range of the prediction at guidance scale MIMIC (default {DYN_DEFAULT[0]:g})")
+    ap.add_argument("--dynthresh-percentile", type=float, default=None, metavar="F", help=f"with --dynthresh: the quantile of the prediction's own deviations the clamp stays above, in (0, 1] (default {DYN_DEFAULT[1]:g})")
+    ap.add_argument("--dynthresh-interpolate", type=float, default=None, metavar="F", help=f"with --dynthresh: weight of the thresholded prediction against the plain one, in [0, 1] (default {DYN_DEFAULT[2]:g})")
     ap.add_argument("--negative-prompt", default=None, help="the negative prompt; default: the fixed one of the training-time renders")
     ap.add_argument("--hires-scale", type=float, default=None, help="two passes: sample at --size, enlarge by this factor (each axis rounded to the VAE's multiple), finish at the large size")
     ap.add_argument("--hires-size", type=int, nargs=2, metavar=("W", "H"), default=None, help="two passes with the final size given in pixels instead of a factor")
@@ -948,6 +1000,17 @@ def main(argv=None, runtime=None):
             apg = dict(apg=apg_args(given or True))
         except ValueError as e:
             ap.error(f"--apg-eta / --apg-norm-threshold / --apg-momentum: {e}")
+    dyn = {}
+    given = {k: v for k, v in zip(DYN_KEYS[1:], (a.dynthresh_percentile, a.dynthresh_interpolate)) if v is not None}
+    if given and a.dynthresh is None:
+        ap.error("--dynthresh-percentile and --dynthresh-interpolate need --dynthresh")
+    if a.dynthresh is not None:
+        if a.apg or a.guidance_rescale:
+            ap.error("--dynthresh does not combine with " + ("--apg" if a.apg else "--guidance-rescale") + ": they are alternative answers to the same fault")
+        try:
+            dyn = dict(dynthresh=dynthresh_args(dict(given, mimic=a.dynthresh)))
+        except ValueError as e:
+            ap.error(f"--dynthresh / --dynthresh-percentile / --dynthresh-interpolate: {e}")
     if a.strength is not None and not 0.0 < a.strength <= 1.0:
         ap.error(f"--strength must be in (0, 1], got {a.strength}")
     if a.heatmap_grid is not None and a.heatmap is None:
@@ -1036,7 +1099,7 @@ def main(argv=None, runtime=None):
                  images_per_batch=a.images_per_batch, graph=not a.eager, n_validation=a.n_validation, init_image=a.init_image, strength=a.strength,
                  mask_image=a.mask, sampler=a.sampler, sigmas=a.sigmas, eta=a.eta, guidance_rescale=a.guidance_rescale,
                  guidance_interval=a.guidance_interval, negative_prompt=a.negative_prompt, **({} if hires is None else dict(hires=hires)),
-                 **({} if freeu is None else dict(freeu=freeu)), **kvd, **vtile, **tdiff, **regs, **apg,
+                 **({} if freeu is None else dict(freeu=freeu)), **kvd, **vtile, **tdiff, **regs, **apg, **dyn,
                  **({} if a.change_map is None else dict(change_map_image=a.change_map)), **({} if a.mask_blur is None else dict(mask_blur=a.mask_blur)),
                  **({} if a.heatmap is None else dict(heatmap=a.heatmap, heatmap_grid=a.heatmap_grid or "max")))
     for scale, paths in res.items():

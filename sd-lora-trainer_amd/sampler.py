@@ -31,6 +31,12 @@ Guidance Scales"; diffusers' normalized_guidance): the guidance update e_pos - e
 clipped to norm_threshold, and its part parallel to the positive prediction - the part that drives saturation - scaled by eta.  `apg_table` holds
 (eta_i, tau_i, beta_i) per step; ops.guidance_apg evaluates it in ops.guidance's place, the running average in a device buffer that the launch itself
 restarts at step row 0.
+
+Dynamic thresholding (`sample(dynthresh=(mimic, percentile, interpolate))`; the "Dynamic Thresholding (CFG scale fix)" extension of A1111 / ComfyUI /
+SwarmUI, a latent-space form of Imagen's dynamic thresholding): sample at a strong guidance scale, but give every latent channel of the prediction the
+value range it would have had at the mild `mimic` scale - the centred guided prediction is clamped to max(the mimic prediction's largest deviation, the
+percentile of its own) and scaled back to the mimic prediction's range.  `dyn_table` holds (mimic_i, q_i, psi_i) per step; ops.guidance_dyn evaluates it
+in ops.guidance's place, the quantile by an exact radix select inside the launch.
 """
 import collections
 import math
@@ -338,6 +344,32 @@ def apg_table(sched, apg, k=None):
         if not abs(beta) < 1.0:
             raise ValueError(f"apg: momentum must lie in (-1, 1), got {beta!r}")
         tab[1 + i, :3] = (eta, tau, beta)
+    return torch.from_numpy(tab)
+
+
+def dyn_table(sched, dynthresh, k=None):
+    """The device table of ops.guidance_dyn beside guidance_table's, for a scheduler whose set_timesteps(n[, start]) has run: fp32 [1 + k, 4] for the k
+    steps that run (None: all of the scheduler's), row 0 (k, 0, 0, 0), row 1 + i (mimic_i, q_i, psi_i, 0).  dynthresh: (mimic, percentile, interpolate)
+    as numbers, or one such tuple per step that runs.  mimic >= 1 is the guidance scale whose value range every channel gets, percentile in (0, 1] the
+    quantile of the guided prediction's own deviations that the clamp may not go below (1: the maximum), interpolate in [0, 1] the weight of the
+    thresholded prediction against the plain guided one (1: all of it).  ValueError otherwise."""
+    k = len(sched.timesteps) if k is None else k
+    real = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)  # noqa: E731
+    rows = list(dynthresh) if isinstance(dynthresh, (tuple, list)) else None
+    if rows is not None and len(rows) == 3 and all(real(v) for v in rows):
+        rows = [tuple(rows)] * k
+    elif rows is None or len(rows) != k or not all(isinstance(r, (tuple, list)) and len(r) == 3 and all(real(v) for v in r) for r in rows):
+        raise ValueError(f"dynthresh takes (mimic, percentile, interpolate) as three numbers, or one such tuple for each of the {k} step(s) that run, got {dynthresh!r}")
+    tab = np.zeros((1 + k, 4), dtype=np.float32)
+    tab[0, 0] = k
+    for i, (mimic, q, psi) in enumerate(rows):
+        if not (mimic >= 1.0 and math.isfinite(mimic)):
+            raise ValueError(f"dynthresh: mimic must be a finite guidance scale >= 1, got {mimic!r}")
+        if not 0.0 < q <= 1.0:
+            raise ValueError(f"dynthresh: percentile must lie in (0, 1], got {q!r}")
+        if not 0.0 <= psi <= 1.0:
+            raise ValueError(f"dynthresh: interpolate must be in [0, 1], got {psi!r}")
+        tab[1 + i, :3] = (mimic, q, psi)
     return torch.from_numpy(tab)
 
 
@@ -712,13 +744,14 @@ def step_family(sampler, img, held=False):
     return "sde" if sampler in SDE_KINDS else "multistep" if sampler == "dpmpp_2m" else "euler" if img is None else "img"
 
 
-class Trajectory(collections.namedtuple("Trajectory", "h w steps start sampler sigmas eta seeds guide guidance_scale img hold plan heat size family reg apg", defaults=(None, None))):
+class Trajectory(collections.namedtuple("Trajectory", "h w steps start sampler sigmas eta seeds guide guidance_scale img hold plan heat size family reg apg dyn", defaults=(None, None, None))):
     """sample()'s arguments, checked and resolved once; both drivers (the torch loop, the fused / graph path) take it.  h, w: the latent; steps: those that
     run, from entry `start` of the steps + start entries of the schedule; sampler, sigmas, eta, seeds: as given; guide: None, or guidance_table's
     (scale(s), rescale, interval) - the pre-pass runs; guidance_scale: the scalar of the step itself (1 with the pre-pass: e - e = 0 takes any); img: None
     or (x0, mask | None, start) (_img_args); hold: None or the change map's hold map; plan: None or the TilePlan; heat: None or heatmap_args' dict with
     its weights; size: (H, W) of SDXL's size conditioning; family: the step launch (FAMILIES); reg: None or region_args' dict (regional prompts); apg: None or apg_table's argument - the pre-pass
-    is then ops.guidance_apg (guide is set with it)."""
+    is then ops.guidance_apg (guide is set with it); dyn: None or dyn_table's argument - the pre-pass is then ops.guidance_dyn (guide is set with it; never
+    with apg)."""
     __slots__ = ()
     masked = property(lambda self: self.img is not None and self.img[1] is not None)
 
@@ -752,6 +785,7 @@ class LatentSampler:
         self._dd_graphs = {}               # the same key + (False, "dd", form) -> hipGraph of one iteration whose step launch is ops.sampler_step_dd
         self._guided_graphs = {}           # any of the four keys above + (its family,) -> hipGraph of that iteration with ops.guidance before the step launch
         self._apg_graphs = {}              # the same + ("apg",) -> hipGraph of that iteration with ops.guidance_apg there instead: a dict of their own, so they evict no other
+        self._dyn_graphs = {}              # the guided key + ("dyn",) -> hipGraph of that iteration with ops.guidance_dyn there instead: a dict of their own as well
         # the torch loop where the pre-pass runs: the deterministic samplers in their step kernels' order (dpmpp_2m: the SDE form's eta = 0 rows are
         # ms_coefficients with d = 0)
         self.sched_exact = dict(euler=EulerStepOrder(prediction_type=prediction_type), dpmpp_2m=DpmSolverPP2MSDE(prediction_type=prediction_type, eta=0.0))
@@ -772,7 +806,8 @@ class LatentSampler:
     @torch.no_grad()
     def sample(self, embeds, h, w, *, steps=25, guidance_scale=8.0, generator=None, size=None, latents=None, graph=False, fused=False, n_images=1,
                init_latents=None, strength=1.0, mask=None, sampler="euler", sigmas="trailing", eta=1.0, seeds=None, guidance_rescale=0.0,
-               guidance_interval=None, freeu=None, heatmap=None, kv_downsample=None, kv_downsample_mode=None, change_map=None, tile=None, regions=None, apg=None):
+               guidance_interval=None, freeu=None, heatmap=None, kv_downsample=None, kv_downsample_mode=None, change_map=None, tile=None, regions=None, apg=None,
+               dynthresh=None):
         """embeds = (c [1,77,D], uc [1,77,D], pc [1,P] | None, puc | None); h, w latent size.  Returns latents [1,4,h,w] fp32
         (still multiplied by the VAE scaling factor, as the pipeline holds them before `vae.decode(latents / scaling_factor)`).
         fused: guidance, the Euler update and the next model input are ONE kernel between two forwards (ops.sampler_step) instead of torch
@@ -841,7 +876,13 @@ class LatentSampler:
         device memory and the running average is a persistent buffer per shape that the launch restarts at step row 0 by itself: one capture (in a
         dict of its own, the key ending in "apg") serves every setting and every picture.  apg=None is the path without it: the same launches,
         capture keys and bits.  The neutral values (1, 0, 0) are still the new launch: e_pos + (g - 1) d equals classifier-free guidance's
-        e_neg + g d mathematically, not bit for bit."""
+        e_neg + g d mathematically, not bit for bit.
+        dynthresh: None, or (mimic, percentile, interpolate) - numbers, or one tuple per step that runs (dyn_table): dynamic thresholding.  The
+        pre-pass is then ops.guidance_dyn where it would be ops.guidance - with dynthresh alone too: it counts as guidance in use - on all three
+        paths, with every sampler, per-step guidance scales, guidance_interval (g_i = 1 steps pass e_pos through), init latents, mask, change map,
+        and with tile / regions on the fused full-size prediction.  The three values per step are device memory: one capture (in a dict of its own,
+        the guided key plus "dyn") serves every setting.  dynthresh=None is the path without it: the same launches, capture keys and bits.  Not with
+        guidance_rescale > 0 and not with apg (ValueError): the three are alternative answers to the same fault."""
         ops = self.rt.ops
         if regions is not None and (tile is not None or heatmap is not None):      # refused before anything is built
             raise ValueError("regions do not combine with " + ("tile: windows of regions are not built" if tile is not None else
@@ -887,18 +928,25 @@ class LatentSampler:
         hm = heatmap_args(heatmap, n_images, steps - start)      # (the weights: one per step that runs)
         if hm is not None:
             require_op(ops, "heatmap_accum", ": the heat maps are accumulated by that launch (ops.heatmap_accum), in the torch loop too")
-        guide = (guidance_scale, guidance_rescale, guidance_interval) if apg is not None or guidance_in_use(guidance_scale, guidance_rescale, guidance_interval) else None
+        if dynthresh is not None and (apg is not None or guidance_rescale):      # refused before anything is built
+            raise ValueError("dynthresh does not combine with " + ("apg" if apg is not None else "guidance_rescale") + ": they are alternative answers to the "
+                             "burnt contrast of a strong guidance scale")
+        guide = (guidance_scale, guidance_rescale, guidance_interval) if apg is not None or dynthresh is not None or guidance_in_use(guidance_scale, guidance_rescale, guidance_interval) else None
         if apg is not None:
             apg_table(None, apg, steps - start)            # refused before anything is built
             require_op(ops, "guidance_apg", " (sdlt_guidance_apg): sample(apg=...) forms the projected prediction by that launch (ops.guidance_apg), in "
                        "the torch loop too", kernel="sdlt_guidance_apg")
+        elif dynthresh is not None:
+            dyn_table(None, dynthresh, steps - start)      # refused before anything is built
+            require_op(ops, "guidance_dyn", " (sdlt_guidance_dyn): sample(dynthresh=...) forms the thresholded prediction by that launch (ops.guidance_dyn), in "
+                       "the torch loop too", kernel="sdlt_guidance_dyn")
         elif guide is not None:
             require_op(ops, "guidance", ": a per-step guidance_scale, guidance_rescale and guidance_interval are evaluated by that launch (ops.guidance), "
                        "in the torch loop too")
         assert 1 <= steps <= TABLE_ROWS - 2
         traj = Trajectory(h, w, steps - start, start, sampler, sigmas, eta, seeds, guide, guidance_scale if guide is None else 1.0, img, hold, plan, hm,
                           size if size is not None else (8 * h, 8 * w), step_family(sampler, img, hold is not None),
-                          None if reg is None else dict(reg, bootstrap=min(reg["bootstrap"], steps - start)), apg)
+                          None if reg is None else dict(reg, bootstrap=min(reg["bootstrap"], steps - start)), apg, dynthresh)
         if graph or fused:
             if traj.family == "sde":
                 require_op(ops, "sampler_step_sde", f": sample(sampler={sampler!r}) draws its per-step noise inside that launch")
@@ -1118,6 +1166,11 @@ class LatentSampler:
             st["atab"][: atab.shape[0]].copy_(atab)
             if "mom" not in sh:
                 sh["mom"] = rt.zeros(n * h * w, 4, dtype=F32)
+        if traj.dyn is not None:                          # the table beside gtab, rewritten per trajectory
+            dtab = dyn_table(sch, traj.dyn, traj.steps)
+            if "dtab" not in st:
+                st["dtab"] = rt.zeros(TABLE_ROWS - 1, 4, dtype=F32)
+            st["dtab"][: dtab.shape[0]].copy_(dtab)
         noise = latents if latents is not None else torch.randn(n, 4, h, w, generator=generator, device=dev, dtype=F32)
         noise = noise.to(dev, F32).contiguous()
         assert tuple(noise.shape) == (n, 4, h, w)
@@ -1161,7 +1214,8 @@ class LatentSampler:
         """The forward stage of one iteration, on either driver: the UNet on sh["x64"] at st["tf"] - with a tile plan: gather, the forward on the windows,
         blend; with regions: gather, the forward on every region's rows, blend - then ops.heatmap_accum on the forward's score sums (heat, a dict of sh["heat"]: the weight of row ctr[0] of st["hw"]; the maps are
         allocated at the first iteration, when the forward has told the resolutions), then ops.guidance (row ctr[0] of st["gtab"]) where the pre-pass
-        runs - with apg: ops.guidance_apg (the same row of st["atab"] as well, the running average in sh["mom"]) -> eps fp32 [2 n h w, 4]."""
+        runs - with apg: ops.guidance_apg (the same row of st["atab"] as well, the running average in sh["mom"]); with dyn: ops.guidance_dyn (the same row of
+        st["dtab"] as well) -> eps fp32 [2 n h w, 4]."""
         u, h, w = self.unet, traj.h, traj.w
         tid = st["tid"] if u.cfg["addition"] else None
         if traj.plan is not None:
@@ -1177,6 +1231,8 @@ class LatentSampler:
             self.rt.ops.heatmap_accum(ents, heat["cols"], st["ctr"], st["hw"], heat["heat"], row_off=1, row_stride=2)
         if traj.apg is not None:
             self.rt.ops.guidance_apg(eps, st["gtab"], st["atab"], sh["mom"], st["ctr"], self.n)
+        elif traj.dyn is not None:
+            self.rt.ops.guidance_dyn(eps, st["gtab"], st["dtab"], st["ctr"], self.n)
         elif traj.guide is not None:
             self.rt.ops.guidance(eps, st["gtab"], st["ctr"], self.n)
         return eps
@@ -1199,6 +1255,7 @@ class LatentSampler:
         guided: the captures with the guidance pre-pass in them, in a fifth dict, keyed by the key the iteration has above plus its family, so they
         neither collide with those captures nor evict them; the scales, phi and the interval are in st["gtab"]: one capture per family serves all.
         apg: the captures with ops.guidance_apg instead, in a sixth dict, that key plus "apg"; eta, threshold and momentum are in st["atab"].
+        dyn: the captures with ops.guidance_dyn instead, in a seventh dict, the guided key plus "dyn"; the three values per step are in st["dtab"].
         heat: the captures with ops.heatmap_accum in them are keyed by ("heat", grid, T, P) as well - the launch's shape; which columns and which
         step weights are device memory."""
         h, w, fam, masked, guided = traj.h, traj.w, traj.family, traj.masked, traj.guide is not None
@@ -1223,6 +1280,8 @@ class LatentSampler:
             key, graphs = key + (fam,), self._guided_graphs
         if traj.apg is not None:                          # ops.guidance_apg is another launch: captures of their own; eta, threshold and momentum are in st["atab"]
             key, graphs = key + ("apg",), self._apg_graphs
+        if traj.dyn is not None:                          # ops.guidance_dyn likewise; mimic, percentile and interpolate are in st["dtab"]
+            key, graphs = key + ("dyn",), self._dyn_graphs
         g = graphs.get(key)
         if g is not None:
             return g

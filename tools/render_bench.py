@@ -10,13 +10,16 @@ are timed at eta = 1 with fixed seeds.  --guidance-rescale F adds (r) the defaul
 --apg adds the default iteration with adaptive projected guidance - (p) sdlt_guidance_apg at eta 0, norm threshold 15, momentum -0.5; (q) the same with
 --guidance-rescale's phi (0.7 when not given) - against (c) and (r), and, after the table, the device-event time of 50 back-to-back launches of
 sdlt_guidance_apg (momentum and clip on, with and without phi) and of sdlt_guidance (phi) on one image of the latent's size.
+--dynthresh adds (t) the default iteration with dynamic thresholding - sdlt_guidance_dyn at mimic 7, percentile 0.999, interpolate 1 - against (c), and,
+after the table, the device-event time of 50 back-to-back launches of sdlt_guidance_dyn and of sdlt_guidance (--guidance-rescale's phi, 0.7 when not given)
+on one image of the latent's size.
 --freeu B1 B2 S1 S2 adds the default iteration with FreeU in its forward - (u) version 1, (v) version 2: six sdlt_freeu calls per forward on SDXL - against
 (c); with --trace-iteration the traced loop runs it (version 2 with --freeu-v2).
 --kv-downsample SPEC [SPEC ...] adds (k, l, m, ...) the default iteration with key / value token downsampling - SPEC = factors, largest grid first, and
 optionally a mode: `2`, `2:area`, `4,2` - against (c); with --trace-iteration the traced loop runs the first SPEC.  --graph-only drops (a) and (b), which
 take long at large latents.  --dump FILE saves the final latents of (c), for a bit comparison between two builds.
 
-    python tools/render_bench.py [--out FILE] [--rounds 5] [--version sdxl] [--latent 128] [--n 1 2] [--img2img] [--sampler dpmpp_2m] [--sigmas karras] [--guidance-rescale 0.7] [--apg] [--freeu 1.3 1.4 0.9 0.2]
+    python tools/render_bench.py [--out FILE] [--rounds 5] [--version sdxl] [--latent 128] [--n 1 2] [--img2img] [--sampler dpmpp_2m] [--sigmas karras] [--guidance-rescale 0.7] [--apg] [--dynthresh] [--freeu 1.3 1.4 0.9 0.2]
                                   [--kv-downsample 2 2:area 4,2] [--graph-only] [--dump FILE]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/render_bench.py --trace-iteration --n 1      # kernel time of one iteration: sum the stats
 
@@ -101,6 +104,49 @@ def launch_times(h, phi, launches=50, rounds=5):
     return lines
 
 
+def dyn_launch_times(h, phi, launches=50, rounds=5):
+    """launch_times for sdlt_guidance_dyn (guidance 8, mimic 7, percentile 0.999, interpolate 1) beside sdlt_guidance at phi, in the same session.  eps is
+    restored before every timed sequence; within it later launches see a thresholded prediction in both row blocks - the same passes, traffic and histogram load (the deviations
+    stay distinct).  The "first launch" row times one launch on the fresh pair, the events' own cost included."""
+    from sd_lora_trainer_amd import ops
+    g = torch.Generator(device="cuda").manual_seed(5)
+    hw = h * h
+    src = torch.randn(2 * hw, 4, device="cuda", generator=g)
+    src[hw:] = src[:hw] + 0.12 * torch.randn(hw, 4, device="cuda", generator=g)
+    eps = src.clone()
+    ctr = torch.tensor([1, 0], dtype=torch.int32, device="cuda")
+    gtab = torch.tensor([[2.0, 0, 0, 0], [8.0, phi, 0, 0], [8.0, phi, 0, 0]], device="cuda")
+    gdyn = torch.tensor([[2.0, 0, 0, 0], [8.0, 0, 0, 0], [8.0, 0, 0, 0]], device="cuda")
+    dtab = torch.tensor([[2.0, 0, 0, 0], [7.0, 0.999, 1.0, 0], [7.0, 0.999, 1.0, 0]], device="cuda")
+    kinds = {"sdlt_guidance_dyn": lambda: ops.guidance_dyn(eps, gdyn, dtab, ctr, 1),
+             "sdlt_guidance_dyn, first launch": None,
+             f"sdlt_guidance, phi {phi:g}": lambda: ops.guidance(eps, gtab, ctr, 1)}
+    times = {k: [] for k in kinds}
+    for r in range(rounds + 1):
+        for k, fn in kinds.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            eps.copy_(src)
+            if fn is None:                                  # ONE launch on the fresh pair (distinct keys), the event overhead included
+                e0.record()
+                ops.guidance_dyn(eps, gdyn, dtab, ctr, 1)
+                e1.record()
+                torch.cuda.synchronize()
+                t = e0.elapsed_time(e1) * 1e3
+            else:
+                e0.record()
+                for _ in range(launches):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                t = e0.elapsed_time(e1) * 1e3 / launches
+            if r:
+                times[k].append(t)
+    lines = [f"# device-event us per launch, n = 1, hw = {hw}, {launches} launches back to back: median (min .. max) of {rounds} rounds, alternated"]
+    for k, t in times.items():
+        lines.append(f"   {k:<32} {statistics.median(t):>12.2f} {min(t):>8.2f} {max(t):>8.2f}")
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -117,6 +163,7 @@ def main():
     ap.add_argument("--sigmas", nargs="+", choices=("trailing", "karras"), default=["trailing"], help="... on these noise levels")
     ap.add_argument("--guidance-rescale", type=float, default=0.0, help="also time the default graph sampler with the guidance pre-pass at this rescale weight")
     ap.add_argument("--apg", action="store_true", help="also time the default graph sampler with adaptive projected guidance (with and without the rescale), and the pre-pass launches alone")
+    ap.add_argument("--dynthresh", action="store_true", help="also time the default graph sampler with dynamic thresholding, and the pre-pass launch alone")
     ap.add_argument("--freeu", type=float, nargs=4, metavar=("B1", "B2", "S1", "S2"), default=None, help="also time the default graph sampler with FreeU, versions 1 and 2")
     ap.add_argument("--freeu-v2", action="store_true", help="with --trace-iteration --freeu: trace version 2")
     ap.add_argument("--kv-downsample", nargs="+", metavar="SPEC", default=[], help="also time the default graph sampler with key / value token downsampling: "
@@ -157,6 +204,8 @@ def main():
             phi = a.guidance_rescale or 0.7
             variants["p graph, APG"], ran["p graph, APG"] = (lambda: one(graph=True, apg=(0.0, 15.0, -0.5))), a.steps
             variants["q graph, APG + rescale"], ran["q graph, APG + rescale"] = (lambda: one(graph=True, apg=(0.0, 15.0, -0.5), guidance_rescale=phi)), a.steps
+        if a.dynthresh:
+            variants["t graph, dynthresh"], ran["t graph, dynthresh"] = (lambda: one(graph=True, dynthresh=(7.0, 0.999, 1.0))), a.steps
         if a.freeu:
             for tag, ver in (("u", 1), ("v", 2)):
                 fz = dict(zip(("b1", "b2", "s1", "s2"), a.freeu), version=ver)
@@ -194,6 +243,8 @@ def main():
             torch.cuda.empty_cache()
     if a.apg:
         lines += launch_times(h, a.guidance_rescale or 0.7)
+    if a.dynthresh:
+        lines += dyn_launch_times(h, a.guidance_rescale or 0.7)
     text = "\n".join(lines) + "\n"
     print(text, end="")
     if a.out:
