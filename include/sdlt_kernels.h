@@ -263,6 +263,23 @@ enum {
   SDLT_ATTN_ROUTE_SPLITSUM = 1 << 18   /* the slab-sum launch follows it */
 };
 int32_t sdlt_attn_route(const sdlt_attn_params* p, int32_t backward);
+/* One-pass attention forward for ONE WIDE HEAD - the mid-block attention of AutoencoderKL, one head as wide as the block - in one launch and with no
+ * [N, N] buffer:  O[b] = softmax(scale Q[b] K[b]^T) V[b], non-causal.  Q, O: bf16 [B Nq, d], K, V: bf16 [B Nk, d], token-major, row strides ld* in elements
+ * (ld % 8 == 0, ld >= d): image b owns query rows [b Nq, (b+1) Nq) and key / value rows [b Nk, (b+1) Nk).  There are NO pad rows: Nq and Nk are any integers
+ * >= 1; keys at or beyond an image's Nk are masked, no row at or beyond B Nk (B Nq) is read and none beyond B Nq is written.  fp32 scores and online softmax,
+ * P rounded to bf16 for the P V products, fp32 accumulation, one rounding at the store; no atomics and one summation order (bit-reproducible), no workspace.
+ * d = 512 (SD / SDXL) or 128 (the toy VAE): any other width is refused (heads of d <= 160: sdlt_attn_fwd).  B max(Nq, Nk) <= 2^31 - 65 (in-image row indices
+ * and the grid are 32-bit; row offsets are 64-bit).  Every refusal returns before anything is launched, outputs untouched.  Forward only and no log-sum-exp
+ * output: the VAE is frozen, nobody trains through it. */
+typedef struct {
+  const void* Q; int64_t ldq;
+  const void* K; int64_t ldk;
+  const void* V; int64_t ldv;
+  void* O; int64_t ldo;
+  int32_t B, Nq, Nk, d;
+  float scale;
+} sdlt_attn_wide_params;      /* 88 bytes; tagless, no index in sdlt_struct_size (like sdlt_resize_params): a binding checks its mirror against this figure */
+int sdlt_attn_wide_fwd(const sdlt_attn_wide_params* p, void* stream);
 /* out0 / out1 [B*Nkp, C] bf16 = sum over nsplit slabs of s0 / s1 (fp32 [nsplit][B*Nkp][ld32]) in slab order (rows with key >= Nk: zeros;
  * acc0: out0 += instead of =), for a table of layers: block_desc[b] = descriptor of block b, block_first[d] = first block of descriptor d,
  * a layer owns ceil(B*Nkp*C/2 / 256) blocks (capped at 64; the kernel strides). */

@@ -667,6 +667,8 @@ def _pair_ok(lib, a, b):
         return bool(pa.ln) == bool(pb.ln) and wide(pa.N) == wide(pb.N) and not (pa.splitk > 1 and not pa.P) and not (pb.splitk > 1 and not pb.P)
     if kind in ("attn_fwd", "attn_bwd"):
         return bool(lib.sdlt_attn_pair_ok(C.byref(pa), C.byref(pb)))
+    if kind == "attn_wide":      # no paired entry: two single launches
+        return False
     return True
 
 
@@ -677,6 +679,8 @@ def _launch_single(lib, kind, p, st):
         _lib.check(lib.sdlt_attn_fwd(C.byref(p), st), "sdlt_attn_fwd")
     elif kind == "attn_bwd":
         _lib.check(lib.sdlt_attn_bwd(C.byref(p), st), "sdlt_attn_bwd")
+    elif kind == "attn_wide":
+        _lib.check(lib.sdlt_attn_wide_fwd(C.byref(p), st), "sdlt_attn_wide_fwd")
     else:
         _lib.check(lib.sdlt_layernorm_bwd_slabs(p.x, p.ldx, p.dy32, p.lddy32, p.nslab, p.M, p.C, p.gamma, p.stats, p.dres, p.lddres, p.dx, p.lddx, st),
                    "sdlt_layernorm_bwd_slabs")
@@ -914,6 +918,20 @@ def attn_fwd(Q, K, V, Vt, O, L, *, B, H, Nq, Nk, Nqp, Nkp, d, scale, causal=Fals
         assert zero_D.is_contiguous() and zero_D.numel() >= B * H * Nq
         p.D = _p(zero_D)
     _issue("attn_fwd", p)
+    return O
+
+
+def attn_wide_fwd(Q, K, V, O, *, B, Nq, Nk, scale):
+    """sdlt_attn_wide_fwd: O[b] = softmax(scale Q[b] K[b]^T) V[b] for ONE head as wide as the rows (d = Q.shape[1]: 512 or 128) in one launch with no [N, N]
+    buffer - the VAE's mid-block attention.  Q, O bf16 [B Nq, d], K, V bf16 [B Nk, d] (row-major views, any row stride % 8 == 0), no pad rows."""
+    p = _lib.AttnWideParams()
+    _chk2(Q), _chk2(K), _chk2(V), _chk2(O)
+    d = Q.shape[1]
+    assert Q.shape == (B * Nq, d) and O.shape == (B * Nq, d) and K.shape == (B * Nk, d) and V.shape == (B * Nk, d), \
+        f"Q {tuple(Q.shape)} K {tuple(K.shape)} V {tuple(V.shape)} O {tuple(O.shape)} for B={B} Nq={Nq} Nk={Nk}"
+    p.Q, p.ldq, p.K, p.ldk, p.V, p.ldv, p.O, p.ldo = _p(Q), _ld(Q), _p(K), _ld(K), _p(V), _ld(V), _p(O), _ld(O)
+    p.B, p.Nq, p.Nk, p.d, p.scale = B, Nq, Nk, d, scale
+    _issue("attn_wide", p, keep=(Q, K, V, O))
     return O
 
 

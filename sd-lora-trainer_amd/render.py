@@ -337,7 +337,8 @@ def _vae_encoder(loaded):
     from . import unet as M
     from . import vae as V
     rt = loaded.stack.rt
-    return V.VaeEncoder(M.Runtime(rt.device, 1, act_dtype=rt.act, ops=rt.ops), loaded.models.vae_state())
+    va = getattr(loaded.stack, "vae_attention", "dense")      # (render(vae_attention=) leaves it on the stack)
+    return V.VaeEncoder(M.Runtime(rt.device, 1, act_dtype=rt.act, ops=rt.ops), loaded.models.vae_state(), **({} if va == "dense" else dict(attention=va)))
 
 
 VAE_TILE, VAE_TILE_OVERLAP = 64, 16      # --vae-tile's defaults, in latent units (512 and 128 px with the SD / SDXL VAE)
@@ -553,7 +554,7 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
            graph=True, n_validation=4, init_image=None, strength=None, mask_image=None, sampler="euler", sigmas="trailing", eta=None,
            guidance_rescale=0.0, guidance_interval=None, negative_prompt=None, hires=None, freeu=None, heatmap=None, heatmap_grid="max",
            kv_downsample=None, kv_downsample_mode="nearest", kv_downsample_pass="hires", vae_tile=None, change_map_image=None, mask_blur=None, tile_diffusion=None, regions=None, region_feather=None,
-           region_base=None, region_bootstrap=None, apg=None, dynthresh=None):
+           region_base=None, region_bootstrap=None, apg=None, dynthresh=None, vae_attention="dense"):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
     seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
@@ -584,6 +585,9 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     vae_tile: None, a tile length or (tile, overlap) in latent units (vae_tile_args; the overlap defaults to 16): every VAE pass of the render - the
     decode of each picture, the decode and encode of the pixel upscaler, the encode of init_image - runs in tiles (VaeDecoder.decode_tiled,
     VaeEncoder.encode_moments_tiled; ops.tile_blend).  The decoder then runs at the tile's shape and is not rebuilt with the UNet by the hires pass.
+    vae_attention: "dense" (default) or "flash" - the mid-block attention of every VAE the render builds (the decoder, init_image's encoder, the pixel
+    upscaler's pair, the rebuilt ones of a hires render) as one sdlt_attn_wide_fwd launch with no [N, N] score buffer (vae.check_attention).
+    With vae_tile every tile runs it at N = T^2.
     change_map_image (path or PIL image; needs init_image, excludes mask_image and hires): differential diffusion - its luminance, area-resized to the
     latent grid (dataset.latent_change_map), is LatentSampler.sample's change_map: white the whole `strength`, black keep.  mask_blur (a sigma in latent
     pixels, >= 0): the change map - or mask_image's mask, which then takes the blend path as before - is blurred on the device first (sampler.blur_map).
@@ -676,6 +680,7 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     vt = vae_tile_args(vae_tile)                                     # (raises before anything is built)
     if vt is not None:
         SM.require_op(stack.rt.ops, "tile_blend", " (sdlt_tile_blend): vae_tile puts the VAE's tiles together by that launch (ops.tile_blend)")
+    _vae.check_attention(stack.rt, vae_attention)                    # (raises before anything is built)
     td_plan = SM.tile_plan(h, w, tile_diffusion)                     # (raises before anything is built)
     td_plan2 = None
     if tile_diffusion is not None:
@@ -703,6 +708,10 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         td_plan2 = SM.tile_plan(hi["size"][1] // f, hi["size"][0] // f, tile_diffusion)
     for pl in (td_plan, td_plan2):
         SM.window_multiple(cfg, pl, "tile_diffusion")
+    stack.vae_attention = vae_attention                              # every VAE this render builds takes it: RenderStack.build_decoder, _vae_encoder
+    if getattr(stack.decoder, "attention", "dense") != vae_attention:
+        stack.build_decoder()
+        loaded.dec_shape = None
     img_kw = {}
     if guidance_rescale != 0.0:
         img_kw.update(guidance_rescale=guidance_rescale)
@@ -883,6 +892,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             meta.update(heatmap=dict(maps=hm_names, grid=heatmap_grid, positions=hm_cols.tolist()))
         if vt is not None:
             meta.update(vae_tile=dict(tile=vt[0], overlap=vt[1]))
+        if vae_attention != "dense":
+            meta.update(vae_attention=vae_attention)
         if tile_diffusion is not None:                  # (tiles: of the last pass; [1, 1]: every pass fitted one window and ran plain)
             T_, O_ = (tile_diffusion, tile_diffusion // 4) if isinstance(tile_diffusion, int) else tile_diffusion
             pl = td_plan2 if hi is not None else td_plan
@@ -955,6 +966,9 @@ def main(argv=None, runtime=None):
                     "and one decoder shape at any picture size")
     ap.add_argument("--vae-tile-overlap", type=int, default=None, metavar="O",
                     help=f"with --vae-tile: least overlap of neighbouring tiles in latent units, 0 <= 2 O <= T (default {VAE_TILE_OVERLAP})")
+    ap.add_argument("--vae-attention", choices=("dense", "flash"), default=None,
+                    help="the VAE's mid-block attention: dense (default) - two GEMMs around a row softmax over an [N, N] score buffer; flash - one launch, no "
+                    "score buffer (what an untiled 2048 px decode needs)")
     ap.add_argument("--tile-diffusion", type=int, nargs="?", const=TILE_DIFFUSION_JOB, default=None, metavar="T",
                     help="tiled diffusion (MultiDiffusion): where a pass's latent exceeds T x T latent units the UNet runs on overlapping T x T windows, fused "
                     "on the device at every step - one UNet shape at any picture size (default T: the job's resolution // 8)")
@@ -1101,6 +1115,7 @@ def main(argv=None, runtime=None):
                  guidance_interval=a.guidance_interval, negative_prompt=a.negative_prompt, **({} if hires is None else dict(hires=hires)),
                  **({} if freeu is None else dict(freeu=freeu)), **kvd, **vtile, **tdiff, **regs, **apg, **dyn,
                  **({} if a.change_map is None else dict(change_map_image=a.change_map)), **({} if a.mask_blur is None else dict(mask_blur=a.mask_blur)),
+                 **({} if a.vae_attention is None else dict(vae_attention=a.vae_attention)),
                  **({} if a.heatmap is None else dict(heatmap=a.heatmap, heatmap_grid=a.heatmap_grid or "max")))
     for scale, paths in res.items():
         print(f"lora_scale {scale}: {len(paths)} image(s), {os.path.join(a.out, 'grid_scale' + _scale_tag(scale) + '.jpg')}")

@@ -318,11 +318,13 @@ class RenderStack:
             self.build_decoder()
 
     def build_decoder(self):
-        """(Re)build the VAE decoder alone: its buffers belong to the first latent shape it decodes."""
+        """(Re)build the VAE decoder alone: its buffers belong to the first latent shape it decodes.  `vae_attention` set on the stack ("flash",
+        render(vae_attention=)): its mid-block attention mode (vae.check_attention)."""
         from . import unet as M
         from . import vae as V
         self.decoder = None
-        self.decoder = V.VaeDecoder(M.Runtime(self.models.rt.device, 1, ops=self.models.rt.ops), self.models.vae_state())
+        va = getattr(self, "vae_attention", "dense")
+        self.decoder = V.VaeDecoder(M.Runtime(self.models.rt.device, 1, ops=self.models.rt.ops), self.models.vae_state(), **({} if va == "dense" else dict(attention=va)))
 
     def encode(self, prompt, negative):
         """pipe.encode_prompt(prompt, do_classifier_free_guidance=True, negative_prompt=...) -> (c, uc[, pc, puc]); batch row 0 = negative."""

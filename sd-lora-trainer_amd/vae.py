@@ -9,6 +9,8 @@ image: 1 GB of fp32 scores, trivial next to 288 GB).  The encoder's stride-2 con
 Downsample2D(padding=0)): computed as the pad-1 stride-1 conv sampled at the odd pixels, which reads exactly those taps.
 Past that size the scores do not stay trivial (17 GB at 2048 px, more than the card at 4096 px): decode_tiled / encode_moments_tiled run the same plans
 tile by tile at one fixed shape and put the tiles together with a normalised feather on the device (tile_starts, tile_weights, ops.tile_blend).
+attention="flash" (VaeDecoder / VaeEncoder; the default stays "dense") runs that attention as ONE sdlt_attn_wide_fwd launch over all images instead: no score,
+P or V^T buffer, no pad rows (ops.attn_wide_fwd).
 """
 import math
 
@@ -46,19 +48,40 @@ class VaeResnet(_Module):
         return self.conv2.forward(self.norm2.forward(h, None, B, H * W), B, H, W, residual=sc, train=False)
 
 
+VAE_ATTENTIONS = ("dense", "flash")
+FLASH_WIDTHS = (128, 512)      # the head widths sdlt_attn_wide_fwd is built for
+
+
+def check_attention(rt, attention):
+    """`attention` of VaeAttention / VaeDecoder / VaeEncoder, checked before anything is built: "dense" (the default: two GEMMs around a row softmax over an
+    [N, N] score buffer) or "flash" (one sdlt_attn_wide_fwd launch, no [N, N] buffer).  There is no torch fallback for a missing kernel."""
+    if attention not in VAE_ATTENTIONS:
+        raise ValueError(f"VAE attention must be one of {VAE_ATTENTIONS}, got {attention!r}")
+    if attention == "flash" and not hasattr(rt.ops, "attn_wide_fwd"):
+        raise NotImplementedError("this op table has no attn_wide_fwd kernel (sdlt_attn_wide_fwd): the flash VAE attention is that one launch (ops.attn_wide_fwd)")
+    return attention
+
+
 class VaeAttention(_Module):
-    def __init__(self, rt, name, sd):
+    def __init__(self, rt, name, sd, attention="dense"):
         super().__init__(rt, name)
+        self.attention = check_attention(rt, attention)
         self.norm = GroupNorm(rt, name + ".group_norm", sd, 1e-6, silu=False)
         self.q = Linear(rt, name + ".to_q", sd, need_dx=False)
         self.k = Linear(rt, name + ".to_k", sd, need_dx=False)
         self.v = Linear(rt, name + ".to_v", sd, need_dx=False)
         self.o = Linear(rt, name + ".to_out.0", sd, need_dx=False)
         self.C = self.q.N
+        if attention == "flash" and self.C not in FLASH_WIDTHS:
+            raise ValueError(f"{name}: the flash VAE attention is built for mid-block widths {FLASH_WIDTHS}, this one is {self.C} wide")
 
     def forward(self, x, B, N):
         rt, C = self.rt, self.C
         hn = self.norm.forward(x, None, B, N)
+        if self.attention == "flash":      # q, k, v row-major, all B images in ONE launch, no S / P / V^T buffer
+            q, k, v = self.q.forward(hn, train=False), self.k.forward(hn, train=False), self.v.forward(hn, train=False)
+            O = rt.ops.attn_wide_fwd(q, k, v, self.buf("O", B * N, C), B=B, Nq=N, Nk=N, scale=1.0 / math.sqrt(C))
+            return self.o.forward(O, residual=x, train=False)
         q, k = self.q.forward(hn, train=False), self.k.forward(hn, train=False)
         Np = _pad_to(N, 64)
         vt = self.buf("vt", C, B * Np, zero=True)
@@ -75,10 +98,10 @@ class VaeAttention(_Module):
 
 
 class _Mid(_Module):
-    def __init__(self, rt, name, sd):
+    def __init__(self, rt, name, sd, attention="dense"):
         super().__init__(rt, name)
         self.r0 = VaeResnet(rt, name + ".resnets.0", sd)
-        self.attn = VaeAttention(rt, name + ".attentions.0", sd)
+        self.attn = VaeAttention(rt, name + ".attentions.0", sd, attention)
         self.r1 = VaeResnet(rt, name + ".resnets.1", sd)
 
     def forward(self, x, B, H, W):
@@ -88,8 +111,9 @@ class _Mid(_Module):
 class VaeDecoder(_Module):
     """decode(z [B, 4, h, w] fp32, already / scaling_factor) -> image [B, 3, 8h, 8w] fp32 (before postprocess)."""
 
-    def __init__(self, rt, sd, n_levels=None, layers_per_block=None):
+    def __init__(self, rt, sd, n_levels=None, layers_per_block=None, attention="dense"):
         super().__init__(rt, "vae.decoder")
+        self.attention = check_attention(rt, attention)
         nl = 0
         while f"decoder.up_blocks.{nl}.resnets.0.norm1.weight" in sd:
             nl += 1
@@ -100,7 +124,7 @@ class VaeDecoder(_Module):
         self.pq_b = sd["post_quant_conv.bias"].to(rt.device, F32)
         self.zc = self.pq_w.shape[0]
         self.conv_in = Conv3x3(rt, "decoder.conv_in", sd, cin_pad=64, need_dx=False)
-        self.mid = _Mid(rt, "decoder.mid_block", sd)
+        self.mid = _Mid(rt, "decoder.mid_block", sd, attention)
         self.ups = []
         for i in range(nl):
             res = [VaeResnet(rt, f"decoder.up_blocks.{i}.resnets.{j}", sd) for j in range(L)]
@@ -216,8 +240,9 @@ def tile_weights(L, T, O, g):
 class VaeEncoder(_Module):
     """encode_moments(img [B, 3, H, W] fp32 in [-1, 1]) -> [B, 8, H/8, W/8] fp32 (mean | logvar) = latent_dist.parameters."""
 
-    def __init__(self, rt, sd):
+    def __init__(self, rt, sd, attention="dense"):
         super().__init__(rt, "vae.encoder")
+        self.attention = check_attention(rt, attention)
         nl = 0
         while f"encoder.down_blocks.{nl}.resnets.0.norm1.weight" in sd:
             nl += 1
@@ -231,7 +256,7 @@ class VaeEncoder(_Module):
             res = [VaeResnet(rt, f"encoder.down_blocks.{i}.resnets.{j}", sd) for j in range(L)]
             ds = Conv3x3(rt, f"encoder.down_blocks.{i}.downsamplers.0.conv", sd, need_dx=False) if i != nl - 1 else None
             self.downs.append((res, ds))
-        self.mid = _Mid(rt, "encoder.mid_block", sd)
+        self.mid = _Mid(rt, "encoder.mid_block", sd, attention)
         self.norm_out = GroupNorm(rt, "encoder.conv_norm_out", sd, 1e-6, silu=True)
         self.conv_out = Conv3x3(rt, "encoder.conv_out", sd, need_dx=False)
         self.q_w = sd["quant_conv.weight"].to(rt.device, F32).reshape(sd["quant_conv.weight"].shape[0], -1)
