@@ -280,6 +280,27 @@ typedef struct {
   float scale;
 } sdlt_attn_wide_params;      /* 88 bytes; tagless, no index in sdlt_struct_size (like sdlt_resize_params): a binding checks its mirror against this figure */
 int sdlt_attn_wide_fwd(const sdlt_attn_wide_params* p, void* stream);
+/* Region-coupled cross-attention forward ("Attention Couple": regional prompts inside one UNet pass).  For batch row b, head hd, query q:
+ *   O[b, q, hd] = sum over r < Rb of  Wt[r, q] * softmax_k(scale Q[b, q, hd] . K[b, r, k, hd]) V[b, r, k, hd],   Rb = clamp(rcount[b], 1, R) (rcount NULL: R).
+ * Q, O: bf16 token-major [B Nq, ld], head hd in columns [hd d, (hd + 1) d), NO pad rows (any Nq >= 1).  K, V: bf16 [B R Nkp, ld]; region r of batch row b owns
+ * rows [(b R + r) Nkp, + Nk), 1 <= Nk <= Nkp <= ... with Nk <= 128 and Nkp % 8 == 0; rows [Nk, Nkp) are masked (the kernel does not read them) and regions
+ * r >= Rb of a batch row are never read (they may hold NaN).  Wt: fp32 [R, Nq], finite and >= 0, shared by all batch rows, NOT normalised by the kernel.
+ * rcount: int32 [B] device memory or NULL.  d % 8 == 0 and d <= 160, R <= 16, every ld % 8 == 0 and >= H d.  fp32 scores, exact softmax over the resident key
+ * row, bf16 P for the P V products, fp32 accumulation, region results added in ascending r from +0.0 as acc += (Wt[r, q] / l) * O_r, one rounding at the store;
+ * regions whose weight is zero for all 64 queries of a tile are skipped.  No atomics, no workspace: two runs give the same bits.  Forward only, no log-sum-exp.
+ * A null block or operand, an extent < 1, R > 16, Nk > 128, Nkp < Nk, ld < H d, O overlapping an input, an index range beyond 32 bits (-1); Nkp % 8, ld % 8,
+ * Q / K / V / O not 16-byte or Wt / rcount not 4-byte aligned (-2); an unsupported d (-4): the code is returned before anything is launched, outputs untouched. */
+typedef struct {
+  const void* Q; int64_t ldq;
+  const void* K; int64_t ldk;
+  const void* V; int64_t ldv;
+  void* O; int64_t ldo;
+  const float* Wt;
+  const int32_t* rcount;
+  int32_t B, H, Nq, Nk, Nkp, R, d;
+  float scale;
+} sdlt_attn_couple_params;    /* 112 bytes; tagless, no index in sdlt_struct_size (like sdlt_attn_wide_params): a binding checks its mirror against this figure */
+int sdlt_attn_couple_fwd(const sdlt_attn_couple_params* p, void* stream);
 /* out0 / out1 [B*Nkp, C] bf16 = sum over nsplit slabs of s0 / s1 (fp32 [nsplit][B*Nkp][ld32]) in slab order (rows with key >= Nk: zeros;
  * acc0: out0 += instead of =), for a table of layers: block_desc[b] = descriptor of block b, block_first[d] = first block of descriptor d,
  * a layer owns ceil(B*Nkp*C/2 / 256) blocks (capped at 64; the kernel strides). */

@@ -667,7 +667,7 @@ def _pair_ok(lib, a, b):
         return bool(pa.ln) == bool(pb.ln) and wide(pa.N) == wide(pb.N) and not (pa.splitk > 1 and not pa.P) and not (pb.splitk > 1 and not pb.P)
     if kind in ("attn_fwd", "attn_bwd"):
         return bool(lib.sdlt_attn_pair_ok(C.byref(pa), C.byref(pb)))
-    if kind == "attn_wide":      # no paired entry: two single launches
+    if kind in ("attn_wide", "attn_couple"):      # no paired entry: two single launches
         return False
     return True
 
@@ -681,6 +681,8 @@ def _launch_single(lib, kind, p, st):
         _lib.check(lib.sdlt_attn_bwd(C.byref(p), st), "sdlt_attn_bwd")
     elif kind == "attn_wide":
         _lib.check(lib.sdlt_attn_wide_fwd(C.byref(p), st), "sdlt_attn_wide_fwd")
+    elif kind == "attn_couple":
+        _lib.check(lib.sdlt_attn_couple_fwd(C.byref(p), st), "sdlt_attn_couple_fwd")
     else:
         _lib.check(lib.sdlt_layernorm_bwd_slabs(p.x, p.ldx, p.dy32, p.lddy32, p.nslab, p.M, p.C, p.gamma, p.stats, p.dres, p.lddres, p.dx, p.lddx, st),
                    "sdlt_layernorm_bwd_slabs")
@@ -933,6 +935,66 @@ def attn_wide_fwd(Q, K, V, O, *, B, Nq, Nk, scale):
     p.B, p.Nq, p.Nk, p.d, p.scale = B, Nq, Nk, d, scale
     _issue("attn_wide", p, keep=(Q, K, V, O))
     return O
+
+
+COUPLE_MAX_KEYS = 128      # keys per region of sdlt_attn_couple_fwd (a whole key row is resident)
+
+
+def attn_couple_fwd(Q, K, V, O, Wt, *, B, H, Nq, Nk, Nkp, R, d, scale, rcount=None):
+    """sdlt_attn_couple_fwd: region-coupled cross-attention, O[b, q, hd] = sum over r < Rb of Wt[r, q] softmax_k(scale Q[b, q, hd] . K[b, r, k, hd]) V[b, r, k, hd],
+    Rb = clamp(rcount[b], 1, R) (rcount None: R).  Q, O bf16 [B Nq, >= H d] (no pad rows), K, V bf16 [B R Nkp, >= H d] (row-major views, any row stride % 8
+    == 0; region r of batch row b in rows [(b R + r) Nkp, + Nk), the rest masked; regions >= Rb are never read), Wt fp32 [R, Nq] contiguous (finite, >= 0, not
+    normalised by the kernel), rcount int32 [B] on the device.  ValueError for a wrong shape or dtype, before the call."""
+    def bad(msg):
+        raise ValueError(f"attn_couple_fwd: {msg}")
+    for name, v in (("B", B), ("H", H), ("Nq", Nq), ("Nk", Nk), ("R", R), ("d", d)):
+        if not isinstance(v, int) or v < 1:
+            bad(f"{name}={v!r} (an integer >= 1)")
+    if R > REGION_MAX or Nk > COUPLE_MAX_KEYS or Nkp < Nk or Nkp % 8:
+        bad(f"R={R} (<= {REGION_MAX}) Nk={Nk} (<= {COUPLE_MAX_KEYS}) Nkp={Nkp} (>= Nk, a multiple of 8)")
+    if d % 8 or d > 160:
+        bad(f"d={d} (a multiple of 8, <= 160)")
+    for name, t, rows in (("Q", Q, B * Nq), ("O", O, B * Nq), ("K", K, B * R * Nkp), ("V", V, B * R * Nkp)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == BF16 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == rows and t.shape[1] >= H * d):
+            bad(f"{name}: expected a cuda bf16 row-major view [{rows}, >= {H * d}], got {tuple(t.shape) if torch.is_tensor(t) else type(t)}")
+    if not (torch.is_tensor(Wt) and Wt.is_cuda and Wt.dtype == F32 and tuple(Wt.shape) == (R, Nq) and Wt.is_contiguous()):
+        bad(f"Wt: expected a contiguous cuda fp32 [{R}, {Nq}]")
+    if rcount is not None and not (torch.is_tensor(rcount) and rcount.is_cuda and rcount.dtype == torch.int32 and tuple(rcount.shape) == (B,) and rcount.is_contiguous()):
+        bad(f"rcount: expected a contiguous cuda int32 [{B}]")
+    p = _lib.AttnCoupleParams()
+    p.Q, p.ldq, p.K, p.ldk, p.V, p.ldv, p.O, p.ldo = _p(Q), _ld(Q), _p(K), _ld(K), _p(V), _ld(V), _p(O), _ld(O)
+    p.Wt, p.rcount = _p(Wt), _p(rcount)
+    p.B, p.H, p.Nq, p.Nk, p.Nkp, p.R, p.d, p.scale = B, H, Nq, Nk, Nkp, R, d, float(scale)
+    _issue("attn_couple", p, keep=(Q, K, V, O, Wt, rcount))
+    return O
+
+
+def couple_weights(wn, levels):
+    """The weight tables of attn_couple_fwd for the UNet's token grids: wn fp32 [R, h, w] (region_tables' normalised weights), levels an iterable of l >= 0 ->
+    {N_l: fp32 [R, N_l]} with the grid (h >> l) x (w >> l), the UNet's own // 2 per level.  Token (y, x) of level l covers latent pixels [2^l y, 2^l (y + 1)) x
+    [2^l x, 2^l (x + 1)), clipped to the latent (a no-op: 2^l (h >> l) <= h; the odd last row / column of a level has no token, as in the UNet); the entry is the
+    mean of wn[r] over those pixels divided by its sum over r, formed in fp64 and rounded once.  Level 0 is wn itself."""
+    wn = torch.as_tensor(wn)
+    if wn.dim() != 3 or wn.dtype != F32:
+        raise ValueError(f"couple_weights: wn {tuple(wn.shape)} {wn.dtype}: expected fp32 [R, h, w]")
+    R, h, w = wn.shape
+    out = {}
+    for l in sorted(set(int(v) for v in levels)):
+        gh, gw = h >> l, w >> l
+        if l < 0 or gh < 1 or gw < 1:
+            raise ValueError(f"couple_weights: level {l} of a {h} x {w} latent has no tokens")
+        if l == 0:
+            t = wn.reshape(R, h * w).clone()
+        else:
+            s = 1 << l
+            t = wn.double()[:, :gh * s, :gw * s].reshape(R, gh, s, gw, s).mean(dim=(2, 4))
+            tot = t.sum(0, keepdim=True)
+            assert bool((tot > 0).all()), "couple_weights: a token without weight (region_tables makes the total positive at every pixel)"
+            t = (t / tot).to(F32).reshape(R, gh * gw)
+        if gh * gw in out:
+            raise ValueError(f"couple_weights: levels {sorted(set(levels))} of a {h} x {w} latent give the token count {gh * gw} twice")
+        out[gh * gw] = t.contiguous()
+    return out
 
 
 def attn_bwd(Q, K, V, Kt, Qt, O, L, dO, dOt, D, dQ, dK, dV, *, B, H, Nq, Nk, Nqp, Nkp, d, scale, causal=False,

@@ -13,7 +13,7 @@ scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-squ
                                          [--hires-resample nearest|bilinear|bicubic] [--heatmap [WORD ...]] [--heatmap-grid max|min]
                                          [--kv-downsample F [F2 ...]] [--kv-downsample-mode nearest|area] [--kv-downsample-pass hires|all]
                                          [--vae-tile [T]] [--vae-tile-overlap O] [--tile-diffusion [T]] [--tile-diffusion-overlap O]
-                                         [--region MASK.png|x0,y0,x1,y1 PROMPT ...] [--region-feather SIGMA] [--region-base F] [--region-bootstrap SHARE]
+                                         [--region MASK.png|x0,y0,x1,y1 PROMPT ...] [--region-feather SIGMA] [--region-base F] [--region-bootstrap SHARE] [--region-mode fuse|couple]
                                          [--unet F] [--text-encoder F] [--text-encoder-2 F] [--vae F] [--tokenizer DIR]
 
 DIR is a checkpoint directory of train(): training_args.json (the job's TrainingConfig), adapter_config.json + the kohya adapter file
@@ -120,7 +120,9 @@ as one batch of 2 N R rows, copied by sdlt_region_gather and fused by sdlt_regio
 (sampler.LatentSampler.sample(regions=)).  --region-feather SIGMA blurs each mask by a Gaussian of SIGMA latent pixels (sdlt_blur_planes);
 --region-base F gives the main prompt the extra weight F everywhere (default 0); --region-bootstrap SHARE (default 0.2, the paper's; 0: off) is the share
 of the steps at which a region sees a solid colour noised to the step's level outside its mask, so that its object forms inside.  Not with
---tile-diffusion, --heatmap or --hires-*.  Without the flag nothing changes.
+--tile-diffusion, --heatmap or --hires-*.  Without the flag nothing changes.  --region-mode couple (default fuse: the above) runs the UNet ONCE, at batch
+2 N, and couples the regions where the prompts enter it: every cross-attention attends to each region's tokens separately and mixes the results with the
+pixel's normalised region weights (sdlt_attn_couple_fwd; "Attention Couple"): "--region 0,0,0.5,1 'a red barn' --region-mode couple".  No bootstrap there.
 """
 import argparse
 import json
@@ -152,16 +154,17 @@ class Loaded:
         if self.lora is not None:
             self.stack.unet.arena.load(self.lora)
 
-    def prepare(self, n_images, h, w, keep_decoder=False, plan=None, regions=1):
+    def prepare(self, n_images, h, w, keep_decoder=False, plan=None, regions=1, couple=False):
         """The UNet's activation buffers belong to the first latent shape it runs: another batch or size starts from fresh instances.  keep_decoder: the
         VAE decoder is not rebuilt with them (a tiled decode runs at the tile's shape whatever the picture's: prepare_decoder).  plan (a
         sampler.TilePlan): tiled diffusion - the UNet runs at the window's shape on 2 n_images ty tx rows whatever the picture's size, so the shape
         is the windows' extents and counts: another picture size with the same ones keeps the instances.  regions (R > 1): regional prompts - the UNet
-        runs at the picture's shape on 2 n_images R rows."""
+        runs at the picture's shape on 2 n_images R rows; couple: at batch 2 n_images (the regions meet inside cross-attention; fresh instances all the same:
+        the cross-attention k | v buffers hold R times the rows)."""
         shape = (n_images, h, w) if plan is None else (n_images,) + tuple(plan[2:])
         tiles = 1 if plan is None else plan.ty * plan.tx
         if regions > 1:
-            shape, tiles = (n_images, h, w, "region", regions), regions
+            shape, tiles = (n_images, h, w, "couple" if couple else "region", regions), 1 if couple else regions
         if self.shape is not None and self.shape != shape or n_images != self.stack.n_images or tiles != getattr(self.stack, "tiles", 1):
             self.stack.keep_decoder = keep_decoder
             try:
@@ -477,7 +480,7 @@ def region_spec(text):
     return text
 
 
-def region_args(regions, region_feather=None, region_base=None, region_bootstrap=None):
+def region_args(regions, region_feather=None, region_base=None, region_bootstrap=None, region_mode=None):
     """render()'s `regions`, `region_feather`, `region_base` and `region_bootstrap`, checked -> None | dict(regions [(mask image | box, prompt)], feather,
     base, bootstrap).  regions: None, or a non-empty list of (mask image - a path or PIL image - | box (x0, y0, x1, y1) in fractions of the picture with
     0 <= x0 < x1 <= 1 and 0 <= y0 < y1 <= 1, prompt); at most 7 (sampler.region_plan: 8 with the background).  feather: a Gaussian sigma in latent
@@ -485,9 +488,11 @@ def region_args(regions, region_feather=None, region_base=None, region_bootstrap
     for any of the three without regions."""
     from . import sampler as SM
     num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)  # noqa: E731
+    if region_mode is not None and region_mode not in SM.REGION_MODES:
+        raise ValueError(f"region_mode must be one of {SM.REGION_MODES}, got {region_mode!r}")
     if regions is None:
-        if region_feather is not None or region_base is not None or region_bootstrap is not None:
-            raise ValueError("region_feather, region_base and region_bootstrap need regions")
+        if region_feather is not None or region_base is not None or region_bootstrap is not None or region_mode is not None:
+            raise ValueError("region_feather, region_base, region_bootstrap and region_mode need regions")
         return None
     regions = list(regions)
     if not regions or len(regions) + 1 > SM.REGION_PLAN_MAX:
@@ -508,10 +513,13 @@ def region_args(regions, region_feather=None, region_base=None, region_bootstrap
     base = 0.0 if region_base is None else region_base
     if not (num(base) and base >= 0.0):
         raise ValueError(f"region_base must be a finite number >= 0, got {region_base!r}")
-    boot = REGION_BOOTSTRAP if region_bootstrap is None else region_bootstrap
+    couple = region_mode == "couple"      # one UNet pass, the regions coupled in cross-attention: no region rows to bootstrap, so its default is 0 there
+    boot = (0.0 if couple else REGION_BOOTSTRAP) if region_bootstrap is None else region_bootstrap
     if not (num(boot) and 0.0 <= boot <= 1.0):
         raise ValueError(f"region_bootstrap must be a share of the steps in [0, 1], got {region_bootstrap!r}")
-    return dict(regions=out, feather=float(feather), base=float(base), bootstrap=float(boot))
+    if couple and boot != 0:
+        raise ValueError(f"region_bootstrap must be 0 with region_mode='couple' (bootstrap edits the model input per region row; this mode has no such rows), got {region_bootstrap!r}")
+    return dict(regions=out, feather=float(feather), base=float(base), bootstrap=float(boot), mode=region_mode)
 
 
 def region_masks(loaded, rg, size, latent_hw):
@@ -554,7 +562,7 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
            graph=True, n_validation=4, init_image=None, strength=None, mask_image=None, sampler="euler", sigmas="trailing", eta=None,
            guidance_rescale=0.0, guidance_interval=None, negative_prompt=None, hires=None, freeu=None, heatmap=None, heatmap_grid="max",
            kv_downsample=None, kv_downsample_mode="nearest", kv_downsample_pass="hires", vae_tile=None, change_map_image=None, mask_blur=None, tile_diffusion=None, regions=None, region_feather=None,
-           region_base=None, region_bootstrap=None, apg=None, dynthresh=None, vae_attention="dense"):
+           region_base=None, region_bootstrap=None, apg=None, dynthresh=None, vae_attention="dense", region_mode=None):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
     seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
@@ -640,13 +648,16 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         SM.require_op(stack.rt.ops, "guidance_apg", " (sdlt_guidance_apg): apg forms the projected prediction by that launch (ops.guidance_apg)", kernel="sdlt_guidance_apg")
     if dt is not None:
         SM.require_op(stack.rt.ops, "guidance_dyn", " (sdlt_guidance_dyn): dynthresh forms the thresholded prediction by that launch (ops.guidance_dyn)", kernel="sdlt_guidance_dyn")
-    rg = region_args(regions, region_feather, region_base, region_bootstrap)      # (raises before anything is built)
+    rg = region_args(regions, region_feather, region_base, region_bootstrap, region_mode)      # (raises before anything is built)
     if rg is not None:
         for other, name in ((tile_diffusion, "tile_diffusion: windows of regions are not built"), (hires, "hires: the masks would need a second grid"),
                             (heatmap, "heatmap: the hooked score sums are per region row, and fusing them is not built")):
             if other is not None:
                 raise ValueError(f"regions do not combine with {name}")
-        SM.require_op(stack.rt.ops, "region_blend", " (sdlt_region_blend): regions copy the model input and fuse the predictions by two launches (ops.region_gather, ops.region_blend)")
+        if rg["mode"] == "couple":
+            SM.require_op(stack.rt.ops, "attn_couple_fwd", " (sdlt_attn_couple_fwd): region_mode='couple' mixes the regions inside every cross-attention by that launch", kernel="sdlt_attn_couple_fwd")
+        else:
+            SM.require_op(stack.rt.ops, "region_blend", " (sdlt_region_blend): regions copy the model input and fuse the predictions by two launches (ops.region_gather, ops.region_blend)")
         if rg["feather"] > 0.0:
             SM.require_op(stack.rt.ops, "blur_planes", ": region_feather blurs the masks on the device by that launch (ops.blur_planes)")
     fz = SM.freeu_args(freeu)                                          # (raises before anything is built)
@@ -752,9 +763,9 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     if rg is not None:                                  # masks, backgrounds and the bootstrap's step count: the same for every picture of the render
         k_run = steps if init_image is None else SM.img2img_steps(steps, strength)[0]
         k_boot = int(round(rg["bootstrap"] * k_run))
-        reg_kw = dict(masks=region_masks(loaded, rg, size, (h, w)), base=rg["base"], bootstrap=k_boot,
+        reg_kw = dict(masks=region_masks(loaded, rg, size, (h, w)), base=rg["base"], bootstrap=k_boot, mode=rg["mode"] or "fuse",
                       bg=None if k_boot == 0 else region_backgrounds(loaded, R_, seed)[None].expand(n, R_, 4).contiguous())
-    loaded.prepare(n, h, w, **({} if vt is None else dict(keep_decoder=True)), **td_kw(td_plan), **({} if rg is None else dict(regions=R_)))
+    loaded.prepare(n, h, w, **({} if vt is None else dict(keep_decoder=True)), **td_kw(td_plan), **({} if rg is None else dict(regions=R_, couple=rg["mode"] == "couple")))
     fused = hasattr(stack.rt.ops, "sampler_step_dd" if change_map_image is not None else "sampler_step_sde" if sde else "sampler_step_ms" if sampler == "dpmpp_2m"
                     else "sampler_step")
     graph = graph and dev.type == "cuda"
@@ -900,7 +911,7 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             meta.update(tile_diffusion=dict(tile=T_, overlap=O_, tiles=[1, 1] if pl is None else [pl.ty, pl.tx]))
         if rg is not None:
             meta.update(regions=[dict(prompt=p, **(dict(box=list(wh)) if isinstance(wh, tuple) else dict(mask=wh if isinstance(wh, str) else None))) for wh, p in rg["regions"]],
-                        region_base=rg["base"], region_bootstrap=rg["bootstrap"], region_feather=rg["feather"])
+                        region_base=rg["base"], region_bootstrap=rg["bootstrap"], region_feather=rg["feather"], **({} if rg["mode"] is None else dict(region_mode=rg["mode"])))
         json.dump(meta, fh, indent=2)
     return result
 
@@ -979,6 +990,9 @@ def main(argv=None, runtime=None):
                     "allowed in PROMPT; --prompt rules wherever no region has weight")
     ap.add_argument("--region-feather", type=float, default=None, metavar="SIGMA", help="with --region: blur each mask by a Gaussian of SIGMA latent pixels")
     ap.add_argument("--region-base", type=float, default=None, metavar="F", help="with --region: extra weight of the main prompt everywhere (default 0)")
+    ap.add_argument("--region-mode", choices=("fuse", "couple"), default=None,
+                    help="with --region: fuse (default) runs the UNet once per region and fuses the predictions; couple runs it once and mixes the regions inside every "
+                    "cross-attention (Attention Couple, sdlt_attn_couple_fwd): --region 0,0,0.5,1 'a red barn' --region-mode couple; --region-bootstrap is 0 there")
     ap.add_argument("--region-bootstrap", type=float, default=None, metavar="SHARE",
                     help=f"with --region: share of the steps at which a region sees a noised solid colour outside its mask (default {REGION_BOOTSTRAP}; 0: off)")
     ap.add_argument("--device", default="cuda:0")
@@ -1065,19 +1079,19 @@ def main(argv=None, runtime=None):
         ap.error("--tile-diffusion does not combine with --heatmap")
     regs = {}
     if a.region is None:
-        if a.region_feather is not None or a.region_base is not None or a.region_bootstrap is not None:
-            ap.error("--region-feather, --region-base and --region-bootstrap need --region")
+        if a.region_feather is not None or a.region_base is not None or a.region_bootstrap is not None or a.region_mode is not None:
+            ap.error("--region-feather, --region-base, --region-bootstrap and --region-mode need --region")
     else:
         for flag, on in (("--tile-diffusion", a.tile_diffusion is not None), ("--heatmap", a.heatmap is not None),
                          ("--hires-scale / --hires-size", any(v is not None for v in (a.hires_scale, a.hires_size, a.hires_strength, a.hires_steps, a.hires_upscaler, a.hires_resample)))):
             if on:
                 ap.error(f"--region does not combine with {flag}")
         regs = dict(regions=[(region_spec(where), prompt) for where, prompt in a.region],
-                    **{k: v for k, v in dict(region_feather=a.region_feather, region_base=a.region_base, region_bootstrap=a.region_bootstrap).items() if v is not None})
+                    **{k: v for k, v in dict(region_feather=a.region_feather, region_base=a.region_base, region_bootstrap=a.region_bootstrap, region_mode=a.region_mode).items() if v is not None})
         try:
             region_args(**regs)
         except ValueError as e:
-            ap.error(f"--region / --region-feather / --region-base / --region-bootstrap: {e}")
+            ap.error(f"--region / --region-feather / --region-base / --region-bootstrap / --region-mode: {e}")
         for where, _ in regs["regions"]:
             if isinstance(where, str) and not os.path.exists(where):
                 ap.error(f"--region: {where!r} is neither a box x0,y0,x1,y1 nor a mask picture that exists")

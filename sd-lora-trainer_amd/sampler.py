@@ -569,7 +569,8 @@ def window_multiple(cfg, plan, name="tile"):
 
 
 REGION_PLAN_MAX = 8        # regions of sample(regions=) with the background: the UNet batch is 2 n R (the kernels take 16)
-REGION_KEYS = ("masks", "embeds", "base", "bootstrap", "bg")
+REGION_KEYS = ("masks", "embeds", "base", "bootstrap", "bg", "mode")
+REGION_MODES = ("fuse", "couple")      # fuse: the UNet once per region, predictions fused (MultiDiffusion); couple: one pass, regions coupled in cross-attention
 
 
 def region_plan(h, w, masks, base=0.0):
@@ -592,14 +593,19 @@ def region_args(regions, h, w, n, k):
         return None
     unknown = sorted(set(regions) - set(REGION_KEYS))
     if unknown or "masks" not in regions or "embeds" not in regions:
-        raise ValueError(f"regions: keys masks, embeds and optionally base, bootstrap, bg; unknown {unknown}")
+        raise ValueError(f"regions: keys masks, embeds and optionally base, bootstrap, bg, mode; unknown {unknown}")
     masks = regions["masks"]
     if masks is not None and not torch.is_tensor(masks):
         masks = torch.as_tensor(np.asarray(masks, dtype=np.float32))
-    tabs = region_plan(h, w, masks, regions.get("base", 0.0))
+    mode = regions.get("mode", "fuse")
+    if mode not in REGION_MODES:
+        raise ValueError(f"regions: mode must be one of {REGION_MODES}, got {mode!r}")
     boot = regions.get("bootstrap", 0)
     if not (isinstance(boot, int) and not isinstance(boot, bool) and boot >= 0):
         raise ValueError(f"regions: bootstrap must be a step count >= 0, got {boot!r}")
+    if mode == "couple" and boot > 0:      # (before anything is built)
+        raise ValueError("regions: bootstrap edits the model input per region row, and mode='couple' has no such rows (one UNet pass): bootstrap must be 0")
+    tabs = region_plan(h, w, masks, regions.get("base", 0.0))
     R = tabs.R
     em = regions["embeds"]
     em = [] if em is None else list(em)
@@ -614,7 +620,7 @@ def region_args(regions, h, w, n, k):
     bg = torch.as_tensor(bg)
     if tuple(bg.shape) != (n, R, 4) or not bool(torch.isfinite(bg).all()):
         raise ValueError(f"regions: bg {tuple(bg.shape)}: expected finite fp32 [{n}, {R}, 4], a background latent per image and region")
-    return dict(tabs=tabs, embeds=per_image, bootstrap=min(boot, k), bg=bg.to(F32).contiguous())
+    return dict(tabs=tabs, embeds=per_image, bootstrap=min(boot, k), bg=bg.to(F32).contiguous(), couple=mode == "couple")
 
 
 def region_rtab(sched, k_boot):
@@ -898,11 +904,17 @@ class LatentSampler:
         reg = None
         if regions is not None:                            # (the step count of the bootstrap is cut to the steps that run below)
             reg = region_args(regions, h, w, n_images, TABLE_ROWS)
-        if reg is not None:
+        couple = reg is not None and reg["couple"]
+        if couple:
+            require_op(ops, "attn_couple_fwd", " (sdlt_attn_couple_fwd): sample(regions=dict(mode='couple')) mixes the regions inside every cross-attention by "
+                       "that launch (ops.attn_couple_fwd), in the torch loop too", kernel="sdlt_attn_couple_fwd")
+        elif getattr(self.unet, "_couple", None) is not None:
+            self.unet.set_attention_couple(None)           # (the setting does not stick)
+        if reg is not None and not couple:
             for op in ("region_blend", "region_gather"):
                 require_op(ops, op, " (sdlt_region_blend): sample(regions=...) copies the model input to the regions' rows and fuses their predictions "
                            "by two launches (ops.region_gather, ops.region_blend), in the torch loop too", kernel="region_blend")
-        rows = reg["tabs"].R if reg is not None else 1 if plan is None else plan.ty * plan.tx
+        rows = reg["tabs"].R if reg is not None and not couple else 1 if plan is None else plan.ty * plan.tx
         if rows != self.tiles:
             raise ValueError(f"this sampler's runtime holds {self.tiles} window(s) per image (batch {self.rt.B}, {self.n} image(s)); the call needs "
                              f"{rows}: build it on a runtime of batch 2 n_images ty tx (LatentSampler(n_images=))")
@@ -971,7 +983,7 @@ class LatentSampler:
         st, sh, x0, noise, heat = self._begin(traj, s, embeds, latents, generator)
         x = noise * s.init_noise_sigma if traj.img is None else x0 + noise * float(s.sigmas[0])
         m, hold = sh["img"]["mask"] if traj.masked else None, None if traj.hold is None else sh["img"]["hold"]
-        sde, counted = traj.sampler in SDE_KINDS, heat is not None or traj.guide is not None or traj.reg is not None      # (the gather reads the bootstrap's row)
+        sde, counted = traj.sampler in SDE_KINDS, heat is not None or traj.guide is not None or (traj.reg is not None and not traj.reg["couple"])      # (the gather reads the bootstrap's row)
         if sde:
             z = rt.zeros(1, 4, h, w, dtype=F32)
         if heat is not None and heat["heat"] is not None:
@@ -1056,14 +1068,31 @@ class LatentSampler:
             self._fused = dict(tf=rt.zeros(2 * n, dtype=F32), tid=rt.zeros(rt.B * 6, dtype=F32), table=rt.zeros(TABLE_ROWS, 4, dtype=F32),
                                ctr=torch.zeros(2, dtype=torch.int32, device=rt.device), shapes={})
         st = self._fused
-        key = (h, w, "region", reg["tabs"].R) if reg is not None else (h, w) if plan is None else (h, w) + tuple(plan[2:])
+        key = (h, w, "couple" if reg["couple"] else "region", reg["tabs"].R) if reg is not None else (h, w) if plan is None else (h, w) + tuple(plan[2:])
         if key not in st["shapes"]:
             st["shapes"][key] = dict(x=rt.zeros(n, 4, h, w, dtype=F32), x64=rt.zeros(2 * n * h * w, 64))
         if plan is not None:
             self._window_state(st["shapes"][key], h, w, plan)
         if reg is not None:
-            self._region_state(st["shapes"][key], h, w, reg)
+            (self._couple_state if reg["couple"] else self._region_state)(st["shapes"][key], h, w, reg)
         return st, st["shapes"][key]
+
+    def _couple_state(self, sh, h, w, reg):
+        """-> sh["couple"]: the persistent buffers of regional prompts in couple mode for this shape - the contexts [2 n R CTX_PAD, D], rcount = [1, R, 1, R,
+        ...] and one weight table per token grid of the UNet's transformers - allocated once (a captured launch holds their pointers); the tables are
+        rewritten per call from the masks (ops.couple_weights): another mask set with the same region count is the same buffers and the same capture.
+        Hands them to the UNet (set_attention_couple)."""
+        from . import ops as _ops
+        rt, n, R = self.rt, self.n, reg["tabs"].R
+        fresh = _ops.couple_weights(reg["tabs"].wn, sorted({l for _, l in self.unet._attn_levels()}))
+        cs = sh.get("couple")
+        if cs is None:
+            cs = sh["couple"] = dict(R=R, ctx=rt.zeros(2 * n * R * CTX_PAD, self.unet.cfg["cross_dim"]), rcount=torch.tensor([1, R] * n, dtype=torch.int32, device=rt.device),
+                                     weights={N: torch.zeros_like(t, device=rt.device) for N, t in fresh.items()})
+        for N, t in fresh.items():
+            cs["weights"][N].copy_(t)
+        self.unet.set_attention_couple(dict(R=R, weights=cs["weights"], rcount=cs["rcount"]))
+        return cs
 
     def _region_state(self, sh, h, w, reg):
         """-> sh["reg"]: the persistent buffers of regional prompts for this shape - the regions' model input x64_regions and timesteps tf_regions, the
@@ -1117,7 +1146,7 @@ class LatentSampler:
         e = self.unet.forward(win["x64_tiles"], win["tf_tiles"], self.ctx, self.pooled, tid, B=rt.B, H=plan.th, W=plan.tw, **self._fwd_kw())
         return rt.ops.window_blend(win["tabs"], e, win["eps_full"], n=self.n, H=h, W=w)
 
-    def _load_conditioning(self, st, embeds, size, reg=None):
+    def _load_conditioning(self, st, embeds, size, reg=None, sh=None):
         """embeds: one (c, uc[, pc, puc]) per image (one image: the tuple itself) -> ctx, pooled and SDXL's size conditioning st["tid"].  UNet batch rows
         2 j tl .. 2 (j + 1) tl - 1 are image j's, (negative, positive) per window: every window row carries the image's conditioning.  reg (regional
         prompts: tl = R): row 2 (j R + r) + 1 then takes region r's positive context and pooled vector for r >= 1; every even row keeps the call's
@@ -1134,11 +1163,18 @@ class LatentSampler:
                 pv = self.pooled.view(n, tl, 2, -1)
                 pv[j, :, 0].copy_(puc[0])
                 pv[j, :, 1].copy_(pc[0])
-            for r, er in enumerate(reg["embeds"][j] if reg is not None else (), start=1):
+            for r, er in enumerate(reg["embeds"][j] if reg is not None and not reg["couple"] else (), start=1):
                 cr, _, pcr, _ = (tuple(er) + (None, None))[:4]
                 cv[j, r, 1, :77].copy_(cr[0])
                 if cfg["addition"]:
                     pv[j, r, 1].copy_(pcr[0])
+        if reg is not None and reg["couple"]:      # couple mode: UNet row 2 j + s holds R context slots; slot 0 the call's own prompt, slot r of the positive row region r's;
+            cc = sh["couple"]["ctx"].view(n, 2, reg["tabs"].R, CTX_PAD, -1)      # the negative row's other slots stay zero (rcount 1: never read)
+            cc.zero_()
+            cc[:, :, 0, :77].copy_(cv[:, 0, :, :77])
+            for j in range(n):
+                for r, er in enumerate(reg["embeds"][j], start=1):
+                    cc[j, 1, r, :77].copy_(er[0][0])
         if cfg["addition"]:
             H, W = size
             st["tid"].copy_(torch.tensor([float(H), float(W), 0.0, 0.0, float(H), float(W)] * rt.B))      # original_size, crop, target_size
@@ -1151,8 +1187,8 @@ class LatentSampler:
         rt, n, h, w = self.rt, self.n, traj.h, traj.w
         dev = rt.device
         st, sh = self._state(h, w, traj.plan, traj.reg)
-        self._load_conditioning(st, embeds, traj.size, traj.reg)
-        if traj.reg is not None:                          # the bootstrap's rows of the steps that run; a captured gather holds the buffer
+        self._load_conditioning(st, embeds, traj.size, traj.reg, sh)
+        if traj.reg is not None and not traj.reg["couple"]:                          # the bootstrap's rows of the steps that run; a captured gather holds the buffer
             sh["reg"]["rtab"].copy_(region_rtab(sch, traj.reg["bootstrap"]))
         if traj.guide is not None:                        # a persistent buffer, rewritten per trajectory: a captured pre-pass holds its pointer
             gtab = guidance_table(sch, *traj.guide)
@@ -1174,7 +1210,7 @@ class LatentSampler:
         noise = latents if latents is not None else torch.randn(n, 4, h, w, generator=generator, device=dev, dtype=F32)
         noise = noise.to(dev, F32).contiguous()
         assert tuple(noise.shape) == (n, 4, h, w)
-        if traj.sampler in SDE_KINDS or traj.reg is not None:      # after the initial latents; a captured launch holds the buffer (regions: the bootstrap's key)
+        if traj.sampler in SDE_KINDS or (traj.reg is not None and not traj.reg["couple"]):      # after the initial latents; a captured launch holds the buffer (regions: the bootstrap's key)
             if "seeds" not in st:
                 st["seeds"] = torch.zeros(n, 2, dtype=torch.int32, device=dev)
             st["seeds"].copy_(seed_words(traj.seeds, n, generator, dev))
@@ -1220,6 +1256,8 @@ class LatentSampler:
         tid = st["tid"] if u.cfg["addition"] else None
         if traj.plan is not None:
             eps = self._window_forward(sh["win"], sh["x64"], st["tf"], tid, h, w)
+        elif traj.reg is not None and traj.reg["couple"]:      # one pass at batch 2 n: every cross-attention mixes the regions (UNet.set_attention_couple)
+            eps = u.forward(sh["x64"], st["tf"], sh["couple"]["ctx"], self.pooled, tid, B=2 * self.n, H=h, W=w, train=False)
         elif traj.reg is not None:
             eps = self._region_forward(sh["reg"], st, sh["x64"], st["tf"], tid, h, w)
         else:
@@ -1274,7 +1312,7 @@ class LatentSampler:
         if "win" in sh:                                   # tiled diffusion: the window extents and counts; starts and weights are device memory
             key += (("tile",) + tuple(sh["win"]["plan"][2:]),)
         if traj.reg is not None:                          # regional prompts: the region count; masks, weights, backgrounds and the bootstrap table are device memory
-            key += (("region", traj.reg["tabs"].R),)
+            key += (("couple" if traj.reg["couple"] else "region", traj.reg["tabs"].R),)
         graphs = getattr(self, f.graphs)
         if guided:
             key, graphs = key + (fam,), self._guided_graphs

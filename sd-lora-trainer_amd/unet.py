@@ -636,11 +636,17 @@ class StackedLinear(_Module):
     def prepare(self, x):
         """Allocates the stacked output / T buffers for input x and points the members at their slices (no launch)."""
         M, N, G = x.shape[0], self.N, self.G
-        y = self.buf("y", M, G * N)
+        # the buffers are keyed by the row count: the first one keeps the plain keys "y" / "T", any other gets buffers of its own, and none is ever freed - a
+        # captured graph of either row count keeps valid addresses.  Only a cross-attention k | v stack sees a second count (B R CTX_PAD rows under
+        # UNet.set_attention_couple, B CTX_PAD without); every other stack sees one for life
+        if getattr(self, "_rows0", None) is None:
+            self._rows0 = M
+        ky, kt = ("y", "T") if M == self._rows0 else (("y", M), ("T", M))
+        y = self.buf(ky, M, G * N)
         T = None
         if self.has_lora:
             Rp = self.arena.Rp
-            T = self.buf("T", M, G * Rp)
+            T = self.buf(kt, M, G * Rp)
         outs = []
         xin = x if self.ln is None or not self.has_lora else self.ln.ybuf()      # (folded LayerNorm: the adapter gradients read the rows its backward writes)
         for g, m in enumerate(self.members):
@@ -974,6 +980,7 @@ class Attention(_Module):
         self.d = self.C // heads
         self.scale = 1.0 / math.sqrt(self.d)
 
+    _couple = None      # the state of UNet.set_attention_couple: this cross-attention mixes R regions' results per query (inference only)
     _kv = None          # (factor > 1, mode) of UNet.set_kv_downsample: this self-attention takes k | v from pooled tokens (inference only)
     norm = None         # the LayerNorm in front of a self-attention (TransformerBlock.norm1): the pooling launch normalises with it
 
@@ -1026,10 +1033,17 @@ class Attention(_Module):
         pooled_kv = not self.cross and self._kv is not None
         if pooled_kv:
             q, k, v, Nk, Nkp = self._kv_forward(x, residual, B, N, grid)
-        Mq, Mk = B * N, B * Nkp
+        cp = self._couple if self.cross else None
+        if cp is not None:
+            if N not in cp["weights"]:
+                raise ValueError(f"attention couple: no weight table for the {N} tokens of {self.name} (tables for {sorted(cp['weights'])})")
+            if self.hooked and rt.keep_daam_maps:
+                raise ValueError(f"attention couple: the score side output of {self.name} (heat maps) sees one key set per row - keep_daam_maps is set")
+            self._qk = None      # (no score side output in this mode: it is per key set)
+        Mq, Mk = B * N, B * Nkp * (cp["R"] if cp is not None else 1)
         # transposed copies of Q and K are only needed as GEMM operands of the score side output's backward (hooked
         # cross-attention); the attention kernels themselves read every tile in its natural layout
-        need_t = self.cross and self.hooked
+        need_t = self.cross and self.hooked and cp is None
         if self.cross:
             q = self.to_q.forward(x, Ct=self.buf("Qt", C, Mq) if need_t else None)
             if self.kv_batched:          # to_k|to_v of every cross-attention layer ran in one batched launch (UNet._cross_kv_forward)
@@ -1050,11 +1064,13 @@ class Attention(_Module):
                         and not (self.to_out.lora is not None and self.to_out.arena.wide)
                         and getattr(rt.ops, "wsk_rowdot_shape", None) is not None and rt.ops.wsk_rowdot_shape(Mq, C, C, self.to_out.lora is not None, self.d))
         kwz = {"zero_D": self.buf("D", B * self.heads * N, dtype=F32)} if self._rowdot else {}
-        if N % 8:
+        if cp is not None:      # no pad rows, no log-sum-exp: the 4- and 6-token maps of the toys go straight in
+            rt.ops.attn_couple_fwd(q, k, v, O, cp["weights"][N], B=B, H=self.heads, Nq=N, Nk=Nk, Nkp=Nkp, R=cp["R"], d=self.d, scale=self.scale, rcount=cp["rcount"])
+        elif N % 8:
             self._attn_fwd_padded(q, k, v, O, L, B, N, Nk, Nkp, kv_padded=pooled_kv)
         else:
             rt.ops.attn_fwd(q, k, v, None, O, L, B=B, H=self.heads, Nq=N, Nk=Nk, Nqp=N, Nkp=Nkp, d=self.d, scale=self.scale, **kwz)
-        if self.cross and self.hooked:
+        if self.cross and self.hooked and cp is None:
             # DAAM side output (ti_cross_attn_loss.py:201-212): sum over heads of Q_h K_h^T / sqrt(d) = Q K^T / sqrt(d).
             # The token-attention loss only ever uses the MEAN over layers of these maps (loss.py:23-52), so the layers
             # of one resolution accumulate into one fp32 sum (GEMM epilogue, C += ...).
@@ -1392,6 +1408,7 @@ class UNet(_Module):
         self._grad_plan = None
         self._freeu = None               # set_freeu: (b1, b2, s1, s2, version) of an inference instance
         self._kv_ds = None               # set_kv_downsample: (factors, mode) of an inference instance
+        self._couple = None              # set_attention_couple: dict(R, weights, rcount) of an inference instance
         # time_emb_proj of every resnet reads the same silu(emb): ONE GEMM over the stacked weights [sum Cout, tdim] per pass instead of
         # one M = B launch per resnet (17 in SDXL, 22 in SD1.5); the same for their input gradients (dsemb) when B == 1.  Not with the
         # full fine-tune (the projections are trained layer by layer there).
@@ -1411,7 +1428,7 @@ class UNet(_Module):
         tfs = [t for (_, att, _) in self.down for t in att] + [self.mid[1]] + [t for (_, att, _) in self.up for t in att]
         self.cross_attns = [blk.attn2 for t in tfs for blk in t.blocks]
         ok = all(a.stack.has_lora and a.stack.kgrouped and not a.stack.wide for a in self.cross_attns) and len(self.cross_attns) > 1
-        self._kv_groups = None
+        self._kv_groups = {}             # (ctx rows, couple state set) -> the batched k | v operand tables (_cross_kv_forward)
         for a in self.cross_attns:
             a.kv_batched = ok
 
@@ -1424,6 +1441,12 @@ class UNet(_Module):
         if train and self._kv_ds is not None:
             raise NotImplementedError("kv_downsample is an inference option: a training forward (train=True, TrainStep) has no backward through the pooled "
                                       "keys and values - set_kv_downsample(None) first")
+        if self._couple is not None:
+            if train:
+                raise NotImplementedError("attention couple is an inference option: a training forward (train=True, TrainStep) has no backward through the "
+                                          "coupled cross-attention - set_attention_couple(None) first")
+            if ctx.shape[0] != B * self._couple["R"] * CTX_PAD:
+                raise ValueError(f"attention couple: ctx has {ctx.shape[0]} rows, expected B R CTX_PAD = {B * self._couple['R'] * CTX_PAD}")
         rt.gn_clear("fwd")          # one fill for the statistics of every GroupNorm of this pass
         rt.gn_prezero = True
         try:
@@ -1509,6 +1532,29 @@ class UNet(_Module):
         if not hasattr(self.rt.ops, "freeu"):
             raise NotImplementedError("this op table has no freeu kernel: FreeU's skip filter and backbone scale are that launch (ops.freeu)")
         self._freeu = vals + (int(version),)
+
+    # ------------------------------------------------------------------------------------ region-coupled cross-attention (inference only)
+    def set_attention_couple(self, state):
+        """None: off (the plain launch sequence).  dict(R=, weights={N: fp32 [R, N]}, rcount=int32 [B]): "Attention Couple" - regional prompts inside one
+        pass.  forward(train=False) then takes ctx as [B R CTX_PAD, D] (slot r of row b = region r's prompt), every cross-attention projects k | v from all
+        those rows and runs ops.attn_couple_fwd in attn_fwd's place with the table of its own token count N (ops.couple_weights); row b mixes its first
+        clamp(rcount[b], 1, R) slots and never reads the others.  The three objects are device buffers the caller owns and may rewrite between forwards: a
+        captured graph serves every mask set of the same (shape, R).  Self-attention, kv_downsample and FreeU are untouched."""
+        if state is not None:
+            unknown = sorted(set(state) - {"R", "weights", "rcount"})
+            if unknown or not {"R", "weights", "rcount"} <= set(state):
+                raise ValueError(f"attention couple takes dict(R=, weights=, rcount=), got keys {sorted(state)}")
+            R = state["R"]
+            if not isinstance(R, int) or not 1 <= R <= _ops.REGION_MAX:
+                raise ValueError(f"attention couple: R={R!r} (1 .. {_ops.REGION_MAX})")
+            if getattr(self.rt.ops, "attn_couple_fwd", None) is None:
+                raise NotImplementedError("this op table has no region-coupled attention kernel (sdlt_attn_couple_fwd): there is no torch fallback")
+            if self.rt.keep_daam_maps:
+                raise ValueError("attention couple: hooked score side outputs (keep_daam_maps, the heat maps) see one key set per row")
+            state = dict(R=R, weights=dict(state["weights"]), rcount=state["rcount"])
+        self._couple = state
+        for a in self.cross_attns:
+            a._couple = state
 
     # ------------------------------------------------------------------------------------ key / value token downsampling (inference only)
     def _attn_levels(self):
@@ -1745,12 +1791,20 @@ class UNet(_Module):
         if not self.cross_attns or not self.cross_attns[0].kv_batched:
             return
         rt = self.rt
-        if self._kv_groups is None:
+        # one operand table per (row count, couple state): set_attention_couple changes the rows to B R CTX_PAD and drops the hooked layers' transposed K; the
+        # tables and their buffers of both states stay alive side by side, so a captured graph of either keeps valid addresses
+        key = (ctx.shape[0], self._couple is not None)
+        if key in self._kv_groups:
+            if len(self._kv_groups) > 1:                    # the members' views may be the other state's: point them at this row count's slices (no launch)
+                for members, _, _ in self._kv_groups[key]:
+                    for a in members:
+                        a.stack.prepare(ctx)
+        else:
             groups = {}
             for a in self.cross_attns:
                 groups.setdefault((a.C, a.hooked), []).append(a)
-            self._kv_groups = []
-            Mk = B * CTX_PAD
+            built = self._kv_groups[key] = []
+            Mk = ctx.shape[0]
             for (C, hooked), members in groups.items():
                 items = []
                 for a in members:
@@ -1759,13 +1813,13 @@ class UNet(_Module):
                     it = dict(W=st.W, Adown=st.A_cat, Bup=st.B_cat, T_out=T, C=y)
                     if st.dora:
                         it["col_scale"] = st.col_scale()
-                    if hooked:      # transposed K for the score side output's backward (see Attention.backward)
-                        KVt = a.buf("KVt", 2 * C, _pad_to(Mk, 8))
+                    if hooked and self._couple is None:      # transposed K for the score side output's backward (see Attention.backward)
+                        KVt = a.buf("KVt" if Mk == st._rows0 else ("KVt", Mk), 2 * C, _pad_to(Mk, 8))
                         a._b["Kt"] = KVt[:C]
                         it["Ct"] = KVt
                     items.append(it)
-                self._kv_groups.append((members, items, rt.ops.GemmBatch(items, rt.device)))
-        for members, items, batch in self._kv_groups:
+                built.append((members, items, rt.ops.GemmBatch(items, rt.device)))
+        for members, items, batch in self._kv_groups[key]:
             st, it = members[0].stack, items[0]
             rt.ops.gemm(ctx, st.W, it["C"], lora=(st.A_cat, st.B_cat, st.arena.scale, it["T_out"]), Ct=it.get("Ct"),
                         lora_group_n=st.N, batch=batch, **({"col_scale": it["col_scale"]} if st.dora else {}))
@@ -1781,7 +1835,7 @@ class UNet(_Module):
             Mk, D = dctx.shape
             part = self.buf("dctx_parts", n, Mk, D, dtype=F32)
             self._kv_bwd, i = [], 0
-            for members, _, _ in self._kv_groups:
+            for members, _, _ in self._kv_groups[(Mk, False)]:      # (a training pass: the plain forward's table)
                 items = []
                 for a in members:
                     st = a.stack
