@@ -301,6 +301,25 @@ typedef struct {
   float scale;
 } sdlt_attn_couple_params;    /* 112 bytes; tagless, no index in sdlt_struct_size (like sdlt_attn_wide_params): a binding checks its mirror against this figure */
 int sdlt_attn_couple_fwd(const sdlt_attn_couple_params* p, void* stream);
+/* Tiled self-attention forward ("HyperTile"): every token attends to the tokens of its own rectangular tile of the token grid only.
+ * Q, K, V, O: bf16 token-major [B Hg Wg, ld], head hd in columns [hd d, (hd + 1) d), NO pad rows.  Hg x Wg is the token grid, row-major: token (y, x) of
+ * image b is row b Hg Wg + y Wg + x.  ty | Hg, tx | Wg, th = Hg / ty, tw = Wg / tx; token (y, x) lies in tile (y / th, x / tw).  For every image, head, tile:
+ *   O[q] = softmax_k(scale Q[q] . K[k]) V[k]   over the th tw keys k of q's own tile.
+ * Nothing crosses tiles (rows of another tile are not read: they may hold NaN); ty = tx = 1 is plain self-attention.  scale > 0.  d % 8 == 0 and d <= 96, every
+ * ld % 8 == 0 and >= H d (separate ld*: the operands may be column views of a stacked q | k | v buffer).  fp32 scores, online softmax over 64-key blocks in
+ * ascending tile-local order, bf16 P for the P V products, fp32 accumulation, one rounding at the store.  One launch for all images, heads and tiles; no
+ * [N, N] buffer, no gathered copy, no atomics, no workspace, no log-sum-exp: two runs give the same bits.  Forward only.
+ * A null block or operand, an extent < 1, ty not dividing Hg or tx not dividing Wg, ld < H d, O overlapping an input, row indices beyond 32 bits (-1); ld % 8,
+ * Q / K / V / O not 16-byte aligned (-2); an unsupported d (-4): the code is returned before anything is launched, outputs untouched. */
+typedef struct {
+  const void* Q; int64_t ldq;
+  const void* K; int64_t ldk;
+  const void* V; int64_t ldv;
+  void* O; int64_t ldo;
+  int32_t B, H, Hg, Wg, ty, tx, d;
+  float scale;
+} sdlt_attn_window_params;    /* 96 bytes; tagless, no index in sdlt_struct_size (like sdlt_attn_couple_params): a binding checks its mirror against this figure */
+int sdlt_attn_window_fwd(const sdlt_attn_window_params* p, void* stream);
 /* out0 / out1 [B*Nkp, C] bf16 = sum over nsplit slabs of s0 / s1 (fp32 [nsplit][B*Nkp][ld32]) in slab order (rows with key >= Nk: zeros;
  * acc0: out0 += instead of =), for a table of layers: block_desc[b] = descriptor of block b, block_first[d] = first block of descriptor d,
  * a layer owns ceil(B*Nkp*C/2 / 256) blocks (capped at 64; the kernel strides). */

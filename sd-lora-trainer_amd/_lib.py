@@ -125,6 +125,12 @@ class AttnCoupleParams(C.Structure):
                 ("B", i32), ("H", i32), ("Nq", i32), ("Nk", i32), ("Nkp", i32), ("R", i32), ("d", i32), ("scale", f32)]
 
 
+class AttnWindowParams(C.Structure):
+    # sdlt_attn_window_params: 96 bytes by the header's text (tagless, like sdlt_attn_couple_params)
+    _fields_ = [("Q", vp), ("ldq", i64), ("K", vp), ("ldk", i64), ("V", vp), ("ldv", i64), ("O", vp), ("ldo", i64),
+                ("B", i32), ("H", i32), ("Hg", i32), ("Wg", i32), ("ty", i32), ("tx", i32), ("d", i32), ("scale", f32)]
+
+
 # the packed code of sdlt_attn_route (include/sdlt_kernels.h, SDLT_ATTN_ROUTE_*)
 ATTN_ROUTES = ("FWD32", "FWD16_KS2", "FWD16", "BWD_CROSS_ROLES", "BWD_CROSS", "BWD_BOTH32", "BWD_BOTH16", "BWD_SPLIT")
 ATTN_ROUTE_MASK = 0xF
@@ -289,6 +295,7 @@ SYMBOLS = {
     "sdlt_attn_route": (i32, [C.POINTER(AttnParams), i32]),
     "sdlt_attn_wide_fwd": (i32, [C.POINTER(AttnWideParams), vp]),
     "sdlt_attn_couple_fwd": (i32, [C.POINTER(AttnCoupleParams), vp]),
+    "sdlt_attn_window_fwd": (i32, [C.POINTER(AttnWindowParams), vp]),
     "sdlt_attn_splitsum_batch": (i32, [vp, vp, vp, i32, vp]),
     "sdlt_groupnorm_ws_floats": (i32, [i32, i32, i32]),
     "sdlt_colsum_finish_batch": (i32, [vp, i32, i32, vp]),
@@ -397,7 +404,7 @@ def load():
     if C.sizeof(ResizeParams) != 48:
         raise KernelLibraryError(f"struct layout mismatch for ResizeParams: header 48 vs binding {C.sizeof(ResizeParams)}")
     for cls, size in ((HeatAccumParams, 152), (HeatOverlayParams, 80), (GemmPlan, 64), (SamplerDdParams, 128), (WindowParams, 64), (RegionParams, 64),
-                      (GuidanceApgParams, 56), (GuidanceDynParams, 48), (AttnWideParams, 88), (AttnCoupleParams, 112)):
+                      (GuidanceApgParams, 56), (GuidanceDynParams, 48), (AttnWideParams, 88), (AttnCoupleParams, 112), (AttnWindowParams, 96)):
         if C.sizeof(cls) != size:
             raise KernelLibraryError(f"struct layout mismatch for {cls.__name__}: header {size} vs binding {C.sizeof(cls)}")
     _lib = lib

@@ -667,7 +667,7 @@ def _pair_ok(lib, a, b):
         return bool(pa.ln) == bool(pb.ln) and wide(pa.N) == wide(pb.N) and not (pa.splitk > 1 and not pa.P) and not (pb.splitk > 1 and not pb.P)
     if kind in ("attn_fwd", "attn_bwd"):
         return bool(lib.sdlt_attn_pair_ok(C.byref(pa), C.byref(pb)))
-    if kind in ("attn_wide", "attn_couple"):      # no paired entry: two single launches
+    if kind in ("attn_wide", "attn_couple", "attn_window"):      # no paired entry: two single launches
         return False
     return True
 
@@ -683,6 +683,8 @@ def _launch_single(lib, kind, p, st):
         _lib.check(lib.sdlt_attn_wide_fwd(C.byref(p), st), "sdlt_attn_wide_fwd")
     elif kind == "attn_couple":
         _lib.check(lib.sdlt_attn_couple_fwd(C.byref(p), st), "sdlt_attn_couple_fwd")
+    elif kind == "attn_window":
+        _lib.check(lib.sdlt_attn_window_fwd(C.byref(p), st), "sdlt_attn_window_fwd")
     else:
         _lib.check(lib.sdlt_layernorm_bwd_slabs(p.x, p.ldx, p.dy32, p.lddy32, p.nslab, p.M, p.C, p.gamma, p.stats, p.dres, p.lddres, p.dx, p.lddx, st),
                    "sdlt_layernorm_bwd_slabs")
@@ -966,6 +968,35 @@ def attn_couple_fwd(Q, K, V, O, Wt, *, B, H, Nq, Nk, Nkp, R, d, scale, rcount=No
     p.Wt, p.rcount = _p(Wt), _p(rcount)
     p.B, p.H, p.Nq, p.Nk, p.Nkp, p.R, p.d, p.scale = B, H, Nq, Nk, Nkp, R, d, float(scale)
     _issue("attn_couple", p, keep=(Q, K, V, O, Wt, rcount))
+    return O
+
+
+def attn_window_fwd(Q, K, V, O, *, B, H, grid, tiles, d, scale):
+    """sdlt_attn_window_fwd: tiled self-attention ("HyperTile").  grid = (Hg, Wg), the row-major token grid of every image; tiles = (ty, tx) with ty | Hg and
+    tx | Wg; token (y, x) attends to the (Hg / ty) (Wg / tx) tokens of its own tile (y // (Hg / ty), x // (Wg / tx)) only.  Q, K, V, O bf16 [B Hg Wg, >= H d]
+    (row-major views, any row stride % 8 == 0: the column views of a stacked q | k | v buffer go straight in), no pad rows, d % 8 == 0 and d <= 96.  One
+    launch, no gathered copy.  ValueError for a wrong shape or dtype, before the call."""
+    def bad(msg):
+        raise ValueError(f"attn_window_fwd: {msg}")
+    ok_int = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
+    for name, pair in (("grid", grid), ("tiles", tiles)):
+        if not (isinstance(pair, (tuple, list)) and len(pair) == 2 and all(ok_int(v) and v >= 1 for v in pair)):
+            bad(f"{name}={pair!r} (two integers >= 1)")
+    (Hg, Wg), (ty, tx) = grid, tiles
+    for name, v in (("B", B), ("H", H), ("d", d)):
+        if not ok_int(v) or v < 1:
+            bad(f"{name}={v!r} (an integer >= 1)")
+    if Hg % ty or Wg % tx:
+        bad(f"{ty} x {tx} tiles do not divide the {Hg} x {Wg} token grid")
+    if d % 8 or d > 96:
+        bad(f"d={d} (a multiple of 8, <= 96)")
+    for name, t in (("Q", Q), ("K", K), ("V", V), ("O", O)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == BF16 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == B * Hg * Wg and t.shape[1] >= H * d):
+            bad(f"{name}: expected a cuda bf16 row-major view [{B * Hg * Wg}, >= {H * d}], got {tuple(t.shape) if torch.is_tensor(t) else type(t)}")
+    p = _lib.AttnWindowParams()
+    p.Q, p.ldq, p.K, p.ldk, p.V, p.ldv, p.O, p.ldo = _p(Q), _ld(Q), _p(K), _ld(K), _p(V), _ld(V), _p(O), _ld(O)
+    p.B, p.H, p.Hg, p.Wg, p.ty, p.tx, p.d, p.scale = B, H, Hg, Wg, ty, tx, d, float(scale)
+    _issue("attn_window", p, keep=(Q, K, V, O))
     return O
 
 

@@ -12,6 +12,7 @@ scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-squ
                                          [--hires-scale F | --hires-size W H] [--hires-strength F] [--hires-steps N] [--hires-upscaler latent|pixel]
                                          [--hires-resample nearest|bilinear|bicubic] [--heatmap [WORD ...]] [--heatmap-grid max|min]
                                          [--kv-downsample F [F2 ...]] [--kv-downsample-mode nearest|area] [--kv-downsample-pass hires|all]
+                                         [--hypertile [TILE_PX]] [--hypertile-depth D] [--hypertile-pass hires|all]
                                          [--vae-tile [T]] [--vae-tile-overlap O] [--tile-diffusion [T]] [--tile-diffusion-overlap O]
                                          [--region MASK.png|x0,y0,x1,y1 PROMPT ...] [--region-feather SIGMA] [--region-base F] [--region-bootstrap SHARE] [--region-mode fuse|couple]
                                          [--unet F] [--text-encoder F] [--text-encoder-2 F] [--vae F] [--tokenizer DIR]
@@ -97,6 +98,15 @@ paper's) takes every F-th token, area the mean of each F x F window.  One more l
 self-attention inside the replayed graph.  It is meant for the second pass of a hires render - where the grids are large, and after the first pass has
 decided the composition - so --kv-downsample-pass defaults to hires and the flag without --hires-scale / --hires-size is an error; all uses it in
 every pass.  Without the flag nothing changes.
+
+--hypertile [TILE_PX] is "HyperTile" (A1111's optimisation of that name, ComfyUI's HyperTile node) for large renders: the largest self-attention token grid
+is cut into rectangular tiles of at least TILE_PX picture pixels a side (default 256; a multiple of 8) and every token attends inside its own tile only,
+which cuts the score work by the tile count, keeps every token and needs no weights; convolutions, cross-attention and the deeper self-attentions still see
+the whole picture.  The tile count per axis is the largest divisor of the grid side that keeps the tile at least that large (a prime side stays whole).
+--hypertile-depth D tiles the D next smaller grids as well (default 0), at the same picture area per tile.  One launch (sdlt_attn_window_fwd, which walks the
+tile map itself: no gathered copies) in the plain attention launch's place inside the replayed graph.  --hypertile-pass hires (the default where the render
+has a hires pass) tiles the second pass only, all (the default where it has none) every pass.  It does not combine with --kv-downsample on the same token
+grid.  Without the flag nothing changes.
 
 --vae-tile [T] (diffusers' enable_vae_tiling) runs the VAE in tiles of T x T latent units (default 64: 512 px) that overlap by at least --vae-tile-overlap O
 (default 16: 128 px) and are put together on the device with a normalised feather (sdlt_tile_blend; vae.VaeDecoder.decode_tiled,
@@ -438,7 +448,31 @@ def _heat_tag(name):
 
 HIRES_KEYS = ("scale", "size", "strength", "steps", "upscaler", "resample")
 HIRES_UPSCALERS = ("latent", "pixel")
-KV_PASSES = ("hires", "all")      # which passes of a render carry kv_downsample
+KV_PASSES = ("hires", "all")      # which passes of a render carry kv_downsample / hypertile
+HYPERTILE_PX = 256                # --hypertile's default minimum tile side in picture pixels
+
+
+def hypertile_args(hypertile, depth=None, passes=None, hires=False, f=8):
+    """render()'s hypertile / hypertile_depth / hypertile_pass, checked -> None | dict(tile_px, tile, depth, passes).  hypertile: None (off; depth and
+    passes must be None too), True (HYPERTILE_PX) or the minimum tile side in picture pixels, a multiple of the VAE's factor f (tile = hypertile // f
+    latent cells).  depth: an integer >= 0 (default 0).  passes: "hires" | "all"; default "hires" where the render has a hires pass, else "all"; "hires"
+    without one is refused."""
+    if hypertile is None or hypertile is False:
+        if depth is not None or passes is not None:
+            raise ValueError("hypertile_depth and hypertile_pass need hypertile (--hypertile [TILE_PX])")
+        return None
+    px = HYPERTILE_PX if hypertile is True else hypertile
+    if not (isinstance(px, int) and not isinstance(px, bool) and px >= f and px % f == 0):
+        raise ValueError(f"hypertile must be a tile side in picture pixels, a positive multiple of {f}, got {hypertile!r}")
+    depth = 0 if depth is None else depth
+    if not (isinstance(depth, int) and not isinstance(depth, bool) and depth >= 0):
+        raise ValueError(f"hypertile_depth must be an integer >= 0, got {depth!r}")
+    passes = passes or ("hires" if hires else "all")
+    if passes not in KV_PASSES:
+        raise ValueError(f"hypertile_pass must be one of {KV_PASSES}, got {passes!r}")
+    if passes == "hires" and not hires:
+        raise ValueError("hypertile_pass 'hires' tiles the second pass of a hires render and this render has none: pass hypertile_pass='all' (--hypertile-pass all)")
+    return dict(tile_px=px, tile=px // f, depth=depth, passes=passes)
 
 
 def hires_args(hires, size, steps, f=8):
@@ -562,7 +596,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
            graph=True, n_validation=4, init_image=None, strength=None, mask_image=None, sampler="euler", sigmas="trailing", eta=None,
            guidance_rescale=0.0, guidance_interval=None, negative_prompt=None, hires=None, freeu=None, heatmap=None, heatmap_grid="max",
            kv_downsample=None, kv_downsample_mode="nearest", kv_downsample_pass="hires", vae_tile=None, change_map_image=None, mask_blur=None, tile_diffusion=None, regions=None, region_feather=None,
-           region_base=None, region_bootstrap=None, apg=None, dynthresh=None, vae_attention="dense", region_mode=None):
+           region_base=None, region_bootstrap=None, apg=None, dynthresh=None, vae_attention="dense", region_mode=None, hypertile=None, hypertile_depth=None,
+           hypertile_pass=None):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
     seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
@@ -590,6 +625,9 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     LatentSampler.sample's key / value token downsampling (sampler.kv_downsample_args; UNet.set_kv_downsample).  kv_downsample_pass "hires" (default):
     only the second pass of a hires render carries it - that is where the self-attentions are large, and the first pass decides the composition -
     so without `hires` it is refused; "all": every pass.
+    hypertile: None, True (HYPERTILE_PX) or the minimum tile side in picture pixels (a multiple of 8), with hypertile_depth (default 0) and hypertile_pass
+    "hires" | "all" (default: hires where the render has a hires pass, else all) - hypertile_args: LatentSampler.sample's tiled self-attention
+    (sampler.hypertile_plan; UNet.set_hypertile).  Not on a token grid that kv_downsample shortens.
     vae_tile: None, a tile length or (tile, overlap) in latent units (vae_tile_args; the overlap defaults to 16): every VAE pass of the render - the
     decode of each picture, the decode and encode of the pixel upscaler, the encode of init_image - runs in tiles (VaeDecoder.decode_tiled,
     VaeEncoder.encode_moments_tiled; ops.tile_blend).  The decoder then runs at the tile's shape and is not rebuilt with the UNet by the hires pass.
@@ -688,6 +726,11 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
                              "kv_downsample_pass='all' (--kv-downsample-pass all) to use it in a single-pass render")
         SM.require_op(stack.rt.ops, "token_pool", " (sdlt_token_pool): kv_downsample pools the keys' tokens by that launch (ops.token_pool)")
     kd_kw = {} if kd is None else dict(kv_downsample=kd[0], kv_downsample_mode=kd[1])
+    hy = hypertile_args(hypertile, hypertile_depth, hypertile_pass, hires=hires is not None, f=f)      # (raises before anything is built)
+    if hy is not None:
+        SM.require_op(stack.rt.ops, "attn_window_fwd", " (sdlt_attn_window_fwd): hypertile runs the tiled self-attentions by that launch (ops.attn_window_fwd)",
+                      kernel="sdlt_attn_window_fwd")
+        kd_kw = dict(kd_kw, hypertile=dict(tile=hy["tile"], depth=hy["depth"]))      # (the second pass has it either way)
     vt = vae_tile_args(vae_tile)                                     # (raises before anything is built)
     if vt is not None:
         SM.require_op(stack.rt.ops, "tile_blend", " (sdlt_tile_blend): vae_tile puts the VAE's tiles together by that launch (ops.tile_blend)")
@@ -739,7 +782,9 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     if fz is not None:
         img_kw.update(freeu=fz)
     if kv_downsample_pass == "all":
-        img_kw.update(kd_kw)
+        img_kw.update({k: v for k, v in kd_kw.items() if k != "hypertile"})
+    if hy is not None and hy["passes"] == "all":
+        img_kw.update(hypertile=kd_kw["hypertile"])
     if init_image is None:
         if mask_image is not None:
             raise ValueError("mask_image needs init_image: the region to keep is taken from it")
@@ -899,6 +944,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             meta.update(freeu=fz)
         if kd is not None:
             meta.update(kv_downsample=dict(factors=list(kd[0]), mode=kd[1], passes=kv_downsample_pass))
+        if hy is not None:
+            meta.update(hypertile=hy)
         if hm_cols is not None:
             meta.update(heatmap=dict(maps=hm_names, grid=heatmap_grid, positions=hm_cols.tolist()))
         if vt is not None:
@@ -972,6 +1019,12 @@ def main(argv=None, runtime=None):
     ap.add_argument("--kv-downsample-mode", choices=("nearest", "area"), default=None, help="with --kv-downsample: take every F-th token (default), or the mean of each F x F window")
     ap.add_argument("--kv-downsample-pass", choices=KV_PASSES, default=None,
                     help="with --kv-downsample: hires (default) - only the second pass of a --hires-scale / --hires-size render; all - every pass")
+    ap.add_argument("--hypertile", type=int, nargs="?", const=HYPERTILE_PX, default=None, metavar="TILE_PX",
+                    help=f"tiled self-attention (HyperTile): the largest self-attention grid attends inside tiles of at least TILE_PX picture pixels a side (default {HYPERTILE_PX}; "
+                    "a multiple of 8); every token is kept")
+    ap.add_argument("--hypertile-depth", type=int, default=None, metavar="D", help="with --hypertile: tile the D next smaller self-attention grids as well (default 0)")
+    ap.add_argument("--hypertile-pass", choices=KV_PASSES, default=None,
+                    help="with --hypertile: hires - only the second pass of a --hires-scale / --hires-size render (the default where there is one); all - every pass")
     ap.add_argument("--vae-tile", type=int, nargs="?", const=VAE_TILE, default=None, metavar="T",
                     help=f"run the VAE in tiles of T x T latent units (default {VAE_TILE}: {8 * VAE_TILE} px with the SD / SDXL VAE) blended on the device: bounded memory "
                     "and one decoder shape at any picture size")
@@ -1058,6 +1111,11 @@ def main(argv=None, runtime=None):
                  "pass --kv-downsample-pass all to use it in a single-pass render")
     kvd = {} if a.kv_downsample is None else dict(kv_downsample=tuple(a.kv_downsample), kv_downsample_mode=a.kv_downsample_mode or "nearest",
                                                    kv_downsample_pass=a.kv_downsample_pass or "hires")
+    try:
+        hyp = hypertile_args(a.hypertile, a.hypertile_depth, a.hypertile_pass, hires=a.hires_scale is not None or a.hires_size is not None)
+    except ValueError as e:
+        ap.error(f"--hypertile / --hypertile-depth / --hypertile-pass: {e}")
+    hyp = {} if hyp is None else dict(hypertile=hyp["tile_px"], hypertile_depth=hyp["depth"], hypertile_pass=hyp["passes"])
     if a.vae_tile is None and a.vae_tile_overlap is not None:
         ap.error("--vae-tile-overlap needs --vae-tile [T]")
     vtile = {}
@@ -1127,7 +1185,7 @@ def main(argv=None, runtime=None):
                  images_per_batch=a.images_per_batch, graph=not a.eager, n_validation=a.n_validation, init_image=a.init_image, strength=a.strength,
                  mask_image=a.mask, sampler=a.sampler, sigmas=a.sigmas, eta=a.eta, guidance_rescale=a.guidance_rescale,
                  guidance_interval=a.guidance_interval, negative_prompt=a.negative_prompt, **({} if hires is None else dict(hires=hires)),
-                 **({} if freeu is None else dict(freeu=freeu)), **kvd, **vtile, **tdiff, **regs, **apg, **dyn,
+                 **({} if freeu is None else dict(freeu=freeu)), **kvd, **hyp, **vtile, **tdiff, **regs, **apg, **dyn,
                  **({} if a.change_map is None else dict(change_map_image=a.change_map)), **({} if a.mask_blur is None else dict(mask_blur=a.mask_blur)),
                  **({} if a.vae_attention is None else dict(vae_attention=a.vae_attention)),
                  **({} if a.heatmap is None else dict(heatmap=a.heatmap, heatmap_grid=a.heatmap_grid or "max")))

@@ -510,6 +510,34 @@ def kv_downsample_args(factors, mode="nearest"):
     return (tuple(fs), mode) if fs else None
 
 
+def hypertile_args(hypertile):
+    """sample()'s `hypertile`, checked -> None | (tile, depth).  None or False: off; dict(tile=, depth=0): tile the minimum tile side in latent cells
+    (an integer >= 1), depth the number of self-attention token grids below the largest that are tiled as well (an integer >= 0)."""
+    if hypertile is None or hypertile is False:
+        return None
+    ok_int = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
+    if not isinstance(hypertile, dict) or set(hypertile) - {"tile", "depth"} or "tile" not in hypertile:
+        raise ValueError(f"hypertile takes dict(tile=, depth=0), got {hypertile!r}")
+    tile, depth = hypertile["tile"], hypertile.get("depth", 0)
+    if not (ok_int(tile) and tile >= 1 and ok_int(depth) and depth >= 0):
+        raise ValueError(f"hypertile: tile must be an integer >= 1 (latent cells) and depth an integer >= 0, got tile={tile!r} depth={depth!r}")
+    return tile, depth
+
+
+def hypertile_plan(h, w, levels, tile, depth):
+    """The tile counts of UNet.set_hypertile for an h x w latent: ((ty, tx), ...) for the first depth + 1 of `levels` (the UNet's self-attention levels,
+    ascending: level l runs on the (h >> l) x (w >> l) token grid), trailing (1, 1) dropped - () is "all plain".  tile: the minimum tile side in latent
+    cells; on level l that is max(tile >> l, 1) tokens, the same picture area on every level.  Per axis the count is the largest divisor n of the grid
+    side with side / n >= that minimum (HyperTile's rule; a prime side stays whole).  Pure integer arithmetic."""
+    out = []
+    for l in sorted(levels)[:depth + 1]:
+        m = max(tile >> l, 1)
+        out.append(tuple(max(n for n in range(1, side + 1) if side % n == 0 and side // n >= m) if side >= 1 else 1 for side in (h >> l, w >> l)))
+    while out and out[-1] == (1, 1):
+        out.pop()
+    return tuple(out)
+
+
 def freeu_args(freeu):
     """sample()'s / render()'s `freeu`, checked -> None | dict(b1, b2, s1, s2, version).  None; four numbers (b1, b2, s1, s2) - diffusers'
     enable_freeu order, version 1 - or a dict with those keys and optionally version (1: diffusers' constant backbone factor; 2: the authors' current
@@ -767,11 +795,12 @@ class LatentSampler:
     reference's render loop, up to the latents.  `unet` is an inference instance built for batch 2 (negative | positive, the
     order diffusers concatenates them in); its LoRA arena holds the trained adapters."""
 
-    def __init__(self, rt, unet, prediction_type="epsilon", kv_downsample=None, kv_downsample_mode="nearest", n_images=None):
+    def __init__(self, rt, unet, prediction_type="epsilon", kv_downsample=None, kv_downsample_mode="nearest", n_images=None, hypertile=None):
         """kv_downsample / kv_downsample_mode: the default of sample()'s keywords of the same names (kv_downsample_args).  n_images: the images sampled
         together where the runtime's batch is 2 n_images ty tx - a sampler for tiled diffusion (sample(tile=)) with ty tx windows per image; None:
         rt.B // 2, no windows."""
         self.kv_downsample = kv_downsample_args(kv_downsample, kv_downsample_mode)
+        self.hypertile = hypertile_args(hypertile)      # the default of sample()'s keyword of the same name
         assert rt.B >= 2 and rt.B % 2 == 0, "classifier-free guidance runs the negative and the positive prompt of every image as one pair: an even batch"
         self.rt, self.unet = rt, unet
         self.n = rt.B // 2 if n_images is None else n_images      # images sampled together; image j = rows 2j (negative), 2j + 1 (positive)
@@ -798,8 +827,8 @@ class LatentSampler:
 
     def _fwd_kw(self):
         """Keywords of the UNet forward: with key / value downsampling set it is declared an inference forward (UNet.forward refuses a training one);
-        without, the call is the plain one."""
-        return {} if getattr(self.unet, "_kv_ds", None) is None else {"train": False}
+        the same with tiled self-attention (hypertile); without, the call is the plain one."""
+        return {} if getattr(self.unet, "_kv_ds", None) is None and getattr(self.unet, "_ht", None) is None else {"train": False}
 
     def set_lora_scale(self, lora_scale, train_scale=None):
         """set_adapter_scales (checkpoint.py:31-55): every adapter's contribution is multiplied by lora_scale."""
@@ -813,7 +842,7 @@ class LatentSampler:
     def sample(self, embeds, h, w, *, steps=25, guidance_scale=8.0, generator=None, size=None, latents=None, graph=False, fused=False, n_images=1,
                init_latents=None, strength=1.0, mask=None, sampler="euler", sigmas="trailing", eta=1.0, seeds=None, guidance_rescale=0.0,
                guidance_interval=None, freeu=None, heatmap=None, kv_downsample=None, kv_downsample_mode=None, change_map=None, tile=None, regions=None, apg=None,
-               dynthresh=None):
+               dynthresh=None, hypertile=None):
         """embeds = (c [1,77,D], uc [1,77,D], pc [1,P] | None, puc | None); h, w latent size.  Returns latents [1,4,h,w] fp32
         (still multiplied by the VAE scaling factor, as the pipeline holds them before `vae.decode(latents / scaling_factor)`).
         fused: guidance, the Euler update and the next model input are ONE kernel between two forwards (ops.sampler_step) instead of torch
@@ -888,7 +917,12 @@ class LatentSampler:
         paths, with every sampler, per-step guidance scales, guidance_interval (g_i = 1 steps pass e_pos through), init latents, mask, change map,
         and with tile / regions on the fused full-size prediction.  The three values per step are device memory: one capture (in a dict of its own,
         the guided key plus "dyn") serves every setting.  dynthresh=None is the path without it: the same launches, capture keys and bits.  Not with
-        guidance_rescale > 0 and not with apg (ValueError): the three are alternative answers to the same fault."""
+        guidance_rescale > 0 and not with apg (ValueError): the three are alternative answers to the same fault.
+        hypertile: dict(tile=, depth=0) (hypertile_args): "HyperTile" - the self-attentions of the depth + 1 largest token grids attend inside rectangular
+        tiles of at least `tile` latent cells a side (hypertile_plan; UNet.set_hypertile: ops.attn_window_fwd in attn_fwd's place, score work cut by
+        the tile count) in every forward of the trajectory, on all three paths, with every sampler; with `tile` windows it acts per window.  None: the
+        constructor's setting; False: off, and the launch sequence is the plain one.  The tile counts are part of the capture key.  Not on a token grid
+        that kv_downsample shortens (ValueError)."""
         ops = self.rt.ops
         if regions is not None and (tile is not None or heatmap is not None):      # refused before anything is built
             raise ValueError("regions do not combine with " + ("tile: windows of regions are not built" if tile is not None else
@@ -930,6 +964,13 @@ class LatentSampler:
             kd = kv_downsample_args(kd[0] if kv_downsample is None and kd is not None else kv_downsample, kv_downsample_mode or (kd[1] if kd is not None else "nearest"))
         if kd != getattr(self.unet, "_kv_ds", None):
             self.unet.set_kv_downsample(*(kd or (None,)))      # (an op table without the kernel raises NotImplementedError here)
+        hp = self.hypertile if hypertile is None else hypertile_args(hypertile)
+        ht = None
+        if hp is not None:
+            uh, uw = (h, w) if plan is None else (plan.th, plan.tw)      # (the UNet's own latent: a window of tiled diffusion)
+            ht = hypertile_plan(uh, uw, {lv for _, lv in self.unet._attn_levels()}, *hp) or None
+        if ht != getattr(self.unet, "_ht", None):
+            self.unet.set_hypertile(ht, **({} if ht is None else dict(latent=(uh, uw))))      # (an op table without the kernel raises NotImplementedError here)
         fz = freeu_args(freeu)
         if fz is not None or getattr(self.unet, "_freeu", None) is not None:
             self.unet.set_freeu(fz)          # (None: the plain launch sequence; an op table without the kernel raises NotImplementedError here)
@@ -1309,6 +1350,9 @@ class LatentSampler:
         kd = getattr(self.unet, "_kv_ds", None)
         if kd is not None:                                # key / value downsampling changes the launch sequence: a capture per (factors, mode)
             key += (("kv_downsample",) + kd,)
+        ht = getattr(self.unet, "_ht", None)
+        if ht is not None:                                # tiled self-attention changes the launch sequence and its arguments: a capture per tile counts
+            key += (("hypertile",) + ht,)
         if "win" in sh:                                   # tiled diffusion: the window extents and counts; starts and weights are device memory
             key += (("tile",) + tuple(sh["win"]["plan"][2:]),)
         if traj.reg is not None:                          # regional prompts: the region count; masks, weights, backgrounds and the bootstrap table are device memory

@@ -982,6 +982,7 @@ class Attention(_Module):
 
     _couple = None      # the state of UNet.set_attention_couple: this cross-attention mixes R regions' results per query (inference only)
     _kv = None          # (factor > 1, mode) of UNet.set_kv_downsample: this self-attention takes k | v from pooled tokens (inference only)
+    _ht = None          # (ty, tx) of UNet.set_hypertile: this self-attention attends inside the tiles of its token grid only (inference only)
     norm = None         # the LayerNorm in front of a self-attention (TransformerBlock.norm1): the pooling launch normalises with it
 
     def _kv_forward(self, x, raw, B, N, grid):
@@ -1026,8 +1027,11 @@ class Attention(_Module):
 
     def forward(self, x, ctx, B, N, residual, parts_for=None, grid=None):
         """x [B*N, C]; ctx [B*CTX_PAD, D] for cross attention.  Returns residual + to_out(attn).  grid (H, W): the token grid, read by a
-        self-attention with key / value downsampling only."""
+        self-attention with key / value downsampling or tiles (UNet.set_hypertile) only."""
         rt, C = self.rt, self.C
+        ht = None if self.cross else self._ht
+        if ht is not None and (grid is None or grid[0] * grid[1] != N or grid[0] % ht[0] or grid[1] % ht[1]):
+            raise ValueError(f"hypertile: {ht[0]} x {ht[1]} tiles do not divide the token grid {grid!r} ({N} tokens) of {self.name}")
         kv = ctx if self.cross else x
         Nk, Nkp = (77, CTX_PAD) if self.cross else (N, N)
         pooled_kv = not self.cross and self._kv is not None
@@ -1056,16 +1060,18 @@ class Attention(_Module):
         elif not pooled_kv:
             q, k, v = self.stack.forward(x)
         O = self.buf("O", Mq, C)
-        L = self.buf("L", B * self.heads * N, dtype=F32)
+        L = self.buf("L", B * self.heads * N, dtype=F32) if ht is None else None      # (the tiled kernel leaves no log-sum-exp)
         self._dims = (B, N, Nk, Nkp)
         # self-attention whose to_out.0 input gradient runs on the wave-split-K kernel: that product leaves the backward's row term D = rowsum(dO o O) as a side output
         # (no D pre-pass launch); its slots are cleared here, by the forward kernel's epilogue
-        self._rowdot = (not self.cross and not pooled_kv and getattr(self, "_rowdot_ok", True) and self.to_out.trainer is None
+        self._rowdot = (not self.cross and not pooled_kv and ht is None and getattr(self, "_rowdot_ok", True) and self.to_out.trainer is None
                         and not (self.to_out.lora is not None and self.to_out.arena.wide)
                         and getattr(rt.ops, "wsk_rowdot_shape", None) is not None and rt.ops.wsk_rowdot_shape(Mq, C, C, self.to_out.lora is not None, self.d))
         kwz = {"zero_D": self.buf("D", B * self.heads * N, dtype=F32)} if self._rowdot else {}
         if cp is not None:      # no pad rows, no log-sum-exp: the 4- and 6-token maps of the toys go straight in
             rt.ops.attn_couple_fwd(q, k, v, O, cp["weights"][N], B=B, H=self.heads, Nq=N, Nk=Nk, Nkp=Nkp, R=cp["R"], d=self.d, scale=self.scale, rcount=cp["rcount"])
+        elif ht is not None:    # one launch walks the tile map: no gathered copies, no pad rows, any tile size
+            rt.ops.attn_window_fwd(q, k, v, O, B=B, H=self.heads, grid=tuple(grid), tiles=ht, d=self.d, scale=self.scale)
         elif N % 8:
             self._attn_fwd_padded(q, k, v, O, L, B, N, Nk, Nkp, kv_padded=pooled_kv)
         else:
@@ -1409,6 +1415,7 @@ class UNet(_Module):
         self._freeu = None               # set_freeu: (b1, b2, s1, s2, version) of an inference instance
         self._kv_ds = None               # set_kv_downsample: (factors, mode) of an inference instance
         self._couple = None              # set_attention_couple: dict(R, weights, rcount) of an inference instance
+        self._ht = None                  # set_hypertile: ((ty, tx), ...) of an inference instance, largest self-attention token grid first
         # time_emb_proj of every resnet reads the same silu(emb): ONE GEMM over the stacked weights [sum Cout, tdim] per pass instead of
         # one M = B launch per resnet (17 in SDXL, 22 in SD1.5); the same for their input gradients (dsemb) when B == 1.  Not with the
         # full fine-tune (the projections are trained layer by layer there).
@@ -1441,6 +1448,9 @@ class UNet(_Module):
         if train and self._kv_ds is not None:
             raise NotImplementedError("kv_downsample is an inference option: a training forward (train=True, TrainStep) has no backward through the pooled "
                                       "keys and values - set_kv_downsample(None) first")
+        if train and self._ht is not None:
+            raise NotImplementedError("hypertile is an inference option: a training forward (train=True, TrainStep) has no backward through the tiled "
+                                      "self-attention - set_hypertile(None) first")
         if self._couple is not None:
             if train:
                 raise NotImplementedError("attention couple is an inference option: a training forward (train=True, TrainStep) has no backward through the "
@@ -1588,6 +1598,9 @@ class UNet(_Module):
             raise ValueError(f"kv_downsample: {len(factors)} factors, but this UNet has self-attention on {len(grids)} token grid(s)")
         if all(f == 1 for f in factors):
             return {}
+        clash = [lv for lv, f, t in zip(grids, factors, getattr(self, "_ht", None) or ()) if f > 1 and t != (1, 1)]
+        if clash:
+            raise ValueError(f"kv_downsample: level {clash[0]} already runs tiled self-attention (set_hypertile): one of the two per token grid")
         if not hasattr(self.rt.ops, "token_pool"):
             raise NotImplementedError("this op table has no token_pool kernel (sdlt_token_pool): the pooled LayerNorm rows of kv_downsample are that launch "
                                       "(ops.token_pool)")
@@ -1601,6 +1614,59 @@ class UNet(_Module):
         while factors[-1] == 1:
             factors = factors[:-1]
         self._kv_ds = (factors, mode)
+        return applied
+
+    # ------------------------------------------------------------------------------------ tiled self-attention (inference only)
+    def set_hypertile(self, tiles, latent=None):
+        """"HyperTile" for the self-attentions of inference forwards (forward(train=False)): a large self-attention's token grid is cut into ty x tx
+        rectangular tiles and every token attends inside its own tile only (ops.attn_window_fwd, one launch in attn_fwd's place: no gathered copies),
+        which cuts the score work by ty tx and keeps every token - unlike set_kv_downsample, which shortens the keys alone.  tiles: a tuple of (ty, tx)
+        pairs counted from the LARGEST self-attention token grid downwards (sampler.hypertile_plan makes it); grids not named, and (1, 1), keep the plain
+        path launch for launch; None, () or all (1, 1): off.  ty and tx must divide the layer's grid: ValueError naming the layer, here where latent =
+        (H, W) of the coming forwards is given (level l runs on (H >> l) x (W >> l) tokens), else in forward.  Not on a grid that also has a kv_downsample factor > 1.  Cross-attention, the couple mode, FreeU and the heat maps are untouched.  The
+        counts are launch arguments: a capture made with one setting does not serve another (sampler.LatentSampler keys its captures by it).
+        -> {transformer name: (ty, tx)} of the transformers it applies to."""
+        levels = self._attn_levels()
+        for t, _ in levels:
+            for blk in t.blocks:
+                blk.attn1._ht = None
+        self._ht = None
+        if tiles is None:
+            return {}
+        ok_int = lambda v: isinstance(v, int) and not isinstance(v, bool) and v >= 1  # noqa: E731
+        try:
+            tiles = tuple(tuple(t) for t in tiles)
+        except TypeError:
+            tiles = None
+        if tiles is None or not all(len(t) == 2 and ok_int(t[0]) and ok_int(t[1]) for t in tiles):
+            raise ValueError(f"hypertile takes (ty, tx) pairs of integers >= 1, largest token grid first, got {tiles!r}")
+        grids = sorted({lv for _, lv in levels})
+        if len(tiles) > len(grids):
+            raise ValueError(f"hypertile: {len(tiles)} pairs, but this UNet has self-attention on {len(grids)} token grid(s)")
+        while tiles and tiles[-1] == (1, 1):
+            tiles = tiles[:-1]
+        if not tiles:
+            return {}
+        if getattr(self.rt.ops, "attn_window_fwd", None) is None:
+            raise NotImplementedError("this op table has no tiled self-attention kernel (sdlt_attn_window_fwd): there is no torch fallback")
+        by_level = {lv: t for lv, t in zip(grids, tiles) if t != (1, 1)}
+        kv = dict(zip(grids, self._kv_ds[0])) if self._kv_ds is not None else {}
+        applied = {}
+        for t, lv in levels:
+            if lv in by_level:
+                if kv.get(lv, 1) > 1:
+                    raise ValueError(f"hypertile: {t.name} (level {lv}) already takes pooled keys and values (kv_downsample factor {kv[lv]}): one of the two per token grid")
+                if latent is not None and ((latent[0] >> lv) % by_level[lv][0] or (latent[1] >> lv) % by_level[lv][1]):
+                    raise ValueError(f"hypertile: {by_level[lv][0]} x {by_level[lv][1]} tiles do not divide the {latent[0] >> lv} x {latent[1] >> lv} token grid of {t.name}")
+                for blk in t.blocks:
+                    if blk.attn1.d % 8 or blk.attn1.d > 96:
+                        raise ValueError(f"hypertile: the heads of {blk.attn1.name} are {blk.attn1.d} wide; the kernel takes multiples of 8 up to 96 (a smaller depth)")
+                applied[t.name] = by_level[lv]
+        for t, lv in levels:
+            if lv in by_level:
+                for blk in t.blocks:
+                    blk.attn1._ht = by_level[lv]
+        self._ht = tiles
         return applied
 
     def _freeu_apply(self, i, j, h, s, B, H, W):
@@ -1655,6 +1721,8 @@ class UNet(_Module):
         (caller zeroes it).  LoRA gradients land in arena.grads."""
         if self._freeu is not None:
             raise RuntimeError("UNet.backward with freeu set: FreeU is an inference-time change of the forward and has no backward here (set_freeu(None))")
+        if self._ht is not None:
+            raise NotImplementedError("UNet.backward with hypertile set: the tiled self-attention has no backward here (set_hypertile(None))")
         if self._kv_ds is not None:
             raise NotImplementedError("UNet.backward with kv_downsample set: the pooled keys and values have no backward here (set_kv_downsample(None))")
         rt = self.rt
