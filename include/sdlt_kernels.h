@@ -320,6 +320,58 @@ typedef struct {
   float scale;
 } sdlt_attn_window_params;    /* 96 bytes; tagless, no index in sdlt_struct_size (like sdlt_attn_couple_params): a binding checks its mirror against this figure */
 int sdlt_attn_window_fwd(const sdlt_attn_window_params* p, void* stream);
+/* Token merging for self-attention ("ToMe", Bolya & Hoffman: "Token Merging for Fast Stable Diffusion"), four launches; forward only.  Per image b of B, the same
+ * for all heads.  The token grid is Hg x Wg, row-major, N = Hg Wg <= 16384, Hg and Wg even; it is cut into 2 x 2 cells.  Each cell gives ONE destination token:
+ * mode 0 (fixed) its top-left token; mode 1 (random) the token at offset o = philox4x32_10(counter (cell, ctr[0], layer, 'TOM1'), key seed)[0] & 3 (dy = o >> 1,
+ * dx = o & 1; csrc/philox.h; ctr: the sampler's device step counter, read only) - the same for every image, another per step and per layer.  N_dst = N / 4
+ * destinations in cell raster order; the other N_src = 3 N / 4 tokens are the sources, in ascending token index.
+ * sdlt_tome_match: y bf16 [B N, ld] (C % 8 == 0, ld % 8 == 0) -> dst_tok int32 [N_dst] (shared by the batch), node_max fp32 [B, N_src], node_idx int32 [B, N_src]:
+ *   s(i, j) = dot(y_i, y_j) inv_i inv_j, the dot product of bf16 products accumulated in fp32, inv = 1 / sqrt(sum y^2) in fp32 and 0 for a zero row (which
+ *   scores 0 everywhere); normalised rows are never rounded or stored.  node_max[i] = max_j s(i, j) (= max_j(dot inv_j) inv_i), node_idx[i] the LOWEST j
+ *   attaining it.  One MFMA kernel behind a small index launch; no [N_src, N_dst] buffer, no workspace (node_idx carries the source token table between the two
+ *   launches), no atomics.
+ * sdlt_tome_plan: the r sources with the largest node_max are merged (ties: the lower source index - the stable descending order), each into destination
+ *   node_idx[i]; 0 <= r <= N_src, N' = N - r, N' % 8 == 0.  -> kept_tok int32 [B, N']: the tokens that keep a row (destinations and unmerged sources), ascending;
+ *   map int32 [B, N]: a token's own kept row, or that of its destination; offsets int32 [B, N_dst + 1] and list int32 [B, max(r, 1)]: per destination j the
+ *   TOKEN indices of its merged sources, list[offsets[j] .. offsets[j + 1]), ascending.  Exact integer work (LDS counters only: counts do not depend on arrival order).
+ *   Cost: one workgroup per image; a list of len entries is put in order by counting, len^2 reads - linear in N for the short lists a cosine match gives, but
+ *   a node_idx that sends every source to ONE destination costs N_src^2 reads (about 1.5e8 at N = 16384): legal and exact, only slow.
+ * sdlt_tome_merge: ym bf16 [B N', ldm]: row k is row kept_tok[k] of y, bit for bit - except a destination with merged sources: (own row + its sources in
+ *   ascending order, fp32) / count, one rounding.
+ * sdlt_tome_unmerge: out[t] = residual[t] + a[map[t]] over all B N rows (a bf16 [B N', lda]): fp32 add, one rounding.
+ * Two runs give the same bits.  Null block or operand, an extent < 1, odd Hg or Wg, N > 16384, r outside 0 .. N_src, (N - r) % 8, ld < C, an output overlapping
+ * an input or another output, row indices beyond 32 bits (-1); C % 8, ld % 8, rows not 16-byte or tables not 4-byte aligned (-2); an unknown mode (-4): the code
+ * is returned before anything is launched, outputs untouched.  Table CONTENTS are device memory and cannot be checked: every index read from one is clamped to
+ * its range, so a bad table gives wrong rows, never an access outside the operands. */
+typedef struct {
+  const void* y; int64_t ld;
+  const int32_t* ctr;                /* int32 [>= 1], read in mode 1 only (may be null in mode 0) */
+  int32_t* dst_tok; float* node_max; int32_t* node_idx;
+  uint64_t seed;
+  int32_t B, Hg, Wg, C, mode, layer;
+} sdlt_tome_match_params;      /* 80 bytes; tagless, no index in sdlt_struct_size (like sdlt_attn_window_params): a binding checks its mirror against this figure */
+int sdlt_tome_match(const sdlt_tome_match_params* p, void* stream);
+typedef struct {
+  const float* node_max; const int32_t* node_idx; const int32_t* dst_tok;
+  int32_t* map; int32_t* kept_tok; int32_t* offsets; int32_t* list;
+  int32_t B, Hg, Wg, r;
+} sdlt_tome_plan_params;       /* 72 bytes; tagless */
+int sdlt_tome_plan(const sdlt_tome_plan_params* p, void* stream);
+typedef struct {
+  const void* y; int64_t ld;
+  const int32_t* dst_tok; const int32_t* kept_tok; const int32_t* offsets; const int32_t* list;
+  void* ym; int64_t ldm;
+  int32_t B, Hg, Wg, C, r, pad_;
+} sdlt_tome_merge_params;      /* 88 bytes; tagless */
+int sdlt_tome_merge(const sdlt_tome_merge_params* p, void* stream);
+typedef struct {
+  const void* residual; int64_t ldr;
+  const void* a; int64_t lda;
+  const int32_t* map;
+  void* out; int64_t ldo;
+  int32_t B, N, Np, C;
+} sdlt_tome_unmerge_params;    /* 72 bytes; tagless */
+int sdlt_tome_unmerge(const sdlt_tome_unmerge_params* p, void* stream);
 /* out0 / out1 [B*Nkp, C] bf16 = sum over nsplit slabs of s0 / s1 (fp32 [nsplit][B*Nkp][ld32]) in slab order (rows with key >= Nk: zeros;
  * acc0: out0 += instead of =), for a table of layers: block_desc[b] = descriptor of block b, block_first[d] = first block of descriptor d,
  * a layer owns ceil(B*Nkp*C/2 / 256) blocks (capped at 64; the kernel strides). */

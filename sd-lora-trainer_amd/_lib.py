@@ -131,6 +131,27 @@ class AttnWindowParams(C.Structure):
                 ("B", i32), ("H", i32), ("Hg", i32), ("Wg", i32), ("ty", i32), ("tx", i32), ("d", i32), ("scale", f32)]
 
 
+class TomeMatchParams(C.Structure):
+    # sdlt_tome_match_params: 80 bytes by the header's text (tagless, like sdlt_attn_window_params); the three below likewise: 72, 88, 72
+    _fields_ = [("y", vp), ("ld", i64), ("ctr", vp), ("dst_tok", vp), ("node_max", vp), ("node_idx", vp), ("seed", C.c_uint64),
+                ("B", i32), ("Hg", i32), ("Wg", i32), ("C", i32), ("mode", i32), ("layer", i32)]
+
+
+class TomePlanParams(C.Structure):
+    _fields_ = [("node_max", vp), ("node_idx", vp), ("dst_tok", vp), ("map", vp), ("kept_tok", vp), ("offsets", vp), ("list", vp),
+                ("B", i32), ("Hg", i32), ("Wg", i32), ("r", i32)]
+
+
+class TomeMergeParams(C.Structure):
+    _fields_ = [("y", vp), ("ld", i64), ("dst_tok", vp), ("kept_tok", vp), ("offsets", vp), ("list", vp), ("ym", vp), ("ldm", i64),
+                ("B", i32), ("Hg", i32), ("Wg", i32), ("C", i32), ("r", i32), ("pad_", i32)]
+
+
+class TomeUnmergeParams(C.Structure):
+    _fields_ = [("residual", vp), ("ldr", i64), ("a", vp), ("lda", i64), ("map", vp), ("out", vp), ("ldo", i64),
+                ("B", i32), ("N", i32), ("Np", i32), ("C", i32)]
+
+
 # the packed code of sdlt_attn_route (include/sdlt_kernels.h, SDLT_ATTN_ROUTE_*)
 ATTN_ROUTES = ("FWD32", "FWD16_KS2", "FWD16", "BWD_CROSS_ROLES", "BWD_CROSS", "BWD_BOTH32", "BWD_BOTH16", "BWD_SPLIT")
 ATTN_ROUTE_MASK = 0xF
@@ -296,6 +317,10 @@ SYMBOLS = {
     "sdlt_attn_wide_fwd": (i32, [C.POINTER(AttnWideParams), vp]),
     "sdlt_attn_couple_fwd": (i32, [C.POINTER(AttnCoupleParams), vp]),
     "sdlt_attn_window_fwd": (i32, [C.POINTER(AttnWindowParams), vp]),
+    "sdlt_tome_match": (i32, [C.POINTER(TomeMatchParams), vp]),
+    "sdlt_tome_plan": (i32, [C.POINTER(TomePlanParams), vp]),
+    "sdlt_tome_merge": (i32, [C.POINTER(TomeMergeParams), vp]),
+    "sdlt_tome_unmerge": (i32, [C.POINTER(TomeUnmergeParams), vp]),
     "sdlt_attn_splitsum_batch": (i32, [vp, vp, vp, i32, vp]),
     "sdlt_groupnorm_ws_floats": (i32, [i32, i32, i32]),
     "sdlt_colsum_finish_batch": (i32, [vp, i32, i32, vp]),
@@ -404,7 +429,8 @@ def load():
     if C.sizeof(ResizeParams) != 48:
         raise KernelLibraryError(f"struct layout mismatch for ResizeParams: header 48 vs binding {C.sizeof(ResizeParams)}")
     for cls, size in ((HeatAccumParams, 152), (HeatOverlayParams, 80), (GemmPlan, 64), (SamplerDdParams, 128), (WindowParams, 64), (RegionParams, 64),
-                      (GuidanceApgParams, 56), (GuidanceDynParams, 48), (AttnWideParams, 88), (AttnCoupleParams, 112), (AttnWindowParams, 96)):
+                      (GuidanceApgParams, 56), (GuidanceDynParams, 48), (AttnWideParams, 88), (AttnCoupleParams, 112), (AttnWindowParams, 96),
+                      (TomeMatchParams, 80), (TomePlanParams, 72), (TomeMergeParams, 88), (TomeUnmergeParams, 72)):
         if C.sizeof(cls) != size:
             raise KernelLibraryError(f"struct layout mismatch for {cls.__name__}: header {size} vs binding {C.sizeof(cls)}")
     _lib = lib

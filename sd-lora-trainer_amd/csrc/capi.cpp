@@ -25,6 +25,8 @@ static_assert(sizeof(sdlt_region_params) == 64, "sdlt_region_params has no index
 static_assert(sizeof(sdlt_guidance_apg_params) == 56, "sdlt_guidance_apg_params has no index below: its size is part of the header's text");
 static_assert(sizeof(sdlt_guidance_dyn_params) == 48, "sdlt_guidance_dyn_params has no index below: its size is part of the header's text");
 static_assert(sizeof(sdlt_attn_window_params) == 96, "sdlt_attn_window_params has no index below: its size is part of the header's text");
+static_assert(sizeof(sdlt_tome_match_params) == 80 && sizeof(sdlt_tome_plan_params) == 72 && sizeof(sdlt_tome_merge_params) == 88 && sizeof(sdlt_tome_unmerge_params) == 72,
+              "the sdlt_tome_* blocks have no index below: their sizes are part of the header's text");
 static_assert(sizeof(sdlt_attn_wide_params) == 88, "sdlt_attn_wide_params has no index below: its size is part of the header's text");
 
 extern "C" int sdlt_struct_size(int which) {

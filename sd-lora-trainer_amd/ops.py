@@ -1000,6 +1000,107 @@ def attn_window_fwd(Q, K, V, O, *, B, H, grid, tiles, d, scale):
     return O
 
 
+TOME_MODES = ("fixed", "random")
+
+
+def tome_rows(N, ratio):
+    """The number r of merged sources of a token-merging layer with N tokens: min(N_src, floor(ratio N)) lowered to the next value with (N - r) % 8 == 0
+    (the rows attn_fwd wants every image to start on); <= 0: the layer stays plain."""
+    r = min(3 * N // 4, int(ratio * N))
+    return r - (8 - (N - r) % 8) % 8
+
+
+def _tome_tab(name, t, n, dtype=torch.int32):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.numel() == n):
+        raise ValueError(f"{name}: expected a contiguous cuda {dtype} tensor of {n} elements, got {(tuple(t.shape), t.dtype) if torch.is_tensor(t) else type(t)}")
+    return t.data_ptr()
+
+
+def _tome_rows2(name, t, rows, Cc):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == BF16 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == rows and t.shape[1] >= Cc):
+        raise ValueError(f"{name}: expected a cuda bf16 row-major view [{rows}, >= {Cc}], got {tuple(t.shape) if torch.is_tensor(t) else type(t)}")
+
+
+def _tome_grid(fn, B, grid):
+    ok_int = lambda v: isinstance(v, int) and not isinstance(v, bool) and v >= 1  # noqa: E731
+    if not (ok_int(B) and isinstance(grid, (tuple, list)) and len(grid) == 2 and all(ok_int(v) for v in grid)):
+        raise ValueError(f"{fn}: B={B!r} grid={grid!r} (integers >= 1)")
+    if grid[0] % 2 or grid[1] % 2:
+        raise ValueError(f"{fn}: the {grid[0]} x {grid[1]} token grid must be even in both directions (2 x 2 cells)")
+    return grid[0], grid[1], grid[0] * grid[1]
+
+
+def tome_match(y, dst_tok, node_max, node_idx, *, B, grid, C_=None, mode="random", seed=0, ctr=None, layer=0):
+    """sdlt_tome_match: for every source token of a 2 x 2-cell token merging, the most cosine-similar destination token.  y bf16 [B Hg Wg, >= C] (the
+    LayerNorm rows; C_ = the width, default y.shape[1]); grid = (Hg, Wg), both even.  mode "fixed": a cell's destination is its top-left token; "random":
+    the token at offset philox(seed, ctr[0], layer, cell) & 3 (ctr: int32 device tensor, the sampler's step counter).  -> dst_tok int32 [N / 4] (shared by
+    the batch), node_max fp32 [B, 3 N / 4], node_idx int32 [B, 3 N / 4] (the lowest destination index attaining the maximum).  ValueError before the call."""
+    Hg, Wg, N = _tome_grid("tome_match", B, grid)
+    Cc = y.shape[1] if C_ is None else C_
+    _tome_rows2("tome_match: y", y, B * N, Cc)
+    if mode not in TOME_MODES:
+        raise ValueError(f"tome_match: mode must be one of {TOME_MODES}, got {mode!r}")
+    p = _lib.TomeMatchParams()
+    p.y, p.ld = _p(y), _ld(y)
+    p.dst_tok, p.node_max, p.node_idx = _tome_tab("tome_match: dst_tok", dst_tok, N // 4), _tome_tab("tome_match: node_max", node_max, B * (N - N // 4), F32), \
+        _tome_tab("tome_match: node_idx", node_idx, B * (N - N // 4))
+    if mode == "random":
+        if not (torch.is_tensor(ctr) and ctr.is_cuda and ctr.dtype == torch.int32 and ctr.numel() >= 1):
+            raise ValueError("tome_match: mode 'random' reads ctr, an int32 device tensor (the sampler's step counter)")
+        p.ctr = ctr.data_ptr()
+    p.seed, p.B, p.Hg, p.Wg, p.C, p.mode, p.layer = int(seed) & (2 ** 64 - 1), B, Hg, Wg, Cc, TOME_MODES.index(mode), int(layer)
+    _lib.check(_lib.load().sdlt_tome_match(C.byref(p), _stream()), "sdlt_tome_match")
+    return dst_tok, node_max, node_idx
+
+
+def tome_plan(node_max, node_idx, dst_tok, map_, kept_tok, offsets, list_, *, B, grid, r):
+    """sdlt_tome_plan: the r sources with the largest node_max (ties: the lower index) are merged into their node_idx destinations.  -> map_ int32 [B, N] (a
+    token's kept row, or its destination's), kept_tok int32 [B, N - r] (ascending), offsets int32 [B, N / 4 + 1] and list_ int32 [B, max(r, 1)]: the merged
+    sources' token indices per destination, ascending.  (N - r) % 8 == 0."""
+    Hg, Wg, N = _tome_grid("tome_plan", B, grid)
+    Nd, Ns = N // 4, N - N // 4
+    if not (isinstance(r, int) and 0 <= r <= Ns and (N - r) % 8 == 0):
+        raise ValueError(f"tome_plan: r={r!r} (0 <= r <= {Ns}, (N - r) % 8 == 0 with N = {N})")
+    p = _lib.TomePlanParams()
+    p.node_max, p.node_idx, p.dst_tok = _tome_tab("tome_plan: node_max", node_max, B * Ns, F32), _tome_tab("tome_plan: node_idx", node_idx, B * Ns), _tome_tab("tome_plan: dst_tok", dst_tok, Nd)
+    p.map, p.kept_tok = _tome_tab("tome_plan: map", map_, B * N), _tome_tab("tome_plan: kept_tok", kept_tok, B * (N - r))
+    p.offsets, p.list = _tome_tab("tome_plan: offsets", offsets, B * (Nd + 1)), _tome_tab("tome_plan: list", list_, B * max(r, 1))
+    p.B, p.Hg, p.Wg, p.r = B, Hg, Wg, r
+    _lib.check(_lib.load().sdlt_tome_plan(C.byref(p), _stream()), "sdlt_tome_plan")
+    return map_, kept_tok, offsets, list_
+
+
+def tome_merge(y, dst_tok, kept_tok, offsets, list_, ym, *, B, grid, r, C_=None):
+    """sdlt_tome_merge: ym bf16 [B (N - r), >= C] = the kept rows of y; a destination's row is the fp32 mean of its own row and its merged sources (ascending),
+    rounded once; every other row is a copy.  Tables: tome_plan's."""
+    Hg, Wg, N = _tome_grid("tome_merge", B, grid)
+    Nd, Cc = N // 4, y.shape[1] if C_ is None else C_
+    if not (isinstance(r, int) and 0 <= r <= N - Nd and (N - r) % 8 == 0):
+        raise ValueError(f"tome_merge: r={r!r} (0 <= r <= {N - Nd}, (N - r) % 8 == 0 with N = {N})")
+    _tome_rows2("tome_merge: y", y, B * N, Cc), _tome_rows2("tome_merge: ym", ym, B * (N - r), Cc)
+    p = _lib.TomeMergeParams()
+    p.y, p.ld, p.ym, p.ldm = _p(y), _ld(y), _p(ym), _ld(ym)
+    p.dst_tok, p.kept_tok = _tome_tab("tome_merge: dst_tok", dst_tok, Nd), _tome_tab("tome_merge: kept_tok", kept_tok, B * (N - r))
+    p.offsets, p.list = _tome_tab("tome_merge: offsets", offsets, B * (Nd + 1)), _tome_tab("tome_merge: list", list_, B * max(r, 1))
+    p.B, p.Hg, p.Wg, p.C, p.r = B, Hg, Wg, Cc, r
+    _lib.check(_lib.load().sdlt_tome_merge(C.byref(p), _stream()), "sdlt_tome_merge")
+    return ym
+
+
+def tome_unmerge(residual, a, map_, out, *, B, N, Np):
+    """sdlt_tome_unmerge: out[t] = residual[t] + a[map_[t]] over all B N rows - the un-merge of token merging fused with the block's residual add.  residual, out
+    bf16 [B N, >= C], a bf16 [B Np, C] (to_out's result on the merged rows), map_ int32 [B, N] (tome_plan).  fp32 add, one rounding."""
+    if not (torch.is_tensor(a) and a.dim() == 2):
+        raise ValueError("tome_unmerge: a must be a 2-D tensor")
+    Cc = a.shape[1]
+    _tome_rows2("tome_unmerge: residual", residual, B * N, Cc), _tome_rows2("tome_unmerge: a", a, B * Np, Cc), _tome_rows2("tome_unmerge: out", out, B * N, Cc)
+    p = _lib.TomeUnmergeParams()
+    p.residual, p.ldr, p.a, p.lda, p.out, p.ldo = _p(residual), _ld(residual), _p(a), _ld(a), _p(out), _ld(out)
+    p.map, p.B, p.N, p.Np, p.C = _tome_tab("tome_unmerge: map", map_, B * N), B, N, Np, Cc
+    _lib.check(_lib.load().sdlt_tome_unmerge(C.byref(p), _stream()), "sdlt_tome_unmerge")
+    return out
+
+
 def couple_weights(wn, levels):
     """The weight tables of attn_couple_fwd for the UNet's token grids: wn fp32 [R, h, w] (region_tables' normalised weights), levels an iterable of l >= 0 ->
     {N_l: fp32 [R, N_l]} with the grid (h >> l) x (w >> l), the UNet's own // 2 per level.  Token (y, x) of level l covers latent pixels [2^l y, 2^l (y + 1)) x

@@ -13,6 +13,7 @@ scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-squ
                                          [--hires-resample nearest|bilinear|bicubic] [--heatmap [WORD ...]] [--heatmap-grid max|min]
                                          [--kv-downsample F [F2 ...]] [--kv-downsample-mode nearest|area] [--kv-downsample-pass hires|all]
                                          [--hypertile [TILE_PX]] [--hypertile-depth D] [--hypertile-pass hires|all]
+                                         [--tome [RATIO]] [--tome-depth D] [--tome-mode random|fixed] [--tome-pass hires|all]
                                          [--vae-tile [T]] [--vae-tile-overlap O] [--tile-diffusion [T]] [--tile-diffusion-overlap O]
                                          [--region MASK.png|x0,y0,x1,y1 PROMPT ...] [--region-feather SIGMA] [--region-base F] [--region-bootstrap SHARE] [--region-mode fuse|couple]
                                          [--unet F] [--text-encoder F] [--text-encoder-2 F] [--vae F] [--tokenizer DIR]
@@ -107,6 +108,15 @@ the whole picture.  The tile count per axis is the largest divisor of the grid s
 tile map itself: no gathered copies) in the plain attention launch's place inside the replayed graph.  --hypertile-pass hires (the default where the render
 has a hires pass) tiles the second pass only, all (the default where it has none) every pass.  It does not combine with --kv-downsample on the same token
 grid.  Without the flag nothing changes.
+
+--tome [RATIO] is "Token Merging" (the tomesd package; the ToMe option of the common front ends): before the largest self-attention, RATIO of the tokens
+(default 0.5, at most 0.75) are averaged into their most similar neighbour - one destination token per 2 x 2 cell, matched by cosine similarity of the
+LayerNorm rows - so queries, keys and values all get shorter; afterwards every token takes the result of the row it was merged into.  --tome-depth D merges
+on the D next smaller grids as well (default 0).  --tome-mode random (default) draws each cell's destination per step and layer from the picture's seed,
+fixed takes the top-left token.  Four launches (sdlt_tome_match, an MFMA kernel that never writes the similarity matrix, sdlt_tome_plan, sdlt_tome_merge,
+sdlt_tome_unmerge) around the plain attention launch inside the replayed graph.  --tome-pass hires (the default where the render has a hires pass) merges
+in the second pass only, all (the default where it has none) in every pass.  Token grids must be even.  It does not combine with --hypertile, nor with
+--kv-downsample on the same token grid.  Without the flag nothing changes.
 
 --vae-tile [T] (diffusers' enable_vae_tiling) runs the VAE in tiles of T x T latent units (default 64: 512 px) that overlap by at least --vae-tile-overlap O
 (default 16: 128 px) and are put together on the device with a normalised feather (sdlt_tile_blend; vae.VaeDecoder.decode_tiled,
@@ -475,6 +485,28 @@ def hypertile_args(hypertile, depth=None, passes=None, hires=False, f=8):
     return dict(tile_px=px, tile=px // f, depth=depth, passes=passes)
 
 
+TOME_RATIO = 0.5                  # --tome's default share of merged tokens
+
+
+def tome_args(tome, depth=None, mode=None, passes=None, hires=False):
+    """render()'s tome / tome_depth / tome_mode / tome_pass, checked -> None | dict(ratio, depth, mode, passes).  tome: None (off; the other three must be
+    None too), True (TOME_RATIO) or the share of merged tokens in (0, 0.75].  depth: an integer >= 0 (default 0).  mode: "random" (default) | "fixed".
+    passes: "hires" | "all"; default "hires" where the render has a hires pass, else "all"; "hires" without one is refused."""
+    from . import sampler as SM
+    if tome is None or tome is False:
+        if depth is not None or mode is not None or passes is not None:
+            raise ValueError("tome_depth, tome_mode and tome_pass need tome (--tome [RATIO])")
+        return None
+    ratio = TOME_RATIO if tome is True else tome
+    passes = passes or ("hires" if hires else "all")
+    if passes not in KV_PASSES:
+        raise ValueError(f"tome_pass must be one of {KV_PASSES}, got {passes!r}")
+    if passes == "hires" and not hires:
+        raise ValueError("tome_pass 'hires' merges in the second pass of a hires render and this render has none: pass tome_pass='all' (--tome-pass all)")
+    SM.token_merge_args(dict(ratio=ratio, depth=0 if depth is None else depth, mode=mode or "random"))      # (raises for a wrong value)
+    return dict(ratio=float(ratio), depth=0 if depth is None else depth, mode=mode or "random", passes=passes)
+
+
 def hires_args(hires, size, steps, f=8):
     """render()'s `hires` dict, checked and completed -> dict(size (W2, H2), base_size, strength, steps, upscaler, resample).  Keys: scale | size
     (exactly one: sampler.hires_plan), strength (default 0.6: the share of the second schedule that runs), steps (default: the first pass's),
@@ -597,7 +629,7 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
            guidance_rescale=0.0, guidance_interval=None, negative_prompt=None, hires=None, freeu=None, heatmap=None, heatmap_grid="max",
            kv_downsample=None, kv_downsample_mode="nearest", kv_downsample_pass="hires", vae_tile=None, change_map_image=None, mask_blur=None, tile_diffusion=None, regions=None, region_feather=None,
            region_base=None, region_bootstrap=None, apg=None, dynthresh=None, vae_attention="dense", region_mode=None, hypertile=None, hypertile_depth=None,
-           hypertile_pass=None):
+           hypertile_pass=None, tome=None, tome_depth=None, tome_mode=None, tome_pass=None):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
     seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
@@ -628,6 +660,9 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     hypertile: None, True (HYPERTILE_PX) or the minimum tile side in picture pixels (a multiple of 8), with hypertile_depth (default 0) and hypertile_pass
     "hires" | "all" (default: hires where the render has a hires pass, else all) - hypertile_args: LatentSampler.sample's tiled self-attention
     (sampler.hypertile_plan; UNet.set_hypertile).  Not on a token grid that kv_downsample shortens.
+    tome: None, True (TOME_RATIO) or the share of tokens merged before the largest self-attention, in (0, 0.75], with tome_depth (default 0), tome_mode
+    "random" | "fixed" and tome_pass "hires" | "all" (default: hires where the render has a hires pass, else all) - tome_args: LatentSampler.sample's
+    token merging (UNet.set_token_merge), seeded with the render's seed.  Not with hypertile, and not on a token grid that kv_downsample shortens.
     vae_tile: None, a tile length or (tile, overlap) in latent units (vae_tile_args; the overlap defaults to 16): every VAE pass of the render - the
     decode of each picture, the decode and encode of the pixel upscaler, the encode of init_image - runs in tiles (VaeDecoder.decode_tiled,
     VaeEncoder.encode_moments_tiled; ops.tile_blend).  The decoder then runs at the tile's shape and is not rebuilt with the UNet by the hires pass.
@@ -731,6 +766,15 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         SM.require_op(stack.rt.ops, "attn_window_fwd", " (sdlt_attn_window_fwd): hypertile runs the tiled self-attentions by that launch (ops.attn_window_fwd)",
                       kernel="sdlt_attn_window_fwd")
         kd_kw = dict(kd_kw, hypertile=dict(tile=hy["tile"], depth=hy["depth"]))      # (the second pass has it either way)
+    tm = tome_args(tome, tome_depth, tome_mode, tome_pass, hires=hires is not None)      # (raises before anything is built)
+    if tm is not None:
+        if hy is not None:
+            raise ValueError("tome does not combine with hypertile: both act on the largest self-attention token grid - one of the two")
+        if kd is not None and any(f_ > 1 for f_ in kd[0][:tm["depth"] + 1]):
+            raise ValueError(f"tome (depth {tm['depth']}) and kv_downsample {kd[0]} act on the same token grid: one of the two per grid")
+        for op in ("tome_match", "tome_plan", "tome_merge", "tome_unmerge"):
+            SM.require_op(stack.rt.ops, op, f" (sdlt_{op}): tome merges the self-attention's tokens by that launch (ops.{op})", kernel=f"sdlt_{op}")
+        kd_kw = dict(kd_kw, token_merge=dict(ratio=tm["ratio"], depth=tm["depth"], mode=tm["mode"], seed=int(seed or 0)))      # (the second pass has it either way)
     vt = vae_tile_args(vae_tile)                                     # (raises before anything is built)
     if vt is not None:
         SM.require_op(stack.rt.ops, "tile_blend", " (sdlt_tile_blend): vae_tile puts the VAE's tiles together by that launch (ops.tile_blend)")
@@ -782,9 +826,11 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     if fz is not None:
         img_kw.update(freeu=fz)
     if kv_downsample_pass == "all":
-        img_kw.update({k: v for k, v in kd_kw.items() if k != "hypertile"})
+        img_kw.update({k: v for k, v in kd_kw.items() if k not in ("hypertile", "token_merge")})
     if hy is not None and hy["passes"] == "all":
         img_kw.update(hypertile=kd_kw["hypertile"])
+    if tm is not None and tm["passes"] == "all":
+        img_kw.update(token_merge=kd_kw["token_merge"])
     if init_image is None:
         if mask_image is not None:
             raise ValueError("mask_image needs init_image: the region to keep is taken from it")
@@ -946,6 +992,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             meta.update(kv_downsample=dict(factors=list(kd[0]), mode=kd[1], passes=kv_downsample_pass))
         if hy is not None:
             meta.update(hypertile=hy)
+        if tm is not None:
+            meta.update(tome=tm)
         if hm_cols is not None:
             meta.update(heatmap=dict(maps=hm_names, grid=heatmap_grid, positions=hm_cols.tolist()))
         if vt is not None:
@@ -1025,6 +1073,14 @@ def main(argv=None, runtime=None):
     ap.add_argument("--hypertile-depth", type=int, default=None, metavar="D", help="with --hypertile: tile the D next smaller self-attention grids as well (default 0)")
     ap.add_argument("--hypertile-pass", choices=KV_PASSES, default=None,
                     help="with --hypertile: hires - only the second pass of a --hires-scale / --hires-size render (the default where there is one); all - every pass")
+    ap.add_argument("--tome", type=float, nargs="?", const=TOME_RATIO, default=None, metavar="RATIO",
+                    help=f"token merging (ToMe): RATIO of the largest self-attention's tokens (default {TOME_RATIO}, at most 0.75) are averaged into their most similar "
+                    "neighbour, so queries, keys and values all get shorter")
+    ap.add_argument("--tome-depth", type=int, default=None, metavar="D", help="with --tome: merge on the D next smaller self-attention grids as well (default 0)")
+    ap.add_argument("--tome-mode", choices=("random", "fixed"), default=None,
+                    help="with --tome: random (default) - a 2 x 2 cell's destination token is drawn per step and layer from the seed; fixed - its top-left token")
+    ap.add_argument("--tome-pass", choices=KV_PASSES, default=None,
+                    help="with --tome: hires - only the second pass of a --hires-scale / --hires-size render (the default where there is one); all - every pass")
     ap.add_argument("--vae-tile", type=int, nargs="?", const=VAE_TILE, default=None, metavar="T",
                     help=f"run the VAE in tiles of T x T latent units (default {VAE_TILE}: {8 * VAE_TILE} px with the SD / SDXL VAE) blended on the device: bounded memory "
                     "and one decoder shape at any picture size")
@@ -1116,6 +1172,15 @@ def main(argv=None, runtime=None):
     except ValueError as e:
         ap.error(f"--hypertile / --hypertile-depth / --hypertile-pass: {e}")
     hyp = {} if hyp is None else dict(hypertile=hyp["tile_px"], hypertile_depth=hyp["depth"], hypertile_pass=hyp["passes"])
+    try:
+        tme = tome_args(a.tome, a.tome_depth, a.tome_mode, a.tome_pass, hires=a.hires_scale is not None or a.hires_size is not None)
+    except ValueError as e:
+        ap.error(f"--tome / --tome-depth / --tome-mode / --tome-pass: {e}")
+    if tme is not None and a.hypertile is not None:
+        ap.error("--tome does not combine with --hypertile: both act on the largest self-attention token grid - one of the two")
+    if tme is not None and a.kv_downsample is not None and any(f_ > 1 for f_ in a.kv_downsample[:tme["depth"] + 1]):
+        ap.error(f"--tome (depth {tme['depth']}) and --kv-downsample {' '.join(map(str, a.kv_downsample))} act on the same token grid: one of the two per grid")
+    tme = {} if tme is None else dict(tome=tme["ratio"], tome_depth=tme["depth"], tome_mode=tme["mode"], tome_pass=tme["passes"])
     if a.vae_tile is None and a.vae_tile_overlap is not None:
         ap.error("--vae-tile-overlap needs --vae-tile [T]")
     vtile = {}
@@ -1185,7 +1250,7 @@ def main(argv=None, runtime=None):
                  images_per_batch=a.images_per_batch, graph=not a.eager, n_validation=a.n_validation, init_image=a.init_image, strength=a.strength,
                  mask_image=a.mask, sampler=a.sampler, sigmas=a.sigmas, eta=a.eta, guidance_rescale=a.guidance_rescale,
                  guidance_interval=a.guidance_interval, negative_prompt=a.negative_prompt, **({} if hires is None else dict(hires=hires)),
-                 **({} if freeu is None else dict(freeu=freeu)), **kvd, **hyp, **vtile, **tdiff, **regs, **apg, **dyn,
+                 **({} if freeu is None else dict(freeu=freeu)), **kvd, **hyp, **tme, **vtile, **tdiff, **regs, **apg, **dyn,
                  **({} if a.change_map is None else dict(change_map_image=a.change_map)), **({} if a.mask_blur is None else dict(mask_blur=a.mask_blur)),
                  **({} if a.vae_attention is None else dict(vae_attention=a.vae_attention)),
                  **({} if a.heatmap is None else dict(heatmap=a.heatmap, heatmap_grid=a.heatmap_grid or "max")))

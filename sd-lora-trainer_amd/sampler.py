@@ -524,6 +524,24 @@ def hypertile_args(hypertile):
     return tile, depth
 
 
+def token_merge_args(token_merge):
+    """sample()'s `token_merge`, checked -> None | (ratios, mode, seed).  None or False: off; dict(ratio=, depth=0, mode="random", seed=0): ratio in
+    (0, 0.75] on the depth + 1 largest self-attention token grids (UNet.set_token_merge; depth beyond the UNet's grids: all of them)."""
+    if token_merge is None or token_merge is False:
+        return None
+    if not isinstance(token_merge, dict) or set(token_merge) - {"ratio", "depth", "mode", "seed"} or "ratio" not in token_merge:
+        raise ValueError(f"token_merge takes dict(ratio=, depth=0, mode='random', seed=0), got {token_merge!r}")
+    ok_int = lambda v: isinstance(v, int) and not isinstance(v, bool) and v >= 0  # noqa: E731
+    ratio, depth, mode, seed = token_merge["ratio"], token_merge.get("depth", 0), token_merge.get("mode", "random"), token_merge.get("seed", 0)
+    if not (isinstance(ratio, (int, float)) and not isinstance(ratio, bool) and 0 < ratio <= 0.75):
+        raise ValueError(f"token_merge: ratio must lie in (0, 0.75] (at most every source token is merged), got {ratio!r}")
+    if not (ok_int(depth) and ok_int(seed) and seed < 2 ** 64):
+        raise ValueError(f"token_merge: depth must be an integer >= 0 and seed an integer in [0, 2^64), got depth={depth!r} seed={seed!r}")
+    if mode not in ("random", "fixed"):
+        raise ValueError(f"token_merge: mode must be 'random' or 'fixed', got {mode!r}")
+    return (float(ratio),) * (depth + 1), mode, seed
+
+
 def hypertile_plan(h, w, levels, tile, depth):
     """The tile counts of UNet.set_hypertile for an h x w latent: ((ty, tx), ...) for the first depth + 1 of `levels` (the UNet's self-attention levels,
     ascending: level l runs on the (h >> l) x (w >> l) token grid), trailing (1, 1) dropped - () is "all plain".  tile: the minimum tile side in latent
@@ -795,12 +813,13 @@ class LatentSampler:
     reference's render loop, up to the latents.  `unet` is an inference instance built for batch 2 (negative | positive, the
     order diffusers concatenates them in); its LoRA arena holds the trained adapters."""
 
-    def __init__(self, rt, unet, prediction_type="epsilon", kv_downsample=None, kv_downsample_mode="nearest", n_images=None, hypertile=None):
+    def __init__(self, rt, unet, prediction_type="epsilon", kv_downsample=None, kv_downsample_mode="nearest", n_images=None, hypertile=None, token_merge=None):
         """kv_downsample / kv_downsample_mode: the default of sample()'s keywords of the same names (kv_downsample_args).  n_images: the images sampled
         together where the runtime's batch is 2 n_images ty tx - a sampler for tiled diffusion (sample(tile=)) with ty tx windows per image; None:
         rt.B // 2, no windows."""
         self.kv_downsample = kv_downsample_args(kv_downsample, kv_downsample_mode)
         self.hypertile = hypertile_args(hypertile)      # the default of sample()'s keyword of the same name
+        self.token_merge = token_merge_args(token_merge)      # likewise
         assert rt.B >= 2 and rt.B % 2 == 0, "classifier-free guidance runs the negative and the positive prompt of every image as one pair: an even batch"
         self.rt, self.unet = rt, unet
         self.n = rt.B // 2 if n_images is None else n_images      # images sampled together; image j = rows 2j (negative), 2j + 1 (positive)
@@ -827,8 +846,8 @@ class LatentSampler:
 
     def _fwd_kw(self):
         """Keywords of the UNet forward: with key / value downsampling set it is declared an inference forward (UNet.forward refuses a training one);
-        the same with tiled self-attention (hypertile); without, the call is the plain one."""
-        return {} if getattr(self.unet, "_kv_ds", None) is None and getattr(self.unet, "_ht", None) is None else {"train": False}
+        the same with tiled self-attention (hypertile) and token merging; without, the call is the plain one."""
+        return {} if all(getattr(self.unet, n, None) is None for n in ("_kv_ds", "_ht", "_tome")) else {"train": False}
 
     def set_lora_scale(self, lora_scale, train_scale=None):
         """set_adapter_scales (checkpoint.py:31-55): every adapter's contribution is multiplied by lora_scale."""
@@ -842,7 +861,7 @@ class LatentSampler:
     def sample(self, embeds, h, w, *, steps=25, guidance_scale=8.0, generator=None, size=None, latents=None, graph=False, fused=False, n_images=1,
                init_latents=None, strength=1.0, mask=None, sampler="euler", sigmas="trailing", eta=1.0, seeds=None, guidance_rescale=0.0,
                guidance_interval=None, freeu=None, heatmap=None, kv_downsample=None, kv_downsample_mode=None, change_map=None, tile=None, regions=None, apg=None,
-               dynthresh=None, hypertile=None):
+               dynthresh=None, hypertile=None, token_merge=None):
         """embeds = (c [1,77,D], uc [1,77,D], pc [1,P] | None, puc | None); h, w latent size.  Returns latents [1,4,h,w] fp32
         (still multiplied by the VAE scaling factor, as the pipeline holds them before `vae.decode(latents / scaling_factor)`).
         fused: guidance, the Euler update and the next model input are ONE kernel between two forwards (ops.sampler_step) instead of torch
@@ -922,7 +941,13 @@ class LatentSampler:
         tiles of at least `tile` latent cells a side (hypertile_plan; UNet.set_hypertile: ops.attn_window_fwd in attn_fwd's place, score work cut by
         the tile count) in every forward of the trajectory, on all three paths, with every sampler; with `tile` windows it acts per window.  None: the
         constructor's setting; False: off, and the launch sequence is the plain one.  The tile counts are part of the capture key.  Not on a token grid
-        that kv_downsample shortens (ValueError)."""
+        that kv_downsample shortens (ValueError).
+        token_merge: dict(ratio=, depth=0, mode="random", seed=0) (token_merge_args): "Token Merging" - the self-attentions of the depth + 1 largest token
+        grids run on tokens merged by similarity (UNet.set_token_merge: ops.tome_match / tome_plan / tome_merge, attn_fwd on the short rows, tome_unmerge)
+        in every forward of the trajectory, on all three paths, with every sampler.  The random destinations are drawn on the device from the step
+        counter the step kernels keep, so the torch loop, the fused path and a replayed graph merge the same tokens.  None: the constructor's setting;
+        False: off, and the launch sequence is the plain one.  The setting is part of the capture key.  Token grids must be even, and a grid takes one
+        of kv_downsample, hypertile and token_merge (ValueError)."""
         ops = self.rt.ops
         if regions is not None and (tile is not None or heatmap is not None):      # refused before anything is built
             raise ValueError("regions do not combine with " + ("tile: windows of regions are not built" if tile is not None else
@@ -959,6 +984,9 @@ class LatentSampler:
                 raise ValueError("change_map and mask exclude each other: the map selects per pixel and step, the mask blends after every step")
             if graph or fused:
                 require_op(ops, "sampler_step_dd", ": sample(change_map=..., graph=False, fused=False) is the torch loop")
+        tm = self.token_merge if token_merge is None else token_merge_args(token_merge)
+        if getattr(self.unet, "_tome", None) is not None:      # an earlier call's merging is cleared first: the setting does not stick, and the two options
+            self.unet.set_token_merge(None)                    # below are judged against this call's grids only
         kd = self.kv_downsample
         if kv_downsample is not None or kv_downsample_mode is not None:
             kd = kv_downsample_args(kd[0] if kv_downsample is None and kd is not None else kv_downsample, kv_downsample_mode or (kd[1] if kd is not None else "nearest"))
@@ -971,6 +999,9 @@ class LatentSampler:
             ht = hypertile_plan(uh, uw, {lv for _, lv in self.unet._attn_levels()}, *hp) or None
         if ht != getattr(self.unet, "_ht", None):
             self.unet.set_hypertile(ht, **({} if ht is None else dict(latent=(uh, uw))))      # (an op table without the kernel raises NotImplementedError here)
+        if tm is not None:      # (an op table without the kernels raises NotImplementedError here; depth beyond the UNet's grids: all of them)
+            uh, uw = (h, w) if plan is None else (plan.th, plan.tw)
+            self.unet.set_token_merge(tm[0][:len({lv for _, lv in self.unet._attn_levels()})], tm[1], tm[2], ctr=self._fused_state()["ctr"], latent=(uh, uw))
         fz = freeu_args(freeu)
         if fz is not None or getattr(self.unet, "_freeu", None) is not None:
             self.unet.set_freeu(fz)          # (None: the plain launch sequence; an op table without the kernel raises NotImplementedError here)
@@ -1025,6 +1056,7 @@ class LatentSampler:
         x = noise * s.init_noise_sigma if traj.img is None else x0 + noise * float(s.sigmas[0])
         m, hold = sh["img"]["mask"] if traj.masked else None, None if traj.hold is None else sh["img"]["hold"]
         sde, counted = traj.sampler in SDE_KINDS, heat is not None or traj.guide is not None or (traj.reg is not None and not traj.reg["couple"])      # (the gather reads the bootstrap's row)
+        counted = counted or getattr(self.unet, "_tome", None) is not None      # (token merging draws its destinations at the step counter)
         if sde:
             z = rt.zeros(1, 4, h, w, dtype=F32)
         if heat is not None and heat["heat"] is not None:
@@ -1101,14 +1133,19 @@ class LatentSampler:
             return contextlib.nullcontext()
         return own(id(self))
 
-    def _state(self, h, w, plan=None, reg=None):
-        """plan (a TilePlan): the shape's state is keyed by the window extents and counts as well, and holds the windows' buffers (_window_state); reg
-        (region_args' dict): by the region count, and holds the regions' buffers (_region_state)."""
+    def _fused_state(self):
+        """The persistent state every shape shares: timesteps, time ids, the step table and the device step counter."""
         rt, n = self.rt, self.n
         if self._fused is None:      # (tid: one row of six per UNET batch row - 2 n without windows)
             self._fused = dict(tf=rt.zeros(2 * n, dtype=F32), tid=rt.zeros(rt.B * 6, dtype=F32), table=rt.zeros(TABLE_ROWS, 4, dtype=F32),
                                ctr=torch.zeros(2, dtype=torch.int32, device=rt.device), shapes={})
-        st = self._fused
+        return self._fused
+
+    def _state(self, h, w, plan=None, reg=None):
+        """plan (a TilePlan): the shape's state is keyed by the window extents and counts as well, and holds the windows' buffers (_window_state); reg
+        (region_args' dict): by the region count, and holds the regions' buffers (_region_state)."""
+        rt, n = self.rt, self.n
+        st = self._fused_state()
         key = (h, w, "couple" if reg["couple"] else "region", reg["tabs"].R) if reg is not None else (h, w) if plan is None else (h, w) + tuple(plan[2:])
         if key not in st["shapes"]:
             st["shapes"][key] = dict(x=rt.zeros(n, 4, h, w, dtype=F32), x64=rt.zeros(2 * n * h * w, 64))
@@ -1353,6 +1390,9 @@ class LatentSampler:
         ht = getattr(self.unet, "_ht", None)
         if ht is not None:                                # tiled self-attention changes the launch sequence and its arguments: a capture per tile counts
             key += (("hypertile",) + ht,)
+        tm = getattr(self.unet, "_tome", None)
+        if tm is not None:                                # token merging changes the launch sequence and its arguments: a capture per (ratios, mode, seed)
+            key += (("token_merge",) + tm,)
         if "win" in sh:                                   # tiled diffusion: the window extents and counts; starts and weights are device memory
             key += (("tile",) + tuple(sh["win"]["plan"][2:]),)
         if traj.reg is not None:                          # regional prompts: the region count; masks, weights, backgrounds and the bootstrap table are device memory

@@ -983,7 +983,59 @@ class Attention(_Module):
     _couple = None      # the state of UNet.set_attention_couple: this cross-attention mixes R regions' results per query (inference only)
     _kv = None          # (factor > 1, mode) of UNet.set_kv_downsample: this self-attention takes k | v from pooled tokens (inference only)
     _ht = None          # (ty, tx) of UNet.set_hypertile: this self-attention attends inside the tiles of its token grid only (inference only)
+    _tome = None        # dict(ratio, mode, seed, ctr, layer) of UNet.set_token_merge: this self-attention runs on merged tokens (inference only)
     norm = None         # the LayerNorm in front of a self-attention (TransformerBlock.norm1): the pooling launch normalises with it
+
+    def tome_rows(self, N, grid):
+        """The merged source count r of this self-attention on N tokens under UNet.set_token_merge; 0: the plain path (no setting, or the ratio merges
+        nothing here).  ValueError for a grid that is unknown or odd."""
+        tm = self._tome
+        if tm is None:
+            return 0
+        r = _ops.tome_rows(N, tm["ratio"])
+        if r <= 0:
+            return 0
+        if grid is None or grid[0] * grid[1] != N or grid[0] % 2 or grid[1] % 2:
+            raise ValueError(f"token_merge: {self.name} needs an even token grid (H, W) with H W = {N} (2 x 2 cells), got {grid!r}: a latent whose sides "
+                             "divide by 2 on this level, or ratio 0 for this grid")
+        return r
+
+    def _tome_forward(self, x, B, N, grid, r):
+        """Token merging (UNet.set_token_merge): the LayerNorm rows y of x by their own launch; ops.tome_match / tome_plan / tome_merge shorten them to
+        N' = N - r rows per image; q | k | v from those by the PLAIN weights (a folded stack's operand is W o gamma: the plain one comes back once from
+        its dX operand, as _kv_forward does for to_k | to_v; member by member where the stack is wide, DoRA or trained); ops.attn_fwd on N' tokens; to_out
+        without residual; ops.tome_unmerge writes residual + the un-merged rows.  -> x + attn [B N, C]."""
+        rt, C, st, tm, ops = self.rt, self.C, self.stack, self._tome, self.rt.ops
+        Np, Nd, Ns, i32 = N - r, N // 4, N - N // 4, torch.int32
+        y = self.norm.forward(x, unfolded=True)
+        key = lambda k: (k, N, r)      # noqa: E731  (another grid or ratio on the same instance is another set of buffers: captured graphs keep their addresses)
+        dst, nmax, nidx = self.buf(key("tm_dst"), Nd, dtype=i32), self.buf(key("tm_max"), B * Ns, dtype=F32), self.buf(key("tm_idx"), B * Ns, dtype=i32)
+        tmap, kept = self.buf(key("tm_map"), B * N, dtype=i32), self.buf(key("tm_kept"), B * Np, dtype=i32)
+        offs, lst = self.buf(key("tm_off"), B * (Nd + 1), dtype=i32), self.buf(key("tm_list"), B * r, dtype=i32)
+        ctr = tm["ctr"]
+        if ctr is None and tm["mode"] == "random":      # no sampler: step 0 of every forward
+            ctr = self.buf("tm_ctr", 2, dtype=i32, zero=True)
+        ops.tome_match(y, dst, nmax, nidx, B=B, grid=tuple(grid), mode=tm["mode"], seed=tm["seed"], ctr=ctr, layer=tm["layer"])
+        ops.tome_plan(nmax, nidx, dst, tmap, kept, offs, lst, B=B, grid=tuple(grid), r=r)
+        ym = ops.tome_merge(y, dst, kept, offs, lst, self.buf(key("tm_ym"), B * Np, C), B=B, grid=tuple(grid), r=r)
+        qkv = self.buf(key("tm_qkv"), B * Np, 3 * C)
+        q, k, v = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
+        if st.wide or st.dora or st.trainer is not None:
+            for m, o in zip(st.members, (q, k, v)):
+                m.forward(ym, out=o, train=False)
+        else:
+            if st.ln is None:
+                W, bias = st.W, st.bias
+            else:
+                if "Wqkv_plain" not in self._b:
+                    self._b["Wqkv_plain"] = (st.Wt.t().contiguous(), torch.cat([m.bias for m in st.members]).contiguous() if self.to_q.bias is not None else None)
+                W, bias = self._b["Wqkv_plain"]
+            lora = (st.A_cat, st.B_cat, st.arena.scale, None) if st.has_lora else None
+            ops.gemm(ym, W, qkv, lora=lora, bias=bias, lora_group_n=C if st.has_lora else 0)
+        O, L = self.buf(key("tm_O"), B * Np, C), self.buf(key("tm_L"), B * self.heads * Np, dtype=F32)
+        ops.attn_fwd(q, k, v, None, O, L, B=B, H=self.heads, Nq=Np, Nk=Np, Nqp=Np, Nkp=Np, d=self.d, scale=self.scale)
+        a = self.to_out.forward(O, out=self.buf(key("tm_a"), B * Np, C), train=False)
+        return ops.tome_unmerge(x, a, tmap, self.buf(key("tm_out"), B * N, C), B=B, N=N, Np=Np)
 
     def _kv_forward(self, x, raw, B, N, grid):
         """Key / value token downsampling (UNet.set_kv_downsample): q from all N tokens by the route it has without the option - the stack's operands
@@ -1232,7 +1284,12 @@ class TransformerBlock(_Module):
 
     def forward(self, x, ctx, B, N, next_norm=None, grid=None):
         """next_norm: the LayerNorm that reads this block's output (the next block's norm1) - see Linear.forward parts_for.  grid: Attention.forward."""
-        x1 = self.attn1.forward(self.norm1.forward(x), None, B, N, residual=x, parts_for=self.norm2, grid=grid)
+        r = self.attn1.tome_rows(N, grid)
+        if r:       # token merging: the self-attention runs on N - r rows; its last launch leaves no row partials for norm2
+            x1 = self.attn1._tome_forward(x, B, N, grid, r)
+            self.norm2._parts = None
+        else:
+            x1 = self.attn1.forward(self.norm1.forward(x), None, B, N, residual=x, parts_for=self.norm2, grid=grid)
         x2 = self.attn2.forward(self.norm2.forward(x1), ctx, B, N, residual=x1, parts_for=self.norm3)
         if self.fused_geglu:
             g = self.buf("g", x.shape[0], self.ff2.K)
@@ -1416,6 +1473,7 @@ class UNet(_Module):
         self._kv_ds = None               # set_kv_downsample: (factors, mode) of an inference instance
         self._couple = None              # set_attention_couple: dict(R, weights, rcount) of an inference instance
         self._ht = None                  # set_hypertile: ((ty, tx), ...) of an inference instance, largest self-attention token grid first
+        self._tome = None                # set_token_merge: (ratios, mode, seed) of an inference instance, largest self-attention token grid first
         # time_emb_proj of every resnet reads the same silu(emb): ONE GEMM over the stacked weights [sum Cout, tdim] per pass instead of
         # one M = B launch per resnet (17 in SDXL, 22 in SD1.5); the same for their input gradients (dsemb) when B == 1.  Not with the
         # full fine-tune (the projections are trained layer by layer there).
@@ -1451,6 +1509,9 @@ class UNet(_Module):
         if train and self._ht is not None:
             raise NotImplementedError("hypertile is an inference option: a training forward (train=True, TrainStep) has no backward through the tiled "
                                       "self-attention - set_hypertile(None) first")
+        if train and self._tome is not None:
+            raise NotImplementedError("token_merge is an inference option: a training forward (train=True, TrainStep) has no backward through the merged "
+                                      "tokens - set_token_merge(None) first")
         if self._couple is not None:
             if train:
                 raise NotImplementedError("attention couple is an inference option: a training forward (train=True, TrainStep) has no backward through the "
@@ -1601,6 +1662,9 @@ class UNet(_Module):
         clash = [lv for lv, f, t in zip(grids, factors, getattr(self, "_ht", None) or ()) if f > 1 and t != (1, 1)]
         if clash:
             raise ValueError(f"kv_downsample: level {clash[0]} already runs tiled self-attention (set_hypertile): one of the two per token grid")
+        clash = [lv for lv, f, q in zip(grids, factors, (getattr(self, "_tome", None) or ((),))[0]) if f > 1 and q > 0]
+        if clash:
+            raise ValueError(f"kv_downsample: level {clash[0]} already merges tokens (set_token_merge): one of the two per token grid")
         if not hasattr(self.rt.ops, "token_pool"):
             raise NotImplementedError("this op table has no token_pool kernel (sdlt_token_pool): the pooled LayerNorm rows of kv_downsample are that launch "
                                       "(ops.token_pool)")
@@ -1649,6 +1713,9 @@ class UNet(_Module):
             return {}
         if getattr(self.rt.ops, "attn_window_fwd", None) is None:
             raise NotImplementedError("this op table has no tiled self-attention kernel (sdlt_attn_window_fwd): there is no torch fallback")
+        clash = [lv for lv, t, q in zip(grids, tiles, (getattr(self, "_tome", None) or ((),))[0]) if t != (1, 1) and q > 0]
+        if clash:
+            raise ValueError(f"hypertile: level {clash[0]} already merges tokens (set_token_merge): one of the two per token grid")
         by_level = {lv: t for lv, t in zip(grids, tiles) if t != (1, 1)}
         kv = dict(zip(grids, self._kv_ds[0])) if self._kv_ds is not None else {}
         applied = {}
@@ -1667,6 +1734,67 @@ class UNet(_Module):
                 for blk in t.blocks:
                     blk.attn1._ht = by_level[lv]
         self._ht = tiles
+        return applied
+
+    # ------------------------------------------------------------------------------------ token merging (inference only)
+    def set_token_merge(self, ratios, mode="random", seed=0, ctr=None, latent=None):
+        """"Token Merging" (Bolya & Hoffman; the tomesd package) for the self-attentions of inference forwards (forward(train=False)): on a 2 x 2-cell
+        partition of the token grid one token per cell is a destination, and the r = ops.tome_rows(N, ratio) sources most similar to a destination are
+        averaged into it, so queries, keys AND values shrink to N - r rows; afterwards every token takes its (merged) row's result (ops.tome_match,
+        tome_plan, tome_merge, attn_fwd on the short rows, tome_unmerge).  ratios: a tuple counted from the LARGEST self-attention token grid downwards,
+        each in [0, 0.75]; grids not named, ratio 0, and a layer where r comes to <= 0 keep the plain path launch for launch; None, () or all zeros: off.
+        mode "random": a cell's destination is drawn per step and layer from philox(seed, ctr[0], layer, cell) - ctr is the sampler's device step counter
+        (None: step 0) - the same for every batch row; "fixed": the top-left token.  Token grids must be even: ValueError naming the layer, here where
+        latent = (H, W) of the coming forwards is given, else in forward.  Not on a grid that has a kv_downsample factor > 1 or hypertile tiles.
+        Cross-attention, the couple mode, FreeU and the heat maps are untouched.  -> {transformer name: ratio} of the transformers it applies to."""
+        levels = self._attn_levels()
+        for t, _ in levels:
+            for blk in t.blocks:
+                blk.attn1._tome = None
+        self._tome = None
+        if ratios is None:
+            return {}
+        ratios = (ratios,) if isinstance(ratios, (int, float)) and not isinstance(ratios, bool) else tuple(ratios)
+        if not all(isinstance(q, (int, float)) and not isinstance(q, bool) and 0 <= q <= 0.75 for q in ratios):
+            raise ValueError(f"token_merge takes ratios in [0, 0.75], largest token grid first, got {ratios!r}")
+        if mode not in _ops.TOME_MODES:
+            raise ValueError(f"token_merge mode must be one of {_ops.TOME_MODES}, got {mode!r}")
+        if not (isinstance(seed, int) and not isinstance(seed, bool) and 0 <= seed < 2 ** 64):
+            raise ValueError(f"token_merge seed must be an integer in [0, 2^64), got {seed!r}")
+        grids = sorted({lv for _, lv in levels})
+        if len(ratios) > len(grids):
+            raise ValueError(f"token_merge: {len(ratios)} ratios, but this UNet has self-attention on {len(grids)} token grid(s)")
+        ratios = tuple(float(q) for q in ratios)
+        while ratios and ratios[-1] == 0:
+            ratios = ratios[:-1]
+        if not ratios:
+            return {}
+        missing = [n for n in ("tome_match", "tome_plan", "tome_merge", "tome_unmerge") if getattr(self.rt.ops, n, None) is None]
+        if missing:
+            raise NotImplementedError(f"this op table has no token-merging kernels (sdlt_{missing[0]}, ops.{missing[0]}): there is no torch fallback")
+        by_level = {lv: q for lv, q in zip(grids, ratios) if q > 0}
+        kv = dict(zip(grids, self._kv_ds[0])) if self._kv_ds is not None else {}
+        ht = dict(zip(grids, self._ht)) if self._ht is not None else {}
+        applied = {}
+        for t, lv in levels:
+            if lv in by_level:
+                if kv.get(lv, 1) > 1:
+                    raise ValueError(f"token_merge: {t.name} (level {lv}) already takes pooled keys and values (kv_downsample factor {kv[lv]}): one of the two per token grid "
+                                     "- a ratio of 0 there, or set_kv_downsample(None)")
+                if ht.get(lv, (1, 1)) != (1, 1):
+                    raise ValueError(f"token_merge: {t.name} (level {lv}) already runs tiled self-attention (hypertile {ht[lv]}): one of the two per token grid "
+                                     "- a ratio of 0 there, or set_hypertile(None)")
+                if latent is not None and ((latent[0] >> lv) % 2 or (latent[1] >> lv) % 2):
+                    raise ValueError(f"token_merge: the {latent[0] >> lv} x {latent[1] >> lv} token grid of {t.name} is odd (2 x 2 cells): a latent whose sides "
+                                     f"divide by {2 << lv}, or a ratio of 0 for this grid")
+                applied[t.name] = by_level[lv]
+        layer = 0
+        for t, lv in levels:
+            for blk in t.blocks:
+                if lv in by_level:
+                    blk.attn1._tome = dict(ratio=by_level[lv], mode=mode, seed=seed, ctr=ctr, layer=layer)
+                layer += 1
+        self._tome = (ratios, mode, seed)
         return applied
 
     def _freeu_apply(self, i, j, h, s, B, H, W):
@@ -1721,6 +1849,8 @@ class UNet(_Module):
         (caller zeroes it).  LoRA gradients land in arena.grads."""
         if self._freeu is not None:
             raise RuntimeError("UNet.backward with freeu set: FreeU is an inference-time change of the forward and has no backward here (set_freeu(None))")
+        if self._tome is not None:
+            raise NotImplementedError("UNet.backward with token_merge set: the merged self-attention has no backward here (set_token_merge(None))")
         if self._ht is not None:
             raise NotImplementedError("UNet.backward with hypertile set: the tiled self-attention has no backward here (set_hypertile(None))")
         if self._kv_ds is not None:
