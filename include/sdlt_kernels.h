@@ -372,6 +372,54 @@ typedef struct {
   int32_t B, N, Np, C;
 } sdlt_tome_unmerge_params;    /* 72 bytes; tagless */
 int sdlt_tome_unmerge(const sdlt_tome_unmerge_params* p, void* stream);
+/* Self-attention guidance (SAG; Hong et al. 2023, "Improving Sample Quality of Diffusion Models Using Self-Attention Guidance"), three entry points.
+ *
+ * sdlt_attn_colmass : the attention mass every key receives, from the operands one sdlt_attn_fwd call left behind - no [N, N] buffer, no second softmax:
+ *   mass[j, k] = (1 / H) sum over heads h < H and queries q < N of exp(scale Q_h[q] . K_h[k] - L[b, h, q]),   b = row_off + j row_stride, j < n.
+ * Q, K: bf16 token-major [B N, ld], head h in columns [h d, (h + 1) d), NO pad rows (any N >= 1); separate ldq / ldk (column views of a stacked q | k | v
+ * buffer go straight in).  L: fp32 [B, H, N] exactly as sdlt_attn_fwd writes it at Nq = N: the NATURAL logarithm of sum_k exp(scale s[q, k]) - the scale is
+ * inside, the base is e - so exp(scale s - L) is the softmax probability and the mean of mass[j, :] is 1.  Only the n batch rows b are read (the others may hold
+ * NaN; heatmap_accum's row_off / row_stride).  ws: fp32 [n H N] workspace (per-head sums, every element the finish reads is written first); mass: fp32 [n, N].
+ * d % 8 == 0 and d <= 160, every ld % 8 == 0 and >= H d.  fp32 scores from bf16 MFMAs, fp32 exponentials, sums in a fixed order (ascending queries per lane, a
+ * fixed shuffle tree over 16 lanes, heads ascending, one multiply by 1 / H): no atomics, two runs give the same bits.  Two launches (per-head sums, finish).
+ * A null block or operand, an extent < 1, row_off < 0, a batch row >= B, ld < H d, B N beyond 32 bits, H or n > 65535 (-1); ld % 8, Q / K not 16-byte or
+ * L / ws / mass not 4-byte aligned (-2); an unsupported d (-4): the code is returned before anything is launched, outputs untouched. */
+typedef struct {
+  const void* Q; int64_t ldq;
+  const void* K; int64_t ldk;
+  const float* L;
+  float* ws;
+  float* mass;
+  int32_t B, H, N, d, n, row_off, row_stride;
+  float scale;
+} sdlt_attn_colmass_params;    /* 88 bytes; tagless, no index in sdlt_struct_size (like sdlt_attn_window_params): a binding checks its mirror against this figure */
+int sdlt_attn_colmass(const sdlt_attn_colmass_params* p, void* stream);
+/* sdlt_sag_degrade : the degraded model input of SAG's second forward, one launch.  Per image j < n and latent pixel (y, x), 4 channels, with the step row
+ * i = clamp(ctr[0], 0, k - 1) of stab fp32 [stab_rows >= 1 + k, 4] (row 0 = (k, 0, 0, 0), row 1 + i = (sigma_i, s_i, threshold_i, 0); sampler.sag_table):
+ *     x0   = x - sigma e_neg                                   x fp32 [n, 4, h w] (sigma space), e_neg = rows [2 j h w, (2 j + 1) h w) of eps fp32 [2 n h w, 4]
+ *     blur = the 9-tap filter `taps` (fp32 [9], offsets -4 .. +4) of x0 along x, then along y; index -1 reads 1 and index h reads h - 2 (REFLECTED edges
+ *            that do not repeat the edge pixel - sdlt_blur_planes replicates); each sum starts at taps[0] v and adds taps[t] v in ascending offset
+ *     mask = mass[j, (y hm / h) wm + x wm / w] > threshold     mass fp32 [n, hm wm]; integer arithmetic: a nearest resize of the hm x wm grid
+ *     out  = bf16(((mask ? blur : x0) + sigma e_neg) / sqrt(sigma sigma + 1))   columns 0 .. 3 of out bf16 [n h w, ld]; columns >= 4 are never written
+ * fp32, one rounding per operation (no contraction), IEEE division and square root.  ctr is read, never written.  h, w >= 5 (the reflection's room),
+ * hm <= h, wm <= w.  A null block or operand, n / hm / wm < 1, h or w < 5 or > 2^15, h w > 2^24, stab_rows < 2, ld < 4 (-1); ld % 4, eps not 16-byte, out not
+ * 8-byte or another operand not 4-byte aligned (-2): returned before anything is launched, outputs untouched. */
+typedef struct {
+  const float* x; const float* eps; const float* mass; const float* taps; const float* stab; const int32_t* ctr;
+  void* out; int64_t ld;
+  int32_t n, h, w, hm, wm, stab_rows;
+} sdlt_sag_degrade_params;     /* 88 bytes; tagless */
+int sdlt_sag_degrade(const sdlt_sag_degrade_params* p, void* stream);
+/* sdlt_sag_apply : SAG's combine, element-wise with 16-byte accesses, on eps fp32 [2 n hw, 4] (rows 2 j negative, 2 j + 1 positive) and t fp32 [n hw, 4]:
+ *     phase 0:  t = s_i (e_neg - t)       in place on the second forward's prediction; s_i from the step row of stab (sdlt_sag_degrade)
+ *     phase 1:  e_neg += t, e_pos += t    stab and ctr are not read
+ * A guidance pre-pass, if any, runs between the two.  A null block or operand, n or hw < 1, stab_rows < 2 (-1); eps / t not 16-byte, stab / ctr not 4-byte
+ * aligned (-2); another phase (-4): returned before anything is launched. */
+typedef struct {
+  float* eps; float* t; const float* stab; const int32_t* ctr;
+  int32_t n, hw, stab_rows, phase;
+} sdlt_sag_apply_params;       /* 48 bytes; tagless */
+int sdlt_sag_apply(const sdlt_sag_apply_params* p, void* stream);
 /* out0 / out1 [B*Nkp, C] bf16 = sum over nsplit slabs of s0 / s1 (fp32 [nsplit][B*Nkp][ld32]) in slab order (rows with key >= Nk: zeros;
  * acc0: out0 += instead of =), for a table of layers: block_desc[b] = descriptor of block b, block_first[d] = first block of descriptor d,
  * a layer owns ceil(B*Nkp*C/2 / 256) blocks (capped at 64; the kernel strides). */

@@ -152,6 +152,21 @@ class TomeUnmergeParams(C.Structure):
                 ("B", i32), ("N", i32), ("Np", i32), ("C", i32)]
 
 
+class AttnColmassParams(C.Structure):
+    # sdlt_attn_colmass_params: 88 bytes by the header's text (tagless, like sdlt_attn_window_params); the two below likewise: 88, 48
+    _fields_ = [("Q", vp), ("ldq", i64), ("K", vp), ("ldk", i64), ("L", vp), ("ws", vp), ("mass", vp),
+                ("B", i32), ("H", i32), ("N", i32), ("d", i32), ("n", i32), ("row_off", i32), ("row_stride", i32), ("scale", f32)]
+
+
+class SagDegradeParams(C.Structure):
+    _fields_ = [("x", vp), ("eps", vp), ("mass", vp), ("taps", vp), ("stab", vp), ("ctr", vp), ("out", vp), ("ld", i64),
+                ("n", i32), ("h", i32), ("w", i32), ("hm", i32), ("wm", i32), ("stab_rows", i32)]
+
+
+class SagApplyParams(C.Structure):
+    _fields_ = [("eps", vp), ("t", vp), ("stab", vp), ("ctr", vp), ("n", i32), ("hw", i32), ("stab_rows", i32), ("phase", i32)]
+
+
 # the packed code of sdlt_attn_route (include/sdlt_kernels.h, SDLT_ATTN_ROUTE_*)
 ATTN_ROUTES = ("FWD32", "FWD16_KS2", "FWD16", "BWD_CROSS_ROLES", "BWD_CROSS", "BWD_BOTH32", "BWD_BOTH16", "BWD_SPLIT")
 ATTN_ROUTE_MASK = 0xF
@@ -321,6 +336,9 @@ SYMBOLS = {
     "sdlt_tome_plan": (i32, [C.POINTER(TomePlanParams), vp]),
     "sdlt_tome_merge": (i32, [C.POINTER(TomeMergeParams), vp]),
     "sdlt_tome_unmerge": (i32, [C.POINTER(TomeUnmergeParams), vp]),
+    "sdlt_attn_colmass": (i32, [C.POINTER(AttnColmassParams), vp]),
+    "sdlt_sag_degrade": (i32, [C.POINTER(SagDegradeParams), vp]),
+    "sdlt_sag_apply": (i32, [C.POINTER(SagApplyParams), vp]),
     "sdlt_attn_splitsum_batch": (i32, [vp, vp, vp, i32, vp]),
     "sdlt_groupnorm_ws_floats": (i32, [i32, i32, i32]),
     "sdlt_colsum_finish_batch": (i32, [vp, i32, i32, vp]),
@@ -430,7 +448,8 @@ def load():
         raise KernelLibraryError(f"struct layout mismatch for ResizeParams: header 48 vs binding {C.sizeof(ResizeParams)}")
     for cls, size in ((HeatAccumParams, 152), (HeatOverlayParams, 80), (GemmPlan, 64), (SamplerDdParams, 128), (WindowParams, 64), (RegionParams, 64),
                       (GuidanceApgParams, 56), (GuidanceDynParams, 48), (AttnWideParams, 88), (AttnCoupleParams, 112), (AttnWindowParams, 96),
-                      (TomeMatchParams, 80), (TomePlanParams, 72), (TomeMergeParams, 88), (TomeUnmergeParams, 72)):
+                      (TomeMatchParams, 80), (TomePlanParams, 72), (TomeMergeParams, 88), (TomeUnmergeParams, 72),
+                      (AttnColmassParams, 88), (SagDegradeParams, 88), (SagApplyParams, 48)):
         if C.sizeof(cls) != size:
             raise KernelLibraryError(f"struct layout mismatch for {cls.__name__}: header {size} vs binding {C.sizeof(cls)}")
     _lib = lib

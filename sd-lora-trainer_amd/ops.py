@@ -1511,12 +1511,12 @@ def sampler_step_dd(eps, x, xin, timesteps, table, ctr, *, x0, noise, hold, form
     return _sampler_launch("sdlt_sampler_step_dd", params, 4 if form == 0 else 8, eps, x, xin, timesteps, table, ctr, init, **operands)
 
 
-def blur_taps(sigma):
+def blur_taps(sigma, R=None):
     """The tap table of blur_planes for a Gaussian of standard deviation sigma > 0 (samples): fp32 [2 R + 1] on the CPU, R = min(ceil(3 sigma), 64),
-    weights exp(-d^2 / (2 sigma^2)) for d = -R .. R, normalised in fp64 and rounded once to fp32."""
+    weights exp(-d^2 / (2 sigma^2)) for d = -R .. R, normalised in fp64 and rounded once to fp32.  R: a radius of the caller's own (sag_degrade: 4)."""
     if not (isinstance(sigma, (int, float)) and not isinstance(sigma, bool) and math.isfinite(sigma) and sigma > 0.0):
         raise ValueError(f"blur_taps: sigma must be a finite number > 0, got {sigma!r}")
-    R = min(int(math.ceil(3.0 * sigma)), 64)
+    R = min(int(math.ceil(3.0 * sigma)), 64) if R is None else int(R)
     d = torch.arange(-R, R + 1, dtype=torch.float64)
     wgt = torch.exp(-(d * d) / (2.0 * float(sigma) ** 2))
     return (wgt / wgt.sum()).to(F32)
@@ -1593,6 +1593,99 @@ def guidance_dyn(eps, gtab, dtab, ctr, n):
                                gtab_rows=gtab.shape[0])
     _lib.check(lib.sdlt_guidance_dyn(C.byref(p), _stream()), "sdlt_guidance_dyn")
     return eps
+
+
+SAG_RADIUS = 4      # the blur of sag_degrade: 9 taps (blur_taps(sigma, SAG_RADIUS))
+
+
+def _sag_fail(fn, msg):
+    raise ValueError(f"{fn}: {msg}")
+
+
+def _sag_tensor(fn, name, t, dtype, shape=None, numel=None):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and (shape is None or tuple(t.shape) == tuple(shape))
+            and (numel is None or t.numel() >= numel)):
+        want = f"{list(shape)}" if shape is not None else f"[>= {numel}]"
+        _sag_fail(fn, f"{name}: expected a contiguous cuda {dtype} tensor {want}, got {tuple(t.shape) if torch.is_tensor(t) else type(t)}")
+
+
+def attn_colmass(Q, K, L, mass, *, B, H, N, d, scale, n=None, row_off=0, row_stride=1, ws=None):
+    """sdlt_attn_colmass: mass fp32 [n, N] = the attention every key receives, summed over queries and averaged over heads, from the operands an attn_fwd
+    call left: Q, K bf16 [B N, >= H d] (row-major views, any row stride % 8 == 0), L fp32 [B H N] its log-sum-exp.  Image j reads batch row
+    row_off + j row_stride only (n None: every row from row_off on that the stride reaches).  ws: fp32 [>= n H N] workspace of the caller's own - a
+    captured launch holds its pointer - or None: allocated here.  d % 8 == 0, d <= 160.  ValueError for a wrong shape or dtype, before the call."""
+    fn = "attn_colmass"
+    ok_int = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
+    for name, v, lo in (("B", B, 1), ("H", H, 1), ("N", N, 1), ("d", d, 1), ("row_off", row_off, 0), ("row_stride", row_stride, 1)):
+        if not ok_int(v) or v < lo:
+            _sag_fail(fn, f"{name}={v!r} (an integer >= {lo})")
+    if n is None:
+        n = (B - row_off + row_stride - 1) // row_stride
+    if not ok_int(n) or n < 1 or row_off + (n - 1) * row_stride >= B:
+        _sag_fail(fn, f"n={n!r} image(s) from batch row {row_off} in steps of {row_stride} do not fit B={B}")
+    if d % 8 or d > 160:
+        _sag_fail(fn, f"d={d} (a multiple of 8, <= 160)")
+    for name, t in (("Q", Q), ("K", K)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == BF16 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == B * N and t.shape[1] >= H * d):
+            _sag_fail(fn, f"{name}: expected a cuda bf16 row-major view [{B * N}, >= {H * d}], got {tuple(t.shape) if torch.is_tensor(t) else type(t)}")
+    _sag_tensor(fn, "L", L, F32, numel=B * H * N)
+    _sag_tensor(fn, "mass", mass, F32, shape=(n, N))
+    if ws is None:
+        ws = torch.empty(n * H * N, dtype=F32, device=mass.device)
+    _sag_tensor(fn, "ws", ws, F32, numel=n * H * N)
+    p = _lib.AttnColmassParams()
+    p.Q, p.ldq, p.K, p.ldk, p.L, p.ws, p.mass = _p(Q), _ld(Q), _p(K), _ld(K), _p(L), _p(ws), _p(mass)
+    p.B, p.H, p.N, p.d, p.n, p.row_off, p.row_stride, p.scale = B, H, N, d, n, row_off, row_stride, float(scale)
+    _lib.check(_lib.load().sdlt_attn_colmass(C.byref(p), _stream()), "sdlt_attn_colmass")
+    return mass
+
+
+def sag_degrade(x, eps, mass, taps, stab, ctr, out, *, grid):
+    """sdlt_sag_degrade: the degraded model input of self-attention guidance's second forward, one launch.  x fp32 [n, 4, h, w] (sigma space), eps fp32
+    [2 n h w, 4] (the negative rows are read), mass fp32 [n, hm wm] with grid = (hm, wm), taps fp32 [9] (blur_taps(sigma, SAG_RADIUS)), stab fp32
+    [>= 2, 4] (sampler.sag_table), ctr int32 [>= 1] (read, never written) -> columns 0 .. 3 of out bf16 [n h w, ld]: bf16(((mass > threshold ? blur(x0) :
+    x0) + sigma e_neg) / sqrt(sigma^2 + 1)), x0 = x - sigma e_neg, edges reflected.  h, w >= 5.  ValueError for a wrong shape or dtype, before the call."""
+    fn = "sag_degrade"
+    if not (torch.is_tensor(x) and x.dim() == 4 and x.shape[1] == 4):
+        _sag_fail(fn, f"x: expected fp32 [n, 4, h, w], got {tuple(x.shape) if torch.is_tensor(x) else type(x)}")
+    n, _, h, w = x.shape
+    if h < 5 or w < 5:
+        _sag_fail(fn, f"a {h} x {w} latent: the reflected 4-pixel halo needs 5 on both axes")
+    if not (isinstance(grid, (tuple, list)) and len(grid) == 2 and all(isinstance(v, int) and not isinstance(v, bool) for v in grid) and 1 <= grid[0] <= h and 1 <= grid[1] <= w):
+        _sag_fail(fn, f"grid={grid!r} (hm, wm) with 1 <= hm <= {h} and 1 <= wm <= {w}")
+    _sag_tensor(fn, "x", x, F32)
+    _sag_tensor(fn, "eps", eps, F32, shape=(2 * n * h * w, 4))
+    _sag_tensor(fn, "mass", mass, F32, shape=(n, grid[0] * grid[1]))
+    _sag_tensor(fn, "taps", taps, F32, shape=(2 * SAG_RADIUS + 1,))
+    _sag_tensor(fn, "ctr", ctr, torch.int32, numel=1)
+    if not (torch.is_tensor(stab) and stab.is_cuda and stab.dtype == F32 and stab.dim() == 2 and stab.shape[1] == 4 and stab.shape[0] >= 2 and stab.is_contiguous()):
+        _sag_fail(fn, "stab: expected a contiguous cuda fp32 table [>= 2, 4] (sampler.sag_table)")
+    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == BF16 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] == n * h * w and out.shape[1] >= 4):
+        _sag_fail(fn, f"out: expected a cuda bf16 row-major view [{n * h * w}, >= 4], got {tuple(out.shape) if torch.is_tensor(out) else type(out)}")
+    p = _lib.SagDegradeParams(x=x.data_ptr(), eps=eps.data_ptr(), mass=mass.data_ptr(), taps=taps.data_ptr(), stab=stab.data_ptr(), ctr=ctr.data_ptr(),
+                              out=out.data_ptr(), ld=_ld(out), n=n, h=h, w=w, hm=grid[0], wm=grid[1], stab_rows=stab.shape[0])
+    _lib.check(_lib.load().sdlt_sag_degrade(C.byref(p), _stream()), "sdlt_sag_degrade")
+    return out
+
+
+def sag_apply(eps, t, stab, ctr, n, phase):
+    """sdlt_sag_apply: self-attention guidance's combine on eps fp32 [2 n hw, 4] and t fp32 [n hw, 4], in place.  phase 0: t = s_i (e_neg - t) with s_i
+    from the step row ctr[0] of stab (t comes in as the second forward's prediction); phase 1: both row blocks of every image += t.  A guidance pre-pass
+    runs between the two.  ValueError for a wrong shape or dtype, before the call."""
+    fn = "sag_apply"
+    if phase not in (0, 1):
+        _sag_fail(fn, f"phase={phase!r} (0 or 1)")
+    if not (isinstance(n, int) and n >= 1 and torch.is_tensor(t) and t.dim() == 2 and t.shape[0] % n == 0):
+        _sag_fail(fn, f"n={n!r} image(s) do not divide t {tuple(t.shape) if torch.is_tensor(t) else type(t)}")
+    hw = t.shape[0] // n
+    _sag_tensor(fn, "t", t, F32, shape=(n * hw, 4))
+    _sag_tensor(fn, "eps", eps, F32, shape=(2 * n * hw, 4))
+    _sag_tensor(fn, "ctr", ctr, torch.int32, numel=1)
+    if not (torch.is_tensor(stab) and stab.is_cuda and stab.dtype == F32 and stab.dim() == 2 and stab.shape[1] == 4 and stab.shape[0] >= 2 and stab.is_contiguous()):
+        _sag_fail(fn, "stab: expected a contiguous cuda fp32 table [>= 2, 4] (sampler.sag_table)")
+    p = _lib.SagApplyParams(eps=eps.data_ptr(), t=t.data_ptr(), stab=stab.data_ptr(), ctr=ctr.data_ptr(), n=n, hw=hw, stab_rows=stab.shape[0], phase=phase)
+    _lib.check(_lib.load().sdlt_sag_apply(C.byref(p), _stream()), "sdlt_sag_apply")
+    return t if phase == 0 else eps
 
 
 def resize_planes(src, out, mode):

@@ -8,6 +8,7 @@ scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-squ
                                          [--sigmas trailing|karras] [--guidance-rescale F] [--guidance-interval SIGMA_LO SIGMA_HI]
                                          [--apg [--apg-eta F] [--apg-norm-threshold F] [--apg-momentum F]]
                                          [--dynthresh [MIMIC] [--dynthresh-percentile F] [--dynthresh-interpolate F]]
+                                         [--sag [SCALE] [--sag-blur SIGMA] [--sag-threshold T]]
                                          [--negative-prompt TEXT] [--freeu B1 B2 S1 S2 [--freeu-v2]]
                                          [--hires-scale F | --hires-size W H] [--hires-strength F] [--hires-steps N] [--hires-upscaler latent|pixel]
                                          [--hires-resample nearest|bilinear|bicubic] [--heatmap [WORD ...]] [--heatmap-grid max|min]
@@ -70,6 +71,15 @@ choice; the two sub-flags are errors without --dynthresh.  One launch (sdlt_guid
 quantile is an exact order statistic from a radix select inside the launch, so it needs no host work and repeats bit for bit.  With every sampler, noise
 schedule, --guidance-interval, --init-image / --mask / --change-map, --tile-diffusion, --region and --heatmap; both passes of a hires render use it.  Not
 with --guidance-rescale or --apg: they are alternative answers to the same fault.  Without the flag nothing changes.
+
+--sag [SCALE] is self-attention guidance (Hong et al. 2023; ComfyUI's "Self-Attention Guidance" node, whose defaults these are: SCALE 0.5, --sag-blur 2,
+--sag-threshold 1): sharper structure without a higher --guidance, no extra weights.  Every step, the attention each token of the mid block's first
+self-attention receives is summed over queries and heads (sdlt_attn_colmass, an MFMA kernel that reads the q, k and log-sum-exp the forward left and never
+writes the attention matrix); the predicted clean latent is blurred where that mass exceeds T and noised back (sdlt_sag_degrade, one launch); the UNet
+runs a SECOND time on it with the negative prompt alone, at half the batch; and SCALE times the difference of the two negative predictions is added to the
+guided one (sdlt_sag_apply).  All inside the replayed graph; measured on the MI355X at 1024 px a step costs 1.57 plain ones.  With every sampler, --guidance-*, --apg,
+--dynthresh, --init-image and both passes of a hires render.  Epsilon-prediction models only; not with --tile-diffusion, --region or --heatmap, nor with
+--kv-downsample / --hypertile / --tome at a depth that reaches the mid block's token grid.  Without the flag nothing changes.
 
 --hires-scale F / --hires-size W H render in two passes (the "hires fix"): a picture much larger than the model was trained for falls apart when it is
 sampled in one go (doubled subjects, tiled compositions), so the first pass samples at --size, the result is enlarged on the device
@@ -323,6 +333,21 @@ def apg_args(apg):
 
 DYN_DEFAULT = (7.0, 0.999, 1.0)      # mimic scale, percentile, interpolate: this project's choice
 DYN_KEYS = ("mimic", "percentile", "interpolate")
+
+
+SAG_KEYS = ("scale", "blur_sigma", "threshold")
+
+
+def sag_args(sag, blur=None, threshold=None):
+    """render()'s sag / sag_blur / sag_threshold, checked -> None | (scale, blur_sigma, threshold).  sag: None or False (off; the other two must be None
+    then), True (the default scale) or the scale; the defaults and the ranges are sampler.SAG_DEFAULT's and sampler.sag_args'."""
+    from . import sampler as SM
+    if sag is None or sag is False:
+        if blur is not None or threshold is not None:
+            raise ValueError("sag_blur and sag_threshold need sag (--sag [SCALE])")
+        return None
+    d = SM.SAG_DEFAULT
+    return SM.sag_args((d[0] if sag is True else sag, d[1] if blur is None else blur, d[2] if threshold is None else threshold))
 
 
 def dynthresh_args(dynthresh):
@@ -629,7 +654,7 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
            guidance_rescale=0.0, guidance_interval=None, negative_prompt=None, hires=None, freeu=None, heatmap=None, heatmap_grid="max",
            kv_downsample=None, kv_downsample_mode="nearest", kv_downsample_pass="hires", vae_tile=None, change_map_image=None, mask_blur=None, tile_diffusion=None, regions=None, region_feather=None,
            region_base=None, region_bootstrap=None, apg=None, dynthresh=None, vae_attention="dense", region_mode=None, hypertile=None, hypertile_depth=None,
-           hypertile_pass=None, tome=None, tome_depth=None, tome_mode=None, tome_pass=None):
+           hypertile_pass=None, tome=None, tome_depth=None, tome_mode=None, tome_pass=None, sag=None, sag_blur=None, sag_threshold=None):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
     seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
@@ -642,6 +667,10 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     `apg` - in every pass, of a hires render too (each pass is a trajectory of its own: the running average restarts); with everything else.
     dynthresh: None, True (DYN_DEFAULT), (mimic, percentile, interpolate) or a dict of them (dynthresh_args): dynamic thresholding - LatentSampler.sample's
     `dynthresh` - in every pass, of a hires render too; not with apg or guidance_rescale > 0 (ValueError).
+    sag: None, True (sampler.SAG_DEFAULT's scale 0.5) or the scale, with sag_blur (the blur's sigma in latent pixels, default 2) and sag_threshold (on the
+    attention mass, whose mean is 1; default 1) - sag_args: self-attention guidance, LatentSampler.sample's `sag`, in every pass of a hires render and with
+    every sampler.  Epsilon prediction only (NotImplementedError); not with tile_diffusion, regions or heatmap, nor with kv_downsample, hypertile or tome
+    at a depth that reaches the mid block's token grid (ValueError).
     hires (a dict, hires_args: scale | size, strength, steps, upscaler, resample): two passes - every image is first sampled at `size`, for all adapter
     scales and prompt batches, its latents staying on the device; they are enlarged (sampler.upscale_latents: the latents, or with upscaler "pixel"
     the decoded picture, encoded again); then the UNet is rebuilt ONCE for the large shape and every second pass runs: sample(init_latents=the
@@ -721,6 +750,13 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         SM.require_op(stack.rt.ops, "guidance_apg", " (sdlt_guidance_apg): apg forms the projected prediction by that launch (ops.guidance_apg)", kernel="sdlt_guidance_apg")
     if dt is not None:
         SM.require_op(stack.rt.ops, "guidance_dyn", " (sdlt_guidance_dyn): dynthresh forms the thresholded prediction by that launch (ops.guidance_dyn)", kernel="sdlt_guidance_dyn")
+    sg = sag_args(sag, sag_blur, sag_threshold)                        # (raises before anything is built)
+    if sg is not None:
+        for other, name in ((tile_diffusion, "tile_diffusion"), (regions, "regions"), (heatmap, "heatmap")):
+            if other is not None:
+                raise ValueError(f"sag does not combine with {name}")
+        SM.require_op(stack.rt.ops, "attn_colmass", " (sdlt_attn_colmass, sdlt_sag_degrade, sdlt_sag_apply): sag takes the attention mass, the degraded input and the "
+                      "combine from those launches; there is no torch fallback", kernel="sdlt_attn_colmass")
     rg = region_args(regions, region_feather, region_base, region_bootstrap, region_mode)      # (raises before anything is built)
     if rg is not None:
         for other, name in ((tile_diffusion, "tile_diffusion: windows of regions are not built"), (hires, "hires: the masks would need a second grid"),
@@ -806,7 +842,14 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         td_plan2 = SM.tile_plan(hi["size"][1] // f, hi["size"][0] // f, tile_diffusion)
     for pl in (td_plan, td_plan2):
         SM.window_multiple(cfg, pl, "tile_diffusion")
-    stack.vae_attention = vae_attention                              # every VAE this render builds takes it: RenderStack.build_decoder, _vae_encoder
+    if sg is not None:      # (raises before anything is built) every pass's self-attention options must stay above the mid block's token grid
+        levels = {lv for _, lv in stack.unet._attn_levels()}
+        for ph, pw, second in [(h, w, False)] + ([(hi["size"][1] // f, hi["size"][0] // f, True)] if hi is not None else []):
+            on = lambda passes: second or passes == "all"  # noqa: E731
+            SM.sag_depth_check(stack.unet, ph, pw, kd if kd is not None and on(kv_downsample_pass) else None,
+                               (SM.hypertile_plan(ph, pw, levels, hy["tile"], hy["depth"]) or None) if hy is not None and on(hy["passes"]) else None,
+                               ((tm["ratio"],) * (tm["depth"] + 1), tm["mode"], 0) if tm is not None and on(tm["passes"]) else None)
+    stack.vae_attention = vae_attention                             # every VAE this render builds takes it: RenderStack.build_decoder, _vae_encoder
     if getattr(stack.decoder, "attention", "dense") != vae_attention:
         stack.build_decoder()
         loaded.dec_shape = None
@@ -819,6 +862,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         img_kw.update(apg=ag)
     if dt is not None:
         img_kw.update(dynthresh=dt)
+    if sg is not None:
+        img_kw.update(sag=sg)
     if (sampler, sigmas) != ("euler", "trailing"):
         img_kw.update(sampler=sampler, sigmas=sigmas)
     if sde:
@@ -982,6 +1027,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             meta.update(apg=dict(zip(APG_KEYS, ag)))
         if dt is not None:
             meta.update(dynthresh=dict(zip(DYN_KEYS, dt)))
+        if sg is not None:
+            meta.update(sag=dict(zip(SAG_KEYS, sg)))
         if negative_prompt is not None:
             meta.update(negative_prompt=negative_prompt)
         if hi is not None:
@@ -1047,6 +1094,11 @@ def main(argv=None, runtime=None):
                     help=f"dynamic thresholding: every latent channel of the guided prediction gets the value range of the prediction at guidance scale MIMIC (default {DYN_DEFAULT[0]:g})")
     ap.add_argument("--dynthresh-percentile", type=float, default=None, metavar="F", help=f"with --dynthresh: the quantile of the prediction's own deviations the clamp stays above, in (0, 1] (default {DYN_DEFAULT[1]:g})")
     ap.add_argument("--dynthresh-interpolate", type=float, default=None, metavar="F", help=f"with --dynthresh: weight of the thresholded prediction against the plain one, in [0, 1] (default {DYN_DEFAULT[2]:g})")
+    from .sampler import SAG_DEFAULT
+    ap.add_argument("--sag", type=float, nargs="?", const=SAG_DEFAULT[0], default=None, metavar="SCALE",
+                    help=f"self-attention guidance: a second UNet forward on a latent blurred where the mid block's self-attention looks, pushed away from by SCALE (default {SAG_DEFAULT[0]:g})")
+    ap.add_argument("--sag-blur", type=float, default=None, metavar="SIGMA", help=f"with --sag: the blur's standard deviation in latent pixels (default {SAG_DEFAULT[1]:g})")
+    ap.add_argument("--sag-threshold", type=float, default=None, metavar="T", help=f"with --sag: blur where a token's attention mass (mean 1) exceeds T (default {SAG_DEFAULT[2]:g})")
     ap.add_argument("--negative-prompt", default=None, help="the negative prompt; default: the fixed one of the training-time renders")
     ap.add_argument("--hires-scale", type=float, default=None, help="two passes: sample at --size, enlarge by this factor (each axis rounded to the VAE's multiple), finish at the large size")
     ap.add_argument("--hires-size", type=int, nargs=2, metavar=("W", "H"), default=None, help="two passes with the final size given in pixels instead of a factor")
@@ -1148,6 +1200,14 @@ def main(argv=None, runtime=None):
             dyn = dict(dynthresh=dynthresh_args(dict(given, mimic=a.dynthresh)))
         except ValueError as e:
             ap.error(f"--dynthresh / --dynthresh-percentile / --dynthresh-interpolate: {e}")
+    try:
+        sgk = sag_args(a.sag, a.sag_blur, a.sag_threshold)
+    except ValueError as e:
+        ap.error(f"--sag / --sag-blur / --sag-threshold: {e}")
+    for flag, on in (("--tile-diffusion", a.tile_diffusion is not None), ("--region", a.region is not None), ("--heatmap", a.heatmap is not None)):
+        if sgk is not None and on:
+            ap.error(f"--sag does not combine with {flag}")
+    sgk = {} if sgk is None else dict(sag=sgk[0], sag_blur=sgk[1], sag_threshold=sgk[2])
     if a.strength is not None and not 0.0 < a.strength <= 1.0:
         ap.error(f"--strength must be in (0, 1], got {a.strength}")
     if a.heatmap_grid is not None and a.heatmap is None:
@@ -1250,7 +1310,7 @@ def main(argv=None, runtime=None):
                  images_per_batch=a.images_per_batch, graph=not a.eager, n_validation=a.n_validation, init_image=a.init_image, strength=a.strength,
                  mask_image=a.mask, sampler=a.sampler, sigmas=a.sigmas, eta=a.eta, guidance_rescale=a.guidance_rescale,
                  guidance_interval=a.guidance_interval, negative_prompt=a.negative_prompt, **({} if hires is None else dict(hires=hires)),
-                 **({} if freeu is None else dict(freeu=freeu)), **kvd, **hyp, **tme, **vtile, **tdiff, **regs, **apg, **dyn,
+                 **({} if freeu is None else dict(freeu=freeu)), **kvd, **hyp, **tme, **vtile, **tdiff, **regs, **apg, **dyn, **sgk,
                  **({} if a.change_map is None else dict(change_map_image=a.change_map)), **({} if a.mask_blur is None else dict(mask_blur=a.mask_blur)),
                  **({} if a.vae_attention is None else dict(vae_attention=a.vae_attention)),
                  **({} if a.heatmap is None else dict(heatmap=a.heatmap, heatmap_grid=a.heatmap_grid or "max")))

@@ -373,6 +373,69 @@ def dyn_table(sched, dynthresh, k=None):
     return torch.from_numpy(tab)
 
 
+SAG_DEFAULT = (0.5, 2.0, 1.0)      # scale, blur sigma (latent pixels), threshold on the attention mass (its mean is 1): ComfyUI's node
+
+
+def sag_args(sag):
+    """sample()'s / render()'s `sag`, checked -> None | (scale, blur_sigma, threshold).  None or False: off; True: SAG_DEFAULT; three values; or a dict with
+    any of scale, blur_sigma, threshold.  scale: a finite number >= 0, or one per step that runs (sag_table checks the count); blur_sigma finite and > 0;
+    threshold a finite number.  ValueError otherwise."""
+    if sag is None or sag is False:
+        return None
+    real = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool) and math.isfinite(v)  # noqa: E731
+    if sag is True:
+        sag = SAG_DEFAULT
+    elif isinstance(sag, dict):
+        unknown = sorted(set(sag) - {"scale", "blur_sigma", "threshold"})
+        if unknown:
+            raise ValueError(f"sag: keys scale, blur_sigma, threshold; unknown {unknown}")
+        sag = tuple(sag.get(k, v) for k, v in zip(("scale", "blur_sigma", "threshold"), SAG_DEFAULT))
+    if not (isinstance(sag, (tuple, list)) and len(sag) == 3):
+        raise ValueError(f"sag takes True, (scale, blur_sigma, threshold) or a dict of those, got {sag!r}")
+    scale, blur, thr = sag
+    scales = list(scale) if isinstance(scale, (tuple, list)) else [scale]
+    if not scales or not all(real(v) and v >= 0.0 for v in scales):
+        raise ValueError(f"sag: scale must be a finite number >= 0 (or one per step that runs), got {scale!r}")
+    if not (real(blur) and blur > 0.0):
+        raise ValueError(f"sag: blur_sigma must be a finite number > 0 (latent pixels), got {blur!r}")
+    if not real(thr):
+        raise ValueError(f"sag: threshold must be a finite number, got {thr!r}")
+    return (tuple(float(v) for v in scales) if isinstance(scale, (tuple, list)) else float(scale)), float(blur), float(thr)
+
+
+def sag_table(sched, sag, k=None):
+    """The device table of ops.sag_degrade / ops.sag_apply for a scheduler whose set_timesteps(n[, start]) has run: fp32 [1 + k, 4] for the k steps that
+    run (None: all of the scheduler's), row 0 (k, 0, 0, 0), row 1 + i (sigma_i, s_i, threshold, 0).  sag: sag_args' argument; a scale per step must come as
+    k values.  ValueError otherwise."""
+    k = len(sched.timesteps) if k is None else k
+    scale, _, thr = sag_args(sag) or (None, None, None)
+    if scale is None:
+        raise ValueError("sag_table: sag is off")
+    if isinstance(scale, tuple) and len(scale) != k:
+        raise ValueError(f"sag: {len(scale)} scale(s) for the {k} step(s) that run (one each, or a number)")
+    tab = np.zeros((1 + k, 4), dtype=np.float32)
+    tab[0, 0] = k
+    tab[1:, 0] = np.asarray(sched.sigmas[:k], dtype=np.float32)
+    tab[1:, 1] = scale
+    tab[1:, 2] = thr
+    return torch.from_numpy(tab)
+
+
+def sag_depth_check(unet, h, w, kd, ht, tm):
+    """ValueError where kv_downsample (kd: kv_downsample_args' result), hypertile (ht: hypertile_plan's result) or token_merge (tm: token_merge_args')
+    reaches the mid block's token grid of an h x w latent: self-attention guidance probes that layer's plain N x N softmax.  Settings that stay above
+    it combine.  Reads the UNet's levels only; nothing is set."""
+    from . import ops as _ops
+    grids, last = sorted({lv for _, lv in unet._attn_levels()}), len(unet.cfg["block_out_channels"]) - 1
+    i, N = grids.index(last), (h >> last) * (w >> last)
+    hit = ("kv_downsample" if kd is not None and len(kd[0]) > i and kd[0][i] > 1 else
+           "hypertile" if ht is not None and len(ht) > i and tuple(ht[i]) != (1, 1) else
+           "token_merge" if tm is not None and len(tm[0]) > i and _ops.tome_rows(N, tm[0][i]) > 0 else None)
+    if hit is not None:
+        raise ValueError(f"sag does not combine with {hit} at a depth that reaches the mid block's {h >> last} x {w >> last} token grid (its first "
+                         "self-attention is probed): a smaller depth")
+
+
 SAMPLERS = ("euler", "dpmpp_2m", "euler_a", "dpmpp_2m_sde")
 SIGMAS = ("trailing", "karras")
 
@@ -840,6 +903,10 @@ class LatentSampler:
         self._guided_graphs = {}           # any of the four keys above + (its family,) -> hipGraph of that iteration with ops.guidance before the step launch
         self._apg_graphs = {}              # the same + ("apg",) -> hipGraph of that iteration with ops.guidance_apg there instead: a dict of their own, so they evict no other
         self._dyn_graphs = {}              # the guided key + ("dyn",) -> hipGraph of that iteration with ops.guidance_dyn there instead: a dict of their own as well
+        self._sag_graphs = {}              # the key the iteration has otherwise + ("sag",) -> hipGraph of that iteration with self-attention guidance in it: their own dict too
+        self._sag = None                   # sag_args of the running call (self-attention guidance): the setting lives here, not on the Trajectory
+        self._unet_sag = {}                # (freeu, kv_downsample, hypertile, token_merge) of the UNet -> UNet.clone_for_batch on a runtime of n rows: SAG's second
+                                           # forward (the negative rows alone).  A clone freezes those settings when it is made, and a capture holds its buffers: one each, kept
         # the torch loop where the pre-pass runs: the deterministic samplers in their step kernels' order (dpmpp_2m: the SDE form's eta = 0 rows are
         # ms_coefficients with d = 0)
         self.sched_exact = dict(euler=EulerStepOrder(prediction_type=prediction_type), dpmpp_2m=DpmSolverPP2MSDE(prediction_type=prediction_type, eta=0.0))
@@ -847,7 +914,8 @@ class LatentSampler:
     def _fwd_kw(self):
         """Keywords of the UNet forward: with key / value downsampling set it is declared an inference forward (UNet.forward refuses a training one);
         the same with tiled self-attention (hypertile) and token merging; without, the call is the plain one."""
-        return {} if all(getattr(self.unet, n, None) is None for n in ("_kv_ds", "_ht", "_tome")) else {"train": False}
+        plain = all(getattr(self.unet, n, None) is None for n in ("_kv_ds", "_ht", "_tome")) and not getattr(self.unet, "_probe", False)
+        return {} if plain else {"train": False}
 
     def set_lora_scale(self, lora_scale, train_scale=None):
         """set_adapter_scales (checkpoint.py:31-55): every adapter's contribution is multiplied by lora_scale."""
@@ -861,7 +929,7 @@ class LatentSampler:
     def sample(self, embeds, h, w, *, steps=25, guidance_scale=8.0, generator=None, size=None, latents=None, graph=False, fused=False, n_images=1,
                init_latents=None, strength=1.0, mask=None, sampler="euler", sigmas="trailing", eta=1.0, seeds=None, guidance_rescale=0.0,
                guidance_interval=None, freeu=None, heatmap=None, kv_downsample=None, kv_downsample_mode=None, change_map=None, tile=None, regions=None, apg=None,
-               dynthresh=None, hypertile=None, token_merge=None):
+               dynthresh=None, hypertile=None, token_merge=None, sag=None):
         """embeds = (c [1,77,D], uc [1,77,D], pc [1,P] | None, puc | None); h, w latent size.  Returns latents [1,4,h,w] fp32
         (still multiplied by the VAE scaling factor, as the pipeline holds them before `vae.decode(latents / scaling_factor)`).
         fused: guidance, the Euler update and the next model input are ONE kernel between two forwards (ops.sampler_step) instead of torch
@@ -947,8 +1015,32 @@ class LatentSampler:
         in every forward of the trajectory, on all three paths, with every sampler.  The random destinations are drawn on the device from the step
         counter the step kernels keep, so the torch loop, the fused path and a replayed graph merge the same tokens.  None: the constructor's setting;
         False: off, and the launch sequence is the plain one.  The setting is part of the capture key.  Token grids must be even, and a grid takes one
-        of kv_downsample, hypertile and token_merge (ValueError)."""
+        of kv_downsample, hypertile and token_merge (ValueError).
+        sag: None, True, (scale, blur_sigma, threshold) or a dict of those (sag_args; SAG_DEFAULT): self-attention guidance (Hong et al. 2023).  Every
+        forward leaves q, k and the log-sum-exp of the mid block's first self-attention on the negative rows (UNet.set_attention_probe: no launch added);
+        ops.attn_colmass turns them into the attention mass per key, ops.sag_degrade blurs the predicted clean latent where the mass exceeds the
+        threshold and re-noises it, a SECOND forward - the negative conditioning only, at batch n_images, on a plan clone that shares every weight
+        (UNet.clone_for_batch) - predicts e_sag from it, and ops.sag_apply adds s_i (e_neg - e_sag) to both rows around the guidance pre-pass, if any:
+        the step forms e_neg + s (e_neg - e_sag) + g (e_pos - e_neg).  scale may be one value per step that runs.  On all three paths, with every
+        sampler, init latents, mask, change map and every guidance option; sigma, scale and threshold per step and the taps are device memory: one
+        capture (in a dict of its own, the key ending in "sag") serves every setting.  sag=None is the path without it: the same launches, capture keys
+        and bits.  Epsilon prediction only (NotImplementedError); not with tile, regions or heatmap, nor with kv_downsample, hypertile or token_merge at
+        a depth that reaches the mid block's token grid (ValueError); latent sides >= 5."""
         ops = self.rt.ops
+        sg = sag_args(sag)                                 # refused before anything is built
+        if sg is not None:
+            if self.sched.prediction_type != "epsilon":
+                raise NotImplementedError(f"sag: the degraded input is formed from an epsilon prediction; {self.sched.prediction_type} (v_prediction) is not built")
+            for name, v in (("tile", tile), ("regions", regions), ("heatmap", heatmap)):
+                if v is not None:
+                    raise ValueError(f"sag does not combine with {name}: " + dict(
+                        tile="the probed attention and the blur are per window", regions="the probed attention is per region row",
+                        heatmap="the second forward would add to the hooked score sums")[name])
+            for op in ("attn_colmass", "sag_degrade", "sag_apply"):
+                require_op(ops, op, " (sdlt_attn_colmass, sdlt_sag_degrade, sdlt_sag_apply): sample(sag=...) takes the attention mass, the degraded input and "
+                           "the combine from those launches, in the torch loop too; there is no torch fallback", kernel="sdlt_attn_colmass")
+            if h < 5 or w < 5:
+                raise ValueError(f"sag: a {h} x {w} latent: the blur's reflected 4-pixel halo needs 5 on both axes")
         if regions is not None and (tile is not None or heatmap is not None):      # refused before anything is built
             raise ValueError("regions do not combine with " + ("tile: windows of regions are not built" if tile is not None else
                                                                "heatmap: the hooked score sums are per region row, and fusing them is not built"))
@@ -985,18 +1077,20 @@ class LatentSampler:
             if graph or fused:
                 require_op(ops, "sampler_step_dd", ": sample(change_map=..., graph=False, fused=False) is the torch loop")
         tm = self.token_merge if token_merge is None else token_merge_args(token_merge)
-        if getattr(self.unet, "_tome", None) is not None:      # an earlier call's merging is cleared first: the setting does not stick, and the two options
-            self.unet.set_token_merge(None)                    # below are judged against this call's grids only
         kd = self.kv_downsample
         if kv_downsample is not None or kv_downsample_mode is not None:
             kd = kv_downsample_args(kd[0] if kv_downsample is None and kd is not None else kv_downsample, kv_downsample_mode or (kd[1] if kd is not None else "nearest"))
-        if kd != getattr(self.unet, "_kv_ds", None):
-            self.unet.set_kv_downsample(*(kd or (None,)))      # (an op table without the kernel raises NotImplementedError here)
         hp = self.hypertile if hypertile is None else hypertile_args(hypertile)
         ht = None
         if hp is not None:
             uh, uw = (h, w) if plan is None else (plan.th, plan.tw)      # (the UNet's own latent: a window of tiled diffusion)
             ht = hypertile_plan(uh, uw, {lv for _, lv in self.unet._attn_levels()}, *hp) or None
+        if sg is not None:      # refused before the UNet is touched
+            sag_depth_check(self.unet, h, w, kd, ht, tm)
+        if getattr(self.unet, "_tome", None) is not None:      # an earlier call's merging is cleared first: the setting does not stick, and the two options
+            self.unet.set_token_merge(None)                    # below are judged against this call's grids only
+        if kd != getattr(self.unet, "_kv_ds", None):
+            self.unet.set_kv_downsample(*(kd or (None,)))      # (an op table without the kernel raises NotImplementedError here)
         if ht != getattr(self.unet, "_ht", None):
             self.unet.set_hypertile(ht, **({} if ht is None else dict(latent=(uh, uw))))      # (an op table without the kernel raises NotImplementedError here)
         if tm is not None:      # (an op table without the kernels raises NotImplementedError here; depth beyond the UNet's grids: all of them)
@@ -1040,12 +1134,26 @@ class LatentSampler:
             if img is not None and hold is None:
                 require_op(ops, "sampler_step_img", ": sample(init_latents=..., graph=False, fused=False) is the torch loop")
             assert n_images == self.n, f"the runtime's batch {self.rt.B} samples {self.n} image(s) together, not {n_images}"
-            return self._sample_fused(traj, embeds, latents, generator, graph)
+            try:                                           # (armed after the last refusal, for the run alone: nothing sticks, whether it ends or raises)
+                self._arm_sag(sg)
+                return self._sample_fused(traj, embeds, latents, generator, graph)
+            finally:
+                self._arm_sag(None)
         assert n_images == 1 and self.n == 1, "the torch loop samples one image on a batch-2 runtime; several images together: fused=True or graph=True"
         if sampler in SDE_KINDS:
             require_op(ops, "sampler_noise", f": sample(sampler={sampler!r}) takes its per-step noise from that kernel's generator (ops.sampler_noise), "
                        "in the torch loop too", kernel="sampler_step_sde")
-        return self._sample_torch(traj, embeds, latents, generator)
+        try:
+            self._arm_sag(sg)
+            return self._sample_torch(traj, embeds, latents, generator)
+        finally:
+            self._arm_sag(None)
+
+    def _arm_sag(self, sg):
+        """Self-attention guidance on (sag_args' tuple) or off (None) for the call that runs: the setting, and the UNet's attention probe with it."""
+        if sg is not None or getattr(self.unet, "_probe", False):
+            self.unet.set_attention_probe(sg is not None)
+        self._sag = sg
 
     def _sample_torch(self, traj, embeds, latents, generator):
         """The torch loop: the setup and the forward stage of the fused path (_begin, _predict) on the same persistent state, then the scheduler's step,
@@ -1057,6 +1165,7 @@ class LatentSampler:
         m, hold = sh["img"]["mask"] if traj.masked else None, None if traj.hold is None else sh["img"]["hold"]
         sde, counted = traj.sampler in SDE_KINDS, heat is not None or traj.guide is not None or (traj.reg is not None and not traj.reg["couple"])      # (the gather reads the bootstrap's row)
         counted = counted or getattr(self.unet, "_tome", None) is not None      # (token merging draws its destinations at the step counter)
+        counted = counted or self._sag is not None                              # (self-attention guidance reads its table's row there)
         if sde:
             z = rt.zeros(1, 4, h, w, dtype=F32)
         if heat is not None and heat["heat"] is not None:
@@ -1067,6 +1176,8 @@ class LatentSampler:
             st["tf"].fill_(float(t))
             if counted:                            # the heat maps' weight and the pre-pass's row are read at a device counter, as in the fused path
                 st["ctr"][0] = i
+            if self._sag is not None:              # ops.sag_degrade reads the latent where the fused path keeps it
+                sh["x"].copy_(x)
             eps = self._predict(st, sh, traj, heat).view(2, h, w, 4).permute(0, 3, 1, 2)
             e = eps[1:2] if traj.guide is not None else eps[0:1] + traj.guidance_scale * (eps[1:2] - eps[0:1])      # (the pre-pass: both rows hold the prediction)
             if sde:                                # the kernel's own noise of step i (not drawn where the row adds none)
@@ -1153,7 +1264,32 @@ class LatentSampler:
             self._window_state(st["shapes"][key], h, w, plan)
         if reg is not None:
             (self._couple_state if reg["couple"] else self._region_state)(st["shapes"][key], h, w, reg)
+        if self._sag is not None:
+            self._sag_state(st["shapes"][key], h, w)
         return st, st["shapes"][key]
+
+    def _sag_state(self, sh, h, w):
+        """-> sh["sag"]: the persistent buffers of self-attention guidance for this shape - the second forward's model input x64 (columns >= 4 stay zero),
+        the attention mass and the workspace of its per-head sums, the taps, the table stab, and the negative-only context and pooled rows - allocated
+        once (a captured launch holds their pointers; _begin rewrites taps, stab and the conditioning per trajectory).  The second forward's UNet
+        (UNet.clone_for_batch on a runtime of n rows) is built here too, one per combination of the UNet settings it freezes (_sag_key)."""
+        ss = sh.get("sag")
+        if ss is None:
+            from . import ops as _ops
+            rt, n, u = self.rt, self.n, self.unet
+            a, last = u.probe_layer(), len(u.cfg["block_out_channels"]) - 1
+            hm, wm = h >> last, w >> last
+            ss = sh["sag"] = dict(grid=(hm, wm), x64=rt.zeros(n * h * w, 64), mass=rt.zeros(n, hm * wm, dtype=F32), ws=rt.zeros(n * a.heads * hm * wm, dtype=F32),
+                                  taps=rt.zeros(2 * _ops.SAG_RADIUS + 1, dtype=F32), stab=rt.zeros(TABLE_ROWS - 1, 4, dtype=F32),
+                                  ctx=rt.zeros(n * CTX_PAD, u.cfg["cross_dim"]), pooled=None if self.pooled is None else rt.zeros(n, self.pooled.shape[1]))
+        if self._sag_key() not in self._unet_sag:      # (this call's settings are on the UNet by now: the clone copies them)
+            from .unet import Runtime
+            self._unet_sag[self._sag_key()] = self.unet.clone_for_batch(Runtime(self.rt.device, self.n, act_dtype=self.rt.act, ops=self.rt.ops))
+        return ss
+
+    def _sag_key(self):
+        """The UNet settings a plan clone freezes (UNet.clone_for_batch): the second forward must run with the first one's."""
+        return tuple(getattr(self.unet, k, None) for k in ("_freeu", "_kv_ds", "_ht", "_tome"))
 
     def _couple_state(self, sh, h, w, reg):
         """-> sh["couple"]: the persistent buffers of regional prompts in couple mode for this shape - the contexts [2 n R CTX_PAD, D], rcount = [1, R, 1, R,
@@ -1285,6 +1421,15 @@ class LatentSampler:
             if "dtab" not in st:
                 st["dtab"] = rt.zeros(TABLE_ROWS - 1, 4, dtype=F32)
             st["dtab"][: dtab.shape[0]].copy_(dtab)
+        if self._sag is not None:                         # the table, the taps and the negative rows of the conditioning just loaded, rewritten per trajectory
+            from . import ops as _ops
+            ss = sh["sag"]
+            stab = sag_table(sch, self._sag, traj.steps)
+            ss["stab"][: stab.shape[0]].copy_(stab)
+            ss["taps"].copy_(_ops.blur_taps(self._sag[1], _ops.SAG_RADIUS))
+            ss["ctx"].view(n, CTX_PAD, -1).copy_(self.ctx.view(n, 2, CTX_PAD, -1)[:, 0])
+            if ss["pooled"] is not None:
+                ss["pooled"].copy_(self.pooled.view(n, 2, -1)[:, 0])
         noise = latents if latents is not None else torch.randn(n, 4, h, w, generator=generator, device=dev, dtype=F32)
         noise = noise.to(dev, F32).contiguous()
         assert tuple(noise.shape) == (n, 4, h, w)
@@ -1329,7 +1474,8 @@ class LatentSampler:
         blend; with regions: gather, the forward on every region's rows, blend - then ops.heatmap_accum on the forward's score sums (heat, a dict of sh["heat"]: the weight of row ctr[0] of st["hw"]; the maps are
         allocated at the first iteration, when the forward has told the resolutions), then ops.guidance (row ctr[0] of st["gtab"]) where the pre-pass
         runs - with apg: ops.guidance_apg (the same row of st["atab"] as well, the running average in sh["mom"]); with dyn: ops.guidance_dyn (the same row of
-        st["dtab"] as well) -> eps fp32 [2 n h w, 4]."""
+        st["dtab"] as well) -> eps fp32 [2 n h w, 4].  With self-attention guidance (self._sag): after the forward ops.attn_colmass on the probed layer's
+        negative rows, ops.sag_degrade, the second forward at batch n on self._unet_sag's clone for the UNet's settings and ops.sag_apply phase 0; after the pre-pass phase 1."""
         u, h, w = self.unet, traj.h, traj.w
         tid = st["tid"] if u.cfg["addition"] else None
         if traj.plan is not None:
@@ -1345,12 +1491,23 @@ class LatentSampler:
             if heat["heat"] is None:
                 heat["heat"] = self.rt.zeros(self.n, heat["cols"].shape[1], *heat_grid(ents, heat["grid"]), dtype=F32)
             self.rt.ops.heatmap_accum(ents, heat["cols"], st["ctr"], st["hw"], heat["heat"], row_off=1, row_stride=2)
+        t_sag = None
+        if self._sag is not None:       # self-attention guidance: mass of the probed layer's negative rows, the degraded input, the second forward at batch n
+            ops, n, ss, pr = self.rt.ops, self.n, sh["sag"], u.probe_layer().probed
+            assert pr["B"] == 2 * n and pr["grid"] == ss["grid"], (pr["B"], pr["grid"], ss["grid"])
+            ops.attn_colmass(pr["q"], pr["k"], pr["L"], ss["mass"], B=pr["B"], H=pr["H"], N=pr["N"], d=pr["d"], scale=pr["scale"], n=n, row_off=0, row_stride=2,
+                             ws=ss["ws"])
+            ops.sag_degrade(sh["x"], eps, ss["mass"], ss["taps"], ss["stab"], st["ctr"], ss["x64"], grid=ss["grid"])
+            t_sag = self._unet_sag[self._sag_key()].forward(ss["x64"], st["tf"][:n], ss["ctx"], ss["pooled"], None if tid is None else tid[: 6 * n], B=n, H=h, W=w, train=False)
+            ops.sag_apply(eps, t_sag, ss["stab"], st["ctr"], n, 0)      # t = s_i (e_neg - e_sag), from the untouched e_neg; added after the pre-pass
         if traj.apg is not None:
             self.rt.ops.guidance_apg(eps, st["gtab"], st["atab"], sh["mom"], st["ctr"], self.n)
         elif traj.dyn is not None:
             self.rt.ops.guidance_dyn(eps, st["gtab"], st["dtab"], st["ctr"], self.n)
         elif traj.guide is not None:
             self.rt.ops.guidance(eps, st["gtab"], st["ctr"], self.n)
+        if t_sag is not None:
+            self.rt.ops.sag_apply(eps, t_sag, sh["sag"]["stab"], st["ctr"], self.n, 1)
         return eps
 
     def _iteration(self, st, sh, traj, heat):
@@ -1404,6 +1561,8 @@ class LatentSampler:
             key, graphs = key + ("apg",), self._apg_graphs
         if traj.dyn is not None:                          # ops.guidance_dyn likewise; mimic, percentile and interpolate are in st["dtab"]
             key, graphs = key + ("dyn",), self._dyn_graphs
+        if self._sag is not None:                         # self-attention guidance adds a forward and four launches; sigma, scale, threshold and the taps are in sh["sag"]
+            key, graphs = key + ("sag",), self._sag_graphs
         g = graphs.get(key)
         if g is not None:
             return g

@@ -985,6 +985,8 @@ class Attention(_Module):
     _ht = None          # (ty, tx) of UNet.set_hypertile: this self-attention attends inside the tiles of its token grid only (inference only)
     _tome = None        # dict(ratio, mode, seed, ctr, layer) of UNet.set_token_merge: this self-attention runs on merged tokens (inference only)
     norm = None         # the LayerNorm in front of a self-attention (TransformerBlock.norm1): the pooling launch normalises with it
+    _probe = False      # UNet.set_attention_probe: this self-attention keeps its q, k and log-sum-exp reachable after a forward (inference only)
+    probed = None       # ... as dict(q, k, L, B, N, H, d, scale, grid): views of this layer's own persistent buffers
 
     def tome_rows(self, N, grid):
         """The merged source count r of this self-attention on N tokens under UNet.set_token_merge; 0: the plain path (no setting, or the ratio merges
@@ -1128,6 +1130,11 @@ class Attention(_Module):
             self._attn_fwd_padded(q, k, v, O, L, B, N, Nk, Nkp, kv_padded=pooled_kv)
         else:
             rt.ops.attn_fwd(q, k, v, None, O, L, B=B, H=self.heads, Nq=N, Nk=Nk, Nqp=N, Nkp=Nkp, d=self.d, scale=self.scale, **kwz)
+        if self._probe:      # the plain launches above, nothing added: q and k are this layer's unpadded rows, L is [B, H, N] on both of its routes
+            if self.cross or ht is not None or pooled_kv:
+                raise ValueError(f"attention probe: {self.name} runs " + ("cross-attention" if self.cross else "tiled self-attention (hypertile)" if ht is not None else
+                                 "on pooled keys (kv_downsample)") + ": there is no N x N softmax with a log-sum-exp to probe")
+            self.probed = dict(q=q, k=k, L=L, B=B, N=N, H=self.heads, d=self.d, scale=self.scale, grid=grid)
         if self.cross and self.hooked and cp is None:
             # DAAM side output (ti_cross_attn_loss.py:201-212): sum over heads of Q_h K_h^T / sqrt(d) = Q K^T / sqrt(d).
             # The token-attention loss only ever uses the MEAN over layers of these maps (loss.py:23-52), so the layers
@@ -1406,6 +1413,7 @@ class ResnetBlock(_Module):
 
 class UNet(_Module):
     """forward(noisy NHWC, timesteps, ctx[, pooled, time_ids]) -> eps_hat [B*h*w, 4] fp32;  backward(dpred)."""
+    _probe = False                       # set_attention_probe
 
     def __init__(self, rt, version, sd, lora_rank=None, lora_alpha_multiplier=1.0, trainer=None, use_dora=False):
         """trainer: a fullft.WeightTrainer -> every parameter of the UNet is registered with it and trained (the
@@ -1512,6 +1520,9 @@ class UNet(_Module):
         if train and self._tome is not None:
             raise NotImplementedError("token_merge is an inference option: a training forward (train=True, TrainStep) has no backward through the merged "
                                       "tokens - set_token_merge(None) first")
+        if train and self._probe:
+            raise NotImplementedError("the attention probe is an inference option: a training forward (train=True, TrainStep) keeps its operands for its own "
+                                      "backward - set_attention_probe(False) first")
         if self._couple is not None:
             if train:
                 raise NotImplementedError("attention couple is an inference option: a training forward (train=True, TrainStep) has no backward through the "
@@ -1603,6 +1614,32 @@ class UNet(_Module):
         if not hasattr(self.rt.ops, "freeu"):
             raise NotImplementedError("this op table has no freeu kernel: FreeU's skip filter and backbone scale are that launch (ops.freeu)")
         self._freeu = vals + (int(version),)
+
+    # ------------------------------------------------------------------------------------ attention probe, batch clone (inference only)
+    def probe_layer(self):
+        """The self-attention that self-attention guidance reads: mid_block.attentions[0].transformer_blocks[0].attn1."""
+        return self.mid[1].blocks[0].attn1
+
+    def set_attention_probe(self, on):
+        """on: an inference forward (forward(train=False)) leaves probe_layer().probed = dict(q, k, L, B, N, H, d, scale, grid) - the operands of that
+        layer's softmax, views of its own persistent buffers, as ops.attn_colmass takes them.  No launch is added or changed.  Not where that layer runs
+        on merged tokens, pooled keys or tiles (ValueError at the forward: there is no N x N softmax to probe)."""
+        self._probe = bool(on)
+        a = self.probe_layer()
+        a._probe, a.probed = self._probe, None
+
+    def clone_for_batch(self, rt):
+        """clone_plan of the whole UNet for ANOTHER batch size (self-attention guidance's second forward runs the negative rows alone): every weight,
+        packed operand and the adapter arena are shared, every activation buffer is the clone's own and lives on `rt`.  The per-level (resnets,
+        transformers, sampler) tuples are rebuilt here: clone_plan follows attributes that are modules or flat lists of modules only.  Inference only."""
+        memo = {}
+        c = clone_plan(self, rt, memo)
+        cl = lambda m: None if m is None else clone_plan(m, rt, memo)  # noqa: E731
+        c.down = [([cl(r) for r in res], [cl(t) for t in att], cl(s)) for res, att, s in self.down]
+        c.up = [([cl(r) for r in res], [cl(t) for t in att], cl(s)) for res, att, s in self.up]
+        c._kv_groups, c._grad_plan, c._daam_fwd = {}, None, None      # (operand tables that hold activation pointers: the clone builds its own)
+        c.set_attention_probe(False)
+        return c
 
     # ------------------------------------------------------------------------------------ region-coupled cross-attention (inference only)
     def set_attention_couple(self, state):
