@@ -420,6 +420,49 @@ typedef struct {
   int32_t n, hw, stab_rows, phase;
 } sdlt_sag_apply_params;       /* 48 bytes; tagless */
 int sdlt_sag_apply(const sdlt_sag_apply_params* p, void* stream);
+/* Style-aligned batches (Hertz et al. 2023, "Style Aligned Image Generation via Shared Attention"), two entry points; forward only.  The B images form groups
+ * of G; the reference of an image is the first of its group.  gs = 1: groups of G consecutive images, r = (b / G) G.  gs > 1: gs groups interleave inside every
+ * span of G gs images - member j of group c is image j gs + c of the span, r = (b / (G gs)) G gs + b % gs - which is how the negative and the positive rows of
+ * a guided batch (negative 0, positive 0, negative 1, ...; gs = 2) form one group each.  B % (G gs) == 0.
+ *
+ * sdlt_adain_affine : the per-image AdaIN tables.  X: bf16 token-major [B N, ld], columns [0, C2) are read (C2 % 8 == 0, ld % 8 == 0, ld >= C2; the q | k
+ *   columns of a stacked q | k | v buffer go in as one call).  Per image b and column c over its N >= 2 tokens: mean = (1 / N) sum x,
+ *   var = sum (x - mean)^2 / (N - 1), std = sqrt(var + 1e-5);   A[b, c] = std_r / std_b,  S[b, c] = mean_r - A[b, c] mean_b;  exactly (1, 0) for b == r.
+ *   A, S: fp32 [B, C2].  ws: fp32 [B ceil(N / 256) 2 C2] workspace (every element the finish reads is written first).  fp32 throughout and safe against
+ *   cancellation: (mean, M2) per chunk of 256 tokens - the mean first, then the centred squares of the same values - combined in ascending chunk order.
+ *   Two launches (chunks, finish), fixed order, no atomics: two runs give the same bits.
+ *   A null block or operand, B / C2 / G / gs < 1, N < 2, G gs not dividing B, ld < C2, an index range beyond 32 bits, B or ceil(N / 256) > 65535 (-1); C2 % 8, ld % 8,
+ *   X not 16-byte or A / S / ws not 4-byte aligned (-2): the code is returned before anything is launched, outputs untouched. */
+typedef struct {
+  const void* X; int64_t ld;
+  float* A; float* S; float* ws;
+  int32_t B, N, C2, G, gs, pad_;
+} sdlt_adain_affine_params;    /* 64 bytes; tagless, no index in sdlt_struct_size (like sdlt_attn_colmass_params): a binding checks its mirror against this figure */
+int sdlt_adain_affine(const sdlt_adain_affine_params* p, void* stream);
+/* sdlt_attn_shared_fwd : shared self-attention.  Q, K, V, O: bf16 token-major [B N, ld], head h in columns [h d, (h + 1) d), NO pad rows (any N >= 1);
+ *   separate ld* (column views of a stacked q | k | v buffer go straight in).  Aq, Sq, Ak, Sk: fp32 [B, ldt] tables over the same H d columns (views of
+ *   sdlt_adain_affine's A and S), all four or none (null: identity).  For image b, query i, with q' = Aq[b] o q + Sq[b] and k' = Ak[b] o k + Sk[b]:
+ *     own keys j < N:                     s = scale q'_i . k'_b[j]
+ *     reference keys j < N, if b != r:    s = scale q'_i . K_r[j] + shift          (the reference's own keys: its affine is the identity)
+ *     O_i = softmax over both segments (s) [V_b ; V_r];   b == r: plain attention over its own N keys.   shift = ln(weight of the reference).
+ *   No [own; reference] copy of K or V: the kernel walks both row ranges, and K is never rewritten - the own segment multiplies the raw keys by
+ *   bf16(q' o Ak) and adds the fp32 constant scale q' . Sk per query, the reference segment by bf16(q') (q' formed in fp32, one rounding per fragment set).
+ *   Images of another group are never read (they may hold NaN).  scale > 0; d % 8 == 0 and d <= 160; every ld % 8 == 0 and >= H d; ldt % 4 == 0 and >= H d.
+ *   fp32 scores, online softmax over 64-key blocks (own ascending, then the reference's ascending; one running maximum and sum), bf16 P for the P V products,
+ *   fp32 accumulation, one rounding at the store.  One launch; no atomics, no workspace, no log-sum-exp: two runs give the same bits.
+ *   A null block or operand, some but not all tables, an extent < 1, G gs not dividing B, a scale that is not finite and > 0, a non-finite shift, ld < H d,
+ *   O overlapping an input, row indices beyond 32 bits (-1); ld % 8, ldt % 4, Q / K / V / O or a table not 16-byte aligned (-2); an unsupported d (-4): the
+ *   code is returned before anything is launched, outputs untouched. */
+typedef struct {
+  const void* Q; int64_t ldq;
+  const void* K; int64_t ldk;
+  const void* V; int64_t ldv;
+  void* O; int64_t ldo;
+  const float* Aq; const float* Sq; const float* Ak; const float* Sk; int64_t ldt;
+  int32_t B, H, N, d, G, gs;
+  float scale, shift;
+} sdlt_attn_shared_params;     /* 136 bytes; tagless */
+int sdlt_attn_shared_fwd(const sdlt_attn_shared_params* p, void* stream);
 /* out0 / out1 [B*Nkp, C] bf16 = sum over nsplit slabs of s0 / s1 (fp32 [nsplit][B*Nkp][ld32]) in slab order (rows with key >= Nk: zeros;
  * acc0: out0 += instead of =), for a table of layers: block_desc[b] = descriptor of block b, block_first[d] = first block of descriptor d,
  * a layer owns ceil(B*Nkp*C/2 / 256) blocks (capped at 64; the kernel strides). */

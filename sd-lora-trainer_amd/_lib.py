@@ -167,6 +167,17 @@ class SagApplyParams(C.Structure):
     _fields_ = [("eps", vp), ("t", vp), ("stab", vp), ("ctr", vp), ("n", i32), ("hw", i32), ("stab_rows", i32), ("phase", i32)]
 
 
+class AdainAffineParams(C.Structure):
+    # sdlt_adain_affine_params: 64 bytes by the header's text (tagless, like sdlt_attn_colmass_params); the one below likewise: 136
+    _fields_ = [("X", vp), ("ld", i64), ("A", vp), ("S", vp), ("ws", vp), ("B", i32), ("N", i32), ("C2", i32), ("G", i32), ("gs", i32), ("pad_", i32)]
+
+
+class AttnSharedParams(C.Structure):
+    _fields_ = [("Q", vp), ("ldq", i64), ("K", vp), ("ldk", i64), ("V", vp), ("ldv", i64), ("O", vp), ("ldo", i64),
+                ("Aq", vp), ("Sq", vp), ("Ak", vp), ("Sk", vp), ("ldt", i64),
+                ("B", i32), ("H", i32), ("N", i32), ("d", i32), ("G", i32), ("gs", i32), ("scale", f32), ("shift", f32)]
+
+
 # the packed code of sdlt_attn_route (include/sdlt_kernels.h, SDLT_ATTN_ROUTE_*)
 ATTN_ROUTES = ("FWD32", "FWD16_KS2", "FWD16", "BWD_CROSS_ROLES", "BWD_CROSS", "BWD_BOTH32", "BWD_BOTH16", "BWD_SPLIT")
 ATTN_ROUTE_MASK = 0xF
@@ -339,6 +350,8 @@ SYMBOLS = {
     "sdlt_attn_colmass": (i32, [C.POINTER(AttnColmassParams), vp]),
     "sdlt_sag_degrade": (i32, [C.POINTER(SagDegradeParams), vp]),
     "sdlt_sag_apply": (i32, [C.POINTER(SagApplyParams), vp]),
+    "sdlt_adain_affine": (i32, [C.POINTER(AdainAffineParams), vp]),
+    "sdlt_attn_shared_fwd": (i32, [C.POINTER(AttnSharedParams), vp]),
     "sdlt_attn_splitsum_batch": (i32, [vp, vp, vp, i32, vp]),
     "sdlt_groupnorm_ws_floats": (i32, [i32, i32, i32]),
     "sdlt_colsum_finish_batch": (i32, [vp, i32, i32, vp]),
@@ -449,7 +462,7 @@ def load():
     for cls, size in ((HeatAccumParams, 152), (HeatOverlayParams, 80), (GemmPlan, 64), (SamplerDdParams, 128), (WindowParams, 64), (RegionParams, 64),
                       (GuidanceApgParams, 56), (GuidanceDynParams, 48), (AttnWideParams, 88), (AttnCoupleParams, 112), (AttnWindowParams, 96),
                       (TomeMatchParams, 80), (TomePlanParams, 72), (TomeMergeParams, 88), (TomeUnmergeParams, 72),
-                      (AttnColmassParams, 88), (SagDegradeParams, 88), (SagApplyParams, 48)):
+                      (AttnColmassParams, 88), (SagDegradeParams, 88), (SagApplyParams, 48), (AdainAffineParams, 64), (AttnSharedParams, 136)):
         if C.sizeof(cls) != size:
             raise KernelLibraryError(f"struct layout mismatch for {cls.__name__}: header {size} vs binding {C.sizeof(cls)}")
     _lib = lib

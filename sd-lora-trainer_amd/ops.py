@@ -1000,6 +1000,83 @@ def attn_window_fwd(Q, K, V, O, *, B, H, grid, tiles, d, scale):
     return O
 
 
+ADAIN_CHUNK = 256      # tokens per statistics chunk of sdlt_adain_affine (csrc/attn_shared.hip SR)
+
+
+def adain_ws_floats(B, N, C2):
+    """Floats of adain_affine's workspace: (mean, M2) per image, chunk of 256 tokens and column."""
+    return B * ((N + ADAIN_CHUNK - 1) // ADAIN_CHUNK) * 2 * C2
+
+
+def _shared_ints(fn, **vals):
+    for name, v in vals.items():
+        if not (isinstance(v, int) and not isinstance(v, bool)) or v < 1:
+            raise ValueError(f"{fn}: {name}={v!r} (an integer >= 1)")
+
+
+def adain_affine(X, A, S, *, B, N, G, gs=1, ws=None):
+    """sdlt_adain_affine: the AdaIN tables of style-aligned batches.  X bf16 [B N, C2] (a row-major view, any row stride % 8 == 0: the q | k columns of a
+    stacked buffer), C2 % 8 == 0; groups of G images, reference the first of each (gs = 1: consecutive images; gs > 1: gs groups interleaved, image
+    j gs + c of a span of G gs is member j of group c - the negative | positive rows of a guided batch are gs = 2).  A, S fp32 [B, C2] contiguous: A = std_r / std_b,
+    S = mean_r - A mean_b per image and column (unbiased variance, std = sqrt(var + 1e-5)); exactly (1, 0) for a reference.  ws: fp32
+    [>= B ceil(N / 256) 2 C2] workspace of the caller's own - a captured launch holds its pointer - or None: allocated here.  N >= 2.  ValueError for
+    a wrong shape or dtype, before the call."""
+    fn = "adain_affine"
+    _shared_ints(fn, B=B, N=N, G=G, gs=gs)
+    if N < 2:
+        raise ValueError(f"{fn}: N={N} (the unbiased variance needs two tokens)")
+    if B % (G * gs):
+        raise ValueError(f"{fn}: {gs} interleaved group(s) of G={G} do not divide B={B}")
+    if not (torch.is_tensor(X) and X.is_cuda and X.dtype == BF16 and X.dim() == 2 and X.stride(1) == 1 and X.shape[0] == B * N and X.shape[1] % 8 == 0 and X.shape[1] >= 8):
+        raise ValueError(f"{fn}: X: expected a cuda bf16 row-major view [{B * N}, C2 % 8 == 0], got {tuple(X.shape) if torch.is_tensor(X) else type(X)}")
+    C2 = X.shape[1]
+    for name, t in (("A", A), ("S", S)):
+        _sag_tensor(fn, name, t, F32, shape=(B, C2))
+    need = adain_ws_floats(B, N, C2)
+    if ws is None:
+        ws = torch.empty(need, dtype=F32, device=X.device)
+    _sag_tensor(fn, "ws", ws, F32, numel=need)
+    p = _lib.AdainAffineParams()
+    p.X, p.ld, p.A, p.S, p.ws = _p(X), _ld(X), _p(A), _p(S), _p(ws)
+    p.B, p.N, p.C2, p.G, p.gs = B, N, C2, G, gs
+    _lib.check(_lib.load().sdlt_adain_affine(C.byref(p), _stream()), "sdlt_adain_affine")
+    return A, S
+
+
+def attn_shared_fwd(Q, K, V, O, *, B, H, N, d, G, scale, shift=0.0, tables=None, gs=1):
+    """sdlt_attn_shared_fwd: shared self-attention of style-aligned batches.  Q, K, V, O bf16 [B N, >= H d] (row-major views, any row stride % 8 == 0), no
+    pad rows; groups of G images (gs as in adain_affine).  Every image attends to its own N keys and - unless it is the first of its group, the reference - to the
+    reference's N keys as well, whose logits get + shift (ln of the reference's weight).  tables = (Aq, Sq, Ak, Sk): fp32 [B, >= H d] views of one row
+    stride (adain_affine's A and S); q' = Aq o q + Sq everywhere, k' = Ak o k + Sk on the image's own keys; None: identity.  d % 8 == 0, d <= 160.  One
+    launch, no [own; reference] copy.  ValueError for a wrong shape or dtype, before the call."""
+    fn = "attn_shared_fwd"
+    _shared_ints(fn, B=B, H=H, N=N, d=d, G=G, gs=gs)
+    if B % (G * gs):
+        raise ValueError(f"{fn}: {gs} interleaved group(s) of G={G} do not divide B={B}")
+    if d % 8 or d > 160:
+        raise ValueError(f"{fn}: d={d} (a multiple of 8, <= 160)")
+    scale, shift = float(scale), float(shift)
+    if not (math.isfinite(scale) and scale > 0.0 and math.isfinite(shift)):
+        raise ValueError(f"{fn}: scale={scale} shift={shift} (scale > 0, both finite)")
+    for name, t in (("Q", Q), ("K", K), ("V", V), ("O", O)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == BF16 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == B * N and t.shape[1] >= H * d):
+            raise ValueError(f"{fn}: {name}: expected a cuda bf16 row-major view [{B * N}, >= {H * d}], got {tuple(t.shape) if torch.is_tensor(t) else type(t)}")
+    p = _lib.AttnSharedParams()
+    if tables is not None:
+        if not (isinstance(tables, (tuple, list)) and len(tables) == 4):
+            raise ValueError(f"{fn}: tables = (Aq, Sq, Ak, Sk) or None, got {type(tables)}")
+        for name, t in zip(("Aq", "Sq", "Ak", "Sk"), tables):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == F32 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == B and t.shape[1] >= H * d
+                    and t.stride(0) == tables[0].stride(0)):
+                raise ValueError(f"{fn}: {name}: expected a cuda float32 row-major view [{B}, >= {H * d}] (one row stride for the four), got "
+                                 f"{tuple(t.shape) if torch.is_tensor(t) else type(t)}")
+        p.Aq, p.Sq, p.Ak, p.Sk, p.ldt = _p(tables[0]), _p(tables[1]), _p(tables[2]), _p(tables[3]), tables[0].stride(0)
+    p.Q, p.ldq, p.K, p.ldk, p.V, p.ldv, p.O, p.ldo = _p(Q), _ld(Q), _p(K), _ld(K), _p(V), _ld(V), _p(O), _ld(O)
+    p.B, p.H, p.N, p.d, p.G, p.gs, p.scale, p.shift = B, H, N, d, G, gs, scale, shift
+    _lib.check(_lib.load().sdlt_attn_shared_fwd(C.byref(p), _stream()), "sdlt_attn_shared_fwd")
+    return O
+
+
 TOME_MODES = ("fixed", "random")
 
 

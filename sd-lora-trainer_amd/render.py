@@ -9,6 +9,7 @@ scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-squ
                                          [--apg [--apg-eta F] [--apg-norm-threshold F] [--apg-momentum F]]
                                          [--dynthresh [MIMIC] [--dynthresh-percentile F] [--dynthresh-interpolate F]]
                                          [--sag [SCALE] [--sag-blur SIGMA] [--sag-threshold T]]
+                                         [--style-align [WEIGHT] [--style-align-adain qk|none]]
                                          [--negative-prompt TEXT] [--freeu B1 B2 S1 S2 [--freeu-v2]]
                                          [--hires-scale F | --hires-size W H] [--hires-strength F] [--hires-steps N] [--hires-upscaler latent|pixel]
                                          [--hires-resample nearest|bilinear|bicubic] [--heatmap [WORD ...]] [--heatmap-grid max|min]
@@ -80,6 +81,14 @@ runs a SECOND time on it with the negative prompt alone, at half the batch; and 
 guided one (sdlt_sag_apply).  All inside the replayed graph; measured on the MI355X at 1024 px a step costs 1.57 plain ones.  With every sampler, --guidance-*, --apg,
 --dynthresh, --init-image and both passes of a hires render.  Epsilon-prediction models only; not with --tile-diffusion, --region or --heatmap, nor with
 --kv-downsample / --hypertile / --tome at a depth that reaches the mid block's token grid.  Without the flag nothing changes.
+
+--style-align [WEIGHT] makes the pictures of a render agree in style (Hertz et al. 2023, "Style Aligned Image Generation via Shared Attention"; diffusers'
+StyleAlignedSDXLPipeline, ComfyUI's "StyleAligned Batch Align"): in every self-attention each picture also attends to the keys and values of the render's
+FIRST picture (prompt 0, seed + 0), whose logits get + ln(WEIGHT) (default 1), after its queries and keys have been moved to that picture's per-channel mean
+and deviation (--style-align-adain qk, the default; none: skip it).  One launch per self-attention walks both key ranges (sdlt_attn_shared_fwd: no copy of K
+or V, K never rewritten) behind one statistics launch pair (sdlt_adain_affine); all inside the replayed graph, in every pass of a hires render.  Needs
+--images-per-batch >= 2; with more prompts than that every later batch is the first prompt again plus the next ones, and the first picture is saved once.  No
+weights, no training; not with --sag, --tile-diffusion, --region, --kv-downsample, --hypertile or --tome.  Cost: DESIGN 4.42.  Without the flag nothing changes.
 
 --hires-scale F / --hires-size W H render in two passes (the "hires fix"): a picture much larger than the model was trained for falls apart when it is
 sampled in one go (doubled subjects, tiled compositions), so the first pass samples at --size, the result is enlarged on the device
@@ -336,6 +345,40 @@ DYN_KEYS = ("mimic", "percentile", "interpolate")
 
 
 SAG_KEYS = ("scale", "blur_sigma", "threshold")
+
+
+STYLE_ALIGN_ADAIN = ("qk", "none")
+
+
+def style_align_args(style_align, weight=None, adain=None, images_per_batch=None):
+    """render()'s style_align / style_align_weight / style_align_adain, checked -> None | dict(weight=, adain="qk" | "none").  style_align: None or False
+    (off; the other two must be None then), True (weight 1) or the weight of the reference keys (> 0; style_align_weight says the same)."""
+    if style_align is None or style_align is False:
+        if weight is not None or adain is not None:
+            raise ValueError("style_align_weight and style_align_adain need style_align (--style-align [WEIGHT])")
+        return None
+    w_ = weight if weight is not None else 1.0 if style_align is True else style_align
+    if not isinstance(w_, (int, float)) or isinstance(w_, bool) or not math.isfinite(w_) or w_ <= 0:
+        raise ValueError(f"style_align: the weight of the reference keys must be finite and > 0, got {w_!r}")
+    adain = "qk" if adain is None else adain
+    if adain not in STYLE_ALIGN_ADAIN:
+        raise ValueError(f"style_align_adain must be one of {STYLE_ALIGN_ADAIN}, got {adain!r}")
+    if images_per_batch is not None and images_per_batch < 2:
+        raise ValueError(f"style_align aligns the pictures of a batch with the render's first picture: images_per_batch={images_per_batch} (at least 2)")
+    return dict(weight=float(w_), adain=adain)
+
+
+def batch_plan(n_prompts, n, style_align=False):
+    """[(idx, keep)] of a render: batch rows idx (prompt indices; a short last batch repeats its last prompt) and the rows keep whose pictures are saved.
+    style_align: the reference of the whole render is its first picture - every batch after the first is [0] + the next n - 1 prompts, and picture 0 is
+    saved from the first batch only."""
+    last = n_prompts - 1
+    if not style_align:
+        return [([min(s0 + j, last) for j in range(n)], list(range(min(n, n_prompts - s0)))) for s0 in range(0, n_prompts, n)]
+    plan = [([min(j, last) for j in range(n)], list(range(min(n, n_prompts))))]
+    for s0 in range(n, n_prompts, n - 1):
+        plan.append(([0] + [min(s0 + j, last) for j in range(n - 1)], [1 + j for j in range(min(n - 1, n_prompts - s0))]))
+    return plan
 
 
 def sag_args(sag, blur=None, threshold=None):
@@ -654,7 +697,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
            guidance_rescale=0.0, guidance_interval=None, negative_prompt=None, hires=None, freeu=None, heatmap=None, heatmap_grid="max",
            kv_downsample=None, kv_downsample_mode="nearest", kv_downsample_pass="hires", vae_tile=None, change_map_image=None, mask_blur=None, tile_diffusion=None, regions=None, region_feather=None,
            region_base=None, region_bootstrap=None, apg=None, dynthresh=None, vae_attention="dense", region_mode=None, hypertile=None, hypertile_depth=None,
-           hypertile_pass=None, tome=None, tome_depth=None, tome_mode=None, tome_pass=None, sag=None, sag_blur=None, sag_threshold=None):
+           hypertile_pass=None, tome=None, tome_depth=None, tome_mode=None, tome_pass=None, sag=None, sag_blur=None, sag_threshold=None,
+           style_align=None, style_align_weight=None, style_align_adain=None):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
     seed + i at every scale.  size = (width, height) in pixels; prompts=None: n_validation validation prompts of the job's concept mode.
@@ -667,6 +711,10 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     `apg` - in every pass, of a hires render too (each pass is a trajectory of its own: the running average restarts); with everything else.
     dynthresh: None, True (DYN_DEFAULT), (mimic, percentile, interpolate) or a dict of them (dynthresh_args): dynamic thresholding - LatentSampler.sample's
     `dynthresh` - in every pass, of a hires render too; not with apg or guidance_rescale > 0 (ValueError).
+    style_align: None, True or the weight of the reference keys, with style_align_weight (the same, by name) and style_align_adain ("qk", the default, or
+    "none") - style_align_args: style-aligned batches, LatentSampler.sample's `style_align`, in every pass; the reference of the whole render is its first
+    picture (batch_plan: later batches are [0] + the next images_per_batch - 1 prompts).  images_per_batch >= 2; not with sag, tile_diffusion, regions,
+    kv_downsample, hypertile or tome.
     sag: None, True (sampler.SAG_DEFAULT's scale 0.5) or the scale, with sag_blur (the blur's sigma in latent pixels, default 2) and sag_threshold (on the
     attention mass, whose mean is 1; default 1) - sag_args: self-attention guidance, LatentSampler.sample's `sag`, in every pass of a hires render and with
     every sampler.  Epsilon prediction only (NotImplementedError); not with tile_diffusion, regions or heatmap, nor with kv_downsample, hypertile or tome
@@ -757,6 +805,13 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
                 raise ValueError(f"sag does not combine with {name}")
         SM.require_op(stack.rt.ops, "attn_colmass", " (sdlt_attn_colmass, sdlt_sag_degrade, sdlt_sag_apply): sag takes the attention mass, the degraded input and the "
                       "combine from those launches; there is no torch fallback", kernel="sdlt_attn_colmass")
+    sa = style_align_args(style_align, style_align_weight, style_align_adain, n)      # (raises before anything is built)
+    if sa is not None:
+        for other, name in ((sag, "sag"), (tile_diffusion, "tile_diffusion"), (regions, "regions"), (kv_downsample, "kv_downsample"), (hypertile, "hypertile"), (tome, "tome")):
+            if other is not None and other is not False:
+                raise ValueError(f"style_align does not combine with {name}")
+        SM.require_op(stack.rt.ops, "attn_shared_fwd", " (sdlt_attn_shared_fwd, sdlt_adain_affine): style_align runs every self-attention by those launches; there "
+                      "is no torch fallback", kernel="sdlt_attn_shared_fwd")
     rg = region_args(regions, region_feather, region_base, region_bootstrap, region_mode)      # (raises before anything is built)
     if rg is not None:
         for other, name in ((tile_diffusion, "tile_diffusion: windows of regions are not built"), (hires, "hires: the masks would need a second grid"),
@@ -864,6 +919,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         img_kw.update(dynthresh=dt)
     if sg is not None:
         img_kw.update(sag=sg)
+    if sa is not None:
+        img_kw.update(style_align=dict(weight=sa["weight"], adain=sa["adain"] == "qk"))
     if (sampler, sigmas) != ("euler", "trailing"):
         img_kw.update(sampler=sampler, sigmas=sigmas)
     if sde:
@@ -934,9 +991,9 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         loaded.prepare_decoder(min(lh, vt[0]), min(lw, vt[0]))
         return stack.decoder.decode_tiled(z, *vt)
 
-    def save(lat, idx, s0, scale, paths):
+    def save(lat, idx, keep, scale, paths):
         lat, heat = lat if isinstance(lat, tuple) else (lat, None)
-        for j, i in enumerate(idx[: len(prompts) - s0]):
+        for j, i in ((j, idx[j]) for j in keep):
             chw = _vae.postprocess(decode(lat[j:j + 1] / cfg["scaling_factor"]))
             img = chw[0].permute(1, 2, 0)
             arr = (img.float().cpu().numpy() * 255).round().astype("uint8")
@@ -973,23 +1030,22 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             SM.upscale_latents(stack.rt.ops, None, h2, w2, hi["resample"])      # (raises: no kernel, no fallback)
         kw2 = dict({k: v for k, v in img_kw.items() if k not in ("init_latents", "strength", "mask")}, **kd_kw)      # (kv_downsample: the second pass has it either way)
         enc = _vae_encoder(loaded) if hi["upscaler"] == "pixel" else None
-        second = []                             # (index of the scale, embeds, first prompt of the batch, idx, enlarged latents, second noise)
+        second = []                             # (index of the scale, embeds, the batch's rows to save, idx, enlarged latents, second noise)
     try:
         for k, scale in enumerate(lora_scales):
             stack.sampler.set_lora_scale(scale)
             embeds = [stack.conditioning(p, scale, token_scale, negative_prompt)[0] for p in prompts]
             reg_embeds = [] if rg is None else [stack.conditioning(p, scale, token_scale, negative_prompt)[0] for _, p in rg["regions"]]
             paths = []
-            for s0 in range(0, len(prompts), n):
-                idx = [min(s0 + j, len(prompts) - 1) for j in range(n)]          # a short last batch repeats its last prompt
+            for idx, keep in batch_plan(len(prompts), n, sa is not None):
                 gens = [torch.Generator(device=dev).manual_seed(seed + i) for i in idx]
                 noise = torch.cat([torch.randn(1, 4, h, w, generator=g, device=dev) for g in gens])
                 lat = sample(embeds, idx, h, w, size, noise, dict(img_kw, **tile_kw(td_plan)), seed, heat=hm_cols is not None and hi is None)
                 if hi is None:
-                    save(lat, idx, s0, scale, paths)
+                    save(lat, idx, keep, scale, paths)
                 else:                                                            # each generator's second draw: the second pass's noise
                     noise2 = torch.cat([torch.randn(1, 4, h2, w2, generator=g, device=dev) for g in gens])
-                    second.append((k, embeds, s0, idx, enlarge(lat, enc), noise2))
+                    second.append((k, embeds, keep, idx, enlarge(lat, enc), noise2))
             if hi is None:
                 finish(scale, paths)
         if hi is not None:
@@ -999,11 +1055,11 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             for k, scale in enumerate(lora_scales):
                 stack.sampler.set_lora_scale(scale)
                 paths = []
-                for k1, embeds, s0, idx, x0, noise2 in second:
+                for k1, embeds, keep, idx, x0, noise2 in second:
                     if k1 == k:
                         lat = sample(embeds, idx, h2, w2, hi["size"], noise2, dict(kw2, init_latents=x0, strength=hi["strength"], **tile_kw(td_plan2)), seed + 2 ** 32, hi["steps"],
                                      heat=hm_cols is not None)
-                        save(lat, idx, s0, scale, paths)
+                        save(lat, idx, keep, scale, paths)
                 finish(scale, paths)
     finally:
         stack.sampler.set_lora_scale(1.0)
@@ -1029,6 +1085,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             meta.update(dynthresh=dict(zip(DYN_KEYS, dt)))
         if sg is not None:
             meta.update(sag=dict(zip(SAG_KEYS, sg)))
+        if sa is not None:
+            meta.update(style_align=sa)
         if negative_prompt is not None:
             meta.update(negative_prompt=negative_prompt)
         if hi is not None:
@@ -1097,6 +1155,11 @@ def main(argv=None, runtime=None):
     from .sampler import SAG_DEFAULT
     ap.add_argument("--sag", type=float, nargs="?", const=SAG_DEFAULT[0], default=None, metavar="SCALE",
                     help=f"self-attention guidance: a second UNet forward on a latent blurred where the mid block's self-attention looks, pushed away from by SCALE (default {SAG_DEFAULT[0]:g})")
+    ap.add_argument("--style-align", type=float, nargs="?", const=1.0, default=None, metavar="WEIGHT",
+                    help="style-aligned batches: every picture's self-attentions also attend to the first picture's keys and values, weighted by WEIGHT (default 1); "
+                         "needs --images-per-batch >= 2")
+    ap.add_argument("--style-align-adain", choices=STYLE_ALIGN_ADAIN, default=None, help="with --style-align: move queries and keys to the first picture's per-channel "
+                    "statistics first (qk, the default) or not (none)")
     ap.add_argument("--sag-blur", type=float, default=None, metavar="SIGMA", help=f"with --sag: the blur's standard deviation in latent pixels (default {SAG_DEFAULT[1]:g})")
     ap.add_argument("--sag-threshold", type=float, default=None, metavar="T", help=f"with --sag: blur where a token's attention mass (mean 1) exceeds T (default {SAG_DEFAULT[2]:g})")
     ap.add_argument("--negative-prompt", default=None, help="the negative prompt; default: the fixed one of the training-time renders")
@@ -1208,6 +1271,15 @@ def main(argv=None, runtime=None):
         if sgk is not None and on:
             ap.error(f"--sag does not combine with {flag}")
     sgk = {} if sgk is None else dict(sag=sgk[0], sag_blur=sgk[1], sag_threshold=sgk[2])
+    try:
+        sak = style_align_args(a.style_align, None, a.style_align_adain, a.images_per_batch)
+    except ValueError as e:
+        ap.error(f"--style-align / --style-align-adain: {e}")
+    for flag, on in (("--sag", a.sag is not None), ("--tile-diffusion", a.tile_diffusion is not None), ("--region", a.region is not None),
+                     ("--kv-downsample", a.kv_downsample is not None), ("--hypertile", a.hypertile is not None), ("--tome", a.tome is not None)):
+        if sak is not None and on:
+            ap.error(f"--style-align does not combine with {flag}")
+    sgk = dict(sgk, **({} if sak is None else dict(style_align=sak["weight"], style_align_adain=sak["adain"])))
     if a.strength is not None and not 0.0 < a.strength <= 1.0:
         ap.error(f"--strength must be in (0, 1], got {a.strength}")
     if a.heatmap_grid is not None and a.heatmap is None:

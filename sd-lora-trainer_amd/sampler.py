@@ -587,6 +587,26 @@ def hypertile_args(hypertile):
     return tile, depth
 
 
+def style_align_args(style_align, n_images):
+    """sample()'s `style_align`, checked -> None | (weight, adain).  None or False: off; True or dict(weight=1.0, adain=True): "Style Aligned" batches -
+    every picture's self-attentions also attend to the keys and values of the batch's first picture, whose logits get + ln(weight); adain: queries and
+    keys are first moved to the first picture's per-channel statistics.  Needs n_images >= 2."""
+    if style_align is None or style_align is False:
+        return None
+    if style_align is True:
+        style_align = {}
+    if not isinstance(style_align, dict) or set(style_align) - {"weight", "adain"}:
+        raise ValueError(f"style_align takes dict(weight=1.0, adain=True), got {style_align!r}")
+    weight, adain = style_align.get("weight", 1.0), style_align.get("adain", True)
+    if not isinstance(weight, (int, float)) or isinstance(weight, bool) or not math.isfinite(weight) or weight <= 0:
+        raise ValueError(f"style_align: weight must be finite and > 0 (the reference keys' logits get + ln(weight)), got {weight!r}")
+    if not isinstance(adain, bool):
+        raise ValueError(f"style_align: adain must be True or False, got {adain!r}")
+    if not isinstance(n_images, int) or n_images < 2:
+        raise ValueError(f"style_align aligns the pictures of one batch with its first: n_images={n_images!r} (at least 2)")
+    return float(weight), adain
+
+
 def token_merge_args(token_merge):
     """sample()'s `token_merge`, checked -> None | (ratios, mode, seed).  None or False: off; dict(ratio=, depth=0, mode="random", seed=0): ratio in
     (0, 0.75] on the depth + 1 largest self-attention token grids (UNet.set_token_merge; depth beyond the UNet's grids: all of them)."""
@@ -914,7 +934,7 @@ class LatentSampler:
     def _fwd_kw(self):
         """Keywords of the UNet forward: with key / value downsampling set it is declared an inference forward (UNet.forward refuses a training one);
         the same with tiled self-attention (hypertile) and token merging; without, the call is the plain one."""
-        plain = all(getattr(self.unet, n, None) is None for n in ("_kv_ds", "_ht", "_tome")) and not getattr(self.unet, "_probe", False)
+        plain = all(getattr(self.unet, n, None) is None for n in ("_kv_ds", "_ht", "_tome", "_share")) and not getattr(self.unet, "_probe", False)
         return {} if plain else {"train": False}
 
     def set_lora_scale(self, lora_scale, train_scale=None):
@@ -929,7 +949,7 @@ class LatentSampler:
     def sample(self, embeds, h, w, *, steps=25, guidance_scale=8.0, generator=None, size=None, latents=None, graph=False, fused=False, n_images=1,
                init_latents=None, strength=1.0, mask=None, sampler="euler", sigmas="trailing", eta=1.0, seeds=None, guidance_rescale=0.0,
                guidance_interval=None, freeu=None, heatmap=None, kv_downsample=None, kv_downsample_mode=None, change_map=None, tile=None, regions=None, apg=None,
-               dynthresh=None, hypertile=None, token_merge=None, sag=None):
+               dynthresh=None, hypertile=None, token_merge=None, sag=None, style_align=None):
         """embeds = (c [1,77,D], uc [1,77,D], pc [1,P] | None, puc | None); h, w latent size.  Returns latents [1,4,h,w] fp32
         (still multiplied by the VAE scaling factor, as the pipeline holds them before `vae.decode(latents / scaling_factor)`).
         fused: guidance, the Euler update and the next model input are ONE kernel between two forwards (ops.sampler_step) instead of torch
@@ -1025,8 +1045,26 @@ class LatentSampler:
         sampler, init latents, mask, change map and every guidance option; sigma, scale and threshold per step and the taps are device memory: one
         capture (in a dict of its own, the key ending in "sag") serves every setting.  sag=None is the path without it: the same launches, capture keys
         and bits.  Epsilon prediction only (NotImplementedError); not with tile, regions or heatmap, nor with kv_downsample, hypertile or token_merge at
-        a depth that reaches the mid block's token grid (ValueError); latent sides >= 5."""
+        a depth that reaches the mid block's token grid (ValueError); latent sides >= 5.
+        style_align: True or dict(weight=1.0, adain=True) (style_align_args): "Style Aligned" batches - in every self-attention each of the n_images >= 2
+        pictures also attends to the keys and values of picture 0, whose logits get + ln(weight), after AdaIN of its queries and keys towards picture 0's
+        statistics (UNet.set_shared_attention on the negative and on the positive rows as one group each: ops.adain_affine + ops.attn_shared_fwd in
+        attn_fwd's place).  Armed for the run alone, fused and graph paths (a capture of its own per setting); not with sag, tile, regions, kv_downsample,
+        hypertile or token_merge (ValueError before the UNet is touched)."""
         ops = self.rt.ops
+        sa = style_align_args(style_align, n_images)       # refused before anything is built
+        if sa is not None:
+            for name, v in (("sag", sag), ("tile", tile), ("regions", regions), ("kv_downsample", kv_downsample if kv_downsample is not None else self.kv_downsample),
+                            ("hypertile", hypertile if hypertile is not None else self.hypertile),
+                            ("token_merge", token_merge if token_merge is not None else self.token_merge)):
+                if v is not None and v is not False:
+                    raise ValueError(f"style_align does not combine with {name}: " + ("the second forward runs the negative rows alone, without their group" if name == "sag"
+                                     else "the batch rows are windows or regions, not pictures" if name in ("tile", "regions")
+                                     else "one self-attention variant per run"))
+            if not (graph or fused):
+                raise ValueError("style_align samples several pictures together: fused=True or graph=True (the torch loop samples one)")
+            require_op(ops, "attn_shared_fwd", " (sdlt_attn_shared_fwd, sdlt_adain_affine): sample(style_align=...) runs every self-attention by those launches; "
+                       "there is no torch fallback", kernel="sdlt_attn_shared_fwd")
         sg = sag_args(sag)                                 # refused before anything is built
         if sg is not None:
             if self.sched.prediction_type != "epsilon":
@@ -1136,9 +1174,13 @@ class LatentSampler:
             assert n_images == self.n, f"the runtime's batch {self.rt.B} samples {self.n} image(s) together, not {n_images}"
             try:                                           # (armed after the last refusal, for the run alone: nothing sticks, whether it ends or raises)
                 self._arm_sag(sg)
+                if sa is not None:      # the rows are (negative j, positive j) pairs: the n negative rows are one group, the n positive rows the other
+                    self.unet.set_shared_attention(dict(group=n_images, stride=2, shift=math.log(sa[0]), adain=sa[1]))
                 return self._sample_fused(traj, embeds, latents, generator, graph)
             finally:
                 self._arm_sag(None)
+                if getattr(self.unet, "_share", None) is not None:
+                    self.unet.set_shared_attention(None)
         assert n_images == 1 and self.n == 1, "the torch loop samples one image on a batch-2 runtime; several images together: fused=True or graph=True"
         if sampler in SDE_KINDS:
             require_op(ops, "sampler_noise", f": sample(sampler={sampler!r}) takes its per-step noise from that kernel's generator (ops.sampler_noise), "
@@ -1550,6 +1592,9 @@ class LatentSampler:
         tm = getattr(self.unet, "_tome", None)
         if tm is not None:                                # token merging changes the launch sequence and its arguments: a capture per (ratios, mode, seed)
             key += (("token_merge",) + tm,)
+        sa = getattr(self.unet, "_share", None)
+        if sa is not None:                                # shared self-attention is another launch sequence; the shift is a launch argument: a capture per setting
+            key += (("style_align", sa["group"], sa["stride"], sa["shift"], sa["adain"]),)
         if "win" in sh:                                   # tiled diffusion: the window extents and counts; starts and weights are device memory
             key += (("tile",) + tuple(sh["win"]["plan"][2:]),)
         if traj.reg is not None:                          # regional prompts: the region count; masks, weights, backgrounds and the bootstrap table are device memory

@@ -985,6 +985,7 @@ class Attention(_Module):
     _ht = None          # (ty, tx) of UNet.set_hypertile: this self-attention attends inside the tiles of its token grid only (inference only)
     _tome = None        # dict(ratio, mode, seed, ctr, layer) of UNet.set_token_merge: this self-attention runs on merged tokens (inference only)
     norm = None         # the LayerNorm in front of a self-attention (TransformerBlock.norm1): the pooling launch normalises with it
+    _share = None       # dict(group, shift, adain) of UNet.set_shared_attention: every image also attends to the keys and values of its group's first (inference only)
     _probe = False      # UNet.set_attention_probe: this self-attention keeps its q, k and log-sum-exp reachable after a forward (inference only)
     probed = None       # ... as dict(q, k, L, B, N, H, d, scale, grid): views of this layer's own persistent buffers
 
@@ -1084,6 +1085,9 @@ class Attention(_Module):
         self-attention with key / value downsampling or tiles (UNet.set_hypertile) only."""
         rt, C = self.rt, self.C
         ht = None if self.cross else self._ht
+        sh = None if self.cross else self._share
+        if sh is not None and B % (sh["group"] * sh["stride"]):
+            raise ValueError(f"shared attention: {sh['stride']} interleaved group(s) of {sh['group']} images do not divide the batch of {B} rows ({self.name})")
         if ht is not None and (grid is None or grid[0] * grid[1] != N or grid[0] % ht[0] or grid[1] % ht[1]):
             raise ValueError(f"hypertile: {ht[0]} x {ht[1]} tiles do not divide the token grid {grid!r} ({N} tokens) of {self.name}")
         kv = ctx if self.cross else x
@@ -1114,11 +1118,11 @@ class Attention(_Module):
         elif not pooled_kv:
             q, k, v = self.stack.forward(x)
         O = self.buf("O", Mq, C)
-        L = self.buf("L", B * self.heads * N, dtype=F32) if ht is None else None      # (the tiled kernel leaves no log-sum-exp)
+        L = self.buf("L", B * self.heads * N, dtype=F32) if ht is None and sh is None else None      # (the tiled and the shared kernel leave no log-sum-exp)
         self._dims = (B, N, Nk, Nkp)
         # self-attention whose to_out.0 input gradient runs on the wave-split-K kernel: that product leaves the backward's row term D = rowsum(dO o O) as a side output
         # (no D pre-pass launch); its slots are cleared here, by the forward kernel's epilogue
-        self._rowdot = (not self.cross and not pooled_kv and ht is None and getattr(self, "_rowdot_ok", True) and self.to_out.trainer is None
+        self._rowdot = (not self.cross and not pooled_kv and ht is None and sh is None and getattr(self, "_rowdot_ok", True) and self.to_out.trainer is None
                         and not (self.to_out.lora is not None and self.to_out.arena.wide)
                         and getattr(rt.ops, "wsk_rowdot_shape", None) is not None and rt.ops.wsk_rowdot_shape(Mq, C, C, self.to_out.lora is not None, self.d))
         kwz = {"zero_D": self.buf("D", B * self.heads * N, dtype=F32)} if self._rowdot else {}
@@ -1126,6 +1130,21 @@ class Attention(_Module):
             rt.ops.attn_couple_fwd(q, k, v, O, cp["weights"][N], B=B, H=self.heads, Nq=N, Nk=Nk, Nkp=Nkp, R=cp["R"], d=self.d, scale=self.scale, rcount=cp["rcount"])
         elif ht is not None:    # one launch walks the tile map: no gathered copies, no pad rows, any tile size
             rt.ops.attn_window_fwd(q, k, v, O, B=B, H=self.heads, grid=tuple(grid), tiles=ht, d=self.d, scale=self.scale)
+        elif sh is not None:    # one launch walks the image's own rows and its reference's: no [own; reference] copy, no pad rows, any N
+            tables = None
+            if sh["adain"]:     # the q | k columns in one call where they are neighbours in the stacked buffer, else one call each
+                tab = self.buf(("sh_tab", B), 2, B, 2 * C, dtype=F32)
+                if k.data_ptr() == q.data_ptr() + 2 * C and k.stride(0) == q.stride(0) >= 2 * C:
+                    ws = self.buf(("sh_ws", B, N), _ops.adain_ws_floats(B, N, 2 * C), dtype=F32)
+                    rt.ops.adain_affine(torch.as_strided(q, (Mq, 2 * C), (q.stride(0), 1)), tab[0], tab[1], B=B, N=N, G=sh["group"], gs=sh["stride"], ws=ws)
+                    tables = (tab[0][:, :C], tab[1][:, :C], tab[0][:, C:], tab[1][:, C:])
+                else:
+                    tab = tab.view(4, B, C)
+                    ws = self.buf(("sh_ws", B, N), _ops.adain_ws_floats(B, N, C), dtype=F32)
+                    rt.ops.adain_affine(q, tab[0], tab[1], B=B, N=N, G=sh["group"], gs=sh["stride"], ws=ws)
+                    rt.ops.adain_affine(k, tab[2], tab[3], B=B, N=N, G=sh["group"], gs=sh["stride"], ws=ws)
+                    tables = tuple(tab)
+            rt.ops.attn_shared_fwd(q, k, v, O, B=B, H=self.heads, N=N, d=self.d, G=sh["group"], gs=sh["stride"], scale=self.scale, shift=sh["shift"], tables=tables)
         elif N % 8:
             self._attn_fwd_padded(q, k, v, O, L, B, N, Nk, Nkp, kv_padded=pooled_kv)
         else:
@@ -1482,6 +1501,7 @@ class UNet(_Module):
         self._couple = None              # set_attention_couple: dict(R, weights, rcount) of an inference instance
         self._ht = None                  # set_hypertile: ((ty, tx), ...) of an inference instance, largest self-attention token grid first
         self._tome = None                # set_token_merge: (ratios, mode, seed) of an inference instance, largest self-attention token grid first
+        self._share = None               # set_shared_attention: dict(group, shift, adain) of an inference instance
         # time_emb_proj of every resnet reads the same silu(emb): ONE GEMM over the stacked weights [sum Cout, tdim] per pass instead of
         # one M = B launch per resnet (17 in SDXL, 22 in SD1.5); the same for their input gradients (dsemb) when B == 1.  Not with the
         # full fine-tune (the projections are trained layer by layer there).
@@ -1520,6 +1540,9 @@ class UNet(_Module):
         if train and self._tome is not None:
             raise NotImplementedError("token_merge is an inference option: a training forward (train=True, TrainStep) has no backward through the merged "
                                       "tokens - set_token_merge(None) first")
+        if train and self._share is not None:
+            raise NotImplementedError("shared attention is an inference option: a training forward (train=True, TrainStep) has no backward through the "
+                                      "shared self-attention - set_shared_attention(None) first")
         if train and self._probe:
             raise NotImplementedError("the attention probe is an inference option: a training forward (train=True, TrainStep) keeps its operands for its own "
                                       "backward - set_attention_probe(False) first")
@@ -1624,6 +1647,8 @@ class UNet(_Module):
         """on: an inference forward (forward(train=False)) leaves probe_layer().probed = dict(q, k, L, B, N, H, d, scale, grid) - the operands of that
         layer's softmax, views of its own persistent buffers, as ops.attn_colmass takes them.  No launch is added or changed.  Not where that layer runs
         on merged tokens, pooled keys or tiles (ValueError at the forward: there is no N x N softmax to probe)."""
+        if on and getattr(self, "_share", None) is not None:
+            raise ValueError("attention probe: shared attention (set_shared_attention) is set on this UNet: its kernel leaves no log-sum-exp to probe")
         self._probe = bool(on)
         a = self.probe_layer()
         a._probe, a.probed = self._probe, None
@@ -1696,6 +1721,8 @@ class UNet(_Module):
             raise ValueError(f"kv_downsample: {len(factors)} factors, but this UNet has self-attention on {len(grids)} token grid(s)")
         if all(f == 1 for f in factors):
             return {}
+        if getattr(self, "_share", None) is not None:
+            raise ValueError("kv_downsample: shared attention (set_shared_attention) is set on this UNet: one self-attention variant per instance")
         clash = [lv for lv, f, t in zip(grids, factors, getattr(self, "_ht", None) or ()) if f > 1 and t != (1, 1)]
         if clash:
             raise ValueError(f"kv_downsample: level {clash[0]} already runs tiled self-attention (set_hypertile): one of the two per token grid")
@@ -1748,6 +1775,8 @@ class UNet(_Module):
             tiles = tiles[:-1]
         if not tiles:
             return {}
+        if getattr(self, "_share", None) is not None:
+            raise ValueError("hypertile: shared attention (set_shared_attention) is set on this UNet: one self-attention variant per instance")
         if getattr(self.rt.ops, "attn_window_fwd", None) is None:
             raise NotImplementedError("this op table has no tiled self-attention kernel (sdlt_attn_window_fwd): there is no torch fallback")
         clash = [lv for lv, t, q in zip(grids, tiles, (getattr(self, "_tome", None) or ((),))[0]) if t != (1, 1) and q > 0]
@@ -1772,6 +1801,46 @@ class UNet(_Module):
                     blk.attn1._ht = by_level[lv]
         self._ht = tiles
         return applied
+
+    # ------------------------------------------------------------------------------------ shared self-attention (inference only)
+    def set_shared_attention(self, state):
+        """"Style Aligned" batches (Hertz et al. 2023) for the self-attentions of inference forwards (forward(train=False)).  None: off (the plain launch
+        sequence).  dict(group=G, shift=float, adain=bool[, stride=1]): the batch rows form groups of G - consecutive rows, or with stride = s the s
+        interleaved groups of every span of G s rows (a guided batch's negative | positive rows: stride 2) - and in EVERY self-attention each row also
+        attends to the keys and values of its group's first row, the reference, whose logits get + shift (ln of the reference's weight); adain: queries and
+        keys are first moved to the reference's per-channel mean and deviation (ops.adain_affine on the q | k columns, into a table of the layer's own).
+        One ops.attn_shared_fwd in attn_fwd's place: no [own; reference] copy of K or V, no pad rows, any token count.  The batch must divide by G
+        (ValueError in forward).  Not together with kv_downsample, hypertile, token merging or the attention probe.  Cross-attention, the couple mode, FreeU
+        and the heat maps are untouched.  The launches differ from the plain ones: a capture made with one setting does not serve another.
+        -> {self-attention name: G} of the layers it applies to."""
+        attns = [blk.attn1 for t, _ in self._attn_levels() for blk in t.blocks]
+        for a in attns:
+            a._share = None
+        self._share = None
+        if state is None:
+            return {}
+        if not isinstance(state, dict) or not {"group", "shift", "adain"} <= set(state) <= {"group", "shift", "adain", "stride"}:
+            raise ValueError(f"shared attention takes dict(group=, shift=, adain=[, stride=1]), got {sorted(state) if isinstance(state, dict) else type(state)}")
+        G, shift, adain, stride = state["group"], state["shift"], state["adain"], state.get("stride", 1)
+        for name, v in (("group", G), ("stride", stride)):
+            if not isinstance(v, int) or isinstance(v, bool) or v < 1:
+                raise ValueError(f"shared attention: {name}={v!r} (an integer >= 1)")
+        if not isinstance(shift, (int, float)) or isinstance(shift, bool) or not math.isfinite(shift):
+            raise ValueError(f"shared attention: shift={shift!r} (a finite number: ln of the reference's weight)")
+        if not isinstance(adain, bool):
+            raise ValueError(f"shared attention: adain={adain!r} (True or False)")
+        for what, on in (("kv_downsample", self._kv_ds), ("hypertile", self._ht), ("token_merge", self._tome), ("the attention probe", self._probe or None)):
+            if on is not None:
+                raise ValueError(f"shared attention: {what} is set on this UNet: one self-attention variant per instance")
+        if getattr(self.rt.ops, "attn_shared_fwd", None) is None or (adain and getattr(self.rt.ops, "adain_affine", None) is None):
+            raise NotImplementedError("this op table has no shared self-attention kernels (sdlt_attn_shared_fwd, sdlt_adain_affine): there is no torch fallback")
+        for a in attns:
+            if a.d % 8 or a.d > 160:
+                raise ValueError(f"shared attention: the heads of {a.name} are {a.d} wide; the kernel takes multiples of 8 up to 160")
+        self._share = dict(group=G, shift=float(shift), adain=adain, stride=stride)
+        for a in attns:
+            a._share = self._share
+        return {a.name: G for a in attns}
 
     # ------------------------------------------------------------------------------------ token merging (inference only)
     def set_token_merge(self, ratios, mode="random", seed=0, ctr=None, latent=None):
@@ -1806,6 +1875,8 @@ class UNet(_Module):
             ratios = ratios[:-1]
         if not ratios:
             return {}
+        if getattr(self, "_share", None) is not None:
+            raise ValueError("token_merge: shared attention (set_shared_attention) is set on this UNet: one self-attention variant per instance")
         missing = [n for n in ("tome_match", "tome_plan", "tome_merge", "tome_unmerge") if getattr(self.rt.ops, n, None) is None]
         if missing:
             raise NotImplementedError(f"this op table has no token-merging kernels (sdlt_{missing[0]}, ops.{missing[0]}): there is no torch fallback")
@@ -1890,6 +1961,8 @@ class UNet(_Module):
             raise NotImplementedError("UNet.backward with token_merge set: the merged self-attention has no backward here (set_token_merge(None))")
         if self._ht is not None:
             raise NotImplementedError("UNet.backward with hypertile set: the tiled self-attention has no backward here (set_hypertile(None))")
+        if self._share is not None:
+            raise NotImplementedError("UNet.backward with shared attention set: the shared self-attention has no backward here (set_shared_attention(None))")
         if self._kv_ds is not None:
             raise NotImplementedError("UNet.backward with kv_downsample set: the pooled keys and values have no backward here (set_kv_downsample(None))")
         rt = self.rt
