@@ -301,6 +301,33 @@ typedef struct {
   float scale;
 } sdlt_attn_couple_params;    /* 112 bytes; tagless, no index in sdlt_struct_size (like sdlt_attn_wide_params): a binding checks its mirror against this figure */
 int sdlt_attn_couple_fwd(const sdlt_attn_couple_params* p, void* stream);
+/* Cross-attention forward with normalized attention guidance ("NAG", Chen et al. 2025: the negative prompt applied inside the attention).  For batch row b with
+ * m = neg_row[b] in [0, B), query i, over the whole H d wide row (all heads h; the SAME queries for both key sets):
+ *   z+[i, h] = softmax_k(scale Q[b, i, h] . K[b, k, h]) V[b, k, h],   z-[i, h] = softmax_k(scale Q[b, i, h] . K[m, k, h]) V[m, k, h],   e = s z+ - (s - 1) z-,
+ *   n+ = sum_c |z+[i, c]|,  ne = sum_c |e[i, c]|  (fp32, from the fp32 accumulators, over all H d columns),  c = 1 if ne <= tau n+ else tau n+ / ne,
+ *   O[b, i, :] = (1 - alpha) z+ + alpha c e.
+ * Rows whose neg_row[b] lies outside [0, B) get O = z+ (plain attention, no second softmax); neg_row is device data, any value is safe.  (s, tau, alpha, -) is
+ * row clamp(ctr[0], 0, tab_rows - 1) of tab (fp32 [tab_rows, 4]); ctr is the sampler's device step counter (read, never written) or NULL: row 0.  A table row with
+ * alpha == 0 or s == 1 gives O = z+ for every batch row.  Q, O: bf16 token-major [B Nq, ld], head h in columns [h d, (h + 1) d), NO pad rows (any Nq >= 1).
+ * K, V: bf16 [B Nkp, ld], keys [0, Nk) of a batch row valid, 1 <= Nk <= 128, Nk <= Nkp, Nkp % 8 == 0; rows [Nk, Nkp) are never read.  d % 8 == 0, d <= 160, and
+ * H <= 20 at d <= 64, H <= 12 at d <= 96, H <= 8 above (a wave keeps both accumulators of ceil(H / 4) heads in registers).  Every ld % 8 == 0 and >= H d.
+ * fp32 scores, exact softmax over the resident key row, bf16 P, fp32 accumulation; the norms are added in a fixed order (in-lane, across lanes, waves 0..3),
+ * one rounding at the store.  No atomics, no workspace: two runs give the same bits.  Forward only, no log-sum-exp.
+ * A null block or operand (ctr may be null), an extent or tab_rows < 1, H > 20, Nk > 128, Nkp < Nk, ld < H d, O overlapping an input, an index range beyond 32
+ * bits, an unsupported d or H for its d (-1); Nkp % 8, ld % 8, Q / K / V / O not 16-byte or neg_row / tab / ctr not 4-byte aligned (-2): the code is returned
+ * before anything is launched, outputs untouched, and sdlt_last_error names sdlt_attn_nag_fwd. */
+typedef struct {
+  const void* Q; int64_t ldq;
+  const void* K; int64_t ldk;
+  const void* V; int64_t ldv;
+  void* O; int64_t ldo;
+  const int32_t* neg_row;            /* int32 [B] */
+  const float* tab;                  /* fp32 [tab_rows, 4]: (s, tau, alpha, -) */
+  const int32_t* ctr;                /* int32 [>= 1] or NULL */
+  float scale;
+  int32_t B, H, Nq, Nk, Nkp, d, tab_rows;
+} sdlt_attn_nag_params;       /* 120 bytes; tagless, no index in sdlt_struct_size (like sdlt_attn_couple_params): a binding checks its mirror against this figure */
+int sdlt_attn_nag_fwd(const sdlt_attn_nag_params* p, void* stream);
 /* Tiled self-attention forward ("HyperTile"): every token attends to the tokens of its own rectangular tile of the token grid only.
  * Q, K, V, O: bf16 token-major [B Hg Wg, ld], head hd in columns [hd d, (hd + 1) d), NO pad rows.  Hg x Wg is the token grid, row-major: token (y, x) of
  * image b is row b Hg Wg + y Wg + x.  ty | Hg, tx | Wg, th = Hg / ty, tw = Wg / tx; token (y, x) lies in tile (y / th, x / tw).  For every image, head, tile:

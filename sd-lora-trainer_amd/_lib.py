@@ -125,6 +125,12 @@ class AttnCoupleParams(C.Structure):
                 ("B", i32), ("H", i32), ("Nq", i32), ("Nk", i32), ("Nkp", i32), ("R", i32), ("d", i32), ("scale", f32)]
 
 
+class AttnNagParams(C.Structure):
+    # sdlt_attn_nag_params: 120 bytes by the header's text (tagless, like sdlt_attn_couple_params)
+    _fields_ = [("Q", vp), ("ldq", i64), ("K", vp), ("ldk", i64), ("V", vp), ("ldv", i64), ("O", vp), ("ldo", i64), ("neg_row", vp), ("tab", vp), ("ctr", vp),
+                ("scale", f32), ("B", i32), ("H", i32), ("Nq", i32), ("Nk", i32), ("Nkp", i32), ("d", i32), ("tab_rows", i32)]
+
+
 class AttnWindowParams(C.Structure):
     # sdlt_attn_window_params: 96 bytes by the header's text (tagless, like sdlt_attn_couple_params)
     _fields_ = [("Q", vp), ("ldq", i64), ("K", vp), ("ldk", i64), ("V", vp), ("ldv", i64), ("O", vp), ("ldo", i64),
@@ -342,6 +348,7 @@ SYMBOLS = {
     "sdlt_attn_route": (i32, [C.POINTER(AttnParams), i32]),
     "sdlt_attn_wide_fwd": (i32, [C.POINTER(AttnWideParams), vp]),
     "sdlt_attn_couple_fwd": (i32, [C.POINTER(AttnCoupleParams), vp]),
+    "sdlt_attn_nag_fwd": (i32, [C.POINTER(AttnNagParams), vp]),
     "sdlt_attn_window_fwd": (i32, [C.POINTER(AttnWindowParams), vp]),
     "sdlt_tome_match": (i32, [C.POINTER(TomeMatchParams), vp]),
     "sdlt_tome_plan": (i32, [C.POINTER(TomePlanParams), vp]),

@@ -971,6 +971,44 @@ def attn_couple_fwd(Q, K, V, O, Wt, *, B, H, Nq, Nk, Nkp, R, d, scale, rcount=No
     return O
 
 
+NAG_MAX_HEADS = {64: 20, 96: 12, 128: 8, 160: 8}      # heads sdlt_attn_nag_fwd serves per padded head width (a wave keeps ceil(H / 4) heads' accumulators)
+
+
+def attn_nag_fwd(Q, K, V, O, neg_row, tab, *, B, H, Nq, Nk, Nkp, d, scale, ctr=None):
+    """sdlt_attn_nag_fwd: cross-attention with normalized attention guidance.  Batch row b with m = neg_row[b] in [0, B) attends to its own keys (z+) and, with
+    the same queries, to row m's (z-); e = s z+ - (s - 1) z-, c = min(1, tau sum|z+| / sum|e|) over the whole H d wide token row, O = (1 - alpha) z+ + alpha c e.
+    Any other neg_row[b] (-1), or a table row with alpha == 0 or s == 1: O = z+.  (s, tau, alpha, -) = row ctr[0] (clamped; ctr None: row 0) of tab fp32 [rows, 4].
+    Q, O bf16 [B Nq, >= H d] (no pad rows), K, V bf16 [B Nkp, >= H d] (row-major views, any row stride % 8 == 0; keys [0, Nk) valid, Nk <= 128), neg_row int32
+    [B] and ctr int32 [>= 1] on the device.  ValueError for a wrong shape or dtype, before the call."""
+    def bad(msg):
+        raise ValueError(f"attn_nag_fwd: {msg}")
+    for name, v in (("B", B), ("H", H), ("Nq", Nq), ("Nk", Nk), ("d", d)):
+        if not isinstance(v, int) or isinstance(v, bool) or v < 1:
+            bad(f"{name}={v!r} (an integer >= 1)")
+    if Nk > COUPLE_MAX_KEYS or Nkp < Nk or Nkp % 8:
+        bad(f"Nk={Nk} (<= {COUPLE_MAX_KEYS}) Nkp={Nkp} (>= Nk, a multiple of 8)")
+    if d % 8 or d > 160:
+        bad(f"d={d} (a multiple of 8, <= 160)")
+    hmax = NAG_MAX_HEADS[64 if d <= 64 else 96 if d <= 96 else 128 if d <= 128 else 160]
+    if H > hmax:
+        bad(f"H={H} heads of d={d} (<= {hmax} at this width)")
+    for name, t, rows in (("Q", Q, B * Nq), ("O", O, B * Nq), ("K", K, B * Nkp), ("V", V, B * Nkp)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == BF16 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == rows and t.shape[1] >= H * d):
+            bad(f"{name}: expected a cuda bf16 row-major view [{rows}, >= {H * d}], got {tuple(t.shape) if torch.is_tensor(t) else type(t)}")
+    if not (torch.is_tensor(neg_row) and neg_row.is_cuda and neg_row.dtype == torch.int32 and tuple(neg_row.shape) == (B,) and neg_row.is_contiguous()):
+        bad(f"neg_row: expected a contiguous cuda int32 [{B}]")
+    if not (torch.is_tensor(tab) and tab.is_cuda and tab.dtype == F32 and tab.dim() == 2 and tab.shape[0] >= 1 and tab.shape[1] == 4 and tab.is_contiguous()):
+        bad("tab: expected a contiguous cuda fp32 [rows >= 1, 4]")
+    if ctr is not None and not (torch.is_tensor(ctr) and ctr.is_cuda and ctr.dtype == torch.int32 and ctr.numel() >= 1 and ctr.is_contiguous()):
+        bad("ctr: expected a contiguous cuda int32 [>= 1]")
+    p = _lib.AttnNagParams()
+    p.Q, p.ldq, p.K, p.ldk, p.V, p.ldv, p.O, p.ldo = _p(Q), _ld(Q), _p(K), _ld(K), _p(V), _ld(V), _p(O), _ld(O)
+    p.neg_row, p.tab, p.ctr = _p(neg_row), _p(tab), _p(ctr)
+    p.B, p.H, p.Nq, p.Nk, p.Nkp, p.d, p.tab_rows, p.scale = B, H, Nq, Nk, Nkp, d, tab.shape[0], float(scale)
+    _lib.check(_lib.load().sdlt_attn_nag_fwd(C.byref(p), _stream()), "sdlt_attn_nag_fwd")
+    return O
+
+
 def attn_window_fwd(Q, K, V, O, *, B, H, grid, tiles, d, scale):
     """sdlt_attn_window_fwd: tiled self-attention ("HyperTile").  grid = (Hg, Wg), the row-major token grid of every image; tiles = (ty, tx) with ty | Hg and
     tx | Wg; token (y, x) attends to the (Hg / ty) (Wg / tx) tokens of its own tile (y // (Hg / ty), x // (Wg / tx)) only.  Q, K, V, O bf16 [B Hg Wg, >= H d]

@@ -9,6 +9,7 @@ scripts/test_inference.py: own prompt list, a sweep over `lora_scale`, a non-squ
                                          [--apg [--apg-eta F] [--apg-norm-threshold F] [--apg-momentum F]]
                                          [--dynthresh [MIMIC] [--dynthresh-percentile F] [--dynthresh-interpolate F]]
                                          [--sag [SCALE] [--sag-blur SIGMA] [--sag-threshold T]]
+                                         [--nag [SCALE] [--nag-tau F] [--nag-alpha F] [--nag-end SIGMA]]
                                          [--style-align [WEIGHT] [--style-align-adain qk|none]]
                                          [--negative-prompt TEXT] [--freeu B1 B2 S1 S2 [--freeu-v2]]
                                          [--hires-scale F | --hires-size W H] [--hires-strength F] [--hires-steps N] [--hires-upscaler latent|pixel]
@@ -89,6 +90,9 @@ and deviation (--style-align-adain qk, the default; none: skip it).  One launch 
 or V, K never rewritten) behind one statistics launch pair (sdlt_adain_affine); all inside the replayed graph, in every pass of a hires render.  Needs
 --images-per-batch >= 2; with more prompts than that every later batch is the first prompt again plus the next ones, and the first picture is saved once.  No
 weights, no training; not with --sag, --tile-diffusion, --region, --kv-downsample, --hypertile or --tome.  Cost: DESIGN 4.42.  Without the flag nothing changes.
+--nag [SCALE] is normalized attention guidance (Chen et al. 2025; the ComfyUI-NAG node): the negative prompt acts inside every cross-attention, so it bites at
+low --guidance too.  Defaults SCALE 5, --nag-tau 2.5, --nag-alpha 0.5, --nag-end 0 (every step).  One launch per cross-attention (sdlt_attn_nag_fwd) inside the
+replayed graph; not with --region or --tile-diffusion.  Cost: DESIGN 4.43.  Without the flag nothing changes.
 
 --hires-scale F / --hires-size W H render in two passes (the "hires fix"): a picture much larger than the model was trained for falls apart when it is
 sampled in one go (doubled subjects, tiled compositions), so the first pass samples at --size, the result is enlarged on the device
@@ -379,6 +383,18 @@ def batch_plan(n_prompts, n, style_align=False):
     for s0 in range(n, n_prompts, n - 1):
         plan.append(([0] + [min(s0 + j, last) for j in range(n - 1)], [1 + j for j in range(min(n - 1, n_prompts - s0))]))
     return plan
+
+
+def nag_args(nag, tau=None, alpha=None, end=None):
+    """render()'s nag / nag_tau / nag_alpha / nag_end, checked -> None | (scale, tau, alpha, end).  nag: None or False (off; the other three must be None
+    then), True (the default scale) or the scale; the defaults and the ranges are sampler.NAG_DEFAULT's and sampler.nag_args'."""
+    from . import sampler as SM
+    if nag is None or nag is False:
+        if tau is not None or alpha is not None or end is not None:
+            raise ValueError("nag_tau, nag_alpha and nag_end need nag (--nag [SCALE])")
+        return None
+    given = dict(scale=None if nag is True else nag, tau=tau, alpha=alpha, end=end)
+    return SM.nag_args({k: v for k, v in given.items() if v is not None})
 
 
 def sag_args(sag, blur=None, threshold=None):
@@ -697,7 +713,7 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
            guidance_rescale=0.0, guidance_interval=None, negative_prompt=None, hires=None, freeu=None, heatmap=None, heatmap_grid="max",
            kv_downsample=None, kv_downsample_mode="nearest", kv_downsample_pass="hires", vae_tile=None, change_map_image=None, mask_blur=None, tile_diffusion=None, regions=None, region_feather=None,
            region_base=None, region_bootstrap=None, apg=None, dynthresh=None, vae_attention="dense", region_mode=None, hypertile=None, hypertile_depth=None,
-           hypertile_pass=None, tome=None, tome_depth=None, tome_mode=None, tome_pass=None, sag=None, sag_blur=None, sag_threshold=None,
+           hypertile_pass=None, tome=None, tome_depth=None, tome_mode=None, tome_pass=None, sag=None, sag_blur=None, sag_threshold=None, nag=None, nag_tau=None, nag_alpha=None, nag_end=None,
            style_align=None, style_align_weight=None, style_align_adain=None):
     """Per adapter scale and prompt: conditioning (prompts.prompt_pair + sampler.blend_conditions, as the training-time renderer) -> latents ->
     VAE decode -> `img_{prompt index:02d}_seed{seed}_scale{scale}.jpg`, plus `grid_scale{scale}.jpg` per scale.  Image i starts from the noise of
@@ -715,6 +731,9 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
     "none") - style_align_args: style-aligned batches, LatentSampler.sample's `style_align`, in every pass; the reference of the whole render is its first
     picture (batch_plan: later batches are [0] + the next images_per_batch - 1 prompts).  images_per_batch >= 2; not with sag, tile_diffusion, regions,
     kv_downsample, hypertile or tome.
+    nag: None, True (sampler.NAG_DEFAULT's scale 5) or the scale, with nag_tau (the clip on the L1 ratio, default 2.5), nag_alpha (the blend, default 0.5) and
+    nag_end (a noise level: guided while sigma is above it; default 0, every step) - nag_args: normalized attention guidance, LatentSampler.sample's `nag`,
+    in every pass; the negative prompt acts inside every cross-attention (sdlt_attn_nag_fwd).  Not with regions or tile_diffusion.
     sag: None, True (sampler.SAG_DEFAULT's scale 0.5) or the scale, with sag_blur (the blur's sigma in latent pixels, default 2) and sag_threshold (on the
     attention mass, whose mean is 1; default 1) - sag_args: self-attention guidance, LatentSampler.sample's `sag`, in every pass of a hires render and with
     every sampler.  Epsilon prediction only (NotImplementedError); not with tile_diffusion, regions or heatmap, nor with kv_downsample, hypertile or tome
@@ -805,6 +824,13 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
                 raise ValueError(f"sag does not combine with {name}")
         SM.require_op(stack.rt.ops, "attn_colmass", " (sdlt_attn_colmass, sdlt_sag_degrade, sdlt_sag_apply): sag takes the attention mass, the degraded input and the "
                       "combine from those launches; there is no torch fallback", kernel="sdlt_attn_colmass")
+    ng = nag_args(nag, nag_tau, nag_alpha, nag_end)                    # (raises before anything is built)
+    if ng is not None:
+        for other, name in ((tile_diffusion, "tile_diffusion: the UNet's rows are windows, not (negative, positive) pairs"),
+                            (regions, "regions: they change the row layout (fuse) or the key sets per row (couple)")):
+            if other is not None:
+                raise ValueError(f"nag does not combine with {name}")
+        SM.require_op(stack.rt.ops, "attn_nag_fwd", " (sdlt_attn_nag_fwd): nag runs every cross-attention by that launch; there is no torch fallback", kernel="sdlt_attn_nag_fwd")
     sa = style_align_args(style_align, style_align_weight, style_align_adain, n)      # (raises before anything is built)
     if sa is not None:
         for other, name in ((sag, "sag"), (tile_diffusion, "tile_diffusion"), (regions, "regions"), (kv_downsample, "kv_downsample"), (hypertile, "hypertile"), (tome, "tome")):
@@ -919,6 +945,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
         img_kw.update(dynthresh=dt)
     if sg is not None:
         img_kw.update(sag=sg)
+    if ng is not None:
+        img_kw.update(nag=dict(zip(("scale", "tau", "alpha", "end"), ng)))
     if sa is not None:
         img_kw.update(style_align=dict(weight=sa["weight"], adain=sa["adain"] == "qk"))
     if (sampler, sigmas) != ("euler", "trailing"):
@@ -1085,6 +1113,8 @@ def render(loaded, prompts, out_dir, *, lora_scales=None, size=None, steps=25, g
             meta.update(dynthresh=dict(zip(DYN_KEYS, dt)))
         if sg is not None:
             meta.update(sag=dict(zip(SAG_KEYS, sg)))
+        if ng is not None:
+            meta.update(nag=dict(zip(("scale", "tau", "alpha", "end"), ng)))
         if sa is not None:
             meta.update(style_align=sa)
         if negative_prompt is not None:
@@ -1152,6 +1182,7 @@ def main(argv=None, runtime=None):
                     help=f"dynamic thresholding: every latent channel of the guided prediction gets the value range of the prediction at guidance scale MIMIC (default {DYN_DEFAULT[0]:g})")
     ap.add_argument("--dynthresh-percentile", type=float, default=None, metavar="F", help=f"with --dynthresh: the quantile of the prediction's own deviations the clamp stays above, in (0, 1] (default {DYN_DEFAULT[1]:g})")
     ap.add_argument("--dynthresh-interpolate", type=float, default=None, metavar="F", help=f"with --dynthresh: weight of the thresholded prediction against the plain one, in [0, 1] (default {DYN_DEFAULT[2]:g})")
+    from . import sampler as SM
     from .sampler import SAG_DEFAULT
     ap.add_argument("--sag", type=float, nargs="?", const=SAG_DEFAULT[0], default=None, metavar="SCALE",
                     help=f"self-attention guidance: a second UNet forward on a latent blurred where the mid block's self-attention looks, pushed away from by SCALE (default {SAG_DEFAULT[0]:g})")
@@ -1160,6 +1191,13 @@ def main(argv=None, runtime=None):
                          "needs --images-per-batch >= 2")
     ap.add_argument("--style-align-adain", choices=STYLE_ALIGN_ADAIN, default=None, help="with --style-align: move queries and keys to the first picture's per-channel "
                     "statistics first (qk, the default) or not (none)")
+    ap.add_argument("--nag", type=float, nargs="?", const=SM.NAG_DEFAULT[0], default=None, metavar="SCALE",
+                    help="normalized attention guidance (Chen et al. 2025): the negative prompt acts inside every cross-attention - each query also attends to the "
+                    f"negative prompt's keys, the two results are extrapolated by SCALE (default {SM.NAG_DEFAULT[0]:g}), clipped and blended (sdlt_attn_nag_fwd, inside the "
+                    "replayed graph); works at low --guidance; not with --region or --tile-diffusion: --nag 5 --nag-tau 2.5 --nag-alpha 0.5")
+    ap.add_argument("--nag-tau", type=float, default=None, metavar="F", help=f"with --nag: the bound on the L1-norm ratio of the extrapolated to the positive result (default {SM.NAG_DEFAULT[1]:g})")
+    ap.add_argument("--nag-alpha", type=float, default=None, metavar="F", help=f"with --nag: the blend weight of the guided result, 0 .. 1 (default {SM.NAG_DEFAULT[2]:g})")
+    ap.add_argument("--nag-end", type=float, default=None, metavar="SIGMA", help="with --nag: guide only while the step's noise level is above SIGMA (default 0: every step)")
     ap.add_argument("--sag-blur", type=float, default=None, metavar="SIGMA", help=f"with --sag: the blur's standard deviation in latent pixels (default {SAG_DEFAULT[1]:g})")
     ap.add_argument("--sag-threshold", type=float, default=None, metavar="T", help=f"with --sag: blur where a token's attention mass (mean 1) exceeds T (default {SAG_DEFAULT[2]:g})")
     ap.add_argument("--negative-prompt", default=None, help="the negative prompt; default: the fixed one of the training-time renders")
@@ -1271,6 +1309,14 @@ def main(argv=None, runtime=None):
         if sgk is not None and on:
             ap.error(f"--sag does not combine with {flag}")
     sgk = {} if sgk is None else dict(sag=sgk[0], sag_blur=sgk[1], sag_threshold=sgk[2])
+    try:
+        ngk = nag_args(a.nag, a.nag_tau, a.nag_alpha, a.nag_end)
+    except ValueError as e:
+        ap.error(f"--nag / --nag-tau / --nag-alpha / --nag-end: {e}")
+    for flag, on in (("--tile-diffusion", a.tile_diffusion is not None), ("--region", a.region is not None)):
+        if ngk is not None and on:
+            ap.error(f"--nag does not combine with {flag}")
+    sgk = dict(sgk, **({} if ngk is None else dict(nag=ngk[0], nag_tau=ngk[1], nag_alpha=ngk[2], nag_end=ngk[3])))
     try:
         sak = style_align_args(a.style_align, None, a.style_align_adain, a.images_per_batch)
     except ValueError as e:

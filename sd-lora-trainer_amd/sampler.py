@@ -421,6 +421,45 @@ def sag_table(sched, sag, k=None):
     return torch.from_numpy(tab)
 
 
+NAG_DEFAULT = (5.0, 2.5, 0.5, 0.0)      # scale, tau, alpha, end: the published defaults; end 0 = every step
+
+
+def nag_args(nag):
+    """sample()'s `nag`, checked -> None | (scale, tau, alpha, end).  None or False: off; True: NAG_DEFAULT; a number: the scale; or a dict with any of scale,
+    tau, alpha, end.  scale finite and >= 1, tau finite and > 0, alpha in [0, 1], end (a noise level: guidance runs on the steps whose sigma is above it)
+    finite and >= 0.  ValueError otherwise."""
+    if nag is None or nag is False:
+        return None
+    if nag is True:
+        nag = {}
+    elif isinstance(nag, numbers.Real):
+        nag = dict(scale=nag)
+    if not isinstance(nag, dict) or set(nag) - {"scale", "tau", "alpha", "end"}:
+        raise ValueError(f"nag takes True, a scale or dict(scale=, tau=, alpha=, end=), got {nag!r}")
+    scale, tau, alpha, end = (nag.get(k, v) for k, v in zip(("scale", "tau", "alpha", "end"), NAG_DEFAULT))
+    for name, v in (("scale", scale), ("tau", tau), ("alpha", alpha), ("end", end)):
+        if not isinstance(v, numbers.Real) or isinstance(v, bool) or not math.isfinite(v):
+            raise ValueError(f"nag: {name} must be a finite number, got {v!r}")
+    if scale < 1.0 or tau <= 0.0 or not 0.0 <= alpha <= 1.0 or end < 0.0:
+        raise ValueError(f"nag: scale >= 1, tau > 0, alpha in [0, 1], end >= 0, got scale={scale!r} tau={tau!r} alpha={alpha!r} end={end!r}")
+    return float(scale), float(tau), float(alpha), float(end)
+
+
+def nag_table(sigmas, scale, tau, alpha, sigma_end):
+    """The device table of ops.attn_nag_fwd for the steps that run: fp32 [k, 4], row i = (scale, tau, alpha_i, 0) - NO header row: the kernel reads row
+    ctr[0].  sigmas: the k noise levels the steps start from; alpha_i = alpha where sigma_i > sigma_end, else 0 (that row's attention is plain)."""
+    sig = np.asarray(sigmas, dtype=np.float64).reshape(-1)
+    tab = np.zeros((len(sig), 4), dtype=np.float32)
+    tab[:, 0], tab[:, 1] = scale, tau
+    tab[:, 2] = np.where(sig > float(sigma_end), alpha, 0.0)
+    return torch.from_numpy(tab)
+
+
+def nag_rows(n):
+    """neg_row of ops.attn_nag_fwd for the sampler's (negative j, positive j) row pairs: [-1, 0, -1, 2, ...] - int32 [2 n]."""
+    return torch.tensor([v for j in range(n) for v in (-1, 2 * j)], dtype=torch.int32)
+
+
 def sag_depth_check(unet, h, w, kd, ht, tm):
     """ValueError where kv_downsample (kd: kv_downsample_args' result), hypertile (ht: hypertile_plan's result) or token_merge (tm: token_merge_args')
     reaches the mid block's token grid of an h x w latent: self-attention guidance probes that layer's plain N x N softmax.  Settings that stay above
@@ -924,6 +963,7 @@ class LatentSampler:
         self._apg_graphs = {}              # the same + ("apg",) -> hipGraph of that iteration with ops.guidance_apg there instead: a dict of their own, so they evict no other
         self._dyn_graphs = {}              # the guided key + ("dyn",) -> hipGraph of that iteration with ops.guidance_dyn there instead: a dict of their own as well
         self._sag_graphs = {}              # the key the iteration has otherwise + ("sag",) -> hipGraph of that iteration with self-attention guidance in it: their own dict too
+        self._nag = None                   # nag_args of the running call (normalized attention guidance): armed for the run alone, like _sag
         self._sag = None                   # sag_args of the running call (self-attention guidance): the setting lives here, not on the Trajectory
         self._unet_sag = {}                # (freeu, kv_downsample, hypertile, token_merge) of the UNet -> UNet.clone_for_batch on a runtime of n rows: SAG's second
                                            # forward (the negative rows alone).  A clone freezes those settings when it is made, and a capture holds its buffers: one each, kept
@@ -933,8 +973,8 @@ class LatentSampler:
 
     def _fwd_kw(self):
         """Keywords of the UNet forward: with key / value downsampling set it is declared an inference forward (UNet.forward refuses a training one);
-        the same with tiled self-attention (hypertile) and token merging; without, the call is the plain one."""
-        plain = all(getattr(self.unet, n, None) is None for n in ("_kv_ds", "_ht", "_tome", "_share")) and not getattr(self.unet, "_probe", False)
+        the same with tiled self-attention (hypertile), token merging and attention nag; without, the call is the plain one."""
+        plain = all(getattr(self.unet, n, None) is None for n in ("_kv_ds", "_ht", "_tome", "_share", "_nag")) and not getattr(self.unet, "_probe", False)
         return {} if plain else {"train": False}
 
     def set_lora_scale(self, lora_scale, train_scale=None):
@@ -949,7 +989,7 @@ class LatentSampler:
     def sample(self, embeds, h, w, *, steps=25, guidance_scale=8.0, generator=None, size=None, latents=None, graph=False, fused=False, n_images=1,
                init_latents=None, strength=1.0, mask=None, sampler="euler", sigmas="trailing", eta=1.0, seeds=None, guidance_rescale=0.0,
                guidance_interval=None, freeu=None, heatmap=None, kv_downsample=None, kv_downsample_mode=None, change_map=None, tile=None, regions=None, apg=None,
-               dynthresh=None, hypertile=None, token_merge=None, sag=None, style_align=None):
+               dynthresh=None, hypertile=None, token_merge=None, sag=None, style_align=None, nag=None):
         """embeds = (c [1,77,D], uc [1,77,D], pc [1,P] | None, puc | None); h, w latent size.  Returns latents [1,4,h,w] fp32
         (still multiplied by the VAE scaling factor, as the pipeline holds them before `vae.decode(latents / scaling_factor)`).
         fused: guidance, the Euler update and the next model input are ONE kernel between two forwards (ops.sampler_step) instead of torch
@@ -1050,7 +1090,12 @@ class LatentSampler:
         pictures also attends to the keys and values of picture 0, whose logits get + ln(weight), after AdaIN of its queries and keys towards picture 0's
         statistics (UNet.set_shared_attention on the negative and on the positive rows as one group each: ops.adain_affine + ops.attn_shared_fwd in
         attn_fwd's place).  Armed for the run alone, fused and graph paths (a capture of its own per setting); not with sag, tile, regions, kv_downsample,
-        hypertile or token_merge (ValueError before the UNet is touched)."""
+        hypertile or token_merge (ValueError before the UNet is touched).        nag: True, a scale or dict(scale=5, tau=2.5, alpha=0.5, end=0) (nag_args): normalized attention guidance (Chen et al. 2025) - every cross-attention
+        runs ops.attn_nag_fwd: the positive row of each (negative j, positive j) pair also attends to its negative row's keys (neg_row = [-1, 2 j]), the two
+        results are extrapolated by scale, clipped by tau on their L1 ratio over the token's row and blended by alpha, on the steps whose sigma is above
+        `end` (nag_table; the table and the step counter are device memory: a capture per nag on / off serves every setting).  On all three paths, with
+        every sampler and guidance variant, hires, freeu, kv_downsample, hypertile, token_merge, style_align and sag; not with regions or tile.
+        """
         ops = self.rt.ops
         sa = style_align_args(style_align, n_images)       # refused before anything is built
         if sa is not None:
@@ -1065,6 +1110,15 @@ class LatentSampler:
                 raise ValueError("style_align samples several pictures together: fused=True or graph=True (the torch loop samples one)")
             require_op(ops, "attn_shared_fwd", " (sdlt_attn_shared_fwd, sdlt_adain_affine): sample(style_align=...) runs every self-attention by those launches; "
                        "there is no torch fallback", kernel="sdlt_attn_shared_fwd")
+        na = nag_args(nag)                                 # refused before anything is built
+        if na is not None:
+            if regions is not None:
+                raise ValueError("nag does not combine with regions: mode='fuse' changes the row layout (a positive row per region), mode='couple' the key "
+                                 "sets per row (a slot per region) - the negative prompt's keys are no longer the neighbouring batch row")
+            if tile is not None:
+                raise ValueError("nag does not combine with tile: the UNet's rows are the windows of all images, not (negative j, positive j) pairs")
+            require_op(ops, "attn_nag_fwd", " (sdlt_attn_nag_fwd): sample(nag=...) runs every cross-attention by that launch (ops.attn_nag_fwd), in the "
+                       "torch loop too", kernel="sdlt_attn_nag_fwd")
         sg = sag_args(sag)                                 # refused before anything is built
         if sg is not None:
             if self.sched.prediction_type != "epsilon":
@@ -1174,11 +1228,13 @@ class LatentSampler:
             assert n_images == self.n, f"the runtime's batch {self.rt.B} samples {self.n} image(s) together, not {n_images}"
             try:                                           # (armed after the last refusal, for the run alone: nothing sticks, whether it ends or raises)
                 self._arm_sag(sg)
+                self._nag = na
                 if sa is not None:      # the rows are (negative j, positive j) pairs: the n negative rows are one group, the n positive rows the other
                     self.unet.set_shared_attention(dict(group=n_images, stride=2, shift=math.log(sa[0]), adain=sa[1]))
                 return self._sample_fused(traj, embeds, latents, generator, graph)
             finally:
                 self._arm_sag(None)
+                self._arm_nag_off()
                 if getattr(self.unet, "_share", None) is not None:
                     self.unet.set_shared_attention(None)
         assert n_images == 1 and self.n == 1, "the torch loop samples one image on a batch-2 runtime; several images together: fused=True or graph=True"
@@ -1187,9 +1243,16 @@ class LatentSampler:
                        "in the torch loop too", kernel="sampler_step_sde")
         try:
             self._arm_sag(sg)
+            self._nag = na
             return self._sample_torch(traj, embeds, latents, generator)
         finally:
             self._arm_sag(None)
+            self._arm_nag_off()
+
+    def _arm_nag_off(self):
+        self._nag = None
+        if getattr(self.unet, "_nag", None) is not None:
+            self.unet.set_attention_nag(None)
 
     def _arm_sag(self, sg):
         """Self-attention guidance on (sag_args' tuple) or off (None) for the call that runs: the setting, and the UNet's attention probe with it."""
@@ -1208,6 +1271,7 @@ class LatentSampler:
         sde, counted = traj.sampler in SDE_KINDS, heat is not None or traj.guide is not None or (traj.reg is not None and not traj.reg["couple"])      # (the gather reads the bootstrap's row)
         counted = counted or getattr(self.unet, "_tome", None) is not None      # (token merging draws its destinations at the step counter)
         counted = counted or self._sag is not None                              # (self-attention guidance reads its table's row there)
+        counted = counted or self._nag is not None                              # (and so does every guided cross-attention)
         if sde:
             z = rt.zeros(1, 4, h, w, dtype=F32)
         if heat is not None and heat["heat"] is not None:
@@ -1463,6 +1527,12 @@ class LatentSampler:
             if "dtab" not in st:
                 st["dtab"] = rt.zeros(TABLE_ROWS - 1, 4, dtype=F32)
             st["dtab"][: dtab.shape[0]].copy_(dtab)
+        if self._nag is not None:                         # the table of the steps that run, rewritten per trajectory; neg_row and the counter are fixed: a capture serves every setting
+            if "ntab" not in st:                          # (SAG's second forward runs the negative rows alone on its clone, which never gets the setting)
+                st["ntab"], st["nneg"] = rt.zeros(TABLE_ROWS - 1, 4, dtype=F32), nag_rows(n).to(dev)
+            ntab = nag_table(sch.sigmas[: traj.steps], *self._nag)
+            st["ntab"][: ntab.shape[0]].copy_(ntab)
+            self.unet.set_attention_nag(dict(neg_row=st["nneg"], tab=st["ntab"], ctr=st["ctr"]))
         if self._sag is not None:                         # the table, the taps and the negative rows of the conditioning just loaded, rewritten per trajectory
             from . import ops as _ops
             ss = sh["sag"]
@@ -1606,6 +1676,8 @@ class LatentSampler:
             key, graphs = key + ("apg",), self._apg_graphs
         if traj.dyn is not None:                          # ops.guidance_dyn likewise; mimic, percentile and interpolate are in st["dtab"]
             key, graphs = key + ("dyn",), self._dyn_graphs
+        if self._nag is not None:                         # another cross-attention launch: a capture per nag on / off; scale, tau, alpha and the end cut are in st["ntab"]
+            key += (("nag",),)
         if self._sag is not None:                         # self-attention guidance adds a forward and four launches; sigma, scale, threshold and the taps are in sh["sag"]
             key, graphs = key + ("sag",), self._sag_graphs
         g = graphs.get(key)

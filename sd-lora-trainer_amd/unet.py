@@ -981,6 +981,7 @@ class Attention(_Module):
         self.scale = 1.0 / math.sqrt(self.d)
 
     _couple = None      # the state of UNet.set_attention_couple: this cross-attention mixes R regions' results per query (inference only)
+    _nag = None         # dict(neg_row, tab, ctr) of UNet.set_attention_nag: this cross-attention also attends to its row's negative prompt (inference only)
     _kv = None          # (factor > 1, mode) of UNet.set_kv_downsample: this self-attention takes k | v from pooled tokens (inference only)
     _ht = None          # (ty, tx) of UNet.set_hypertile: this self-attention attends inside the tiles of its token grid only (inference only)
     _tome = None        # dict(ratio, mode, seed, ctr, layer) of UNet.set_token_merge: this self-attention runs on merged tokens (inference only)
@@ -1102,6 +1103,11 @@ class Attention(_Module):
             if self.hooked and rt.keep_daam_maps:
                 raise ValueError(f"attention couple: the score side output of {self.name} (heat maps) sees one key set per row - keep_daam_maps is set")
             self._qk = None      # (no score side output in this mode: it is per key set)
+        ng = self._nag if self.cross else None
+        if ng is not None and cp is not None:
+            raise ValueError(f"attention nag: {self.name} is region-coupled (set_attention_couple): one cross-attention variant per instance")
+        if ng is not None and ng["neg_row"].shape[0] != B:
+            raise ValueError(f"attention nag: neg_row has {ng['neg_row'].shape[0]} entries for the {B} batch rows of {self.name}")
         Mq, Mk = B * N, B * Nkp * (cp["R"] if cp is not None else 1)
         # transposed copies of Q and K are only needed as GEMM operands of the score side output's backward (hooked
         # cross-attention); the attention kernels themselves read every tile in its natural layout
@@ -1128,6 +1134,8 @@ class Attention(_Module):
         kwz = {"zero_D": self.buf("D", B * self.heads * N, dtype=F32)} if self._rowdot else {}
         if cp is not None:      # no pad rows, no log-sum-exp: the 4- and 6-token maps of the toys go straight in
             rt.ops.attn_couple_fwd(q, k, v, O, cp["weights"][N], B=B, H=self.heads, Nq=N, Nk=Nk, Nkp=Nkp, R=cp["R"], d=self.d, scale=self.scale, rcount=cp["rcount"])
+        elif ng is not None:    # one launch, both key sets, the norms over all heads; no pad rows, no log-sum-exp (the hooked layers' score side output below is its own product on q and k)
+            rt.ops.attn_nag_fwd(q, k, v, O, ng["neg_row"], ng["tab"], B=B, H=self.heads, Nq=N, Nk=Nk, Nkp=Nkp, d=self.d, scale=self.scale, ctr=ng["ctr"])
         elif ht is not None:    # one launch walks the tile map: no gathered copies, no pad rows, any tile size
             rt.ops.attn_window_fwd(q, k, v, O, B=B, H=self.heads, grid=tuple(grid), tiles=ht, d=self.d, scale=self.scale)
         elif sh is not None:    # one launch walks the image's own rows and its reference's: no [own; reference] copy, no pad rows, any N
@@ -1499,6 +1507,7 @@ class UNet(_Module):
         self._freeu = None               # set_freeu: (b1, b2, s1, s2, version) of an inference instance
         self._kv_ds = None               # set_kv_downsample: (factors, mode) of an inference instance
         self._couple = None              # set_attention_couple: dict(R, weights, rcount) of an inference instance
+        self._nag = None                 # set_attention_nag: dict(neg_row, tab, ctr) of an inference instance
         self._ht = None                  # set_hypertile: ((ty, tx), ...) of an inference instance, largest self-attention token grid first
         self._tome = None                # set_token_merge: (ratios, mode, seed) of an inference instance, largest self-attention token grid first
         self._share = None               # set_shared_attention: dict(group, shift, adain) of an inference instance
@@ -1546,6 +1555,9 @@ class UNet(_Module):
         if train and self._probe:
             raise NotImplementedError("the attention probe is an inference option: a training forward (train=True, TrainStep) keeps its operands for its own "
                                       "backward - set_attention_probe(False) first")
+        if train and self._nag is not None:
+            raise NotImplementedError("attention nag is an inference option: a training forward (train=True, TrainStep) has no backward through the guided "
+                                      "cross-attention - set_attention_nag(None) first")
         if self._couple is not None:
             if train:
                 raise NotImplementedError("attention couple is an inference option: a training forward (train=True, TrainStep) has no backward through the "
@@ -1664,6 +1676,7 @@ class UNet(_Module):
         c.up = [([cl(r) for r in res], [cl(t) for t in att], cl(s)) for res, att, s in self.up]
         c._kv_groups, c._grad_plan, c._daam_fwd = {}, None, None      # (operand tables that hold activation pointers: the clone builds its own)
         c.set_attention_probe(False)
+        c.set_attention_nag(None)      # (the clone runs the negative rows alone: plain cross-attention)
         return c
 
     # ------------------------------------------------------------------------------------ region-coupled cross-attention (inference only)
@@ -1688,6 +1701,24 @@ class UNet(_Module):
         self._couple = state
         for a in self.cross_attns:
             a._couple = state
+
+    # ------------------------------------------------------------------------------------ normalized attention guidance (inference only)
+    def set_attention_nag(self, state):
+        """None: off (the plain launch sequence).  dict(neg_row=int32 [B], tab=fp32 [rows, 4], ctr=int32 [>= 1] | None): normalized attention guidance - every
+        cross-attention runs ops.attn_nag_fwd in attn_fwd's place: batch row b also attends to the keys and values of row neg_row[b] (its negative prompt, which
+        the batch already holds: no extra context rows), the two results are extrapolated, clipped by their L1 ratio over the token's whole row and blended
+        with row ctr[0] of tab = (scale, tau, alpha, -).  Rows with neg_row -1 run plain attention in the same launch.  The three objects are device buffers
+        the caller owns and may rewrite between forwards: one captured graph serves every setting.  Not together with set_attention_couple (ValueError in
+        forward).  Self-attention, FreeU and the heat maps' score side output are untouched."""
+        if state is not None:
+            if not isinstance(state, dict) or set(state) != {"neg_row", "tab", "ctr"}:
+                raise ValueError(f"attention nag takes dict(neg_row=, tab=, ctr=), got {sorted(state) if isinstance(state, dict) else type(state)}")
+            if getattr(self.rt.ops, "attn_nag_fwd", None) is None:
+                raise NotImplementedError("this op table has no normalized-attention-guidance kernel (sdlt_attn_nag_fwd): there is no torch fallback")
+            state = dict(state)
+        self._nag = state
+        for a in self.cross_attns:
+            a._nag = state
 
     # ------------------------------------------------------------------------------------ key / value token downsampling (inference only)
     def _attn_levels(self):
@@ -1959,6 +1990,8 @@ class UNet(_Module):
             raise RuntimeError("UNet.backward with freeu set: FreeU is an inference-time change of the forward and has no backward here (set_freeu(None))")
         if self._tome is not None:
             raise NotImplementedError("UNet.backward with token_merge set: the merged self-attention has no backward here (set_token_merge(None))")
+        if self._nag is not None:
+            raise NotImplementedError("UNet.backward with attention nag set: the guided cross-attention has no backward here (set_attention_nag(None))")
         if self._ht is not None:
             raise NotImplementedError("UNet.backward with hypertile set: the tiled self-attention has no backward here (set_hypertile(None))")
         if self._share is not None:
